@@ -12,7 +12,7 @@ consistency scoring) over one batch of 64 pool images.  The timed region (SURVEY
     host  ->  selected indices available,
 bracketed by barrier + synchronize; `value` = images of all ranks / max-over-ranks time.  The JPEG decode + H2D of the
 same pool is timed right before it and reported as `from_host_jpeg_bytes` (PCIe- and decode-inclusive rate; never
-`value`).  At N = 1 the headline run additionally sweeps the FULL configs[1] pool (5 217 images: host JPEG bytes ->
+`value`).  With --full, at N = 1 the headline run additionally sweeps the FULL configs[1] pool (5 217 images: host JPEG bytes ->
 selected 500 indices, everything inside one clock) and reports it as `full_pool`.
 
     python bench.py --gpus N --steps K --warmup W [--scaling strong|weak]
@@ -24,6 +24,12 @@ collective) and one all-gather of the score rows closes the timed region.  Print
 
 --scaling strong (default, SURVEY 8d: a FIXED pool / wall time): K x 64 images in total, split over the N ranks; without
 --steps the pool is the whole configs[1] pool of 5 217 images.  --scaling weak: K x 64 images per GPU.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`ms_per_step` = the timed
+region / K).  --full adds everything else the line used to carry, each in runs of its own after the timed region: `full_pool`,
+`cpu_baseline` + `config0_cpu_plumbing`, `f16x3_mode`, `cfg4_f16x3`, `training_step` (each still switched off by its --no-* option)
+and `parity_vs_independent_fp32`.  --dump-outputs DIR writes what the timed path returned (consistency [n] f64, cls_corr [n, C-1]
+f64, the selected pool indices as f64) to DIR/*.npy; the pool and the weights are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import hashlib
@@ -189,6 +195,30 @@ def cpu_baseline(sd, blobs, augs, positions, gpu_scores, budget_s=48.0, max_imag
                       "scoring loop (oracle/torch_port.py), %.1f s; thread count chosen as the fastest of {T, T/2, T/4, T/8}" % (n, dt)}
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, cons, cls, picked):
+    """--dump-outputs: what a caller of the timed path receives -- the per-image consistency scores, the cls_corr rows and the
+    selected pool indices -- as DIR/<name>.npy in float64.  Above 64 MB in all, a fixed seeded sample of the per-image rows is
+    written instead, with its row numbers (sample_rows.npy); the selected indices are always written whole."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    cons = np.asarray(cons, np.float64)
+    cls = np.asarray(cls, np.float64).reshape(len(cons), -1)
+    sel = np.asarray(picked, np.int64).astype(np.float64)
+    row_bytes = 8 * (1 + cls.shape[1])
+    room = DUMP_CAP_BYTES - 4096 - sel.nbytes                       # 4 KiB for the .npy headers
+    if len(cons) * row_bytes > room:
+        keep = max(1, room // (row_bytes + 8))
+        rows = np.sort(np.random.RandomState(0).choice(len(cons), keep, replace=False))
+        cons, cls = cons[rows], cls[rows]
+        np.save(os.path.join(d, "sample_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "consistency.npy"), cons)
+    np.save(os.path.join(d, "cls_corr.npy"), cls)
+    np.save(os.path.join(d, "selected_indices.npy"), sel)
+
+
 def csrc_sha1():
     """Content hash of the kernel sources the library is built from (cald_amd/csrc/*.hip, *.h, Makefile), file names included.
     Stands where `git rev-parse HEAD:cald_amd/csrc` would: the GPU box receives a snapshot without .git."""
@@ -335,6 +365,11 @@ def main():
                          "buffers, communicator bootstrapped over a TCP socket next to MASTER_PORT: no torch.distributed in the data path); "
                          "torch = torch.distributed.all_gather_into_tensor; auto = cabi when every rank has a GPU of its own, torch (gloo) when "
                          "ranks share a device (RCCL refuses two ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (full pool, CPU baseline + configs[0], f16x3 mode, configs[4], training step) "
+                         "and quote the committed parity file; a plain run only sets up, warms up and times the K steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned (consistency, cls_corr, selected indices) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-full-pool", action="store_true", help="skip the 5 217-image end-to-end run (N = 1 headline only)")
     ap.add_argument("--no-f16x3", action="store_true")
@@ -364,7 +399,8 @@ def main():
     ncls = 21 if args.shape == "voc" else 91
     mn, mx = (600, 1000) if args.shape == "voc" else (800, 1333)
     headline = (args.model == "frcnn" and args.shape == "voc" and args.augs == "FCD" and args.precision == "fp32")
-    do_full = headline and world == 1 and not args.no_full_pool and not full_default   # full_default: the headline IS the full pool
+    legs = headline and world == 1 and args.full       # the runs beyond the headline: only with --full
+    do_full = legs and not args.no_full_pool and not full_default   # full_default: the headline IS the full pool
     full_scores = None
 
     # ---- the pool as files (host JPEG bytes): rank r owns pool positions p % world == r (rank-local inputs) ----
@@ -521,6 +557,8 @@ def main():
     picked = sweep.select(list(cons), [cls[i] for i in range(cls.shape[0])], labeled, budget=budget, mr=1.2)   # every rank, host
     barrier()
     dt = time.time() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cons, cls, picked)
     # who took part: every rank's device identity, shard size and own sweep time, gathered through the SAME process group
     # (RCCL when `backend` is nccl) -- outside the timed region
     props = torch.cuda.get_device_properties(local_rank)
@@ -633,12 +671,12 @@ def main():
                                 "timed_region": "host JPEG bytes -> GPU decode -> get_uncertainty -> argsort + cls_kldiv -> 500 indices"}
             dev_pool = fp
             full_scores = (u, np.stack(ccs))
-        if world == 1 and not args.no_cpu_baseline and headline:
+        if legs and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sd, blobs, augs, positions, cons)
             out["cpu_baseline"]["host_cpus"] = os.cpu_count()
             out["cpu_baseline"]["host_cpus_usable"] = usable_cpus()
             out["config0_cpu_plumbing"] = config0_leg(model, sd, B, threads=out["cpu_baseline"]["cores"])
-        if world == 1 and headline and not args.no_f16x3:
+        if legs and not args.no_f16x3:
             # informational second line, NOT the headline: the opt-in split-fp16 MFMA mode (BASELINE configs[4]'s "fp16 MFMA path")
             # on the SAME timed pool, with its parity statement measured in this run: every image the exact mode just scored is
             # scored again in f16x3 and the two selections are compared
@@ -673,16 +711,17 @@ def main():
                                          "an independent fp32 path does the same (parity_vs_independent_fp32); on a detector trained by this repo "
                                          "0 of 1 024 images move by more than 1e-5 (profiles/r6_trained_weights.json)"}
             del fast
-        if world == 1 and headline and not args.no_cfg4:
+        if legs and not args.no_cfg4:
             out["cfg4_f16x3"] = cfg4_f16x3_leg(local_rank)
-        if world == 1 and headline and not args.no_train:
+        if legs and not args.no_train:
             # informational, NOT the headline: one training step of the same detector, cald_train.py's defaults
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_train
             del model
             torch.cuda.empty_cache()
             out["training_step"] = dict(bench_train.measure(batch=4, steps=10, warmup=3), headline=False)
-        out["parity_vs_independent_fp32"] = parity_file()
+        if args.full:
+            out["parity_vs_independent_fp32"] = parity_file()
         print(json.dumps(out))
     if cabi_comm is not None:
         cabi_comm.close()

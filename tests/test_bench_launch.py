@@ -93,3 +93,51 @@ def test_bench_cabi_collective_falls_back_together_when_a_rank_cannot_join():
     assert r["ranks_seen"] == 2 and r["backend"] == "gloo"
     assert "error" in r["cabi"] and "cald_comm_init_rank" in r["cabi"]["error"]
     assert line["config"]["n_selected"] > 0
+
+
+def test_dump_outputs_writes_what_the_timed_path_returned(tmp_path, monkeypatch):
+    """--dump-outputs: consistency / cls_corr / selected indices as float64 .npy; above the cap a fixed seeded sample of the per-image
+    rows (same rows run to run, their numbers in sample_rows.npy) and the whole selection, all within the cap."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rs = np.random.RandomState(3)
+    cons, cls, picked = rs.rand(640), rs.rand(640, 20), rs.permutation(640)[:61]
+    bench.dump_outputs(str(tmp_path / "a"), cons, cls, picked)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("consistency", "cls_corr", "selected_indices")}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["cls_corr.npy", "consistency.npy", "selected_indices.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["consistency"], cons) and np.array_equal(got["cls_corr"], cls)
+    assert np.array_equal(got["selected_indices"], picked.astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 1 << 20)
+    n = 20000                                                       # 20 000 x 21 doubles = 3.4 MB > the 1 MB cap
+    cons, cls = rs.rand(n), rs.rand(n, 20)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), cons, cls, picked)
+    size = sum(os.path.getsize(str(tmp_path / "b" / f)) for f in os.listdir(str(tmp_path / "b")))
+    assert size <= 1 << 20
+    rows = np.load(str(tmp_path / "b" / "sample_rows.npy")).astype(np.int64)
+    assert np.array_equal(rows, np.load(str(tmp_path / "c" / "sample_rows.npy")))
+    assert len(rows) > 1000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "consistency.npy")), cons[rows])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "cls_corr.npy")), cls[rows])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "selected_indices.npy")), picked.astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run carries the headline only (no leg that takes a run of its own), `ms_per_step` x `steps` is the timed region, and
+    --dump-outputs writes the timed pool's scores and selection: the same inputs give the same arrays in a second run."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        p, line, lines = _run(["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert len(lines) == 1 and line["steps"] == 1
+        for leg in ("full_pool", "cpu_baseline", "config0_cpu_plumbing", "f16x3_mode", "cfg4_f16x3", "training_step", "parity_vs_independent_fp32"):
+            assert leg not in line, leg
+        assert abs(line["ms_per_step"] - 64 / line["value"] * 1e3) < 1e-3 * line["ms_per_step"]
+        outs.append({n: np.load(str(tmp_path / d / (n + ".npy"))) for n in ("consistency", "cls_corr", "selected_indices")})
+        assert outs[-1]["consistency"].shape == (64,) and outs[-1]["cls_corr"].shape == (64, 20)
+        assert len(outs[-1]["selected_indices"]) == line["config"]["n_selected"]
+    assert all(np.array_equal(outs[0][n], outs[1][n]) for n in outs[0])

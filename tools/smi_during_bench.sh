@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/smi_$1
 mkdir -p $OUT
-python $ROOT/bench.py --steps 40 --warmup 2 --no-full-pool --no-cpu-baseline --no-f16x3 > $OUT/bench.json 2> $OUT/bench.err &
+python $ROOT/bench.py --full --steps 40 --warmup 2 --no-full-pool --no-cpu-baseline --no-f16x3 > $OUT/bench.json 2> $OUT/bench.err &
 BP=$!
 sleep 6
 for i in $(seq 1 30); do
