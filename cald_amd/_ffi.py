@@ -89,6 +89,7 @@ SIGNATURES = {
     "cald_op_cls_corr": (C.c_int, [C.c_void_p, C.c_int, c_f, c_i64, C.c_int, c_f]),
     "cald_op_pil_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "cald_op_cutout_rects": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, c_f, C.c_int, c_i, c_i]),
+    "cald_op_cutout_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i, C.c_int, c_i, c_i]),
     "cald_op_augment": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f,
                                   C.c_void_p, c_f, c_i]),
     "cald_op_frcnn_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
@@ -108,6 +109,8 @@ SIGNATURES = {
     "cald_profile_read": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_d]),
     "cald_profile_prune": (C.c_int, [C.c_void_p, c_d, c_d, c_d, c_d, c_d]),
     "cald_profile_roi_rows": (C.c_int, [C.c_void_p, c_d, c_i64]),
+    "cald_profile_cutout": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_i64]),
+    "cald_model_set_cutout_reuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_profile_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     # training step (device pointers as c_void_p)
     "cald_train_packed_floats": (C.c_int, [C.c_int] * 6 + [c_i64]),

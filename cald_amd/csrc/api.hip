@@ -78,6 +78,10 @@ struct cald_ctx {
     unsigned long long* d_roi_rows = nullptr; double prof_roi_rows_cap = 0.0, prof_roi_flops_cap = 0.0; long long prof_roi_views = 0;
     std::map<PilKey, PilCoef> pil;
     char* train_scratch = nullptr; size_t train_scratch_cap = 0;   // train.hip: split-K partial tiles of the weight gradients
+    // cut_out reuse (cald_profile_cutout): per reused stage the conv output rows the cut_out forwards computed and what the dense forwards
+    // would have; batches whose cut_out views reused the reference forward, batches that could not (the retention did not fit)
+    double cut_rows[3] = {0.0, 0.0, 0.0}, cut_dense[3] = {0.0, 0.0, 0.0};
+    long long cut_batches = 0, cut_fallbacks = 0;
 };
 
 __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, unsigned long long* acc) {
@@ -264,6 +268,14 @@ extern "C" int cald_profile_roi_rows(cald_ctx* c, double* mean_rows_per_view, in
     return 0;
 }
 
+extern "C" int cald_profile_cutout(cald_ctx* c, double* rows3, double* dense_rows3, int64_t* batches, int64_t* fallbacks) {
+    if (!c) return fail(CALD_ERR_INVALID, "ctx is null");
+    for (int i = 0; i < 3; i++) { if (rows3) rows3[i] = c->cut_rows[i]; if (dense_rows3) dense_rows3[i] = c->cut_dense[i]; }
+    if (batches) *batches = c->cut_batches;
+    if (fallbacks) *fallbacks = c->cut_fallbacks;
+    return 0;
+}
+
 extern "C" int cald_profile_dump(cald_ctx* c, const char* path) {
     if (!c || !path) return fail(CALD_ERR_INVALID, "null argument");
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -322,6 +334,24 @@ extern "C" int cald_op_cutout_rects(uint64_t seed, int H, int W, int N, const fl
     return 0;
 }
 
+extern "C" int cald_op_cutout_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out) {
+    if (H < 1 || W < 1 || nrect < 0 || nrect > CALD_MAX_CUT || (nrect && !rects) || nblk < 0 || nblk > 64 || (nblk && !strides) || !out)
+        return fail(CALD_ERR_INVALID, "bad argument");
+    int Hr, Wr, Hp, Wp;
+    transform_size(H, W, min_size, max_size, &Hr, &Wr, &Hp, &Wp);
+    std::vector<CutSet> o(nblk + 1), t(nblk + 1);
+    cut_geometry(H, W, Hr, Wr, Hp, Wp, nrect, rects, nblk, strides, &o[0], o.data() + 1, t.data() + 1);
+    t[0].n = 0;
+    for (int e = 0; e <= nblk; e++)
+        for (int k = 0; k < 2; k++) {
+            const CutSet& sset = k ? t[e] : o[e];
+            int* q = out + (size_t)(2 * e + k) * (1 + 4 * CUT_SET_MAX);
+            memset(q, 0, sizeof(int) * (1 + 4 * CUT_SET_MAX));
+            q[0] = sset.n;
+            for (int i = 0; i < sset.n; i++) { q[1 + 4 * i] = sset.r[i].x0; q[2 + 4 * i] = sset.r[i].y0; q[3 + 4 * i] = sset.r[i].x1; q[4 + 4 * i] = sset.r[i].y1; }
+        }
+    return 0;
+}
 static int get_pil(cald_ctx* c, int inSize, int outSize, int fid, PilCoef* out) {
     PilKey key{inSize, outSize, fid};
     auto it = c->pil.find(key);
@@ -468,6 +498,13 @@ struct cald_model {
         hipEvent_t ev_ref[2] = {nullptr, nullptr}, ev_score[2] = {nullptr, nullptr};
     } ss;
     int key_cap = 32768;   // FRCNN candidate (proposal, class) list capacity per view, sized from box_score_thresh at create
+    // cut_out reuse (sweep_impl): the reference forward's block outputs of the first three stages, one slot per batch parity (batch k + 1's
+    // reference forward runs before batch k's cut_out forward), and the gather plans of the cut_out forwards (pinned by parity + device)
+    struct CutReuse {
+        int mode = -1;              // cald_model_set_cutout_reuse: -1 the process default (CALD_CUTOUT_REUSE), 0 off, 1 on, 2 on with every stage dense
+        char* slot[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0};
+        char* h_gp[2] = {nullptr, nullptr}; char* d_gp = nullptr;
+    } cr;
 };
 
 extern "C" int cald_model_create(cald_ctx* ctx, const cald_model_cfg* cfg, cald_model** out) {
@@ -809,6 +846,12 @@ extern "C" int cald_model_set_rpn_prune(cald_model* m, int on, int* was) {
 // Test hooks of the certified pruning: in capture mode cald_forward takes the pruned path as well (it is dense otherwise) and keeps the
 // look-ahead's head map (debug tensors "rpn_look0/1", the per-pixel |patch|_2 "rpn_pnorm0/1", the scattered maps "rpn0/1"); the bound is
 // B_a(p) = c1[a] * rpn_pnorm(p) + c0[a].
+extern "C" int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was) {
+    if (!m || mode < -1 || mode > 2) return fail(CALD_ERR_INVALID, "bad argument");
+    if (was) *was = m->cr.mode;
+    m->cr.mode = mode;
+    return 0;
+}
 extern "C" int cald_model_set_rpn_prune_capture(cald_model* m, int on) {
     if (!m) return fail(CALD_ERR_INVALID, "model is null");
     if (on && !m->prune) return fail(CALD_ERR_STATE, "certified RPN pruning is not active on this model");
@@ -836,6 +879,8 @@ extern "C" int cald_model_destroy(cald_model* m) {
     if (m->ss.dev) hipFree(m->ss.dev);
     if (m->ss.pin) hipHostFree(m->ss.pin);
     if (m->ss.d_aug) hipFree(m->ss.d_aug);
+    for (int i = 0; i < 2; i++) { if (m->cr.slot[i]) hipFree(m->cr.slot[i]); if (m->cr.h_gp[i]) hipHostFree(m->cr.h_gp[i]); }
+    if (m->cr.d_gp) hipFree(m->cr.d_gp);
     for (int i = 0; i < 2; i++) { if (m->ss.ev_ref[i]) hipEventDestroy(m->ss.ev_ref[i]); if (m->ss.ev_score[i]) hipEventDestroy(m->ss.ev_score[i]); }
     delete m;
     return 0;
@@ -897,7 +942,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
     a.in = in; a.out = out; a.w = L.w; a.w4 = L.w4; a.w16 = L.w16; a.w16_unscale = L.w16_unscale; a.bias = L.bias; a.scale = L.scale; a.shift = L.shift;
     a.residual = residual; a.up = up;
     a.seg_in = dp->seg[lin]; a.seg_out = dp->seg[lout]; a.seg_up = dp->seg[lup];
-    a.dyn_rows = dyn; a.row_map = nullptr; a.V = V;
+    a.dyn_rows = dyn; a.row_map = nullptr; a.gather = nullptr; a.V = V;
     a.Cin = L.Cin; a.Cout = L.Cout; a.CoutPad = L.CoutPad; a.Kpad = L.Kpad;
     a.KH = L.KH; a.KW = L.KW; a.stride = L.stride; a.pad = L.pad; a.relu = relu ? 1 : 0;
     a.total_mtiles = level_tiles(m->plan, lout, V);
@@ -1012,6 +1057,37 @@ static int conv_group_on(cald_model* m, const ConvSpec* sp, int n, int V) {
     return 0;
 }
 
+// ---- cut_out reuse: the cut_out views of a sweep batch run as a forward of their own, in the reference forward's image order (same plan),
+// and their first three stages recompute only the pixels the filled rectangles reach (host_logic.h cut_geometry), patching the reference
+// forward's retained block outputs in place ----
+#define CUT_MAX_BLOCKS 32          // blocks of the first three stages (ResNet-101: 3 + 4 + 23)
+struct FwdReuse {
+    int mode = 0;                  // 1: reference forward, the block outputs of the first nblk blocks go to out[]; 2: the cut_out forward
+    int nblk = 0;
+    float* out[CUT_MAX_BLOCKS] = {};
+    // mode 2: per stage gathered launches or dense ones (also written over out[]); the device gather plan (cut_plan_bytes): per block b and
+    // set k (0: the block output's dirty set -- downsample conv, conv2, conv3; 1: conv1's compute set) LevelSeg[V + 1] (the level's
+    // geometry, tile_start counting the set's tiles) then GatherSet[V]
+    bool gather[3] = {false, false, false};
+    const char* d_gp = nullptr;
+    int tiles[CUT_MAX_BLOCKS][2] = {};
+    double rows[CUT_MAX_BLOCKS][2] = {};
+};
+static size_t cut_plan_set_bytes(int V) { return (size_t)(V + 1) * sizeof(LevelSeg) + (size_t)V * sizeof(GatherSet); }
+// one conv of a reused block on the rows of gather set `kind` (conv_p4.hip's gathered-rows mode: every row stored at its own pixel)
+static int gconv_on(cald_model* m, const ConvLayer& L, const float* in, float* out, int lin, int lout, int V, bool relu, const float* residual,
+                    const FwdReuse& ru, int b, int kind) {
+    if (!ru.tiles[b][kind]) return 0;
+    ConvArgs a;
+    const double f = fill_conv_args(m, a, L, in, out, lin, lout, V, relu, residual);
+    if (f < 0.0) return (int)f;
+    const char* base = ru.d_gp + (size_t)(2 * b + kind) * cut_plan_set_bytes(V);
+    a.seg_out = reinterpret_cast<const LevelSeg*>(base);
+    a.gather = reinterpret_cast<const GatherSet*>(base + (size_t)(V + 1) * sizeof(LevelSeg));
+    a.total_mtiles = ru.tiles[b][kind];
+    return run_conv(m->ctx, a, 2.0 * ru.rows[b][kind] * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue));
+}
+
 static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V) {
     const BatchPlan& P = m->plan;
     const long long px[8] = {level_pix(P, 0, V), level_pix(P, 1, V), level_pix(P, 2, V), level_pix(P, 3, V),
@@ -1103,7 +1179,8 @@ static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V) {
 }
 
 // views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled here.
-static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false) {
+static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
+                         const FwdReuse* ru = nullptr) {
     cald_ctx* c = m->ctx;
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
     if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
@@ -1157,11 +1234,21 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
     for (size_t b = 0; b < m->blocks.size(); b++) {
         const Bottleneck& B = m->blocks[b];
         const int lout = lvl + (B.c2.stride == 2 ? 1 : 0);
+        const bool kept = ru && (int)b < ru->nblk;          // cut_out reuse: this block's output is the retained tensor
+        float* dst = kept ? ru->out[b] : (B.layer_end ? F.Cf[layer] : F.X[xi]);
         const float* idn = cur;
-        if (B.has_down) { if ((rc = conv_on(m, B.down, cur, F.D, lvl, lout, V, false))) return rc; idn = F.D; }
-        if ((rc = conv_on(m, B.c1, cur, F.T1, lvl, lvl, V, true))) return rc;
-        float* dst = B.layer_end ? F.Cf[layer] : F.X[xi];
-        if ((rc = conv_pair_on(m, B.c2, B.c3, F.T1, F.T2, dst, lvl, lout, V, idn))) return rc;
+        if (kept && ru->mode == 2 && ru->gather[layer]) {
+            // the dirty pixels only: T1 on what conv2's windows read, the rest on the dirty set of the output, written over the retained tensor
+            if (B.has_down) { if ((rc = gconv_on(m, B.down, cur, F.D, lvl, lout, V, false, nullptr, *ru, (int)b, 0))) return rc; idn = F.D; }
+            if ((rc = gconv_on(m, B.c1, cur, F.T1, lvl, lvl, V, true, nullptr, *ru, (int)b, 1))) return rc;
+            if ((rc = gconv_on(m, B.c2, F.T1, F.T2, lvl, lout, V, true, nullptr, *ru, (int)b, 0))) return rc;
+            if ((rc = gconv_on(m, B.c3, F.T2, dst, lout, lout, V, true, idn, *ru, (int)b, 0))) return rc;
+        } else {
+            if (B.has_down) { if ((rc = conv_on(m, B.down, cur, F.D, lvl, lout, V, false))) return rc; idn = F.D; }
+            if ((rc = conv_on(m, B.c1, cur, F.T1, lvl, lvl, V, true))) return rc;
+            if ((rc = conv_pair_on(m, B.c2, B.c3, F.T1, F.T2, dst, lvl, lout, V, idn))) return rc;
+        }
+        if (B.layer_end) F.Cf[layer] = dst;
         cur = dst; lvl = lout;
         if (B.layer_end) layer++; else xi ^= 1;
     }
@@ -1778,6 +1865,11 @@ static int sweep_fwd_views() {
     static const int env = getenv("CALD_FWD_VIEWS") ? atoi(getenv("CALD_FWD_VIEWS")) : 96;
     return env < 1 ? 1 : (env > CALD_MAX_VIEWS ? CALD_MAX_VIEWS : env);
 }
+// cut_out reuse on by default in the exact sweeps; CALD_CUTOUT_REUSE=0 turns it off for the process (A/B, escape hatch)
+static bool cut_reuse_env() {
+    static const bool on = !(getenv("CALD_CUTOUT_REUSE") && atoi(getenv("CALD_CUTOUT_REUSE")) == 0);
+    return on;
+}
 static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                       const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out) {
     if (!m || !images_dev || !H || !W || !pool_pos || !cfg || !consistency_out || !cls_corr_out) return fail(CALD_ERR_INVALID, "null argument");
@@ -1840,8 +1932,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     struct Batch {
         int i0 = 0, nb = 0, P = 0, VV = 0; bool live = false;
         int* h_count; float* h_boxes; int* h_ints; float* h_par; NoiseJob* h_jobs; float* h_cons; float* h_clsc; float* h_vm; float* h_pm;
-        std::vector<int> ref_n, pair_img, view_img, pair_aug;
+        std::vector<int> ref_n, pair_img, view_img, pair_aug, view_aug;
+        std::vector<char> view_inert;     // cut_out reuse: a stand-in view of an image without detections (its results are not used)
         std::vector<float> cut_margin;
+        bool kept = false;                // the reference forward retained its first three stages (retention slot k & 1)
     } bt[2];
     for (int q = 0; q < 2; q++) {
         Bump b(S.pin + (size_t)q * pin_set, false);
@@ -1853,6 +1947,35 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     int rc = 0;
     const int fwd_views = sweep_fwd_views();
     if (m->prune && !audit) HIPCHK(hipMemsetAsync(c->d_prune_check, 0, 8, c->stream));
+    // ---- cut_out reuse (exact fp32, conv_p4.hip's gathered rows): the reference forward keeps the block outputs of the first three stages,
+    // and the batch's first cut_out augmentation recomputes only its dirty pixels over them ----
+    const bool retina = m->cfg.arch == CALD_ARCH_RETINANET;
+    static const bool p4_on = !(getenv("CALD_CONV_P4") && atoi(getenv("CALD_CONV_P4")) == 0);
+    int cut_a = -1;
+    for (int a = 0; a < A && cut_a < 0; a++) if (cfg->augs[a].kind == CALD_AUG_CUTOUT) cut_a = a;
+    int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
+    for (int b = 0, layer = 0, l = 2; b < (int)m->blocks.size() && layer < 3 && nblk < CUT_MAX_BLOCKS; b++) {
+        const Bottleneck& Bk = m->blocks[b];
+        blk_stride[nblk] = Bk.c2.stride; blk_lin[nblk] = l; l += Bk.c2.stride == 2 ? 1 : 0; blk_lout[nblk] = l; blk_stage[nblk] = layer;
+        nblk++;
+        if (Bk.layer_end) layer++;
+    }
+    const bool reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && p4_on && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
+    std::vector<BatchPlan> rplan(reuse ? 1 : 0);
+    auto plan_of = [&](int nv, const ViewDesc* vs, BatchPlan& P) {
+        int hp[CALD_MAX_VIEWS][2];
+        for (int v = 0; v < nv; v++) { int Hr, Wr; transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &hp[v][0], &hp[v][1]); }
+        build_plan(P, nv, vs, hp, retina);
+    };
+    // retained block outputs of a plan, back to back in one slot
+    auto retain_layout = [&](const BatchPlan& P, int nv, char* base, float** out) {
+        size_t off = 0;
+        for (int b = 0; b < nblk; b++) {
+            if (out) out[b] = reinterpret_cast<float*>(base + off);
+            off += al((size_t)level_pix(P, blk_lout[b], nv) * (size_t)m->blocks[b].c3.Cout * 4);
+        }
+        return off;
+    };
 
     // reference views of batch k -> detections into set k & 1, counts + boxes to the pinned host set, event
     auto enqueue_ref = [&](int k) -> int {
@@ -1864,11 +1987,88 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
             views[i].src = images_dev[b.i0 + i]; views[i].H = H[b.i0 + i]; views[i].W = W[b.i0 + i];
         }
         const DetBuffers& D = *DS[k & 1];
-        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, !audit);     // the audit wants every anchor's own logit: dense RPN head
+        FwdReuse ru; b.kept = false;
+        if (reuse) {
+            plan_of(b.nb, views.data(), rplan[0]);
+            const size_t need = retain_layout(rplan[0], b.nb, nullptr, nullptr);
+            cald_model::CutReuse& R = m->cr;
+            const int q = k & 1;
+            if (need > R.cap[q]) {         // grown on demand; the slot's last reader (batch k - 2's cut_out forward) is in the stream ahead
+                HIPCHK(hipStreamSynchronize(c->stream));
+                if (R.slot[q]) hipFree(R.slot[q]);
+                R.slot[q] = nullptr; R.cap[q] = 0;
+                if (hipMalloc((void**)&R.slot[q], need + (need >> 3)) != hipSuccess) { (void)hipGetLastError(); R.slot[q] = nullptr; }
+                else R.cap[q] = need + (need >> 3);
+            }
+            if (R.slot[q]) { ru.mode = 1; ru.nblk = nblk; retain_layout(rplan[0], b.nb, R.slot[q], ru.out); b.kept = true; }
+            else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
+        }
+        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, !audit, b.kept ? &ru : nullptr);     // the audit wants every anchor's own logit: dense RPN head
         if (r) return r;
         if (hipMemcpyAsync(b.h_count, D.count, (size_t)b.nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(b.h_boxes, D.boxes, (size_t)b.nb * cap * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipEventRecord(S.ev_ref[k & 1], c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "D2H of reference detections failed");
+        return 0;
+    };
+    // gather plan of batch k's cut_out forward (V views in the reference forward's order) into the pinned set k & 1, one H2D, and `ru`
+    auto cut_plan = [&](int k, int V, const ViewDesc* vs, FwdReuse& ru) -> int {
+        static const double cut_max = getenv("CALD_CUTOUT_REUSE_MAX") ? atof(getenv("CALD_CUTOUT_REUSE_MAX")) : 0.7;
+        cald_model::CutReuse& R = m->cr;
+        const size_t per = cut_plan_set_bytes(V), total = per * 2 * (size_t)nblk;
+        if (!R.d_gp) {
+            const size_t cap = cut_plan_set_bytes(CALD_MAX_VIEWS) * 2 * CUT_MAX_BLOCKS;
+            HIPCHK(hipMalloc((void**)&R.d_gp, cap));
+            HIPCHK(hipHostMalloc((void**)&R.h_gp[0], cap)); HIPCHK(hipHostMalloc((void**)&R.h_gp[1], cap));
+        }
+        plan_of(V, vs, rplan[0]);
+        const BatchPlan& P = rplan[0];
+        char* const h = R.h_gp[k & 1];
+        std::vector<CutSet> g_out((size_t)V * nblk), g_t1((size_t)V * nblk);
+        for (int v = 0; v < V; v++) {
+            int Hr, Wr, Hp, Wp; CutSet pool1;
+            transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &Hp, &Wp);
+            cut_geometry(vs[v].H, vs[v].W, Hr, Wr, Hp, Wp, vs[v].nrect, vs[v].rects, nblk, blk_stride, &pool1, &g_out[(size_t)v * nblk], &g_t1[(size_t)v * nblk]);
+        }
+        auto kf = [](const ConvLayer& L) { return (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue); };
+        double cost_g[3] = {0, 0, 0}, cost_d[3] = {0, 0, 0}, rows_g[3] = {0, 0, 0}, rows_d[3] = {0, 0, 0};
+        for (int b = 0; b < nblk; b++)
+            for (int kind = 0; kind < 2; kind++) {
+                const int lvl = kind ? blk_lin[b] : blk_lout[b];
+                LevelSeg* sg = reinterpret_cast<LevelSeg*>(h + (size_t)(2 * b + kind) * per);
+                GatherSet* gs = reinterpret_cast<GatherSet*>(reinterpret_cast<char*>(sg) + (size_t)(V + 1) * sizeof(LevelSeg));
+                int tiles = 0; double rows = 0.0;
+                for (int v = 0; v < V; v++) {
+                    LevelSeg L = P.seg[lvl][v]; L.tile_start = tiles; sg[v] = L;
+                    CutRect rr[CALD_GATHER_RECTS];
+                    int n = cut_disjoint(kind ? g_t1[(size_t)v * nblk + b] : g_out[(size_t)v * nblk + b], rr, CALD_GATHER_RECTS);
+                    if (n < 0) { n = 1; rr[0] = {0, 0, L.W - 1, L.H - 1}; }       // too fragmented: the whole view
+                    GatherSet& G = gs[v]; memset(&G, 0, sizeof(G));
+                    G.nr = n;
+                    for (int q = 0; q < n; q++) {
+                        G.x0[q] = rr[q].x0; G.y0[q] = rr[q].y0; G.w[q] = rr[q].x1 - rr[q].x0 + 1;
+                        G.cum[q + 1] = G.cum[q] + G.w[q] * (rr[q].y1 - rr[q].y0 + 1);
+                    }
+                    tiles += (G.cum[n] + 127) / 128; rows += (double)G.cum[n];
+                }
+                sg[V] = P.seg[lvl][V]; sg[V].tile_start = tiles;
+                ru.tiles[b][kind] = tiles; ru.rows[b][kind] = rows;
+                const Bottleneck& Bk = m->blocks[b];
+                const double w = kind ? kf(Bk.c1) : kf(Bk.c2) + kf(Bk.c3) + (Bk.has_down ? kf(Bk.down) : 0.0);
+                const double nconv = kind ? 1.0 : (Bk.has_down ? 3.0 : 2.0), dense = (double)level_pix(P, lvl, V);
+                const int st = blk_stage[b];
+                cost_g[st] += 128.0 * tiles * w; cost_d[st] += dense * w;
+                rows_g[st] += rows * nconv; rows_d[st] += dense * nconv;
+            }
+        // a stage runs gathered while its tiles cost at most cut_max of the dense stage (the rest pays the halo, the per-view tile tails
+        // and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
+        for (int st = 0; st < 3; st++) {
+            ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= cut_max * cost_d[st];
+            c->cut_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_dense[st] += rows_d[st];
+        }
+        if (hipMemcpyAsync(R.d_gp, h, total, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of the cut_out gather plan failed");
+        ru.mode = 2; ru.nblk = nblk; ru.d_gp = R.d_gp;
+        retain_layout(P, V, m->cr.slot[k & 1], ru.out);
+        c->cut_batches++;
         return 0;
     };
     // float64 means of a scored batch (cald_train.py:225-228); waits for its scores
@@ -1879,7 +2079,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         const int nb = b.nb, P = b.P, VV = b.VV;
         std::vector<std::vector<int>> img_pairs(nb), img_views(nb);
         for (int p = 0; p < P; p++) img_pairs[b.pair_img[p]].push_back(p);
-        for (int v = nb; v < VV; v++) img_views[b.view_img[v]].push_back(v);
+        for (int v = nb; v < VV; v++) if (!b.view_inert[v]) img_views[b.view_img[v]].push_back(v);
+        // float64 sums in augmentation order (the cut_out reuse stores a batch's cut_out views ahead of the others)
+        for (int i = 0; i < nb; i++)
+            std::stable_sort(img_views[i].begin(), img_views[i].end(), [&](int x, int y) { return b.view_aug[x] < b.view_aug[y]; });
         for (int i = 0; i < nb; i++) {
             double* cc = cls_corr_out + (size_t)(b.i0 + i) * (C - 1);
             const int nvw = 1 + (int)img_views[i].size();
@@ -1924,6 +2127,8 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         const int* h_count = b.h_count; const float* h_boxes = b.h_boxes;
         std::vector<int> ref_sel((size_t)B * 50, 0), pair_ref, pair_aug, pair_kind, view_isref(VT, 0);
         b.ref_n.assign(B, 0); b.pair_img.clear(); b.view_img.assign(VT, 0); b.cut_margin.assign(B, INFINITY);
+        b.view_aug.assign(VT, 0); b.view_inert.assign(VT, 0);
+        std::vector<int> av_aug;           // augmentation index of each augmented view
         std::vector<float> pair_par;
         std::vector<ViewDesc> aviews;
         int njobs = 0;
@@ -1966,9 +2171,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
             const uint64_t seed = (uint64_t)cfg->base_seed * 1000003ull + (uint64_t)pool_pos[i0 + i];
             float sub[50 * 4];
             for (int q = 0; q < b.ref_n[i]; q++) memcpy(sub + 4 * q, &h_boxes[((size_t)i * cap + ref_sel[(size_t)i * 50 + q]) * 4], 16);
+            int cur_a = 0;
             auto add_view = [&](const ViewDesc& vd, int kind, const float* par) {
                 const int vidx = nb + (int)aviews.size();
-                aviews.push_back(vd); b.view_img[vidx] = i; view_isref[vidx] = 0;
+                aviews.push_back(vd); av_aug.push_back(cur_a); b.view_img[vidx] = i; view_isref[vidx] = 0; b.view_aug[vidx] = cur_a;
                 pair_ref.push_back(i); pair_aug.push_back(vidx); pair_kind.push_back(kind); b.pair_img.push_back(i);
                 for (int q = 0; q < 12; q++) pair_par.push_back(par ? par[q] : 0.0f);
             };
@@ -1978,6 +2184,7 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
             for (int a = 0; a < A && !r; a++) {
                 const int kd = cfg->augs[a].kind; const double prm = cfg->augs[a].param;
                 float par[12] = {0};
+                cur_a = a;
                 if (kd == CALD_AUG_FLIP) { ViewDesc v = base; v.flip = 1; par[0] = (float)Wi; add_view(v, 1, par); }
                 else if (kd == CALD_AUG_GAUSS) {            // image + torch.randn(size) * std / 255.0
                     NoiseSeg& sg = nj.seg[nj.nseg++]; sg.kind = 0; sg.p0 = (float)prm; sg.p1 = 0.0f;
@@ -2026,16 +2233,54 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         // forward leaves most of its launches under-filled; results do not depend on the split).  96 views per forward: the mid-size
         // layers and fc6 then fill whole rounds of the 768 workgroup slots (measured +1.0 % on the sweep) ----
         const int na = (int)aviews.size();
-        const int n_fw = (na + fwd_views - 1) / fwd_views;
-        for (int f = 0; f < n_fw; f++) {
-            const int a0 = (int)(((long long)na * f) / n_fw), nv = (int)(((long long)na * (f + 1)) / n_fw) - a0;
-            DetBuffers d2 = D; const size_t o = (size_t)(nb + a0);
+        auto det_at = [&](size_t o) {
+            DetBuffers d2 = D;
             d2.boxes += o * cap * 4; d2.scores += o * cap; d2.labels += o * cap; d2.props += o * cap * 4;
             d2.prob_max += o * cap; d2.scores_cls += o * cap * C; d2.count += o;
-            if ((r = forward_model(m, nv, aviews.data() + a0, d2, audit ? d_vm[k & 1] + o * CALD_VM : nullptr, !audit))) return r;
+            return d2;
+        };
+        int VV = nb + na, n_rest = na, rest_slot = nb;
+        const ViewDesc* rest_views = aviews.data();
+        std::vector<ViewDesc> rest;
+        int n_cut = 0;
+        for (int j = 0; j < na; j++) n_cut += av_aug[j] == cut_a;
+        if (b.kept && n_cut > 0 && 2 * nb + (na - n_cut) <= VT) {
+            // cut_out reuse: image i's cut_out view takes slot nb + i (a stand-in copy of the reference view, no rectangle, for an image
+            // without detections: same plan as the reference forward), the other augmented views slots 2 nb + ... in their order
+            std::vector<ViewDesc> cutv(nb);
+            std::vector<int> slot(na), nimg(VT, 0), naug(VT, 0);
+            std::vector<char> has(nb, 0), ninert(VT, 0);
+            for (int i = 0; i < nb; i++) nimg[i] = i;
+            int nr2 = 0;
+            for (int j = 0; j < na; j++) {
+                const int img = b.view_img[nb + j];
+                if (av_aug[j] == cut_a) { slot[j] = nb + img; cutv[img] = aviews[j]; has[img] = 1; }
+                else { slot[j] = 2 * nb + nr2++; rest.push_back(aviews[j]); }
+                nimg[slot[j]] = img; naug[slot[j]] = b.view_aug[nb + j];
+            }
+            for (int i = 0; i < nb; i++)
+                if (!has[i]) {
+                    memset(&cutv[i], 0, sizeof(ViewDesc));
+                    cutv[i].src = images_dev[i0 + i]; cutv[i].H = H[i0 + i]; cutv[i].W = W[i0 + i];
+                    nimg[nb + i] = i; naug[nb + i] = cut_a; ninert[nb + i] = 1;
+                }
+            for (size_t p = 0; p < pair_aug.size(); p++) pair_aug[p] = slot[pair_aug[p] - nb];
+            b.view_img = nimg; b.view_aug = naug; b.view_inert = ninert;
+            FwdReuse ru;
+            if ((r = cut_plan(k, nb, cutv.data(), ru))) return r;
+            if ((r = forward_model(m, nb, cutv.data(), det_at((size_t)nb), nullptr, !audit, &ru))) return r;
+            VV = 2 * nb + nr2; n_rest = nr2; rest_slot = 2 * nb; rest_views = rest.data();
+        } else if (b.kept) {
+            c->cut_fallbacks++;
+        }
+        const int n_fw = (n_rest + fwd_views - 1) / fwd_views;
+        for (int f = 0; f < n_fw; f++) {
+            const int a0 = (int)(((long long)n_rest * f) / n_fw), nv = (int)(((long long)n_rest * (f + 1)) / n_fw) - a0;
+            const size_t o = (size_t)(rest_slot + a0);
+            if ((r = forward_model(m, nv, const_cast<ViewDesc*>(rest_views) + a0, det_at(o), audit ? d_vm[k & 1] + o * CALD_VM : nullptr, !audit))) return r;
         }
         // ---- scoring ----
-        const int P = (int)pair_ref.size(), VV = nb + na;
+        const int P = (int)pair_ref.size();
         b.P = P; b.VV = VV; b.pair_aug = pair_aug;
         int* ints = b.h_ints;
         memset(ints, 0, n_ints * 4);

@@ -38,6 +38,22 @@ struct BatchPlan {
     LevelSeg seg[CALD_MAX_LEVELS][CALD_MAX_VIEWS + 1];
 };
 
+// Gathered rows of one view (conv_p4.hip, the cut_out view's backbone under api.hip's activation reuse): row m of the launch is a pixel
+// of one of nr disjoint rectangles of the view's OUTPUT grid -- rectangle k holds rows [cum[k], cum[k + 1]) in row-major order, starting
+// at pixel (y0, x0), w pixels wide.  Rows are computed at that pixel and stored (and a residual read) at that pixel of the full tensor.
+#define CALD_GATHER_RECTS 8
+struct GatherSet {
+    int nr;
+    int cum[CALD_GATHER_RECTS + 1];
+    int x0[CALD_GATHER_RECTS], y0[CALD_GATHER_RECTS], w[CALD_GATHER_RECTS];
+};
+__device__ __forceinline__ int gather_pixel(const GatherSet& g, const int m, const int W) {
+    int k = 0;
+    while (k + 1 < g.nr && m >= g.cum[k + 1]) k++;
+    const int j = m - g.cum[k], w = g.w[k], ry = j / w;
+    return (g.y0[k] + ry) * W + g.x0[k] + (j - ry * w);
+}
+
 struct ConvArgs {
     const float* in;
     float* out;
@@ -86,6 +102,9 @@ struct ConvArgs {
     // entry, after the prologue's first barrier, after the k-loop, after the epilogue's last store was issued, after the stores drained;
     // HW_ID; XCC_ID; blockIdx -- the timeline of a launch on the chip (tools/conv_trace.py)
     unsigned long long* trace;
+    // conv_p4.hip only: per view the rows of a gathered-and-scattered launch (GatherSet), else null.  seg_out's tile_start then counts
+    // the gathered rows' tiles; pix_off / H / W stay the full tensor's.
+    const GatherSet* gather;
 };
 
 // Several independent conv problems in ONE launch (the five FPN levels under the shared-weight RPN / RetinaNet heads, the

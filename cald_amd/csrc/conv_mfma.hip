@@ -307,6 +307,10 @@ void launch_conv(const ConvArgs& a, hipStream_t stream) {
     static const int stem = conv_env("CALD_CONV_STEM", 1);   // 0: the stem runs on the generic kernels (same bits)
     if (stem && a.wstem && launch_conv_stem(a, stream)) return;
     if (p4 && launch_conv_p4(a, stream)) return;
+    if (a.gather) {                    // likewise the gathered-and-scattered rows of the cut_out reuse (api.hip checks before it turns it on)
+        fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with gather support; launch skipped\n", a.Cin, a.Cout);
+        return;
+    }
     if (a.row_map) {                   // gathered rows exist in conv_p4.hip only (api.hip switches the pruning off when CALD_CONV_P4=0):
                                          // never compute the wrong rows silently -- the sweep's bound check then sends it to the dense head
         fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with row_map support; launch skipped\n", a.Cin, a.Cout);

@@ -17,7 +17,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- fused epilogue (shared by the plain kernels and by the bottleneck-fused kernel's second GEMM) ----
-template <int EPI, bool MASK, int TM, int TN>
+template <int EPI, bool MASK, int TM, int TN, bool GATHER = false>
 __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&acc)[TM][TN], float* smem, const int v, const LevelSeg& so,
                                             const int m0, const int Mv, const int n0) {
     constexpr int BM = 128, WN = 2;
@@ -50,30 +50,48 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
     // dropped by the hardware, so a view's last, partial tile runs the same branch-free code as a full one (no per-element row tests, no
     // 64-bit addresses).  A lane of a padded output channel uses an offset beyond any descriptor.  (exp_flags bit 0, a tuning experiment:
     // a zero-sized output descriptor drops every store.)
-    const unsigned long long vb64 = (unsigned long long)Mv * (unsigned)row_b;
+    // gathered rows (ConvArgs::gather): row m goes to its own pixel of the full tensor -- the descriptors span the whole view, and a row
+    // past the view's count gets the out-of-range offset instead
+    const unsigned long long vb64 = (unsigned long long)(GATHER ? Ho * Wo : Mv) * (unsigned)row_b;
     const unsigned valid_b = vb64 < 0x7FFE0000ull ? (unsigned)vb64 : 0x7FFE0000u;
     const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc((void*)out_v, 0, (a.exp_flags & 1) ? 0 : valid_b, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI != 0 ? ex_v : out_v), 0, EPI == 1 ? valid_b : 0x7FFE0000, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc((void*)mask_v, 0, valid_b, 0x00020000);
     // FPN top-down (EPI 2): the nearest-neighbour source pixel of each of the tile's 128 rows is computed ONCE (one thread per
-    // row; the LDS tile buffers are free after the k-loop's last barrier) instead of by every lane for each of its 32 rows
+    // row; the LDS tile buffers are free after the k-loop's last barrier) instead of by every lane for each of its 32 rows.
+    // Gathered rows: likewise the byte offset of each row's own pixel.
+    static_assert(!(GATHER && EPI == 2), "gathered rows take no top-down term");
     const int Mlast = Mv - 1;
     int* const s_src = reinterpret_cast<int*>(smem);
-    if (EPI == 2) {
+    if (EPI == 2 || GATHER) {
         if (tid < BM) {
             int m = m0 + tid;
-            m = m < Mlast ? m : Mlast;
-            const int oy = m / Wo, ox = m - oy * Wo;
-            int sy = (int)floorf((float)oy * uph_s); sy = sy > upH - 1 ? upH - 1 : sy;
-            int sx = (int)floorf((float)ox * upw_s); sx = sx > upW - 1 ? upW - 1 : sx;
-            s_src[tid] = (sy * upW + sx) * out_ld * 4;
+            if (GATHER) {
+                s_src[tid] = m < Mv ? gather_pixel(a.gather[v], m, Wo) * row_b : 0x7FFF0000;
+            } else {
+                m = m < Mlast ? m : Mlast;
+                const int oy = m / Wo, ox = m - oy * Wo;
+                int sy = (int)floorf((float)oy * uph_s); sy = sy > upH - 1 ? upH - 1 : sy;
+                int sx = (int)floorf((float)ox * upw_s); sx = sx > upW - 1 ? upW - 1 : sx;
+                s_src[tid] = (sy * upW + sx) * out_ld * 4;
+            }
         }
         __syncthreads();
     }
+    // gathered rows: the 16 byte offsets of accumulator tile (i, column n), register r = row (r & 3) + 8 (r >> 2) of the lane's block
+    auto gather_offs = [&](const int i, const int n, const bool nok, int (&go)[16]) {
+        const int rl = wm * TM * 32 + i * 32 + 4 * kh_lane;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const i32x4 so4 = *reinterpret_cast<const i32x4*>(s_src + rl + 8 * q);
+#pragma unroll
+            for (int jj = 0; jj < 4; jj++) go[4 * q + jj] = nok ? so4[jj] + n * 4 : 0x7FFF0000;
+        }
+    };
     // The FPN output convs of P2 / P3 under the certified RPN pruning also leave (i) the split-fp16 copy of their output (h16.h) for the
     // look-ahead conv and (ii) per pixel the sum of squares over this wave's 64 channels for the bound -- what prune_energy_kernel did in a
     // second pass over the tensor.  Compiled into the plain (EPI 0, no mask) kernels only; wave-uniform branches elsewhere.
-    constexpr bool EXTRA = EPI == 0 && !MASK;
+    constexpr bool EXTRA = EPI == 0 && !MASK && !GATHER;
     const bool want16 = EXTRA && a.out16 != nullptr, wantE = EXTRA && TN == 2 && a.energy4 != nullptr;      // energy4 has four slots: 2 n-tiles of 128 x 2 wave columns (Cout = 256)
     unsigned char* const out16_v = want16 ? reinterpret_cast<unsigned char*>(a.out16) + so.pix_off * (long long)out_ld * 4 : nullptr;
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(want16 ? (void*)out16_v : (void*)out_v), 0, valid_b, 0x00020000);
@@ -100,7 +118,7 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
         sc_[j] = has_bn ? a.scale[nc] : 1.0f;
         sh_[j] = has_bn ? a.shift[nc] : 0.0f;
     }
-    constexpr int NTILE = TM * TN, PRE = NTILE;
+    constexpr int NTILE = TM * TN, PRE = GATHER ? 1 : NTILE;     // gathered rows: one tile ahead (deeper prefetch plus the 16 row offsets spills)
     float extra_[EPI != 0 ? NTILE : 1][16];
     auto load_extra = [&](const int t, float (&extra)[16]) {      // tile t = j * TM + i
         const int j = t / TM, i = t - j * TM;
@@ -108,7 +126,12 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
         const bool nok = n < a.Cout;
         const int nc = nok ? n : 0;
         const int mbase = m0 + wm * TM * 32 + i * 32 + 4 * kh_lane;
-        if (EPI == 1) {
+        if (EPI == 1 && GATHER) {
+            int go[16];
+            gather_offs(i, n, nok, go);
+#pragma unroll
+            for (int r = 0; r < 16; r++) extra[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, go[r], 0, 0));
+        } else if (EPI == 1) {
             const int vo = nok ? (mbase * out_ld + n) * 4 : 0x7FFF0000;
 #pragma unroll
             for (int r = 0; r < 16; r++)
@@ -167,9 +190,16 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
 #pragma unroll
                 for (int r = 0; r < 16; r++) val[r] = mk[r] > 0.0f ? val[r] : 0.0f;
             }
+            if (GATHER) {
+                int go[16];
+                gather_offs(i, n, nok, go);
 #pragma unroll
-            for (int r = 0; r < 16; r++)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val[r]), rsO, vo, ((r & 3) + 8 * (r >> 2)) * row_b, 0);
+                for (int r = 0; r < 16; r++) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val[r]), rsO, go[r], 0, 0);
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val[r]), rsO, vo, ((r & 3) + 8 * (r >> 2)) * row_b, 0);
+            }
             if (EXTRA) {
                 if (wantE) {
 #pragma unroll
@@ -219,6 +249,8 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
     constexpr int EPI = EPIX & 3;               // 0 none, 1 residual, 2 nearest-upsampled top-down
     constexpr bool MASK = (EPIX & 4) != 0;      // training backward only: the ReLU-backward mask step is compiled in
     constexpr bool FUSE = (EPIX & 8) != 0;      // bottleneck conv2 (3 x 3, 64 -> 64) + conv3 (1 x 1, 64 -> 256, + residual) in one workgroup
+    constexpr bool GATHER = (EPIX & 16) != 0;   // gathered rows, each stored at its own pixel (ConvArgs::gather)
+    static_assert(!(GATHER && (FUSE || MASK || C4)), "gathered rows: plain EPI 0 / 1 kernels only");
     constexpr int BM = 128, BN = 64 * TN, BK = 16, TM = 2, WN = 2;
     constexpr int TILE_A = 2 * BM * 8, TILE_F = TILE_A + 2 * BN * 8;      // floats: 2048 + 2048 (TN = 2)
     constexpr int FUSE_T = 4 * TILE_A;          // floats: conv2's 128 x 64 output tile as the A operand of four k-tiles (32 KB)
@@ -254,6 +286,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
     const int Ho = so.H, Wo = so.W, Hi = si.H, Wi = si.W;
     int Mv = Ho * Wo;
     if (a.dyn_rows) { const int d = a.dyn_rows[v]; Mv = d < Mv ? d : Mv; }
+    if (GATHER) Mv = a.gather[v].cum[a.gather[v].nr];
     const int m0 = (mt - so.tile_start) * BM;
     if (m0 >= Mv) return;
     const float* __restrict__ in_v = a.in + si.pix_off * (long long)a.Cin;
@@ -269,7 +302,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
         const int m = m0 + arow + 64 * p;
         // gathered rows (ConvArgs::row_map): row m is the output pixel row_map[m] of the view's grid; everything below addresses the INPUT
         // from (oy, ox), the epilogue stores at row m
-        const int mp = (a.row_map && m < Mv) ? a.row_map[so.pix_off + m] : m;
+        const int mp = GATHER ? (m < Mv ? gather_pixel(a.gather[v], m, Wo) : 0) : (a.row_map && m < Mv) ? a.row_map[so.pix_off + m] : m;
         const int oy = mp / Wo, ox = mp - oy * Wo;
         const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
         unsigned msk = 0;
@@ -663,7 +696,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             }
         }
     } else {
-        p4_epilogue<EPI, MASK, TM, TN>(a, acc, smem, v, so, m0, Mv, n0);
+        p4_epilogue<EPI, MASK, TM, TN, GATHER>(a, acc, smem, v, so, m0, Mv, n0);
     }
     if (trace && tid == 0) {
         trace[3] = __builtin_amdgcn_s_memtime();
@@ -705,7 +738,7 @@ bool launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream) {
     ConvGroup g; g.n = n; int blk = 0;
     for (int i = 0; i < n; i++) {
         const ConvArgs& a = p[i];
-        if (!a.w4 || a.w16 || a.CoutPad % 64 != 0 || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return false;
+        if (!a.w4 || a.w16 || a.CoutPad % 64 != 0 || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return false;
         if ((a.mask != nullptr) != (p[0].mask != nullptr)) return false;
         g.blk0[i] = blk; blk += p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a; g.p[i].exp_flags = 0;
     }
@@ -728,7 +761,7 @@ bool launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t st
     static const int on = getenv("CALD_P4_FUSE") ? atoi(getenv("CALD_P4_FUSE")) : 1;
     if (!on || !c2.w4 || !c3.w4 || c2.w16 || c3.w16) return false;
     if (c2.KH != 3 || c2.KW != 3 || c2.stride != 1 || c2.pad != 1 || c2.Cin % 16 || c2.Cout != 64 || c2.CoutPad != 64 || c2.out_ld != 64) return false;
-    if (c2.residual || c2.up || c2.mask || c2.dyn_rows || c2.in_relu || p4_taps(c2) != 9) return false;
+    if (c2.residual || c2.up || c2.mask || c2.dyn_rows || c2.in_relu || c2.gather || c3.gather || p4_taps(c2) != 9) return false;
     if (c3.KH != 1 || c3.KW != 1 || c3.stride != 1 || c3.pad != 0 || c3.Cin != 64 || c3.Kpad != 64 || c3.CoutPad % 64 || c3.Cout != c3.CoutPad) return false;
     if (!c3.residual || !c3.scale || c3.bias || c3.out_ld != c3.Cout || c3.up || c3.mask || c3.dyn_rows || c3.in_relu || c3.in != c2.out || c3.total_mtiles != c2.total_mtiles || c3.V != c2.V) return false;
     ConvGroup g; g.n = 2; g.blk0[0] = 0; g.p[0] = c2; g.p[1] = c3; g.p[0].exp_flags = 0;
@@ -755,6 +788,16 @@ bool launch_conv_p4(const ConvArgs& a_in, hipStream_t stream) {
         if (narrow_env && e1 > e2 && !a.dyn_rows) wide = false;
     }
     dim3 grid((unsigned)(p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)))), block(256);
+    if (a.gather) {      // gathered rows: the unrolled 1 x 1 / 3 x 3 kernels, BN (+ residual) epilogue
+        const int taps = p4_taps(a);
+        if (a.Cin == 4 || a.up || a.mask || a.in_relu || a.dyn_rows || a.row_map || (taps != 1 && taps != 9)) return false;
+        if (a.total_mtiles == 0) return true;
+#define P4_G(EPIV, TNV) { if (taps == 9) hipLaunchKernelGGL((conv_p4_kernel<EPIV, false, TNV, 9>), grid, block, pad_lds, stream, a); \
+                          else hipLaunchKernelGGL((conv_p4_kernel<EPIV, false, TNV, 1>), grid, block, pad_lds, stream, a); }
+        if (wide) { if (a.residual) P4_G(17, 2) else P4_G(16, 2) } else { if (a.residual) P4_G(17, 1) else P4_G(16, 1) }
+#undef P4_G
+        return true;
+    }
     if (a.Cin == 4) {
         if (a.residual || a.up || a.in_relu) return false;
         static const int stem_env = getenv("CALD_P4_UNROLL") ? atoi(getenv("CALD_P4_UNROLL")) : 1;

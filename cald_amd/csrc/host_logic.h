@@ -246,3 +246,106 @@ static inline float np_sum_f32(const float* a, int n) {
     return np_sum_f32(a, n2) + np_sum_f32(a + n2, n - n2);
 }
 
+
+// ---- cut_out view reuse (api.hip): the pixels of each backbone tensor that can differ from the reference view's ----
+// The cut_out view is the reference view with up to CALD_MAX_CUT rectangles filled, same size, same transform.  Every conv output is one
+// fixed k-ordered fma chain over its window, so an output whose window misses every filled input pixel has the reference's bits.  A set
+// is a union of rectangles (inclusive bounds), one per cutout rectangle, each carried through the layers on its own; supersets are safe
+// (a recomputed clean pixel gets the reference's bits again), so the resize step takes one extra source row / column on each side.
+#define CUT_SET_MAX 4
+struct CutRect { int x0, y0, x1, y1; };
+struct CutSet { int n; CutRect r[CUT_SET_MAX]; };
+static inline int cut_floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+// outputs o of a k-wide, stride-s, pad-p window that meet input span [a, b], clipped to [0, n - 1]; false if none
+static inline bool cut_span(int a, int b, int k, int s, int p, int n, int* lo, int* hi) {
+    int l = -cut_floor_div(-(a + p - k + 1), s), h = cut_floor_div(b + p, s);
+    if (l < 0) l = 0;
+    if (h > n - 1) h = n - 1;
+    *lo = l; *hi = h;
+    return l <= h;
+}
+static inline CutSet cut_map(const CutSet& in, int k, int s, int p, int Ho, int Wo) {
+    CutSet o; o.n = 0;
+    for (int i = 0; i < in.n; i++) {
+        CutRect r;
+        if (cut_span(in.r[i].x0, in.r[i].x1, k, s, p, Wo, &r.x0, &r.x1) && cut_span(in.r[i].y0, in.r[i].y1, k, s, p, Ho, &r.y0, &r.y1)) o.r[o.n++] = r;
+    }
+    return o;
+}
+// the input pixels a 3 x 3, stride-s, pad-1 conv reads to produce `out` (conv2's operand T1 = conv1's compute set)
+static inline CutSet cut_window(const CutSet& out, int s, int Hi, int Wi) {
+    CutSet o; o.n = 0;
+    for (int i = 0; i < out.n; i++) {
+        CutRect r = {out.r[i].x0 * s - 1, out.r[i].y0 * s - 1, out.r[i].x1 * s + 1, out.r[i].y1 * s + 1};
+        if (r.x0 < 0) r.x0 = 0; if (r.y0 < 0) r.y0 = 0;
+        if (r.x1 > Wi - 1) r.x1 = Wi - 1; if (r.y1 > Hi - 1) r.y1 = Hi - 1;
+        if (r.x0 <= r.x1 && r.y0 <= r.y1) o.r[o.n++] = r;
+    }
+    return o;
+}
+// resized pixels (preprocess_kernel) whose bilinear taps meet source span [a, b]: tap y0 = floor(max(sh (y + 0.5) - 0.5, 0)) and y0 + 1,
+// widened by one source index on each side against float / double rounding; padding (>= nr) is zeros in both views
+static inline bool cut_resize_span(int a, int b, int n_src, int nr, int* lo, int* hi) {
+    const double sc = (double)n_src / (double)nr;
+    int l = nr, h = -1;
+    for (int y = 0; y < nr; y++) {
+        double f = sc * ((double)y + 0.5) - 0.5; if (f < 0.0) f = 0.0;
+        const int t0 = (int)f;
+        if (t0 + 2 >= a && t0 - 1 <= b) { if (y < l) l = y; h = y; }
+    }
+    *lo = l; *hi = h;
+    return l <= h;
+}
+// nblk blocks (stride of conv2 each, levels from the pooled stem output at /4) -> per block the dirty set of its output (= what conv2,
+// conv3 and the downsample conv recompute) and conv1's compute set; *pool1 = the dirty set of the pooled stem output.  Level sizes are the
+// plan's (Hp >> l, Wp >> l).
+static inline void cut_geometry(int H, int W, int Hr, int Wr, int Hp, int Wp, int nrect, const int* rects, int nblk, const int* stride,
+                                CutSet* pool1, CutSet* out, CutSet* t1) {
+    CutSet s; s.n = 0;
+    for (int i = 0; i < nrect && i < CUT_SET_MAX; i++) {
+        const int* q = rects + 4 * i;           // source pixels [q0, q2) x [q1, q3)
+        if (q[2] <= q[0] || q[3] <= q[1]) continue;
+        CutRect r;
+        if (cut_resize_span(q[0], q[2] - 1, W, Wr, &r.x0, &r.x1) && cut_resize_span(q[1], q[3] - 1, H, Hr, &r.y0, &r.y1)) s.r[s.n++] = r;
+    }
+    s = cut_map(s, 7, 2, 3, Hp >> 1, Wp >> 1);         // stem 7 x 7 / 2
+    s = cut_map(s, 3, 2, 1, Hp >> 2, Wp >> 2);         // max-pool 3 x 3 / 2
+    *pool1 = s;
+    int l = 2;
+    for (int b = 0; b < nblk; b++) {
+        const int lo = l + (stride[b] == 2 ? 1 : 0);
+        out[b] = cut_map(s, 3, stride[b], 1, Hp >> lo, Wp >> lo);
+        t1[b] = cut_window(out[b], stride[b], Hp >> l, Wp >> l);
+        s = out[b]; l = lo;
+    }
+}
+// a set as disjoint rectangles, row bands top to bottom (a band's runs merged, a run that continues one of the band above extends it);
+// -1 if more than cap
+static inline int cut_disjoint(const CutSet& s, CutRect* o, int cap) {
+    int ys[2 * CUT_SET_MAX], ny = 0;
+    for (int i = 0; i < s.n; i++) { ys[ny++] = s.r[i].y0; ys[ny++] = s.r[i].y1 + 1; }
+    for (int i = 1; i < ny; i++) for (int j = i; j > 0 && ys[j] < ys[j - 1]; j--) { const int t = ys[j]; ys[j] = ys[j - 1]; ys[j - 1] = t; }
+    int n = 0;
+    for (int k = 0; k + 1 < ny; k++) {
+        const int ya = ys[k], yb = ys[k + 1] - 1;
+        if (ya > yb) continue;
+        int x0[CUT_SET_MAX], x1[CUT_SET_MAX], nx = 0;
+        for (int i = 0; i < s.n; i++)
+            if (s.r[i].y0 <= ya && s.r[i].y1 >= yb) { x0[nx] = s.r[i].x0; x1[nx] = s.r[i].x1; nx++; }
+        for (int i = 1; i < nx; i++) for (int j = i; j > 0 && x0[j] < x0[j - 1]; j--) {
+            int t = x0[j]; x0[j] = x0[j - 1]; x0[j - 1] = t; t = x1[j]; x1[j] = x1[j - 1]; x1[j - 1] = t;
+        }
+        for (int i = 0; i < nx;) {
+            const int a = x0[i];
+            int b = x1[i++];
+            while (i < nx && x0[i] <= b + 1) { if (x1[i] > b) b = x1[i]; i++; }
+            bool ext = false;
+            for (int q = 0; q < n && !ext; q++)
+                if (o[q].x0 == a && o[q].x1 == b && o[q].y1 == ya - 1) { o[q].y1 = yb; ext = true; }
+            if (ext) continue;
+            if (n == cap) return -1;
+            o[n++] = {a, ya, b, yb};
+        }
+    }
+    return n;
+}

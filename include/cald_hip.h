@@ -196,6 +196,12 @@ int cald_op_cls_corr(cald_ctx* ctx, int n, const float* scores, const int64_t* l
 int cald_op_pil_resize(cald_ctx* ctx, const uint8_t* src_dev, int H, int W, uint8_t* dst_dev, int oh, int ow);
 /* cald_helper.cutout rectangle selection (host side RNG = Python random seeded per image) */
 int cald_op_cutout_rects(uint64_t seed, int H, int W, int N, const float* boxes, int cut_num, int* rects_out, int* n_out);
+/* The cut_out view's dirty sets (host only; what cald_sweep's cut_out reuse recomputes).  H x W source image, detector sizes min_size /
+ * max_size, nrect cutout rectangles (left, top, right, bottom; right / bottom exclusive), nblk bottleneck blocks with the stride of each
+ * block's 3 x 3 conv, starting at the pooled stem output (/4).  out: (1 + nblk) x 2 sets of 17 ints {n, then n x (x0, y0, x1, y1),
+ * inclusive}: set 0 of entry 0 = the pooled stem output; entry 1 + b = block b's output (set 0) and the pixels its conv1 computes (set 1).
+ * A pixel outside a dirty set has the reference view's bits. */
+int cald_op_cutout_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out);
 /* one augmented view outside the sweep (helper API of cald/cald_helper.py; same kernels as inside cald_sweep).  A fresh
  * generator is seeded with `seed` (torch's CPU generator for GAUSS / SALT_PEPPER, Python's `random` for COLOR_SWAP).
  *   CALD_AUG_GAUSS        GaussianNoise :72-75    dst_dev = float [3][H][W], the additive term randn * param / 255
@@ -265,6 +271,13 @@ int cald_profile_prune(cald_ctx* ctx, double* lookahead_ms, double* lookahead_fl
                        double* pruned_flops);
 /* sweeps of this context that were repeated with the dense head (bound exceeded, or an activation outside the look-ahead's range) */
 int cald_profile_prune_fallbacks(cald_ctx* ctx, int64_t* n);
+/* cut_out reuse for one model: -1 = the process default (on unless CALD_CUTOUT_REUSE=0), 0 = off, 1 = on, 2 = on with every reused stage
+ * run dense over the retained tensors (test hook).  Returns the previous setting in *was. */
+int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was);
+/* cut_out reuse of the exact sweeps (CALD_CUTOUT_REUSE=0 disables it): per reused stage (layer1..layer3) the conv output rows the cut_out
+ * forwards computed and the rows the dense stages would have (summed over the stage's convs), the batches that reused the reference
+ * forward, and the batches whose cut_out views ran dense for want of retention memory.  Accumulated over the context's life. */
+int cald_profile_cutout(cald_ctx* ctx, double* rows3, double* dense_rows3, int64_t* batches, int64_t* fallbacks);
 /* mean proposals per view (R of SURVEY 8d) over the Faster R-CNN forwards profiled since cald_profile_enable */
 int cald_profile_roi_rows(cald_ctx* ctx, double* mean_rows_per_view, int64_t* views);
 /* per-launch CSV (shape, algorithmic GFLOP, ms, TFLOP/s) of the launches recorded since cald_profile_enable */
