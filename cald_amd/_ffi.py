@@ -65,6 +65,23 @@ class SweepCfg(C.Structure):
                 ("augs", AugSpec * MAX_AUGS)]
 
 
+PROBE_MAX_VIEWS = 8
+PROBE_MAX_RECTS = 8
+
+
+class ConvProbe(C.Structure):
+    """cald_conv_probe (include/cald_hip.h): one conv launch for cald_op_conv_probe."""
+    _fields_ = [("V", C.c_int), ("in_hw", (C.c_int * 2) * PROBE_MAX_VIEWS), ("up_hw", (C.c_int * 2) * PROBE_MAX_VIEWS),
+                ("dyn_rows", C.c_int * PROBE_MAX_VIEWS), ("has_dyn", C.c_int), ("gather", C.c_int), ("nrect", C.c_int * PROBE_MAX_VIEWS),
+                ("rect", ((C.c_int * 4) * PROBE_MAX_RECTS) * PROBE_MAX_VIEWS),
+                ("Cin", C.c_int), ("Cout", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad", C.c_int),
+                ("relu", C.c_int), ("in_relu", C.c_int), ("out_ld", C.c_int), ("cin_true", C.c_int),
+                ("weight", c_f), ("bias", c_f), ("bn_scale", c_f), ("bn_shift", c_f), ("in_", c_f), ("in16", C.POINTER(C.c_uint32)),
+                ("residual", c_f), ("up", c_f), ("ex16", C.c_int), ("mask", c_f), ("row_map", c_i),
+                ("out", c_f), ("out_n", C.c_int64), ("out16", C.POINTER(C.c_uint32)), ("out16_n", C.c_int64),
+                ("energy4", c_f), ("energy4_n", C.c_int64)]
+
+
 # name -> (restype, argtypes): must list every symbol of include/cald_hip.h
 SIGNATURES = {
     "cald_last_error": (C.c_char_p, []),
@@ -97,6 +114,7 @@ SIGNATURES = {
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),
     "cald_op_conv2d": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),
+    "cald_op_conv_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ConvProbe), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "cald_op_mfma_f16": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]),
     "cald_op_conv2d_f16x3": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),

@@ -302,20 +302,28 @@ extern "C" int cald_profile_dump(cald_ctx* c, const char* path) {
     return 0;
 }
 
-// conv launch with optional event bracketing
+// conv launch with optional event bracketing.  A launch no kernel takes is an error -- except the gathered rows of the certified RPN
+// pruning (row_map), which launch_conv skips loudly: the sweep's bound check then sends those views to the dense head.
+static int conv_refused(const ConvArgs& a) {
+    return fail(CALD_ERR_UNSUPPORTED, "no conv kernel implements this launch (Cin=%d Cout=%d k=%dx%d residual=%d up=%d mask=%d gather=%d energy4=%d out16=%d)",
+                a.Cin, a.Cout, a.KH, a.KW, a.residual != nullptr, a.up != nullptr, a.mask != nullptr, a.gather != nullptr, a.energy4 != nullptr,
+                a.out16 != nullptr);
+}
 static int run_conv(cald_ctx* c, const ConvArgs& a, double flops) {
+    const char* k;
     if (c->prof) {
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
         HIPCHK(hipEventRecord(e0, c->stream));
-        launch_conv(a, c->stream);
+        k = launch_conv(a, c->stream);
         HIPCHK(hipEventRecord(e1, c->stream));
         c->ev0.push_back(e0); c->ev1.push_back(e1); c->prof_flops += flops;
         char d[160]; snprintf(d, sizeof(d), "mt=%d,Cin=%d,Cout=%d,k=%dx%d,s=%d", a.total_mtiles, a.Cin, a.Cout, a.KH, a.KW, a.stride);
         c->prof_desc.push_back(d); c->prof_fl.push_back(flops); c->prof_tag.push_back(c->prof_tag_now);
     } else {
-        launch_conv(a, c->stream);
+        k = launch_conv(a, c->stream);
     }
+    if (!k && !a.row_map) return conv_refused(a);
     return 0;
 }
 
@@ -594,6 +602,47 @@ template <typename T> static int upload(cald_model* m, const std::vector<T>& h, 
 }
 // torch conv weight [Cout][Cin][KH][KW] (optionally several tensors concatenated along Cout)
 // -> K-major [Kpad][CoutPad], k = conv_k_index(kh*KW + kw, ci)
+// Every weight packing the conv kernels read, from torch conv weights [Cout_i][cin][kh][kw] of one or several tensors concatenated along
+// Cout (cin zero-padded to cinp):  w  K-major [Kpad][CoutPad], k = conv_k_index(kh*KW + kw, ci) (conv_mfma.hip);  w4 (conv_p4.hip) where
+// its kernels cover the shape;  wstem (conv_stem.hip) for the 7 x 7 / 2, 3 -> 64 stem;  w16 (conv_h3.hip / conv_h4.hip) when want16.
+// make_conv and cald_op_conv_probe share it, so the probe tests the product's own packing.
+struct ConvPack {
+    std::vector<float> w, w4, wstem;
+    std::vector<uint16_t> w16; float w16_unscale = 1.0f;
+    int Cout = 0, CoutPad = 0, K = 0, Kpad = 0;
+};
+static void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& couts, int cin, int cinp, int kh, int kw, int stride, int pad,
+                      bool want16, ConvPack* P) {
+    int cout = 0;
+    for (int c : couts) cout += c;
+    P->Cout = cout; P->CoutPad = cout_pad(cout); P->K = kh * kw * cinp; P->Kpad = round_up(P->K, 16);
+    const int CoutPad = P->CoutPad;
+    P->w.assign((size_t)P->Kpad * CoutPad, 0.0f);
+    int co0 = 0;
+    for (size_t i = 0; i < ts.size(); i++) {
+        for (int co = 0; co < couts[i]; co++)
+            for (int ci = 0; ci < cin; ci++)
+                for (int y = 0; y < kh; y++)
+                    for (int x = 0; x < kw; x++)
+                        P->w[(size_t)conv_k_index(y * kw + x, ci, kh * kw, cinp) * CoutPad + co0 + co] = ts[i][(((size_t)co * cin + ci) * kh + y) * kw + x];
+        co0 += couts[i];
+    }
+    const bool tiled = CoutPad % 64 == 0 && ((cinp % 16 == 0 && kh * kw <= 32) || cinp == 4);
+    P->w4.clear(); P->wstem.clear(); P->w16.clear(); P->w16_unscale = 1.0f;
+    if (tiled) P->w4 = pack_w4(P->w, P->Kpad, CoutPad);                                    // conv_p4.hip layout
+    if (kh == 7 && kw == 7 && cin == 3 && cinp == 4 && cout == 64 && stride == 2 && pad == 3 && ts.size() == 1) {   // conv_stem.hip layout
+        // chain slot S = 22 kh + f, f = 3 kw + c for f < 21, f = 21 a zero-weight slot; k-pair j = S >> 1 (77 pairs -> 20 quads), h = S & 1
+        P->wstem.assign((size_t)20 * 2 * 64 * 4, 0.0f);
+        for (int y = 0; y < 7; y++)
+            for (int f = 0; f < 21; f++) {
+                const int S = 22 * y + f, j = S >> 1, h = S & 1, q = j >> 2, e = j & 3, x = f / 3, ci = f % 3;
+                for (int co = 0; co < 64; co++)
+                    P->wstem[(((size_t)q * 2 + h) * 64 + co) * 4 + e] = ts[0][(((size_t)co * 3 + ci) * 7 + y) * 7 + x];
+            }
+    }
+    if (want16 && tiled) P->w16 = pack_w16(P->w, P->Kpad, CoutPad, &P->w16_unscale, kh, kw, cinp);   // conv_h3.hip layout
+}
+
 static int make_conv(cald_model* m, ConvLayer& L, const std::vector<std::string>& wkeys, const std::vector<std::string>& bkeys,
                      const std::string& bn_prefix, int stride, int pad, int cin_pad_to = 0, bool force16 = false) {
     std::vector<const HostTensor*> ws;
@@ -607,38 +656,18 @@ static int make_conv(cald_model* m, ConvLayer& L, const std::vector<std::string>
     }
     int cinp = cin_pad_to > cin ? cin_pad_to : cin;
     if (cinp % 4) return fail(CALD_ERR_INVALID, "Cin must be a multiple of 4");
-    L.Cin = cinp; L.CinTrue = cin; L.Cout = cout; L.CoutPad = cout_pad(cout); L.KH = kh; L.KW = kw; L.stride = stride; L.pad = pad;
-    L.K = kh * kw * cinp; L.Kpad = round_up(L.K, 16);
-    std::vector<float> w((size_t)L.Kpad * L.CoutPad, 0.0f);
-    int co0 = 0;
-    for (auto t : ws) {
-        int c0 = (int)t->shape[0];
-        for (int co = 0; co < c0; co++)
-            for (int ci = 0; ci < cin; ci++)
-                for (int y = 0; y < kh; y++)
-                    for (int x = 0; x < kw; x++)
-                        w[(size_t)conv_k_index(y * kw + x, ci, kh * kw, cinp) * L.CoutPad + co0 + co] = t->data[(((size_t)co * cin + ci) * kh + y) * kw + x];
-        co0 += c0;
-    }
-    int rc = upload(m, w, &L.w); if (rc) return rc;
-    if (L.CoutPad % 64 == 0 && ((L.Cin % 16 == 0 && kh * kw <= 32) || L.Cin == 4)) {   // conv_p4.hip layout
-        std::vector<float> w4 = pack_w4(w, L.Kpad, L.CoutPad);
-        if ((rc = upload(m, w4, &L.w4))) return rc;
-    }
-    if (kh == 7 && kw == 7 && cin == 3 && cinp == 4 && cout == 64 && stride == 2 && pad == 3 && ws.size() == 1) {   // conv_stem.hip layout
-        // chain slot S = 22 kh + f, f = 3 kw + c for f < 21, f = 21 a zero-weight slot; k-pair j = S >> 1 (77 pairs -> 20 quads), h = S & 1
-        std::vector<float> wsm((size_t)20 * 2 * 64 * 4, 0.0f);
-        for (int y = 0; y < 7; y++)
-            for (int f = 0; f < 21; f++) {
-                const int S = 22 * y + f, j = S >> 1, h = S & 1, q = j >> 2, e = j & 3, x = f / 3, ci = f % 3;
-                for (int co = 0; co < 64; co++)
-                    wsm[(((size_t)q * 2 + h) * 64 + co) * 4 + e] = ws[0]->data[(((size_t)co * 3 + ci) * 7 + y) * 7 + x];
-            }
-        if ((rc = upload(m, wsm, &L.wstem))) return rc;
-    }
-    if ((m->cfg.precision == CALD_PRECISION_F16X3 || force16) && L.CoutPad % 64 == 0 && ((L.Cin % 16 == 0 && kh * kw <= 32) || L.Cin == 4)) {   // conv_h3.hip layout
-        std::vector<uint16_t> w16 = pack_w16(w, L.Kpad, L.CoutPad, &L.w16_unscale, kh, kw, L.Cin);
-        if ((rc = upload(m, w16, &L.w16))) return rc;
+    std::vector<const float*> tp; std::vector<int> couts;
+    for (auto t : ws) { tp.push_back(t->data.data()); couts.push_back((int)t->shape[0]); }
+    ConvPack P;
+    pack_conv(tp, couts, cin, cinp, kh, kw, stride, pad, m->cfg.precision == CALD_PRECISION_F16X3 || force16, &P);
+    L.Cin = cinp; L.CinTrue = cin; L.Cout = cout; L.CoutPad = P.CoutPad; L.KH = kh; L.KW = kw; L.stride = stride; L.pad = pad;
+    L.K = P.K; L.Kpad = P.Kpad;
+    int rc = upload(m, P.w, &L.w); if (rc) return rc;
+    if (!P.w4.empty() && (rc = upload(m, P.w4, &L.w4))) return rc;
+    if (!P.wstem.empty() && (rc = upload(m, P.wstem, &L.wstem))) return rc;
+    if (!P.w16.empty()) {
+        L.w16_unscale = P.w16_unscale;
+        if ((rc = upload(m, P.w16, &L.w16))) return rc;
     }
     if (!bkeys.empty()) {
         std::vector<float> b(L.CoutPad, 0.0f); int o = 0;
@@ -935,6 +964,15 @@ struct FwdBufs {
     float* prune_look[2];        // capture mode only: the look-ahead's head map before select / scatter overwrite it
 };
 
+// conv_stem.hip wants every view's output to be an exact grid of 8 x 16 pixel blocks (padded sizes are multiples of 32); seg: host copy,
+// V + 1 entries
+static bool stem_grid_exact(const LevelSeg* seg, int V) {
+    for (int v = 0; v < V; v++) {
+        const LevelSeg& s = seg[v];
+        if (!(s.H % 8 == 0 && s.W % 16 == 0 && seg[v + 1].tile_start - s.tile_start == (s.H / 8) * (s.W / 16))) return false;
+    }
+    return true;
+}
 static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, const float* in, float* out, int lin, int lout, int V, bool relu,
                              const float* residual = nullptr, const float* up = nullptr, int lup = 0, const int* dyn = nullptr,
                              bool in_relu = false) {
@@ -978,15 +1016,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
             if (fo->second.fp32_dead) a.out = nullptr;
         }
     }
-    a.wstem = nullptr;
-    if (L.wstem) {       // conv_stem.hip wants every view's output to be an exact grid of 8 x 16 pixel blocks (padded sizes are multiples of 32)
-        bool exact = true;
-        for (int v = 0; v < V && exact; v++) {
-            const LevelSeg& s = m->plan.seg[lout][v];
-            exact = s.H % 8 == 0 && s.W % 16 == 0 && m->plan.seg[lout][v + 1].tile_start - s.tile_start == (s.H / 8) * (s.W / 16);
-        }
-        if (exact) a.wstem = L.wstem;
-    }
+    a.wstem = L.wstem && stem_grid_exact(m->plan.seg[lout], V) ? L.wstem : nullptr;
     return 2.0 * (double)level_pix(m->plan, lout, V) * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue);
 }
 static int conv_on(cald_model* m, const ConvLayer& L, const float* in, float* out, int lin, int lout, int V, bool relu,
@@ -999,7 +1029,6 @@ static int conv_on(cald_model* m, const ConvLayer& L, const float* in, float* ou
 }
 // Bottleneck conv2 (3 x 3) + conv3 (1 x 1 expand, + residual) of one block: ONE launch when conv_p4.hip's fused kernel covers the
 // shapes (the 64-channel blocks of layer 1, exact fp32 mode) -- the 64-channel tensor `mid` is then never written -- else two launches.
-bool launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t stream);   // conv_p4.hip
 static int conv_pair_on(cald_model* m, const ConvLayer& L2, const ConvLayer& L3, const float* in, float* mid, float* out, int lin, int lout,
                         int V, const float* residual) {
     cald_ctx* c = m->ctx;
@@ -1010,7 +1039,7 @@ static int conv_pair_on(cald_model* m, const ConvLayer& L2, const ConvLayer& L3,
         if (f2 < 0.0 || f3 < 0.0) return (int)(f2 < 0.0 ? f2 : f3);
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (c->prof) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, c->stream)); }
-        const bool done = launch_conv_p4_fused(a2, a3, c->stream);
+        const bool done = launch_conv_p4_fused(a2, a3, c->stream) != nullptr;
         if (done) {
             if (c->prof) {
                 HIPCHK(hipEventRecord(e1, c->stream));
@@ -1042,18 +1071,20 @@ static int conv_group_on(cald_model* m, const ConvSpec* sp, int n, int V) {
         flops += f; tiles += a[i].total_mtiles;
     }
     cald_ctx* c = m->ctx;
+    const char* names[CALD_MAX_GROUP];
     if (c->prof) {
         hipEvent_t e0, e1;
         HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
         HIPCHK(hipEventRecord(e0, c->stream));
-        c->prof_extra_launches += launch_conv_group(a, n, c->stream) - 1;
+        c->prof_extra_launches += launch_conv_group(a, n, c->stream, names) - 1;
         HIPCHK(hipEventRecord(e1, c->stream));
         c->ev0.push_back(e0); c->ev1.push_back(e1); c->prof_flops += flops;
         char d[160]; snprintf(d, sizeof(d), "mt=%d,Cin=%d,Cout=%d,k=%dx%d,s=%d,group=%d", tiles, a[0].Cin, a[0].Cout, a[0].KH, a[0].KW, a[0].stride, n);
         c->prof_desc.push_back(d); c->prof_fl.push_back(flops); c->prof_tag.push_back(c->prof_tag_now);
     } else {
-        launch_conv_group(a, n, c->stream);
+        launch_conv_group(a, n, c->stream, names);
     }
+    for (int i = 0; i < n; i++) if (!names[i] && !a[i].row_map) return conv_refused(a[i]);
     return 0;
 }
 
@@ -1511,13 +1542,11 @@ static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, 
     if (Cin % 4) return fail(CALD_ERR_INVALID, "Cin must be a multiple of 4");
     HIPCHK(hipSetDevice(c->device));
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const int CoutPad = cout_pad(Cout), K = KH * KW * Cin, Kpad = round_up(K, 16);
-    std::vector<float> w((size_t)Kpad * CoutPad, 0.0f), b(CoutPad, 0.0f), sc(CoutPad, 0.0f), sh(CoutPad, 0.0f);
-    for (int co = 0; co < Cout; co++)
-        for (int ci = 0; ci < Cin; ci++)
-            for (int y = 0; y < KH; y++)
-                for (int x = 0; x < KW; x++)
-                    w[(size_t)conv_k_index(y * KW + x, ci, KH * KW, Cin) * CoutPad + co] = weight[(((size_t)co * Cin + ci) * KH + y) * KW + x];
+    ConvPack pk;
+    pack_conv({weight}, {Cout}, Cin, Cin, KH, KW, stride, pad, precision == CALD_PRECISION_F16X3, &pk);
+    const int CoutPad = pk.CoutPad, Kpad = pk.Kpad;
+    const std::vector<float>& w = pk.w;
+    std::vector<float> b(CoutPad, 0.0f), sc(CoutPad, 0.0f), sh(CoutPad, 0.0f);
     for (int i = 0; i < Cout; i++) { if (bias) b[i] = bias[i]; if (bn_scale) { sc[i] = bn_scale[i]; sh[i] = bn_shift[i]; } }
     BatchPlan P; memset(&P, 0, sizeof(P));
     P.seg[0][0].H = H; P.seg[0][0].W = W; P.seg[0][1].pix_off = (long long)H * W; P.seg[0][1].tile_start = (H * W + 127) / 128;
@@ -1530,16 +1559,14 @@ static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, 
     HIPCHK(hipMemcpy(d_in, in, (size_t)H * W * Cin * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
     float* d_w4 = nullptr;
-    if (CoutPad % 64 == 0 && ((Cin % 16 == 0 && KH * KW <= 32) || Cin == 4)) {
-        std::vector<float> w4 = pack_w4(w, Kpad, CoutPad);
-        HIPCHK(hipMalloc((void**)&d_w4, w4.size() * 4));
-        HIPCHK(hipMemcpy(d_w4, w4.data(), w4.size() * 4, hipMemcpyHostToDevice));
+    if (!pk.w4.empty()) {
+        HIPCHK(hipMalloc((void**)&d_w4, pk.w4.size() * 4));
+        HIPCHK(hipMemcpy(d_w4, pk.w4.data(), pk.w4.size() * 4, hipMemcpyHostToDevice));
     }
-    uint16_t* d_w16 = nullptr; float w16_unscale = 1.0f;
-    if (precision == CALD_PRECISION_F16X3 && CoutPad % 64 == 0 && ((Cin % 16 == 0 && KH * KW <= 32) || Cin == 4)) {
-        std::vector<uint16_t> w16 = pack_w16(w, Kpad, CoutPad, &w16_unscale, KH, KW, Cin);
-        HIPCHK(hipMalloc((void**)&d_w16, w16.size() * 2));
-        HIPCHK(hipMemcpy(d_w16, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
+    uint16_t* d_w16 = nullptr; const float w16_unscale = pk.w16_unscale;
+    if (!pk.w16.empty()) {
+        HIPCHK(hipMalloc((void**)&d_w16, pk.w16.size() * 2));
+        HIPCHK(hipMemcpy(d_w16, pk.w16.data(), pk.w16.size() * 2, hipMemcpyHostToDevice));
     }
     HIPCHK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_sc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
@@ -1551,19 +1578,136 @@ static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, 
     a.residual = d_res; a.up = nullptr; a.seg_in = d_p->seg[0]; a.seg_out = d_p->seg[1]; a.seg_up = d_p->seg[1]; a.dyn_rows = nullptr;
     a.V = 1; a.Cin = Cin; a.Cout = Cout; a.CoutPad = CoutPad; a.Kpad = Kpad; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
     a.relu = relu; a.total_mtiles = (Ho * Wo + 127) / 128; a.out_ld = Cout; a.in_relu = 0; a.zeros = c->d_zeros;
-    launch_conv(a, c->stream);
+    const bool launched = launch_conv(a, c->stream) != nullptr;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, d_out, (size_t)Ho * Wo * Cout * 4, hipMemcpyDeviceToHost));
     if (d_w4) hipFree(d_w4);
     if (d_w16) hipFree(d_w16);
     hipFree(d_in); hipFree(d_out); hipFree(d_w); hipFree(d_b); hipFree(d_sc); hipFree(d_sh); hipFree(d_p); if (d_res) hipFree(d_res);
-    return 0;
+    return launched ? 0 : conv_refused(a);
 }
 extern "C" int cald_op_conv2d(cald_ctx* c, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
                               int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
                               const float* residual, int relu, float* out) {
     return op_conv2d(c, CALD_PRECISION_FP32, in, H, W, Cin, weight, Cout, KH, KW, stride, pad, bias, bn_scale, bn_shift, residual, relu, out);
+}
+// ---------------------------------------------------------------------------------------------
+// test-only conv probe (tests/test_gpu_conv_variants.py): one launch of the product's launchers on a ragged batch the caller describes,
+// under a forced kernel choice, with the product's own weight packing.  Output buffers are the caller's, copied whole to the device and
+// back, so whatever the caller put beyond the rows / channels a kernel may write (its guard words) comes back for inspection.
+// ---------------------------------------------------------------------------------------------
+extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* pr, int n, int path, int tile, char* kernel, int kernel_cap) {
+    if (!c || !pr || n < 1 || n > CALD_MAX_GROUP || !kernel || kernel_cap < 1) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: bad arguments");
+    if (path < CONV_AUTO || path > CONV_H4_GROUP || tile < TILE_AUTO || tile > TILE_WIDE) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: bad path / tile");
+    if (path == CONV_P4_FUSED && n != 2) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: the fused mode takes two problems (conv2, conv3)");
+    HIPCHK(hipSetDevice(c->device));
+    kernel[0] = 0;
+    ScopedDev sd(c->stream);
+    ConvArgs a[CALD_MAX_GROUP];
+    struct Back { void* dev; void* host; size_t bytes; };
+    std::vector<Back> back;
+    int rc;
+    auto up = [&](const void* h, size_t bytes, void** d) -> int {       // device copy of a host array (null stays null)
+        *d = nullptr;
+        if (!h) return 0;
+        if ((rc = sd.alloc(d, bytes))) return rc;
+        HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    for (int i = 0; i < n; i++) {
+        const cald_conv_probe& p = pr[i];
+        if (p.V < 1 || p.V > CALD_PROBE_MAX_VIEWS || p.Cin < 4 || p.Cin % 4 || p.Cout < 1 || p.KH < 1 || p.KW < 1 || p.stride < 1 || p.pad < 0 ||
+            p.out_ld < p.Cout || !p.weight || !p.in)
+            return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: bad layer", i);
+        // geometry: level 0 input, 1 output, 2 the coarser level of `up`
+        std::vector<LevelSeg> seg(3 * (CALD_PROBE_MAX_VIEWS + 1));
+        memset(seg.data(), 0, seg.size() * sizeof(LevelSeg));
+        LevelSeg* si = &seg[0]; LevelSeg* so = &seg[CALD_PROBE_MAX_VIEWS + 1]; LevelSeg* su = &seg[2 * (CALD_PROBE_MAX_VIEWS + 1)];
+        std::vector<GatherSet> gs(p.V);
+        long long rows_out = 0;
+        for (int v = 0; v < p.V; v++) {
+            const int H = p.in_hw[v][0], W = p.in_hw[v][1];
+            if (H < 0 || W < 0) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: negative view size");
+            const int Ho = H && W ? (H + 2 * p.pad - p.KH) / p.stride + 1 : 0, Wo = H && W ? (W + 2 * p.pad - p.KW) / p.stride + 1 : 0;
+            if (Ho < 0 || Wo < 0 || (H && W && (Ho < 1 || Wo < 1))) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: view %d smaller than the filter", v);
+            si[v].H = H; si[v].W = W; so[v].H = Ho; so[v].W = Wo; su[v].H = p.up_hw[v][0]; su[v].W = p.up_hw[v][1];
+            long long m = (long long)Ho * Wo;
+            if (p.gather) {
+                GatherSet& g = gs[v]; memset(&g, 0, sizeof(g));
+                if (p.nrect[v] < 0 || p.nrect[v] > CALD_GATHER_RECTS) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: 0..%d rectangles", CALD_GATHER_RECTS);
+                g.nr = p.nrect[v];
+                for (int k = 0; k < g.nr; k++) {
+                    const int* r = p.rect[v][k];
+                    if (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || r[0] + r[2] > Wo || r[1] + r[3] > Ho)
+                        return fail(CALD_ERR_INVALID, "cald_op_conv_probe: rectangle outside view %d", v);
+                    g.x0[k] = r[0]; g.y0[k] = r[1]; g.w[k] = r[2]; g.cum[k + 1] = g.cum[k] + r[2] * r[3];
+                }
+                m = g.cum[g.nr];
+            }
+            si[v + 1].pix_off = si[v].pix_off + (long long)H * W;
+            so[v + 1].pix_off = so[v].pix_off + (long long)Ho * Wo;
+            su[v + 1].pix_off = su[v].pix_off + (long long)su[v].H * su[v].W;
+            so[v + 1].tile_start = so[v].tile_start + (int)((m + 127) / 128);
+            si[v + 1].tile_start = si[v].tile_start + (H * W + 127) / 128;
+            rows_out = so[v + 1].pix_off;
+        }
+        const long long pix_in = si[p.V].pix_off, pix_up = su[p.V].pix_off;
+        if ((p.out && p.out_n < rows_out * p.out_ld) || (p.out16 && p.out16_n < rows_out * p.out_ld) || (p.energy4 && p.energy4_n < rows_out * 4))
+            return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: an output buffer is smaller than the output", i);
+        ConvPack pk;
+        const int cin_true = p.cin_true > 0 ? p.cin_true : p.Cin;
+        if (cin_true > p.Cin) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: cin_true > Cin");
+        pack_conv({p.weight}, {p.Cout}, cin_true, p.Cin, p.KH, p.KW, p.stride, p.pad, precision == CALD_PRECISION_F16X3, &pk);
+        std::vector<float> vb(pk.CoutPad, 0.0f), vs(pk.CoutPad, 0.0f), vh(pk.CoutPad, 0.0f);
+        for (int k = 0; k < p.Cout; k++) { if (p.bias) vb[k] = p.bias[k]; if (p.bn_scale) { vs[k] = p.bn_scale[k]; vh[k] = p.bn_shift[k]; } }
+        ConvArgs& A = a[i]; memset(&A, 0, sizeof(A));
+        void* d;
+        const size_t out_b = (size_t)p.out_ld * 4;
+        if ((rc = up(pk.w.data(), pk.w.size() * 4, &d))) return rc; A.w = (const float*)d;
+        if ((rc = up(pk.w4.empty() ? nullptr : pk.w4.data(), pk.w4.size() * 4, &d))) return rc; A.w4 = (const float*)d;
+        if ((rc = up(pk.w16.empty() ? nullptr : pk.w16.data(), pk.w16.size() * 2, &d))) return rc; A.w16 = d; A.w16_unscale = pk.w16_unscale;
+        if ((rc = up(pk.wstem.empty() || !stem_grid_exact(so, p.V) ? nullptr : pk.wstem.data(), pk.wstem.size() * 4, &d))) return rc; A.wstem = (const float*)d;
+        if ((rc = up(p.bias ? vb.data() : nullptr, vb.size() * 4, &d))) return rc; A.bias = (const float*)d;
+        if ((rc = up(p.bn_scale ? vs.data() : nullptr, vs.size() * 4, &d))) return rc; A.scale = (const float*)d;
+        if ((rc = up(p.bn_scale ? vh.data() : nullptr, vh.size() * 4, &d))) return rc; A.shift = (const float*)d;
+        if ((rc = up(p.in, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in = (const float*)d;
+        if ((rc = up(p.in16, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in16 = (const unsigned*)d;
+        if ((rc = up(p.residual, (size_t)rows_out * out_b, &d))) return rc; A.residual = (const float*)d;
+        if ((rc = up(p.up, (size_t)pix_up * out_b, &d))) return rc; A.up = (const float*)d;
+        if ((rc = up(p.mask, (size_t)rows_out * out_b, &d))) return rc; A.mask = (const float*)d;
+        if ((rc = up(p.row_map, (size_t)rows_out * 4, &d))) return rc; A.row_map = (const int*)d;
+        if ((rc = up(p.has_dyn ? p.dyn_rows : nullptr, (size_t)p.V * 4, &d))) return rc; A.dyn_rows = (const int*)d;
+        if ((rc = up(p.gather ? gs.data() : nullptr, gs.size() * sizeof(GatherSet), &d))) return rc; A.gather = (const GatherSet*)d;
+        if ((rc = up(seg.data(), seg.size() * sizeof(LevelSeg), &d))) return rc;
+        A.seg_in = (const LevelSeg*)d; A.seg_out = A.seg_in + CALD_PROBE_MAX_VIEWS + 1; A.seg_up = A.seg_in + 2 * (CALD_PROBE_MAX_VIEWS + 1);
+        if ((rc = up(p.out, (size_t)p.out_n * 4, &d))) return rc; A.out = (float*)d;
+        if (p.out) back.push_back({d, p.out, (size_t)p.out_n * 4});
+        if ((rc = up(p.out16, (size_t)p.out16_n * 4, &d))) return rc; A.out16 = (unsigned*)d;
+        if (p.out16) back.push_back({d, p.out16, (size_t)p.out16_n * 4});
+        if ((rc = up(p.energy4, (size_t)p.energy4_n * 4, &d))) return rc; A.energy4 = (float*)d;
+        if (p.energy4) back.push_back({d, p.energy4, (size_t)p.energy4_n * 4});
+        A.ex16 = p.ex16 ? 1 : 0;
+        A.V = p.V; A.Cin = p.Cin; A.Cout = p.Cout; A.CoutPad = pk.CoutPad; A.Kpad = pk.Kpad;
+        A.KH = p.KH; A.KW = p.KW; A.stride = p.stride; A.pad = p.pad; A.relu = p.relu ? 1 : 0; A.in_relu = p.in_relu ? 1 : 0;
+        A.total_mtiles = so[p.V].tile_start; A.out_ld = p.out_ld; A.zeros = c->d_zeros;
+    }
+    if (path == CONV_P4_FUSED) a[1].in = a[0].out;       // conv3 reads conv2's output (which the fused kernel keeps on chip)
+    const ConvForce f{path, tile};
+    const char* names[CALD_MAX_GROUP] = {nullptr};
+    if (path == CONV_P4_FUSED) names[0] = names[1] = launch_conv_p4_fused(a[0], a[1], c->stream);
+    else if (n > 1 || path == CONV_P4_GROUP || path == CONV_H3_GROUP || path == CONV_H4_GROUP) launch_conv_group(a, n, c->stream, names, f);
+    else names[0] = launch_conv(a[0], c->stream, f);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::string all;
+    for (int i = 0; i < n; i++) {
+        if (!names[i]) return fail(CALD_ERR_UNSUPPORTED, "cald_op_conv_probe: problem %d refused under path %d tile %d", i, path, tile);
+        if (all.find(names[i]) == std::string::npos) { if (!all.empty()) all += ";"; all += names[i]; }
+    }
+    for (const Back& b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    snprintf(kernel, (size_t)kernel_cap, "%s", all.c_str());
+    return 0;
 }
 void launch_mfma_f16_probe(const unsigned short* A, const unsigned short* B, const unsigned* C, unsigned* D, long long n, hipStream_t stream);   // conv_h3.hip
 extern "C" int cald_op_mfma_f16(cald_ctx* c, const uint16_t* A, const uint16_t* B, const uint32_t* C, uint32_t* D, int64_t n) {

@@ -275,6 +275,25 @@ template <typename K> static inline void allow_big_lds(PerDeviceOnce& once, K ke
 // ---------------------------------------------------------------------------------------------
 // kernel launchers (implemented in the .hip files; all asynchronous on `stream`)
 // ---------------------------------------------------------------------------------------------
-void launch_conv(const ConvArgs& a, hipStream_t stream);
-// all problems in one launch when they qualify for the same tiled kernel variant, else one launch each
-int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream);   // returns the number of kernel launches issued
+// Kernel choice of one launch, host side only (never a kernel argument): AUTO is the product's selection; anything else pins the
+// launcher to one family / tile width (cald_op_conv_probe) -- a pinned launcher that cannot take the problem refuses it instead of
+// handing it to another kernel.
+enum ConvPath { CONV_AUTO = 0, CONV_P4, CONV_P4_GROUP, CONV_P4_FUSED, CONV_GENERIC, CONV_STEM, CONV_H3, CONV_H3_GROUP, CONV_H4, CONV_H4_GROUP };
+enum ConvTile { TILE_AUTO = 0, TILE_NARROW, TILE_WIDE };
+struct ConvForce { int path = CONV_AUTO; int tile = TILE_AUTO; };
+
+// The launchers return the name of the kernel instantiation they launched, or nullptr when they refused the problem (a feature of
+// ConvArgs they do not implement, a shape they do not cover, or a pin they cannot honour).
+const char* launch_conv(const ConvArgs& a, hipStream_t stream, ConvForce f = ConvForce());
+// all problems in one launch when they qualify for the same tiled kernel variant, else one launch each; returns the number of kernel
+// launches issued.  names (optional, n entries): the kernel of each problem, nullptr where it was refused.
+int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream, const char** names = nullptr, ConvForce f = ConvForce());
+const char* launch_conv_p4(const ConvArgs& a, hipStream_t stream, ConvForce f = ConvForce());        // conv_p4.hip
+const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, ConvForce f = ConvForce());
+const char* launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t stream);
+const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream);                              // conv_mfma.hip
+const char* launch_conv_stem(const ConvArgs& a, hipStream_t stream);                                 // conv_stem.hip
+const char* launch_conv_h3(const ConvArgs& a, hipStream_t stream);                                   // conv_h3.hip
+const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream);
+const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced = false);              // conv_h4.hip
+const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced = false);

@@ -251,45 +251,51 @@ __global__ __launch_bounds__(256, 3) void conv_h3_group_kernel(const ConvGroup g
     conv_h3_body<EPI, TN, C4>(g.p[i], (int)blockIdx.x - g.blk0[i]);
 }
 
-bool launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream) {
-    if (n < 1 || n > CALD_MAX_GROUP) return false;
+// features no conv_h3 kernel implements: the training mask, gathered rows (row_map / gather), the pruning's energy, residual AND top-down
+static inline bool h3_refuses(const ConvArgs& a) {
+    return !a.w16 || a.CoutPad % 64 != 0 || (a.in16 && a.in_relu) || a.mask || a.gather || a.row_map || a.energy4 || (a.residual && a.up) ||
+           (!a.out && !a.out16);
+}
+template <int EPI, int TN, bool C4>
+static const char* h3_go(const dim3 grid, hipStream_t stream, const ConvArgs& a, const char* name) {
+    hipLaunchKernelGGL((conv_h3_kernel<EPI, TN, C4>), grid, dim3(256), 0, stream, a);
+    return name;
+}
+#define H3_GO(EPI, TN, C4) h3_go<EPI, TN, C4>(grid, stream, a, "conv_h3_kernel<" #EPI "," #TN "," #C4 ">")
+
+const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream) {
+    if (n < 1 || n > CALD_MAX_GROUP) return nullptr;
     const bool wide = p[0].CoutPad % 128 == 0;
     ConvGroup g; g.n = n; int blk = 0;
     for (int i = 0; i < n; i++) {
         const ConvArgs& a = p[i];
-        if (!a.w16 || a.CoutPad % 64 != 0 || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return false;
+        if (h3_refuses(a) || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return nullptr;
         g.blk0[i] = blk; blk += a.total_mtiles * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a;
     }
     g.blk0[n] = blk;
-    if (wide) hipLaunchKernelGGL((conv_h3_group_kernel<0, 2, false>), dim3((unsigned)blk), dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL((conv_h3_group_kernel<0, 1, false>), dim3((unsigned)blk), dim3(256), 0, stream, g);
-    return true;
+    if (wide) { hipLaunchKernelGGL((conv_h3_group_kernel<0, 2, false>), dim3((unsigned)blk), dim3(256), 0, stream, g); return "conv_h3_group_kernel<0,2,false>"; }
+    hipLaunchKernelGGL((conv_h3_group_kernel<0, 1, false>), dim3((unsigned)blk), dim3(256), 0, stream, g);
+    return "conv_h3_group_kernel<0,1,false>";
 }
 
-// returns true if this variant handled the launch
-bool launch_conv_h3(const ConvArgs& a, hipStream_t stream) {
-    if (!a.w16 || a.CoutPad % 64 != 0 || (a.in16 && a.in_relu)) return false;
-    dim3 block(256);
-    if (a.Cin == 4) {      // stem conv (7 x 7, NHWC4 input): per-thread taps
-        if (a.residual || a.up || a.in_relu) return false;
-        if (a.CoutPad % 128 == 0) hipLaunchKernelGGL((conv_h3_kernel<0, 2, true>), dim3((unsigned)(a.total_mtiles * (a.CoutPad / 128))), block, 0, stream, a);
-        else hipLaunchKernelGGL((conv_h3_kernel<0, 1, true>), dim3((unsigned)(a.total_mtiles * (a.CoutPad / 64))), block, 0, stream, a);
-        return true;
+// the kernel if this variant handled the launch, else nullptr
+const char* launch_conv_h3(const ConvArgs& a, hipStream_t stream) {
+    if (h3_refuses(a)) return nullptr;
+    if (a.Cin == 4) {      // stem conv (7 x 7, NHWC4 input): per-thread taps, fp32 input only
+        if (a.residual || a.up || a.in_relu || !a.in) return nullptr;
+        if (a.CoutPad % 128 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128))); return H3_GO(0, 2, true); }
+        const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64)));
+        return H3_GO(0, 1, true);
     }
-    if (a.Cin % 16 != 0 || a.KH * a.KW > 32) return false;
+    if (a.Cin % 16 != 0 || a.KH * a.KW > 32) return nullptr;
     if (a.CoutPad % 128 == 0) {
-        dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128)));
-        if (a.residual) hipLaunchKernelGGL((conv_h3_kernel<1, 2, false>), grid, block, 0, stream, a);
-        else if (a.up) hipLaunchKernelGGL((conv_h3_kernel<2, 2, false>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv_h3_kernel<0, 2, false>), grid, block, 0, stream, a);
-    } else {
-        dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64)));
-        if (a.residual) hipLaunchKernelGGL((conv_h3_kernel<1, 1, false>), grid, block, 0, stream, a);
-        else if (a.up) hipLaunchKernelGGL((conv_h3_kernel<2, 1, false>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((conv_h3_kernel<0, 1, false>), grid, block, 0, stream, a);
+        const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128)));
+        return a.residual ? H3_GO(1, 2, false) : a.up ? H3_GO(2, 2, false) : H3_GO(0, 2, false);
     }
-    return true;
+    const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64)));
+    return a.residual ? H3_GO(1, 1, false) : a.up ? H3_GO(2, 1, false) : H3_GO(0, 1, false);
 }
+#undef H3_GO
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // cald_op_mfma_f16: the instruction itself on caller-supplied operands (parity hook for oracle/mfma_f16_model.h).  One wave evaluates 32

@@ -273,37 +273,40 @@ __global__ __launch_bounds__(512, 2) void conv_h4_group_kernel(const ConvGroup g
 }
 
 static bool h4_covers(const ConvArgs& a) {
-    return a.w16 && a.in16 && !a.in_relu && a.CoutPad % 256 == 0 && a.Cin % 16 == 0 && a.KH * a.KW <= 32 && !a.mask && !(a.residual && a.up);
+    return a.w16 && a.in16 && !a.in_relu && a.CoutPad % 256 == 0 && a.Cin % 16 == 0 && a.KH * a.KW <= 32 && !a.mask && !(a.residual && a.up) &&
+           !a.gather && !a.row_map && !a.energy4 && (a.out || a.out16);
 }
 static int h4_mode() { static const int mode = getenv("CALD_H4") ? atoi(getenv("CALD_H4")) : 1; return mode; }   // 0: off, 1: where it fills the chip, 2: wherever it fits
 static PerDeviceOnce h4_once[4];
-// true if this kernel took the launch
-bool launch_conv_h4(const ConvArgs& a, hipStream_t stream) {
-    if (!h4_mode() || !h4_covers(a)) return false;
+// the kernel if it took the launch, else nullptr.  forced: wherever it is correct (cald_op_conv_probe), not only where it pays
+const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced) {
+    if (!(forced || h4_mode()) || !h4_covers(a)) return nullptr;
     const int wgs = ((a.total_mtiles + 1) >> 1) * (a.CoutPad >> 8);
     // where it pays, measured per layer class on BASELINE configs[4] with CALD_H4=2 against CALD_H4=0 (profiles/r4_h4_everywhere_vs_default.txt):
     // every class with K >= 1024 and at least two rounds of one workgroup per CU gains 4-9 % (3 x 3 layers of >= 256 channels, the
     // 1024 -> 256 / 2048 -> 512 reduce layers, fc6, the predictor); short chains (K <= 512: the expand layers with their residual
     // epilogue, the laterals) lose 10-30 % -- they want several residents per CU to hide prologue / epilogue phases (conv_h3)
-    if (h4_mode() == 1 && (a.Kpad < 1024 || wgs < 512)) return false;
+    if (!forced && h4_mode() == 1 && (a.Kpad < 1024 || wgs < 512)) return nullptr;
+    if (wgs == 0) return "none (no output tiles)";
     const dim3 grid((unsigned)wgs), block(512);
     const size_t lds = (size_t)H4_NSTAGE * H4_STAGE;
-    if (a.residual) { allow_big_lds(h4_once[1], conv_h4_kernel<1>); hipLaunchKernelGGL((conv_h4_kernel<1>), grid, block, lds, stream, a); }
-    else if (a.up) { allow_big_lds(h4_once[2], conv_h4_kernel<2>); hipLaunchKernelGGL((conv_h4_kernel<2>), grid, block, lds, stream, a); }
-    else { allow_big_lds(h4_once[0], conv_h4_kernel<0>); hipLaunchKernelGGL((conv_h4_kernel<0>), grid, block, lds, stream, a); }
-    return true;
+    if (a.residual) { allow_big_lds(h4_once[1], conv_h4_kernel<1>); hipLaunchKernelGGL((conv_h4_kernel<1>), grid, block, lds, stream, a); return "conv_h4_kernel<1>"; }
+    if (a.up) { allow_big_lds(h4_once[2], conv_h4_kernel<2>); hipLaunchKernelGGL((conv_h4_kernel<2>), grid, block, lds, stream, a); return "conv_h4_kernel<2>"; }
+    allow_big_lds(h4_once[0], conv_h4_kernel<0>); hipLaunchKernelGGL((conv_h4_kernel<0>), grid, block, lds, stream, a);
+    return "conv_h4_kernel<0>";
 }
-bool launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream) {
-    if (!h4_mode() || n < 1 || n > CALD_MAX_GROUP) return false;
+const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced) {
+    if (!(forced || h4_mode()) || n < 1 || n > CALD_MAX_GROUP) return nullptr;
     ConvGroup g; g.n = n; int blk = 0;
     for (int i = 0; i < n; i++) {
-        if (!h4_covers(p[i]) || p[i].residual || p[i].up) return false;
+        if (!h4_covers(p[i]) || p[i].residual || p[i].up) return nullptr;
         g.blk0[i] = blk; g.p[i] = p[i];
         blk += (((p[i].total_mtiles + 1) >> 1) * (p[i].CoutPad >> 8) + 7) & ~7;
     }
     g.blk0[n] = blk;
-    if (h4_mode() == 1 && (blk < 512 || p[0].Kpad < 1024)) return false;
+    if (!forced && h4_mode() == 1 && (blk < 512 || p[0].Kpad < 1024)) return nullptr;
+    if (blk == 0) return "none (no output tiles)";
     allow_big_lds(h4_once[3], conv_h4_group_kernel);
     hipLaunchKernelGGL(conv_h4_group_kernel, dim3((unsigned)blk), dim3(512), (size_t)H4_NSTAGE * H4_STAGE, stream, g);
-    return true;
+    return "conv_h4_group_kernel";
 }

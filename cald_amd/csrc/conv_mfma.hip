@@ -268,55 +268,85 @@ static int conv_env(const char* name, int dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) : dflt;
 }
-template <int WM, int WN, int TM, int TN, int BK>
-static void launch_cfg(const ConvArgs& a, int bn, hipStream_t stream) {
-    dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / bn))), block(256);
-    static const int dl = conv_env("CALD_CONV_DYNLDS", 0);   // extra dynamic LDS (experiments): caps workgroups per CU
-    const bool fast = (a.Cin % BK == 0) && (a.KH * a.KW <= 32);
-    if (!fast) { hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, 0, BK, false>), grid, block, dl, stream, a); return; }
-    if (a.residual) hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, 1, BK, true>), grid, block, dl, stream, a);
-    else if (a.up) hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, 2, BK, true>), grid, block, dl, stream, a);
-    else hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, 0, BK, true>), grid, block, dl, stream, a);
+template <int WM, int WN, int TM, int TN, int EPI, bool FAST>
+static const char* cfg_go(const ConvArgs& a, const dim3 grid, const int dl, hipStream_t stream, const char* name) {
+    hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, EPI, 16, FAST>), grid, dim3(256), dl, stream, a);
+    return name;
 }
+#define CFG_NAME(WM, WN, TM, TN, EPI, FAST) "conv_mfma_f32_kernel<" #WM "," #WN "," #TM "," #TN "," #EPI ",16," #FAST ">"
+#define CFG_GO(WM, WN, TM, TN, EPI, FAST) cfg_go<WM, WN, TM, TN, EPI, FAST>(a, grid, dl, stream, CFG_NAME(WM, WN, TM, TN, EPI, FAST))
+// one tile configuration: the fast path (a k-tile inside one tap: Cin % 16 == 0, at most 32 taps) or the general one, each with the
+// plain / residual / top-down epilogue (the epilogue does not depend on the k-loop variant)
+#define CFG_EPI(WM, WN, TM, TN, FAST) (a.residual ? CFG_GO(WM, WN, TM, TN, 1, FAST) : a.up ? CFG_GO(WM, WN, TM, TN, 2, FAST) : CFG_GO(WM, WN, TM, TN, 0, FAST))
+#define CFG_LAUNCH(WM, WN, TM, TN) (fast ? CFG_EPI(WM, WN, TM, TN, true) : CFG_EPI(WM, WN, TM, TN, false))
 
-bool launch_conv_p4(const ConvArgs& a, hipStream_t stream);   // conv_p4.hip
-bool launch_conv_stem(const ConvArgs& a, hipStream_t stream); // conv_stem.hip (only when a.wstem is set)
-bool launch_conv_h3(const ConvArgs& a, hipStream_t stream);   // conv_h3.hip (opt-in split-fp16 mode: only when a.w16 is set)
+// the generic kernel: any Cin % 4 == 0, any filter, Cout tiled by 32 / 64 / 128; bias, FrozenBN, residual OR top-down, ReLU, in_relu,
+// dyn_rows, out_ld.  Refuses what it does not implement.
+const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream) {
+    if (!a.w || !a.out || !a.zeros || a.Cin % 4 != 0 || (a.residual && a.up)) return nullptr;
+    if (a.mask || a.gather || a.row_map || a.energy4 || a.out16 || a.in16 || a.ex16) return nullptr;
+    static const int dl = conv_env("CALD_CONV_DYNLDS", 0);   // extra dynamic LDS (experiments): caps workgroups per CU
+    const bool fast = (a.Cin % 16 == 0) && (a.KH * a.KW <= 32);
+    if (a.CoutPad % 128 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128))); return CFG_LAUNCH(2, 2, 2, 2); }
+    if (a.CoutPad % 64 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64))); return CFG_LAUNCH(2, 2, 2, 1); }
+    if (a.CoutPad % 32 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 32))); return CFG_LAUNCH(4, 1, 1, 1); }
+    return nullptr;
+}
+#undef CFG_LAUNCH
+#undef CFG_EPI
+#undef CFG_GO
+#undef CFG_NAME
 
-bool launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream);
-bool launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream);
-bool launch_conv_h4(const ConvArgs& a, hipStream_t stream);   // conv_h4.hip (the 256 x 256 LDS-DMA kernel of the same mode, where it fills the chip)
-bool launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream);
-void launch_conv(const ConvArgs& a, hipStream_t stream);
-int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream) {   // returns the number of kernel launches issued
+int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream, const char** names, ConvForce f) {
     static const int grp = conv_env("CALD_CONV_GROUP", 1);
     static const int p4 = conv_env("CALD_CONV_P4", 1);
-    if (grp && n > 1) {
-        if (probs[0].w16 && launch_conv_h4_group(probs, n, stream)) return 1;
-        if (probs[0].w16 && launch_conv_h3_group(probs, n, stream)) return 1;
-        if (!probs[0].w16 && p4 && launch_conv_p4_group(probs, n, stream)) return 1;
+    const char* gname = nullptr;
+    if (f.path == CONV_P4_GROUP) gname = launch_conv_p4_group(probs, n, stream, f);
+    else if (f.path == CONV_H3_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h3_group(probs, n, stream) : nullptr;
+    else if (f.path == CONV_H4_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h4_group(probs, n, stream, true) : nullptr;
+    else if (f.path == CONV_AUTO && grp && n > 1) {
+        if (probs[0].w16) gname = launch_conv_h4_group(probs, n, stream);
+        if (!gname && probs[0].w16) gname = launch_conv_h3_group(probs, n, stream);
+        if (!gname && !probs[0].w16 && p4) gname = launch_conv_p4_group(probs, n, stream);
     }
-    for (int i = 0; i < n; i++) launch_conv(probs[i], stream);
-    return n;
+    if (gname || f.path == CONV_P4_GROUP || f.path == CONV_H3_GROUP || f.path == CONV_H4_GROUP) {
+        if (names) for (int i = 0; i < n; i++) names[i] = gname;
+        return gname ? 1 : 0;
+    }
+    int launches = 0;
+    for (int i = 0; i < n; i++) {
+        const char* k = launch_conv(probs[i], stream, f);
+        if (names) names[i] = k;
+        launches += k != nullptr;
+    }
+    return launches;
 }
 
-void launch_conv(const ConvArgs& a, hipStream_t stream) {
+const char* launch_conv(const ConvArgs& a, hipStream_t stream, ConvForce f) {
+    switch (f.path) {
+    case CONV_AUTO: break;
+    case CONV_P4: return launch_conv_p4(a, stream, f);
+    case CONV_GENERIC: return f.tile == TILE_AUTO ? launch_conv_generic(a, stream) : nullptr;
+    case CONV_STEM: return f.tile == TILE_AUTO ? launch_conv_stem(a, stream) : nullptr;
+    case CONV_H3: return f.tile == TILE_AUTO ? launch_conv_h3(a, stream) : nullptr;
+    case CONV_H4: return f.tile == TILE_AUTO ? launch_conv_h4(a, stream, true) : nullptr;
+    default: return nullptr;          // group / fused modes have launchers of their own
+    }
     static const int p4 = conv_env("CALD_CONV_P4", 1);   // conv_p4.hip: 3-buffer pipelined schedule, 128-bit LDS fragment reads; 0 = this file only
-    if (a.w16 && launch_conv_h4(a, stream)) return;
-    if (a.w16 && launch_conv_h3(a, stream)) return;
+    const char* k = nullptr;
+    if (a.w16 && (k = launch_conv_h4(a, stream))) return k;
+    if (a.w16 && (k = launch_conv_h3(a, stream))) return k;
     static const int stem = conv_env("CALD_CONV_STEM", 1);   // 0: the stem runs on the generic kernels (same bits)
-    if (stem && a.wstem && launch_conv_stem(a, stream)) return;
-    if (p4 && launch_conv_p4(a, stream)) return;
+    if (stem && a.wstem && (k = launch_conv_stem(a, stream))) return k;
+    if (p4 && (k = launch_conv_p4(a, stream))) return k;
     if (a.gather) {                    // likewise the gathered-and-scattered rows of the cut_out reuse (api.hip checks before it turns it on)
         fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with gather support; launch skipped\n", a.Cin, a.Cout);
-        return;
+        return nullptr;
     }
     if (a.row_map) {                   // gathered rows exist in conv_p4.hip only (api.hip switches the pruning off when CALD_CONV_P4=0):
                                          // never compute the wrong rows silently -- the sweep's bound check then sends it to the dense head
         fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with row_map support; launch skipped\n", a.Cin, a.Cout);
-        return;
+        return nullptr;
     }
-    if (a.CoutPad % 128 == 0) launch_cfg<2, 2, 2, 2, 16>(a, 128, stream);
-    else if (a.CoutPad % 64 == 0) launch_cfg<2, 2, 2, 1, 16>(a, 64, stream);
-    else launch_cfg<4, 1, 1, 1, 16>(a, 32, stream);
+    return launch_conv_generic(a, stream);
 }

@@ -731,98 +731,128 @@ static inline int p4_taps(const ConvArgs& a) {
 // M-tile slots of the launch grid: the XCD-contiguous map of spatial filters rounds the tile count up to a multiple of 8
 static inline int p4_grid_mtiles(const ConvArgs& a) { return a.KH * a.KW > 1 ? 8 * ((a.total_mtiles + 7) / 8) : a.total_mtiles; }
 
-// grouped launch (EPI 0 only): returns true if every problem qualifies for the same variant
-bool launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream) {
-    if (n < 1 || n > CALD_MAX_GROUP) return false;
-    const bool wide = p[0].CoutPad % 128 == 0;
+// Features no conv_p4 kernel implements (the split-fp16 operands of CALD_PRECISION_F16X3; an fp32 tensor that is not there), and the
+// extras only the plain EPI 0 epilogue produces: every launcher below refuses them at the top instead of launching with one ignored.
+static inline bool p4_refuses(const ConvArgs& a) {
+    if (!a.w4 || !a.out || a.in16 || a.ex16 || a.CoutPad % 64 != 0 || (a.residual && a.up)) return true;
+    const bool extra = a.out16 || a.energy4;                    // compiled into the EPI 0, no-mask, no-gather epilogue only
+    if (extra && (a.residual || a.up || a.mask || a.gather)) return true;
+    if (a.energy4 && a.CoutPad != 256) return true;              // four slots of 64 channels: 2 n-tiles of 128 x 2 wave columns
+    if (a.row_map && (a.residual || a.up || a.mask || a.gather)) return true;   // the epilogue stores (and reads) at the compact row
+    return false;
+}
+static inline bool p4_tile_ok(const ConvArgs& a, const bool wide, const ConvForce f) {
+    if (f.tile == TILE_NARROW && wide) return false;
+    if (f.tile == TILE_WIDE && !wide) return false;
+    return !(a.energy4 && !wide);                               // the energy is written by the 128 x 128 tile only
+}
+
+#define P4_NAME(K, EPIV, C4V, TNV, TAPSV) K "<" #EPIV "," #C4V "," #TNV "," #TAPSV ">"
+template <int EPI, bool C4, int TN, int TAPS>
+static const char* p4_go(const dim3 grid, const int lds, hipStream_t stream, const ConvArgs& a, const char* name) {
+    hipLaunchKernelGGL((conv_p4_kernel<EPI, C4, TN, TAPS>), grid, dim3(256), lds, stream, a);
+    return name;
+}
+template <int EPI, int TN, int TAPS>
+static const char* p4_group_go(const dim3 grid, hipStream_t stream, const ConvGroup& g, const char* name) {
+    hipLaunchKernelGGL((conv_p4_group_kernel<EPI, false, TN, TAPS>), grid, dim3(256), 0, stream, g);
+    return name;
+}
+
+// grouped launch (EPI 0 / mask only): the kernel, or nullptr unless every problem qualifies for the same variant
+const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, ConvForce f) {
+    if (n < 1 || n > CALD_MAX_GROUP) return nullptr;
+    const bool wide = f.tile == TILE_NARROW ? false : p[0].CoutPad % 128 == 0;
     ConvGroup g; g.n = n; int blk = 0;
     for (int i = 0; i < n; i++) {
         const ConvArgs& a = p[i];
-        if (!a.w4 || a.w16 || a.CoutPad % 64 != 0 || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return false;
-        if ((a.mask != nullptr) != (p[0].mask != nullptr)) return false;
+        if (p4_refuses(a) || !p4_tile_ok(a, wide, f) || (a.CoutPad % 128 == 0) != (p[0].CoutPad % 128 == 0)) return nullptr;
+        if (a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return nullptr;
+        if ((a.mask != nullptr) != (p[0].mask != nullptr)) return nullptr;
+        if (a.mask && (a.out16 || a.energy4)) return nullptr;
         g.blk0[i] = blk; blk += p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a; g.p[i].exp_flags = 0;
     }
     g.blk0[n] = blk;
     const int taps = p4_taps(p[0]);
-    for (int i = 1; i < n; i++) if (p4_taps(p[i]) != taps) return false;
-    const dim3 grid((unsigned)blk), block(256);
-#define P4_GROUP(EV, TNV, TAPSV) hipLaunchKernelGGL((conv_p4_group_kernel<EV, false, TNV, TAPSV>), grid, block, 0, stream, g)
-#define P4_GROUP_T(EV) { if (wide) { if (taps == 9) P4_GROUP(EV, 2, 9); else if (taps == 1) P4_GROUP(EV, 2, 1); else P4_GROUP(EV, 2, 0); } \
-                         else { if (taps == 9) P4_GROUP(EV, 1, 9); else if (taps == 1) P4_GROUP(EV, 1, 1); else P4_GROUP(EV, 1, 0); } }
-    if (p[0].mask) P4_GROUP_T(4) else P4_GROUP_T(0)
+    for (int i = 1; i < n; i++) if (p4_taps(p[i]) != taps) return nullptr;
+    const dim3 grid((unsigned)blk);
+#define P4_GROUP(EV, TNV, TAPSV) p4_group_go<EV, TNV, TAPSV>(grid, stream, g, P4_NAME("conv_p4_group_kernel", EV, false, TNV, TAPSV))
+#define P4_GROUP_T(EV) (wide ? (taps == 9 ? P4_GROUP(EV, 2, 9) : taps == 1 ? P4_GROUP(EV, 2, 1) : P4_GROUP(EV, 2, 0)) \
+                             : (taps == 9 ? P4_GROUP(EV, 1, 9) : taps == 1 ? P4_GROUP(EV, 1, 1) : P4_GROUP(EV, 1, 0)))
+    const char* name = p[0].mask ? P4_GROUP_T(4) : P4_GROUP_T(0);
 #undef P4_GROUP_T
 #undef P4_GROUP
-    return true;
+    return name;
 }
 
 // conv2 (3 x 3, stride 1, 64 -> 64, BN + ReLU) followed by conv3 (1 x 1, 64 -> 128 k channels, BN + residual + ReLU) on the same pixels:
-// returns true if the fused kernel took both (same bits as the two separate launches)
-bool launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t stream) {
+// the kernel if the fused kernel took both (same bits as the two separate launches), else nullptr
+const char* launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t stream) {
     static const int on = getenv("CALD_P4_FUSE") ? atoi(getenv("CALD_P4_FUSE")) : 1;
-    if (!on || !c2.w4 || !c3.w4 || c2.w16 || c3.w16) return false;
-    if (c2.KH != 3 || c2.KW != 3 || c2.stride != 1 || c2.pad != 1 || c2.Cin % 16 || c2.Cout != 64 || c2.CoutPad != 64 || c2.out_ld != 64) return false;
-    if (c2.residual || c2.up || c2.mask || c2.dyn_rows || c2.in_relu || c2.gather || c3.gather || p4_taps(c2) != 9) return false;
-    if (c3.KH != 1 || c3.KW != 1 || c3.stride != 1 || c3.pad != 0 || c3.Cin != 64 || c3.Kpad != 64 || c3.CoutPad % 64 || c3.Cout != c3.CoutPad) return false;
-    if (!c3.residual || !c3.scale || c3.bias || c3.out_ld != c3.Cout || c3.up || c3.mask || c3.dyn_rows || c3.in_relu || c3.in != c2.out || c3.total_mtiles != c2.total_mtiles || c3.V != c2.V) return false;
+    if (!on || !c2.w4 || !c3.w4 || c2.w16 || c3.w16) return nullptr;
+    if (c2.KH != 3 || c2.KW != 3 || c2.stride != 1 || c2.pad != 1 || c2.Cin % 16 || c2.Cout != 64 || c2.CoutPad != 64 || c2.out_ld != 64) return nullptr;
+    if (c2.residual || c2.up || c2.mask || c2.dyn_rows || c2.in_relu || c2.gather || c3.gather || p4_taps(c2) != 9) return nullptr;
+    if (c3.KH != 1 || c3.KW != 1 || c3.stride != 1 || c3.pad != 0 || c3.Cin != 64 || c3.Kpad != 64 || c3.CoutPad % 64 || c3.Cout != c3.CoutPad) return nullptr;
+    if (!c3.residual || !c3.scale || c3.bias || c3.out_ld != c3.Cout || c3.up || c3.mask || c3.dyn_rows || c3.in_relu || c3.in != c2.out || c3.total_mtiles != c2.total_mtiles || c3.V != c2.V) return nullptr;
+    if (c2.row_map || c3.row_map || c2.in16 || c3.in16 || c2.out16 || c3.out16 || c2.energy4 || c3.energy4 || c2.ex16 || c3.ex16 || !c3.out) return nullptr;
     ConvGroup g; g.n = 2; g.blk0[0] = 0; g.p[0] = c2; g.p[1] = c3; g.p[0].exp_flags = 0;
     static const int late_env = getenv("CALD_P4_FUSE_LATE") ? atoi(getenv("CALD_P4_FUSE_LATE")) : 0;
     g.p[1].exp_flags = late_env ? 2 : 0;
     const unsigned grid = (unsigned)p4_grid_mtiles(c2);          // one workgroup per 128-row tile (conv2's only N tile)
     hipLaunchKernelGGL(conv_p4_fused_kernel, dim3(grid), dim3(256), 0, stream, g);
-    return true;
+    return "conv_p4_fused_kernel";
 }
 
-// returns true if this variant handled the launch
-bool launch_conv_p4(const ConvArgs& a_in, hipStream_t stream) {
-    if (!a_in.w4 || a_in.CoutPad % 64 != 0) return false;
+// the kernel if this variant handled the launch, else nullptr
+const char* launch_conv_p4(const ConvArgs& a_in, hipStream_t stream, ConvForce f) {
+    if (p4_refuses(a_in)) return nullptr;
     const int exp_env = p4_exp_env();
     static const int pad_lds = getenv("CALD_P4_PADLDS") ? atoi(getenv("CALD_P4_PADLDS")) : 0;    // extra dynamic LDS: caps workgroups per CU
     ConvArgs a = a_in; a.exp_flags = exp_env;
     bool wide = a.CoutPad % 128 == 0;
     if (wide) {
         // tail quantisation: a launch of B equal workgroups on 768 slots (256 CUs x 3) runs at B / (ceil(B / 768) * 768); the
-        // 128 x 64 tile doubles B at ~0.88 of the 128 x 128 tile's per-workgroup efficiency -- use it where that wins
+        // 128 x 64 tile doubles B at ~0.88 of the 128 x 128 tile's per-workgroup efficiency -- use it where that wins (never with
+        // energy4: only the wide tile writes it)
         static const int narrow_env = getenv("CALD_CONV_NARROW") ? atoi(getenv("CALD_CONV_NARROW")) : 1;
         const long long b2 = (long long)a.total_mtiles * (a.CoutPad / 128), b1 = 2 * b2;
         const double e2 = (double)b2 / (double)(((b2 + 767) / 768) * 768), e1 = 0.88 * (double)b1 / (double)(((b1 + 767) / 768) * 768);
-        if (narrow_env && e1 > e2 && !a.dyn_rows) wide = false;
+        if (narrow_env && e1 > e2 && !a.dyn_rows && !a.energy4) wide = false;
     }
-    dim3 grid((unsigned)(p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)))), block(256);
+    if (f.tile == TILE_NARROW) wide = false;
+    else if (f.tile == TILE_WIDE) wide = a.CoutPad % 128 == 0;
+    if (!p4_tile_ok(a, wide, f)) return nullptr;
+    const dim3 grid((unsigned)(p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64))));
+#define P4_ONE(EPIV, C4V, TNV, TAPSV) p4_go<EPIV, C4V, TNV, TAPSV>(grid, pad_lds, stream, a, P4_NAME("conv_p4_kernel", EPIV, C4V, TNV, TAPSV))
     if (a.gather) {      // gathered rows: the unrolled 1 x 1 / 3 x 3 kernels, BN (+ residual) epilogue
         const int taps = p4_taps(a);
-        if (a.Cin == 4 || a.up || a.mask || a.in_relu || a.dyn_rows || a.row_map || (taps != 1 && taps != 9)) return false;
-        if (a.total_mtiles == 0) return true;
-#define P4_G(EPIV, TNV) { if (taps == 9) hipLaunchKernelGGL((conv_p4_kernel<EPIV, false, TNV, 9>), grid, block, pad_lds, stream, a); \
-                          else hipLaunchKernelGGL((conv_p4_kernel<EPIV, false, TNV, 1>), grid, block, pad_lds, stream, a); }
-        if (wide) { if (a.residual) P4_G(17, 2) else P4_G(16, 2) } else { if (a.residual) P4_G(17, 1) else P4_G(16, 1) }
+        if (a.Cin == 4 || a.up || a.mask || a.in_relu || a.dyn_rows || a.row_map || (taps != 1 && taps != 9)) return nullptr;
+        if (a.total_mtiles == 0) return "none (no gathered rows)";
+#define P4_G(EPIV, TNV) (taps == 9 ? P4_ONE(EPIV, false, TNV, 9) : P4_ONE(EPIV, false, TNV, 1))
+        return wide ? (a.residual ? P4_G(17, 2) : P4_G(16, 2)) : (a.residual ? P4_G(17, 1) : P4_G(16, 1));
 #undef P4_G
-        return true;
     }
     if (a.Cin == 4) {
-        if (a.residual || a.up || a.in_relu) return false;
+        if (a.residual || a.up || a.in_relu || a.mask) return nullptr;
         static const int stem_env = getenv("CALD_P4_UNROLL") ? atoi(getenv("CALD_P4_UNROLL")) : 1;
-        if (stem_env && a.KH == 7 && a.KW == 7 && a.Kpad == 208) {      // unrolled stem: per-k-tile tap offsets precomputed
-            if (wide) hipLaunchKernelGGL((conv_p4_kernel<0, true, 2, 13>), grid, block, pad_lds, stream, a);
-            else hipLaunchKernelGGL((conv_p4_kernel<0, true, 1, 13>), grid, block, pad_lds, stream, a);
-            return true;
-        }
-        if (wide) hipLaunchKernelGGL((conv_p4_kernel<0, true, 2, 0>), grid, block, pad_lds, stream, a);
-        else hipLaunchKernelGGL((conv_p4_kernel<0, true, 1, 0>), grid, block, pad_lds, stream, a);
-        return true;
+        if (stem_env && a.KH == 7 && a.KW == 7 && a.Kpad == 208)       // unrolled stem: per-k-tile tap offsets precomputed
+            return wide ? P4_ONE(0, true, 2, 13) : P4_ONE(0, true, 1, 13);
+        return wide ? P4_ONE(0, true, 2, 0) : P4_ONE(0, true, 1, 0);
     }
-    if (a.Cin % 16 != 0 || a.KH * a.KW > 32) return false;
+    if (a.Cin % 16 != 0 || a.KH * a.KW > 32) return nullptr;
     const int taps = p4_taps(a);
-#define P4_ONE(EPIV, TNV, TAPSV) hipLaunchKernelGGL((conv_p4_kernel<EPIV, false, TNV, TAPSV>), grid, block, pad_lds, stream, a)
-#define P4_TAPS(EPIV, TNV) { if (taps == 9) P4_ONE(EPIV, TNV, 9); else if (taps == 1) P4_ONE(EPIV, TNV, 1); else P4_ONE(EPIV, TNV, 0); }
+#define P4_TAPS(EPIV, TNV) (taps == 9 ? P4_ONE(EPIV, false, TNV, 9) : taps == 1 ? P4_ONE(EPIV, false, TNV, 1) : P4_ONE(EPIV, false, TNV, 0))
+    const char* name;
     if (a.mask) {                      // training backward (never set by the inference engine)
-        if (a.up) return false;
-        if (wide) { if (a.residual) P4_TAPS(5, 2) else P4_TAPS(4, 2) } else { if (a.residual) P4_TAPS(5, 1) else P4_TAPS(4, 1) }
+        if (a.up) return nullptr;
+        name = wide ? (a.residual ? P4_TAPS(5, 2) : P4_TAPS(4, 2)) : (a.residual ? P4_TAPS(5, 1) : P4_TAPS(4, 1));
     } else if (wide) {
-        if (a.residual) P4_TAPS(1, 2) else if (a.up) P4_TAPS(2, 2) else P4_TAPS(0, 2)
+        name = a.residual ? P4_TAPS(1, 2) : a.up ? P4_TAPS(2, 2) : P4_TAPS(0, 2);
     } else {
-        if (a.residual) P4_TAPS(1, 1) else if (a.up) P4_TAPS(2, 1) else P4_TAPS(0, 1)
+        name = a.residual ? P4_TAPS(1, 1) : a.up ? P4_TAPS(2, 1) : P4_TAPS(0, 1);
     }
 #undef P4_TAPS
 #undef P4_ONE
-    return true;
+    return name;
 }
+#undef P4_NAME

@@ -139,13 +139,16 @@ __global__ __launch_bounds__(256, 3) void conv_stem_kernel(const ConvArgs a, con
     }
 }
 
-// returns true if this kernel handled the launch (7 x 7 / 2 stem with packed stem weights, every view an exact grid of 8 x 16 blocks)
-bool launch_conv_stem(const ConvArgs& a, hipStream_t stream) {
-    if (!a.wstem || a.KH != 7 || a.KW != 7 || a.stride != 2 || a.pad != 3 || a.Cin != 4 || a.Cout != 64 || a.out_ld != 64) return false;
-    if (a.residual || a.up || a.in_relu || a.bias || !a.scale || a.mask || a.dyn_rows) return false;
+// the kernel if it handled the launch (7 x 7 / 2 stem with packed stem weights -- api.hip sets them only when every view is an exact grid
+// of 8 x 16 blocks), else nullptr
+const char* launch_conv_stem(const ConvArgs& a, hipStream_t stream) {
+    if (!a.wstem || !a.out || a.KH != 7 || a.KW != 7 || a.stride != 2 || a.pad != 3 || a.Cin != 4 || a.Cout != 64 || a.out_ld != 64) return nullptr;
+    if (a.residual || a.up || a.in_relu || a.bias || !a.scale || a.mask || a.dyn_rows) return nullptr;
+    if (a.gather || a.row_map || a.energy4 || a.out16 || a.in16 || a.ex16) return nullptr;
     int grid = 768;
     if (a.total_mtiles < grid) grid = (a.total_mtiles + 7) / 8 * 8;
+    if (grid == 0) return "none (no output tiles)";
     const int per_xcd = (a.total_mtiles + 7) / 8;
     hipLaunchKernelGGL(conv_stem_kernel, dim3((unsigned)grid), dim3(256), 0, stream, a, a.wstem, per_xcd);
-    return true;
+    return "conv_stem_kernel";
 }

@@ -399,7 +399,7 @@ extern "C" int cald_train_conv(cald_ctx* c, int N, int H, int W, const float* in
     const bool fused = mask && p4_takes(g, kh * kw);
     if (mask && !fused && (out_ld != g.n_true || out_ld % 4)) TFAIL(CALD_ERR_INVALID, "mask on this shape needs a dense output with C %% 4 == 0");
     a.mask = fused ? mask : nullptr;
-    launch_conv(a, cald_internal_stream(c));
+    if (!launch_conv(a, cald_internal_stream(c))) TFAIL(CALD_ERR_UNSUPPORTED, "no conv kernel implements this layer's features");
     if (mask && !fused) {
         const long long n4 = (long long)N * Ho * Wo * out_ld / 4;
         hipLaunchKernelGGL(relu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, cald_internal_stream(c), out, mask, (const float*)nullptr, n4, out_ld / 4);
@@ -440,7 +440,9 @@ extern "C" int cald_train_conv_group(cald_ctx* c, int n, int N, const int* hw, c
         a.relu = (flags & 4) ? 1 : 0; a.total_mtiles = N * ((Ho * Wo + 127) / 128); a.out_ld = out_ld; a.zeros = cald_internal_zeros(c);
         a.mask = masks ? masks[i] : nullptr;
     }
-    launch_conv_group(probs, n, cald_internal_stream(c));
+    const char* names[CALD_MAX_GROUP];
+    launch_conv_group(probs, n, cald_internal_stream(c), names);
+    for (int i = 0; i < n; i++) if (!names[i]) TFAIL(CALD_ERR_UNSUPPORTED, "no conv kernel implements problem %d's features", i);
     THIP(hipGetLastError());
     return 0;
 }

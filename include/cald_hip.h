@@ -230,6 +230,43 @@ int cald_op_conv2d(cald_ctx* ctx, const float* in, int H, int W, int Cin, const 
 int cald_op_conv2d_f16x3(cald_ctx* ctx, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
                          int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
                          const float* residual, int relu, float* out);
+/* Test-only conv probe (tests/test_gpu_conv_variants.py): ONE launch of the product's conv launchers, weights packed by the product's own
+ * packing, on a ragged batch of V views laid out as a forward lays them out (per-view pixel offsets and 128-row tile starts).  All arrays
+ * are host memory.  `path` pins the kernel family (0 auto = the product's choice, 1 conv_p4, 2 conv_p4 grouped, 3 conv_p4 fused layer-1
+ * pair, 4 generic conv_mfma, 5 conv_stem, 6 conv_h3, 7 conv_h3 grouped, 8 conv_h4, 9 conv_h4 grouped), `tile` the conv_p4 tile (0 auto,
+ * 1 narrow 128 x 64, 2 wide 128 x 128).  n > 1 problems go through the grouped launcher; the fused mode takes n = 2 (conv2, conv3; conv3's
+ * `in` is conv2's output).  A pinned launcher that cannot take the problem returns CALD_ERR_UNSUPPORTED -- it never hands the problem to
+ * another kernel.  out / out16 / energy4 are copied to the device whole and back whole: words the caller put past what a kernel may write
+ * (guard rows, channels Cout..out_ld) show any stray store.  `kernel` receives the launched instantiation(s), ';'-separated. */
+#define CALD_PROBE_MAX_VIEWS 8
+#define CALD_PROBE_MAX_RECTS 8
+typedef struct cald_conv_probe {
+    int V;
+    int in_hw[CALD_PROBE_MAX_VIEWS][2];    /* input H, W per view (0 x 0: an empty view) */
+    int up_hw[CALD_PROBE_MAX_VIEWS][2];    /* `up`: the coarser level's H, W per view */
+    int dyn_rows[CALD_PROBE_MAX_VIEWS];    /* per-view row counts, used when has_dyn */
+    int has_dyn;
+    int gather;                            /* 1: only the rows of each view's rectangles (x0, y0, w, h in output pixels) */
+    int nrect[CALD_PROBE_MAX_VIEWS];
+    int rect[CALD_PROBE_MAX_VIEWS][CALD_PROBE_MAX_RECTS][4];
+    int Cin, Cout, KH, KW, stride, pad, relu, in_relu, out_ld;
+    int cin_true;                          /* input channels of `weight` (0: Cin); the rest are zero-padded, as the stem's 3 -> 4 */
+    const float* weight;                   /* torch layout [Cout][cin_true][KH][KW] */
+    const float* bias;                     /* [Cout] or null */
+    const float* bn_scale;                 /* FrozenBN [Cout] or null */
+    const float* bn_shift;
+    const float* in;                       /* [sum H W][Cin] */
+    const uint32_t* in16;                  /* the same input in split form (CALD_PRECISION_F16X3) or null */
+    const float* residual;                 /* [sum Ho Wo][out_ld] or null (split words when ex16) */
+    const float* up;                       /* [sum Hu Wu][out_ld] or null (split words when ex16) */
+    int ex16;
+    const float* mask;                     /* [sum Ho Wo][out_ld] or null: out = mask > 0 ? out : 0 */
+    const int* row_map;                    /* [sum Ho Wo] or null: compact row m of a view is the output pixel row_map[pix_off + m] */
+    float* out; int64_t out_n;             /* words, >= sum Ho Wo * out_ld; null = split-form output only */
+    uint32_t* out16; int64_t out16_n;      /* split-form output or null */
+    float* energy4; int64_t energy4_n;     /* [pixel][4] partial sums of squares or null */
+} cald_conv_probe;
+int cald_op_conv_probe(cald_ctx* ctx, int precision, cald_conv_probe* probs, int n, int path, int tile, char* kernel, int kernel_cap);
 /* Parity hook of CALD_PRECISION_F16X3's arithmetic primitive: n independent dot products D[i] = C[i] + sum_{k<16} A[i][k] B[i][k], each
  * evaluated by the hardware as ONE output element of v_mfma_f32_32x32x16_f16 (the instruction conv_h3.hip / conv_h4.hip are built on;
  * there is no reference function -- the reference has no fp16 path).  A, B: fp16 bit patterns [n][16], C / D: fp32

@@ -131,7 +131,9 @@ CONV_CASES = [
     (19, 25, 256, 256, 3, 1, 1, True, False, False, False),  # FPN layer block
     (19, 25, 256, 15, 1, 1, 0, True, False, False, False),   # RPN head (Cout 15 -> tile 32)
     (1, 300, 1024, 105, 1, 1, 0, True, False, False, False), # predictor (Cout 105 -> tile 128)
-    (1, 130, 12544, 1024, 1, 1, 0, True, False, False, True) # fc6: K = 12544 chain
+    (1, 130, 12544, 1024, 1, 1, 0, True, False, False, True), # fc6: K = 12544 chain
+    (19, 25, 20, 64, 3, 1, 1, False, True, True, True),     # Cin 20 + residual: the generic kernel's general k-loop (Kpad > K)
+    (12, 14, 64, 64, 7, 1, 3, False, True, True, True),     # 7x7, Cin 64 (49 taps) + residual: the general k-loop again
 ]
 
 
