@@ -63,7 +63,6 @@ struct cald_ctx {
     int prof_tag_now = 0;                           // set around the look-ahead launches of rpn_prune.hip (per context: ADVICE r5)
     std::vector<int> prof_tag;                      // 0: the model's own arithmetic; 1: the split-fp16 look-ahead pass of rpn_prune.hip (booked apart)
     double prof_prune_flops_cap[2] = {0.0, 0.0};    // FLOPs the gathered P2 / P3 launches are booked with (every pixel, once per selection stage; rescaled to the selected rows at read time)
-    int prof_prune_stage_launches = 1;              // selection stages per forward: the booked FLOPs hold that many copies of the dense head
     hipEvent_t tot0 = nullptr, tot1 = nullptr; bool tot_open = false; double tot_ms = 0.0;
     // RoI-head GEMMs run on a device-side row count (proposals after NMS): the profile counts their algorithmic FLOPs on the
     // MEASURED rows, accumulated on the device while profiling (no host sync inside a forward)
@@ -230,8 +229,8 @@ extern "C" int cald_profile_read(cald_ctx* c, double* gemm_ms, double* gemm_flop
     if (c->prof_roi_rows_cap > 0.0) fl -= c->prof_roi_flops_cap * (1.0 - (double)rows / c->prof_roi_rows_cap);
     unsigned long long st[4] = {0, 0, 0, 0};     // the gathered RPN launches were booked on every pixel of P2 / P3: rescale to the selected rows
     HIPCHK(hipMemcpy(st, c->d_prune_stat, 32, hipMemcpyDeviceToHost));
-    // booked: one dense head per selection stage; executed: the selected rows of all stages together
-    for (int l = 0; l < 2; l++) if (st[2 * l + 1]) fl -= c->prof_prune_flops_cap[l] * (1.0 - (double)st[2 * l] / ((double)c->prof_prune_stage_launches * (double)st[2 * l + 1]));
+    // booked: one dense head per selection stage (two); executed: the selected rows of both stages together
+    for (int l = 0; l < 2; l++) if (st[2 * l + 1]) fl -= c->prof_prune_flops_cap[l] * (1.0 - (double)st[2 * l] / (2.0 * (double)st[2 * l + 1]));
     if (gemm_flops) *gemm_flops = fl;
     if (launches) *launches = (int64_t)c->ev0.size() - look_n + c->prof_extra_launches;   // a timed region can hold several kernel launches
     if (total_ms) *total_ms = c->tot_ms;
@@ -252,7 +251,7 @@ extern "C" int cald_profile_prune(cald_ctx* c, double* look_ms, double* look_flo
     if (worst_bound_ratio) *worst_bound_ratio = (double)c->prune_worst;
     if (pruned_flops) {      // exact FLOPs of the dense head that the gathered launches did NOT execute (cald_profile_read leaves them out)
         double fl2 = 0.0;
-        for (int l = 0; l < 2; l++) if (st[2 * l + 1]) fl2 += c->prof_prune_flops_cap[l] / (double)c->prof_prune_stage_launches * (1.0 - (double)st[2 * l] / (double)st[2 * l + 1]);
+        for (int l = 0; l < 2; l++) if (st[2 * l + 1]) fl2 += c->prof_prune_flops_cap[l] / 2.0 * (1.0 - (double)st[2 * l] / (double)st[2 * l + 1]);
         *pruned_flops = fl2;
     }
     return 0;
@@ -302,8 +301,7 @@ extern "C" int cald_profile_dump(cald_ctx* c, const char* path) {
     return 0;
 }
 
-// conv launch with optional event bracketing.  A launch no kernel takes is an error -- except the gathered rows of the certified RPN
-// pruning (row_map), which launch_conv skips loudly: the sweep's bound check then sends those views to the dense head.
+// conv launch with optional event bracketing.  A launch no kernel takes is an error.
 static int conv_refused(const ConvArgs& a) {
     return fail(CALD_ERR_UNSUPPORTED, "no conv kernel implements this launch (Cin=%d Cout=%d k=%dx%d residual=%d up=%d mask=%d gather=%d energy4=%d out16=%d)",
                 a.Cin, a.Cout, a.KH, a.KW, a.residual != nullptr, a.up != nullptr, a.mask != nullptr, a.gather != nullptr, a.energy4 != nullptr,
@@ -323,7 +321,7 @@ static int run_conv(cald_ctx* c, const ConvArgs& a, double flops) {
     } else {
         k = launch_conv(a, c->stream);
     }
-    if (!k && !a.row_map) return conv_refused(a);
+    if (!k) return conv_refused(a);
     return 0;
 }
 
@@ -481,6 +479,7 @@ struct cald_model {
     ConvLayer fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred;
     // certified RPN pruning of the exact sweep (rpn_prune.hip): the 3 x 3 RPN conv once more with split-fp16 weights, the bound's constants
     ConvLayer rpn_conv16; bool prune = false; float prune_c1[3] = {0, 0, 0}, prune_c0[3] = {0, 0, 0};
+    bool prune_allowed = false;     // finalize's verdict: the look-ahead layer exists and the bound's constants are finite (cald_model_set_rpn_prune* AND it in)
     bool prune_capture = false;     // test hook: cald_forward takes the pruned path too and keeps the look-ahead's logit map (cald_model_set_rpn_prune_capture)
     ConvLayer p6, p7, cls_tower[4], reg_tower[4], cls_out, reg_out;   // RetinaNet
     int det_cap() const { return cfg.arch == CALD_ARCH_RETINANET ? cfg.num_classes * cfg.detections_per_img : cfg.detections_per_img; }
@@ -735,7 +734,6 @@ extern "C" int cald_model_finalize(cald_model* m) {
             if ((rc = get_t(m, "rpn.head.conv.weight", &wc)) || (rc = get_t(m, "rpn.head.conv.bias", &bc)) || (rc = get_t(m, "rpn.head.cls_logits.weight", &wl))) return rc;
             const int K = 2304;
             const double u = std::ldexp(1.0, -24), gK = K * u / (1.0 - K * u);
-            static const double slack = getenv("CALD_RPN_PRUNE_SLACK") ? atof(getenv("CALD_RPN_PRUNE_SLACK")) : 1.0;      // tuning experiments: scales the bound
             // Running error analysis of a chain s_k = fl(s_(k-1) + t_k) (t_j = P_j w_j, fma: one rounding per step): |s_K - sum t| <= u sum_k |s_k|
             // <= u (1 + gK) sum_j r_j |t_j|, r_j = K - j = the number of partial sums term j takes part in (j = its position in the chain, conv_k_index).
             // Cauchy-Schwarz keeps the weights:  sum_j r_j |P_j| |w_j| <= |patch|_2 * A_c,  A_c = sqrt(sum_j (r_j w_cj)^2)  (~ K |w_c|_2 / sqrt 3:
@@ -784,12 +782,12 @@ extern "C" int cald_model_finalize(cald_model* m) {
                     c0 += v * (std::fabs((double)bc->data[c]) * (2.0 * u + 2.0 * g_h) + std::ldexp(1.0, -29) * w1[c] + 8640.0 * std::ldexp(1.0, -42) * wmax[c]);
                 }
                 c0 += 2.0 * u * std::fabs((double)bl->data[a]) * (1.0 + g_h);            // the head's own bias add rounds once on each side: u |L| <= u (|chain| + |b_a|)
-                m->prune_c1[a] = (float)(1.02 * slack * c1);
-                m->prune_c0[a] = (float)(1.02 * slack * c0);
+                m->prune_c1[a] = (float)(1.02 * c1);
+                m->prune_c0[a] = (float)(1.02 * c0);
                 finite = finite && std::isfinite(m->prune_c1[a]) && std::isfinite(m->prune_c0[a]) && m->prune_c0[a] > 0.0f;
             }
-            const bool p4_on = !(getenv("CALD_CONV_P4") && atoi(getenv("CALD_CONV_P4")) == 0);      // ConvArgs::row_map (the gathered launches) exists in conv_p4.hip only
-            m->prune = finite && p4_on && m->rpn_conv16.w16 != nullptr;
+            m->prune_allowed = finite && m->rpn_conv16.w16 != nullptr;
+            m->prune = m->prune_allowed;
         }
         {   // fc6: torch K order is (c, bin); the RoIAlign kernel writes (bin, c) -> permute the weight's K axis
             const HostTensor* t; if ((rc = get_t(m, "roi_heads.box_head.fc6.weight", &t))) return rc;
@@ -869,7 +867,7 @@ extern "C" int cald_model_set_rpn_prune(cald_model* m, int on, int* was) {
     if (!m) return fail(CALD_ERR_INVALID, "model is null");
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
     if (was) *was = m->prune ? 1 : 0;
-    m->prune = on != 0 && m->rpn_conv16.w16 != nullptr && m->cfg.precision == CALD_PRECISION_FP32;
+    m->prune = on != 0 && m->prune_allowed;
     return 0;
 }
 // Test hooks of the certified pruning: in capture mode cald_forward takes the pruned path as well (it is dense otherwise) and keeps the
@@ -883,7 +881,7 @@ extern "C" int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was) {
 }
 extern "C" int cald_model_set_rpn_prune_capture(cald_model* m, int on) {
     if (!m) return fail(CALD_ERR_INVALID, "model is null");
-    if (on && !m->prune) return fail(CALD_ERR_STATE, "certified RPN pruning is not active on this model");
+    if (on && !(m->prune && m->prune_allowed)) return fail(CALD_ERR_STATE, "certified RPN pruning is not active on this model");
     m->prune_capture = on != 0;
     return 0;
 }
@@ -984,7 +982,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
     a.Cin = L.Cin; a.Cout = L.Cout; a.CoutPad = L.CoutPad; a.Kpad = L.Kpad;
     a.KH = L.KH; a.KW = L.KW; a.stride = L.stride; a.pad = L.pad; a.relu = relu ? 1 : 0;
     a.total_mtiles = level_tiles(m->plan, lout, V);
-    a.out_ld = L.Cout; a.in_relu = in_relu ? 1 : 0; a.zeros = m->ctx->d_zeros; a.exp_flags = 0;
+    a.out_ld = L.Cout; a.in_relu = in_relu ? 1 : 0; a.zeros = m->ctx->d_zeros;
     a.mask = nullptr;
     // the kernels address a view's tensor through a buffer resource / 32-bit byte offsets: a view (or a dense RoI-row segment) must stay
     // below 2 GB per operand -- refuse loudly instead of reading zeros past the end (as a 64-view fc6 operand in one segment once did)
@@ -1084,7 +1082,7 @@ static int conv_group_on(cald_model* m, const ConvSpec* sp, int n, int V) {
     } else {
         launch_conv_group(a, n, c->stream, names);
     }
-    for (int i = 0; i < n; i++) if (!names[i] && !a[i].row_map) return conv_refused(a[i]);
+    for (int i = 0; i < n; i++) if (!names[i]) return conv_refused(a[i]);
     return 0;
 }
 
@@ -1092,6 +1090,7 @@ static int conv_group_on(cald_model* m, const ConvSpec* sp, int n, int V) {
 // and their first three stages recompute only the pixels the filled rectangles reach (host_logic.h cut_geometry), patching the reference
 // forward's retained block outputs in place ----
 #define CUT_MAX_BLOCKS 32          // blocks of the first three stages (ResNet-101: 3 + 4 + 23)
+#define CUT_GATHER_MAX_COST 0.7    // a stage runs gathered while its tiles cost at most this fraction of the dense stage
 struct FwdReuse {
     int mode = 0;                  // 1: reference forward, the block outputs of the first nblk blocks go to out[]; 2: the cut_out forward
     int nblk = 0;
@@ -1334,16 +1333,14 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
         return 0;
     }
     // ---- FPN (row A16) ----
-    static const bool look_h4 = !(getenv("CALD_RPN_PRUNE_H4") && atoi(getenv("CALD_RPN_PRUNE_H4")) == 0);     // 0: look-ahead on conv_h3's fp32 loader (A/B)
-    static const bool fuse_env = !(getenv("CALD_RPN_PRUNE_FUSED") && atoi(getenv("CALD_RPN_PRUNE_FUSED")) == 0);   // 0: round 5's separate energy pass (A/B)
-    const bool prune_fused = m->prune && prune_ok && look_h4 && fuse_env;
+    const bool prune = m->prune && prune_ok;
     if ((rc = conv_on(m, m->fpn_inner[3], F.Cf[3], F.inner[3], 5, 5, V, false))) return rc;
     for (int i = 2; i >= 0; i--)
         if ((rc = conv_on(m, m->fpn_inner[i], F.Cf[i], F.inner[i], 2 + i, 2 + i, V, false, nullptr, F.inner[i + 1], 3 + i))) return rc;
     {
         ConvSpec sp[4];
         for (int i = 0; i < 4; i++) sp[i] = {&m->fpn_layer[i], F.inner[i], F.Pf[i], 2 + i, false};
-        if (prune_fused)          // the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
+        if (prune)                // the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
             for (int i = 0; i < 2; i++) { sp[i].out16 = F.prune_p16[i]; sp[i].energy4 = F.prune_energy[i]; }
         if ((rc = conv_group_on(m, sp, 4, V))) return rc;
     }
@@ -1356,28 +1353,25 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
     for (int i = 0; i < 5; i++) m->dbg[pn[i]] = {F.Pf[i], 2 + i, 256, 0};
     // ---- RPN (row A17) ----
     const char* rn[5] = {"rpn0", "rpn1", "rpn2", "rpn3", "rpn4"};
-    if (m->prune && prune_ok) {
+    if (prune) {
         // certified pruning (rpn_prune.hip): P2 / P3 first on the fp16 matrix pipe, then exactly at the pixels that can hold one of the
         // level's pre_nms_top_n anchors; P4..P6 dense as ever.  Same bits at every anchor the top-k can select.
         ConvSpec sp[5];
         RpnPruneArgs pr;
-        static const int stages_env = (getenv("CALD_RPN_PRUNE_STAGES") && atoi(getenv("CALD_RPN_PRUNE_STAGES")) == 1) ? 1 : 2;   // 1: round 5's single-stage rule (A/B)
-        const int stages = stages_env;
         for (int i = 0; i < 2; i++) {
-            pr.feat[i] = F.Pf[i]; pr.seg[i] = dp->seg[2 + i]; pr.energy[i] = F.prune_energy[i]; pr.pnorm[i] = F.prune_pn[i]; pr.head[i] = F.rpn_h[i]; pr.head_out[i] = F.rpn_h[i];
-            pr.split[i] = look_h4 ? F.prune_p16[i] : nullptr;
+            pr.seg[i] = dp->seg[2 + i]; pr.energy[i] = F.prune_energy[i]; pr.pnorm[i] = F.prune_pn[i]; pr.head[i] = F.rpn_h[i]; pr.head_out[i] = F.rpn_h[i];
             for (int s2 = 0; s2 < 2; s2++) { pr.head_rows[s2][i] = F.prune_rows[s2][i]; pr.row_map[s2][i] = F.prune_map[s2][i]; }
         }
-        int log_slot[2] = {-1, -1};
-        for (int s2 = 0; s2 < stages; s2++) log_slot[s2] = (c->prof && c->prune_log_n < CALD_PRUNE_LOG) ? c->prune_log_n++ : -1;
-        for (int s2 = 0; s2 < 2; s2++) { pr.nsel[s2] = F.prune_nsel[s2]; pr.log[s2] = log_slot[s2] >= 0 ? c->d_prune_log + (size_t)log_slot[s2] * 4 : nullptr; }
+        int log_slot[2];
+        for (int s2 = 0; s2 < 2; s2++) {
+            log_slot[s2] = (c->prof && c->prune_log_n < CALD_PRUNE_LOG) ? c->prune_log_n++ : -1;
+            pr.nsel[s2] = F.prune_nsel[s2]; pr.log[s2] = log_slot[s2] >= 0 ? c->d_prune_log + (size_t)log_slot[s2] * 4 : nullptr;
+        }
         pr.tau_key = F.prune_tau; pr.stat = c->prof ? c->d_prune_stat : nullptr; pr.check = c->d_prune_check;
         for (int q = 0; q < 3; q++) { pr.c1[q] = m->prune_c1[q]; pr.c0[q] = m->prune_c0[q]; }
-        pr.head_ld = 15; pr.pre_n = m->cfg.rpn_pre_nms_top_n; pr.V = V; pr.stages = stages;
-        pr.energy_parts = prune_fused ? 4 : 1;
-        if (!prune_fused) launch_rpn_prune_energy(pr, st);
+        pr.head_ld = 15; pr.pre_n = m->cfg.rpn_pre_nms_top_n; pr.V = V;
         c->prof_tag_now = 1;
-        for (int i = 0; i < 2; i++) { sp[i] = {&m->rpn_conv16, F.Pf[i], F.rpn_tl[i], 2 + i, true}; sp[i].in16 = pr.split[i]; }
+        for (int i = 0; i < 2; i++) { sp[i] = {&m->rpn_conv16, F.Pf[i], F.rpn_tl[i], 2 + i, true}; sp[i].in16 = F.prune_p16[i]; }
         rc = conv_group_on(m, sp, 2, V);
         for (int i = 0; i < 2; i++) sp[i] = {&m->rpn_head, F.rpn_tl[i], F.rpn_h[i], 2 + i, false};
         if (!rc) rc = conv_group_on(m, sp, 2, V);
@@ -1392,10 +1386,9 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
                 const char* ln[2] = {"rpn_look0", "rpn_look1"}; const char* bn[2] = {"rpn_pnorm0", "rpn_pnorm1"};
                 m->dbg[ln[i]] = {F.prune_look[i], 2 + i, 15, 0}; m->dbg[bn[i]] = {F.prune_pn[i], 2 + i, 1, 0};
             }
-        // stage s2 < stages - 1 recomputes P2 / P3 rows only; the last stage's launches also carry the dense levels P4..P6
-        for (int s2 = 0; s2 < stages; s2++) {
-            const bool last = s2 == stages - 1;
-            const int np = last ? 5 : 2;
+        // stage 0 recomputes P2 / P3 rows only; stage 1's launches also carry the dense levels P4..P6
+        for (int s2 = 0; s2 < 2; s2++) {
+            const int np = s2 == 1 ? 5 : 2;
             launch_rpn_prune_select(pr, max_pix2, s2, st);
             for (int i = 0; i < np; i++) sp[i] = {&m->rpn_conv, F.Pf[i], F.rpn_tl[i], 2 + i, true};
             for (int i = 0; i < 2; i++) { sp[i].dyn = F.prune_nsel[s2] + i * V; sp[i].row_map = F.prune_map[s2][i]; }      // gathered rows, compact output
@@ -1412,7 +1405,6 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
                 if (log_slot[s2] >= 0) c->prof_gather[c->prof_fl.size() - 1] = {log_slot[s2], {cap_head[0], cap_head[1]}};
             }
         }
-        if (c->prof) c->prof_prune_stage_launches = stages;
         launch_rpn_prune_scatter(pr, st);
         for (int i = m->prune_capture ? 0 : 2; i < 5; i++) m->dbg[rn[i]] = {F.rpn_h[i], 2 + i, 15, 0};      // (P2 / P3 head maps are exact only where selected, -FLT_MAX elsewhere: a debug view in capture mode only)
     } else {   // the shared-weight RPN head over the five levels: one launch for the 3x3 conv, one for the fused 1x1 heads
@@ -1445,12 +1437,10 @@ static int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers
     // rows in fc6).  Rows of a GEMM are independent, so the three layers run as ONE problem of V * 1000 rows (level 8: 500 tiles for
     // 64 views, a tile may straddle two views; segments of 32 views keep byte offsets inside 31 bits).  Rows beyond a view's proposal count hold stale finite-or-not data and are never
     // read downstream (post-processing walks r < count); the profile counts FLOPs on the measured rows as before.
-    static const bool roi_dense = !(getenv("CALD_ROI_DENSE") && atoi(getenv("CALD_ROI_DENSE")) == 0);
-    const int lr = roi_dense ? 8 : 7, Vr = roi_dense ? (V + ROI_DENSE_VIEWS - 1) / ROI_DENSE_VIEWS : V;
-    const int* dynr = roi_dense ? nullptr : F.prop_count;
-    if ((rc = conv_on(m, m->fc6, F.roi, F.f6, lr, lr, Vr, true, nullptr, nullptr, 0, dynr))) return rc;
-    if ((rc = conv_on(m, m->fc7, F.f6, F.f7, lr, lr, Vr, true, nullptr, nullptr, 0, dynr))) return rc;
-    if ((rc = conv_on(m, m->pred, F.f7, F.pr, lr, lr, Vr, false, nullptr, nullptr, 0, dynr))) return rc;
+    const int Vr = (V + ROI_DENSE_VIEWS - 1) / ROI_DENSE_VIEWS;
+    if ((rc = conv_on(m, m->fc6, F.roi, F.f6, 8, 8, Vr, true))) return rc;
+    if ((rc = conv_on(m, m->fc7, F.f6, F.f7, 8, 8, Vr, true))) return rc;
+    if ((rc = conv_on(m, m->pred, F.f7, F.pr, 8, 8, Vr, false))) return rc;
     if (c->prof) {
         hipLaunchKernelGGL(accumulate_rows_kernel, dim3(1), dim3(64), 0, st, F.prop_count, V, c->d_roi_rows);
         c->prof_roi_rows_cap += (double)V * CALD_ROI_CAP; c->prof_roi_flops_cap += c->prof_flops - fl_before_roi; c->prof_roi_views += V;
@@ -2014,10 +2004,13 @@ static bool cut_reuse_env() {
     static const bool on = !(getenv("CALD_CUTOUT_REUSE") && atoi(getenv("CALD_CUTOUT_REUSE")) == 0);
     return on;
 }
+// force_dense: the RPN head runs dense even where the model prunes it (the repeat after a pruning tripwire fired)
 static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
-                      const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out) {
+                      const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out,
+                      bool force_dense) {
     if (!m || !images_dev || !H || !W || !pool_pos || !cfg || !consistency_out || !cls_corr_out) return fail(CALD_ERR_INVALID, "null argument");
     const bool audit = margins_out != nullptr;
+    const bool prune_ok = !audit && !force_dense;      // the audit wants every anchor's own logit: dense RPN head
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
     cald_ctx* c = m->ctx;
     HIPCHK(hipSetDevice(c->device));
@@ -2037,11 +2030,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     int B = cfg->batch_images > 0 ? cfg->batch_images : 64;
     if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
     const int VT = B * (1 + A);
-    static const bool pipelined = !(getenv("CALD_SWEEP_PIPELINE") && atoi(getenv("CALD_SWEEP_PIPELINE")) == 0);   // 0: one batch at a time (A/B)
     const int NB = (n_images + B - 1) / B;
-    // the second set of detection buffers exists only when two batches are really in flight (a one-batch shard, or several ranks
-    // rehearsing on one GPU with the pipeline off, would pay VT x cap x C floats of HBM for nothing)
-    const bool two_sets = pipelined && NB > 1;
+    // the second set of detection buffers exists only when two batches are really in flight (a one-batch shard would pay VT x cap x C
+    // floats of HBM for nothing)
+    const bool two_sets = NB > 1;
     { int rc0 = ensure_sweep_det(m, VT); if (rc0) return rc0; }
     if (two_sets) { int rc0 = ensure_sweep_det2(m, VT); if (rc0) return rc0; }
     DetBuffers* const DS[2] = {&m->sweep_det, two_sets ? &m->sweep_det2 : &m->sweep_det};
@@ -2090,11 +2082,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     }
     int rc = 0;
     const int fwd_views = sweep_fwd_views();
-    if (m->prune && !audit) HIPCHK(hipMemsetAsync(c->d_prune_check, 0, 8, c->stream));
+    if (m->prune && prune_ok) HIPCHK(hipMemsetAsync(c->d_prune_check, 0, 8, c->stream));
     // ---- cut_out reuse (exact fp32, conv_p4.hip's gathered rows): the reference forward keeps the block outputs of the first three stages,
     // and the batch's first cut_out augmentation recomputes only its dirty pixels over them ----
     const bool retina = m->cfg.arch == CALD_ARCH_RETINANET;
-    static const bool p4_on = !(getenv("CALD_CONV_P4") && atoi(getenv("CALD_CONV_P4")) == 0);
     int cut_a = -1;
     for (int a = 0; a < A && cut_a < 0; a++) if (cfg->augs[a].kind == CALD_AUG_CUTOUT) cut_a = a;
     int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
@@ -2104,7 +2095,7 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         nblk++;
         if (Bk.layer_end) layer++;
     }
-    const bool reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && p4_on && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
+    const bool reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
     std::vector<BatchPlan> rplan(reuse ? 1 : 0);
     auto plan_of = [&](int nv, const ViewDesc* vs, BatchPlan& P) {
         int hp[CALD_MAX_VIEWS][2];
@@ -2147,7 +2138,7 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
             if (R.slot[q]) { ru.mode = 1; ru.nblk = nblk; retain_layout(rplan[0], b.nb, R.slot[q], ru.out); b.kept = true; }
             else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
         }
-        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, !audit, b.kept ? &ru : nullptr);     // the audit wants every anchor's own logit: dense RPN head
+        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, prune_ok, b.kept ? &ru : nullptr);
         if (r) return r;
         if (hipMemcpyAsync(b.h_count, D.count, (size_t)b.nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(b.h_boxes, D.boxes, (size_t)b.nb * cap * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -2156,7 +2147,6 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     };
     // gather plan of batch k's cut_out forward (V views in the reference forward's order) into the pinned set k & 1, one H2D, and `ru`
     auto cut_plan = [&](int k, int V, const ViewDesc* vs, FwdReuse& ru) -> int {
-        static const double cut_max = getenv("CALD_CUTOUT_REUSE_MAX") ? atof(getenv("CALD_CUTOUT_REUSE_MAX")) : 0.7;
         cald_model::CutReuse& R = m->cr;
         const size_t per = cut_plan_set_bytes(V), total = per * 2 * (size_t)nblk;
         if (!R.d_gp) {
@@ -2203,10 +2193,10 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
                 cost_g[st] += 128.0 * tiles * w; cost_d[st] += dense * w;
                 rows_g[st] += rows * nconv; rows_d[st] += dense * nconv;
             }
-        // a stage runs gathered while its tiles cost at most cut_max of the dense stage (the rest pays the halo, the per-view tile tails
-        // and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
+        // a stage runs gathered while its tiles cost at most CUT_GATHER_MAX_COST of the dense stage (the rest pays the halo, the per-view
+        // tile tails and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
         for (int st = 0; st < 3; st++) {
-            ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= cut_max * cost_d[st];
+            ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= CUT_GATHER_MAX_COST * cost_d[st];
             c->cut_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_dense[st] += rows_d[st];
         }
         if (hipMemcpyAsync(R.d_gp, h, total, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of the cut_out gather plan failed");
@@ -2412,7 +2402,7 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
             b.view_img = nimg; b.view_aug = naug; b.view_inert = ninert;
             FwdReuse ru;
             if ((r = cut_plan(k, nb, cutv.data(), ru))) return r;
-            if ((r = forward_model(m, nb, cutv.data(), det_at((size_t)nb), nullptr, !audit, &ru))) return r;
+            if ((r = forward_model(m, nb, cutv.data(), det_at((size_t)nb), nullptr, prune_ok, &ru))) return r;
             VV = 2 * nb + nr2; n_rest = nr2; rest_slot = 2 * nb; rest_views = rest.data();
         } else if (b.kept) {
             c->cut_fallbacks++;
@@ -2421,7 +2411,7 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         for (int f = 0; f < n_fw; f++) {
             const int a0 = (int)(((long long)n_rest * f) / n_fw), nv = (int)(((long long)n_rest * (f + 1)) / n_fw) - a0;
             const size_t o = (size_t)(rest_slot + a0);
-            if ((r = forward_model(m, nv, const_cast<ViewDesc*>(rest_views) + a0, det_at(o), audit ? d_vm[k & 1] + o * CALD_VM : nullptr, !audit))) return r;
+            if ((r = forward_model(m, nv, const_cast<ViewDesc*>(rest_views) + a0, det_at(o), audit ? d_vm[k & 1] + o * CALD_VM : nullptr, prune_ok))) return r;
         }
         // ---- scoring ----
         const int P = (int)pair_ref.size();
@@ -2456,19 +2446,15 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
     // the reference forward of batch k + 1, and reads batch k's scores while batch k + 1 is on the GPU
     if (NB > 0) rc = enqueue_ref(0);
     for (int k = 0; k < NB && !rc; k++) {
-        if (pipelined && k + 1 < NB) {
+        if (k + 1 < NB) {
             if ((rc = finish(k - 1))) break;              // set (k + 1) & 1 is batch k - 1's: its means first (its scores are long back)
             if ((rc = enqueue_ref(k + 1))) break;
         }
         if ((rc = enqueue_aug_and_score(k))) break;
-        if (!pipelined) {
-            if ((rc = finish(k))) break;
-            if (k + 1 < NB && (rc = enqueue_ref(k + 1))) break;
-        }
     }
     for (int k = (NB >= 2 ? NB - 2 : 0); k < NB && !rc; k++) rc = finish(k);
     if (rc) hipStreamSynchronize(c->stream);
-    if (!rc && m->prune && !audit && NB > 0) {
+    if (!rc && m->prune && prune_ok && NB > 0) {
         // the certified pruning's two tripwires: the bound, checked on every anchor that was evaluated both ways (15 - 60 % of P2 / P3), and the
         // range of the split (an activation of |x| >= 4094 or a non-finite one).  Either one voids the certificate on this data: the results
         // just computed are discarded and the same call is repeated with the dense head, which needs neither (it used to fail)
@@ -2478,22 +2464,20 @@ static int sweep_impl(cald_model* m, int n_images, const uint8_t* const* images_
         if (chk[0] == chk[0] && !range) c->prune_worst = chk[0] > c->prune_worst ? chk[0] : c->prune_worst;
         if (!(chk[0] <= 1.0f) || range) {
             c->prune_fallbacks++;
-            m->prune = false;
-            rc = sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out);
-            m->prune = true;
+            rc = sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, true);
         }
     }
     return rc;
 }
 extern "C" int cald_sweep(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                           const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out) {
-    return sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, nullptr);
+    return sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, nullptr, false);
 }
 extern "C" int cald_sweep_audit(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                                 const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out,
                                 float* margins_out) {
     if (!margins_out) return fail(CALD_ERR_INVALID, "null argument");
-    return sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out);
+    return sweep_impl(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, false);
 }
 
 

@@ -80,7 +80,6 @@ struct ConvArgs {
     int out_ld;            // output row stride in floats (== Cout normally)
     const float* zeros;    // >= 16 bytes of zeros, 16-byte aligned (source of out-of-image taps)
     int in_relu;           // apply ReLU to the input while gathering (LastLevelP6P7: p7(relu(p6)))
-    int exp_flags;         // kernel-tuning experiments only (0 in the product path): bit 0 = skip the output stores
     // training backward only (train.hip; honoured by conv_p4.hip): after everything else, out = mask > 0 ? out : 0 -- the ReLU backward
     // of the layer whose saved post-ReLU output `mask` (same geometry and row stride as out) this data gradient flows into; else null
     const float* mask;
@@ -95,7 +94,7 @@ struct ConvArgs {
     unsigned* out16;
     // conv_p4.hip, exact mode, the FPN output convs of P2 / P3 under the certified RPN pruning (rpn_prune.hip): per pixel four partial sums of
     // squares over the 256 output channels ([pixel][4]: n-tile x wave column, 64 channels each) -- the energy the pruning's bound needs -- and,
-    // through out16, the split-fp16 copy its look-ahead conv reads.  Both were a separate pass over P2 / P3 (prune_energy_kernel) in round 5.
+    // through out16, the split-fp16 copy its look-ahead conv reads.
     float* energy4;
     int ex16;              // `residual` / `up` point at a split-form tensor (same element count) instead of an fp32 one
     // tuning only (cald_op_conv_bench under CALD_CONV_TRACE; null in the product path): per workgroup eight 64-bit words -- s_memtime at

@@ -170,12 +170,8 @@ __device__ __forceinline__ void conv_h4_body(const ConvArgs& a, const int blk) {
     // barrier; the four DMA pieces of stage kt + 4 are placed in program order after the 4th, 8th, 12th and 16th of the step's 24 MFMAs
     // (pinned with sched_barrier).  A piece costs the issuing wave ~60-180 cycles (MI355X_MICROARCH.md), which only the SIMD's other wave
     // can cover -- and with all four pieces right after the barrier both waves of a SIMD, which leave the barrier together, sit in
-    // their DMA issues at the same time: SQ_VALU_MFMA_BUSY_CYCLES 73 of 128 per XCD-cycle then, 88 now (group launches).
-// H4_VARIANT (compile time, tools/h4_dev.hip): 5 = shipped; 1 = the four pieces up front; 2 / 3 / 4 = TIMING ablations without the DMA /
-// the barrier / the fragment reads -- their results are wrong by construction (profiles/r4_conv_h4_ablations.txt)
-#ifndef H4_VARIANT
-#define H4_VARIANT 5
-#endif
+    // their DMA issues at the same time: SQ_VALU_MFMA_BUSY_CYCLES 73 of 128 per XCD-cycle then, 88 now (group launches;
+    // profiles/r4_conv_h4_ablations.txt).
 #define H4_MFMA4(AX, BX, I0)                                                                                                 \
         _Pragma("unroll") for (int i = (I0); i < (I0) + 2; i++)                                                              \
             _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                    \
@@ -188,31 +184,18 @@ __device__ __forceinline__ void conv_h4_body(const ConvArgs& a, const int blk) {
 #define H4_STEPF(SLOT, AH, AL, BH, BL, NAH, NAL, NBH, NBL)                                                                   \
     {                                                                                                                        \
         asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");                                                          \
-        if (H4_VARIANT != 3) __builtin_amdgcn_s_barrier();                                                                   \
+        __builtin_amdgcn_s_barrier();                                                                                        \
         const int soffA = ((u_kh * Wi_l + u_kw) * Cin + u_ci) * 4, soffB = u_kt * (2 * CoutPad * 32);                        \
         const int soff = ldA ? soffA : soffB;                                                                                \
         const unsigned bit = ldA ? (1u << (u_kh * KW + u_kw)) : 1u;                                                          \
-        if (H4_VARIANT != 4) H4_READ(NAH, NAL, NBH, NBL, ((SLOT) + 1) & 3)                                                   \
-        if (H4_VARIANT == 5) {                                                                                               \
-            /* pieces in program order BETWEEN the MFMAs: the two waves of a SIMD leave the barrier together, and with the  */ \
-            /* four pieces up front both sit in their (60-180 cycle) DMA issues at once while the matrix pipe idles          */ \
-            H4_MFMA4(AL, BH, 0) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 0, soff, bit) __builtin_amdgcn_sched_barrier(0);   \
-            H4_MFMA4(AL, BH, 2) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 1, soff, bit) __builtin_amdgcn_sched_barrier(0);   \
-            H4_MFMA4(AH, BL, 0) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 2, soff, bit) __builtin_amdgcn_sched_barrier(0);   \
-            H4_MFMA4(AH, BL, 2) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 3, soff, bit) __builtin_amdgcn_sched_barrier(0);   \
-            H4_MFMA4(AH, BH, 0) H4_MFMA4(AH, BH, 2)                                                                          \
-        } else {                                                                                                             \
-            if (H4_VARIANT != 2) { H4_PIECE(SLOT, 0, soff, bit) H4_PIECE(SLOT, 1, soff, bit) H4_PIECE(SLOT, 2, soff, bit) H4_PIECE(SLOT, 3, soff, bit) } \
-            _Pragma("unroll") for (int i = 0; i < 4; i++)                                                                    \
-                _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL[i], BH[j], acc[i][j], 0, 0, 0);                    \
-            _Pragma("unroll") for (int i = 0; i < 4; i++)                                                                    \
-                _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BL[j], acc[i][j], 0, 0, 0);                    \
-            _Pragma("unroll") for (int i = 0; i < 4; i++)                                                                    \
-                _Pragma("unroll") for (int j = 0; j < 2; j++)                                                                \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH[i], BH[j], acc[i][j], 0, 0, 0);                    \
-        }                                                                                                                    \
+        H4_READ(NAH, NAL, NBH, NBL, ((SLOT) + 1) & 3)                                                                        \
+        /* pieces in program order BETWEEN the MFMAs: the two waves of a SIMD leave the barrier together, and with the  */     \
+        /* four pieces up front both sit in their (60-180 cycle) DMA issues at once while the matrix pipe idles          */     \
+        H4_MFMA4(AL, BH, 0) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 0, soff, bit) __builtin_amdgcn_sched_barrier(0);       \
+        H4_MFMA4(AL, BH, 2) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 1, soff, bit) __builtin_amdgcn_sched_barrier(0);       \
+        H4_MFMA4(AH, BL, 0) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 2, soff, bit) __builtin_amdgcn_sched_barrier(0);       \
+        H4_MFMA4(AH, BL, 2) __builtin_amdgcn_sched_barrier(0); H4_PIECE(SLOT, 3, soff, bit) __builtin_amdgcn_sched_barrier(0);       \
+        H4_MFMA4(AH, BH, 0) H4_MFMA4(AH, BH, 2)                                                                              \
         u_kt++; u_kw++;                                                                                                      \
         const bool ww = u_kw == KW; u_kw = ww ? 0 : u_kw; u_kh += ww ? 1 : 0;                                                \
         const bool wh = u_kh == KH; u_kh = wh ? 0 : u_kh; u_ci += wh ? 16 : 0;                                               \

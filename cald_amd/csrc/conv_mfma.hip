@@ -19,8 +19,6 @@
 //   Epilogue:   (+bias) -> (*bn_scale, +bn_shift) -> (+residual) -> (+nearest-upsampled top-down)
 //               -> ReLU, fused; residual rows are loaded as a batch before the stores.
 #include "common.h"
-#include <cstdio>
-#include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -264,17 +262,13 @@ __global__ __launch_bounds__(256, (BK == 32 ? 2 : 3)) void conv_mfma_f32_kernel(
     }
 }
 
-static int conv_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 template <int WM, int WN, int TM, int TN, int EPI, bool FAST>
-static const char* cfg_go(const ConvArgs& a, const dim3 grid, const int dl, hipStream_t stream, const char* name) {
-    hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, EPI, 16, FAST>), grid, dim3(256), dl, stream, a);
+static const char* cfg_go(const ConvArgs& a, const dim3 grid, hipStream_t stream, const char* name) {
+    hipLaunchKernelGGL((conv_mfma_f32_kernel<WM, WN, TM, TN, EPI, 16, FAST>), grid, dim3(256), 0, stream, a);
     return name;
 }
 #define CFG_NAME(WM, WN, TM, TN, EPI, FAST) "conv_mfma_f32_kernel<" #WM "," #WN "," #TM "," #TN "," #EPI ",16," #FAST ">"
-#define CFG_GO(WM, WN, TM, TN, EPI, FAST) cfg_go<WM, WN, TM, TN, EPI, FAST>(a, grid, dl, stream, CFG_NAME(WM, WN, TM, TN, EPI, FAST))
+#define CFG_GO(WM, WN, TM, TN, EPI, FAST) cfg_go<WM, WN, TM, TN, EPI, FAST>(a, grid, stream, CFG_NAME(WM, WN, TM, TN, EPI, FAST))
 // one tile configuration: the fast path (a k-tile inside one tap: Cin % 16 == 0, at most 32 taps) or the general one, each with the
 // plain / residual / top-down epilogue (the epilogue does not depend on the k-loop variant)
 #define CFG_EPI(WM, WN, TM, TN, FAST) (a.residual ? CFG_GO(WM, WN, TM, TN, 1, FAST) : a.up ? CFG_GO(WM, WN, TM, TN, 2, FAST) : CFG_GO(WM, WN, TM, TN, 0, FAST))
@@ -285,7 +279,6 @@ static const char* cfg_go(const ConvArgs& a, const dim3 grid, const int dl, hipS
 const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream) {
     if (!a.w || !a.out || !a.zeros || a.Cin % 4 != 0 || (a.residual && a.up)) return nullptr;
     if (a.mask || a.gather || a.row_map || a.energy4 || a.out16 || a.in16 || a.ex16) return nullptr;
-    static const int dl = conv_env("CALD_CONV_DYNLDS", 0);   // extra dynamic LDS (experiments): caps workgroups per CU
     const bool fast = (a.Cin % 16 == 0) && (a.KH * a.KW <= 32);
     if (a.CoutPad % 128 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128))); return CFG_LAUNCH(2, 2, 2, 2); }
     if (a.CoutPad % 64 == 0) { const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64))); return CFG_LAUNCH(2, 2, 2, 1); }
@@ -298,16 +291,14 @@ const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream) {
 #undef CFG_NAME
 
 int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream, const char** names, ConvForce f) {
-    static const int grp = conv_env("CALD_CONV_GROUP", 1);
-    static const int p4 = conv_env("CALD_CONV_P4", 1);
     const char* gname = nullptr;
     if (f.path == CONV_P4_GROUP) gname = launch_conv_p4_group(probs, n, stream, f);
     else if (f.path == CONV_H3_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h3_group(probs, n, stream) : nullptr;
     else if (f.path == CONV_H4_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h4_group(probs, n, stream, true) : nullptr;
-    else if (f.path == CONV_AUTO && grp && n > 1) {
+    else if (f.path == CONV_AUTO && n > 1) {
         if (probs[0].w16) gname = launch_conv_h4_group(probs, n, stream);
         if (!gname && probs[0].w16) gname = launch_conv_h3_group(probs, n, stream);
-        if (!gname && !probs[0].w16 && p4) gname = launch_conv_p4_group(probs, n, stream);
+        if (!gname && !probs[0].w16) gname = launch_conv_p4_group(probs, n, stream);
     }
     if (gname || f.path == CONV_P4_GROUP || f.path == CONV_H3_GROUP || f.path == CONV_H4_GROUP) {
         if (names) for (int i = 0; i < n; i++) names[i] = gname;
@@ -332,21 +323,10 @@ const char* launch_conv(const ConvArgs& a, hipStream_t stream, ConvForce f) {
     case CONV_H4: return f.tile == TILE_AUTO ? launch_conv_h4(a, stream, true) : nullptr;
     default: return nullptr;          // group / fused modes have launchers of their own
     }
-    static const int p4 = conv_env("CALD_CONV_P4", 1);   // conv_p4.hip: 3-buffer pipelined schedule, 128-bit LDS fragment reads; 0 = this file only
     const char* k = nullptr;
     if (a.w16 && (k = launch_conv_h4(a, stream))) return k;
     if (a.w16 && (k = launch_conv_h3(a, stream))) return k;
-    static const int stem = conv_env("CALD_CONV_STEM", 1);   // 0: the stem runs on the generic kernels (same bits)
-    if (stem && a.wstem && (k = launch_conv_stem(a, stream))) return k;
-    if (p4 && (k = launch_conv_p4(a, stream))) return k;
-    if (a.gather) {                    // likewise the gathered-and-scattered rows of the cut_out reuse (api.hip checks before it turns it on)
-        fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with gather support; launch skipped\n", a.Cin, a.Cout);
-        return nullptr;
-    }
-    if (a.row_map) {                   // gathered rows exist in conv_p4.hip only (api.hip switches the pruning off when CALD_CONV_P4=0):
-                                         // never compute the wrong rows silently -- the sweep's bound check then sends it to the dense head
-        fprintf(stderr, "cald: a gathered conv launch (Cin=%d Cout=%d) found no kernel with row_map support; launch skipped\n", a.Cin, a.Cout);
-        return nullptr;
-    }
+    if (a.wstem && (k = launch_conv_stem(a, stream))) return k;
+    if ((k = launch_conv_p4(a, stream))) return k;
     return launch_conv_generic(a, stream);
 }

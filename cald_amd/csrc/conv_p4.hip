@@ -10,7 +10,6 @@
 //     coalesced 16-byte loads + ds_write_b128; A is staged with two ds_write_b64 per gathered float4.
 //   Per k-tile and wave: 32 MFMA, 8 ds_read_b128, 6 LDS writes, 4 buffer loads, ~10 VALU.
 #include "h16.h"
-#include <cstdlib>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -48,13 +47,12 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
     const int row_b = out_ld * 4;
     // The descriptors of everything addressed by output row END at the view's last valid row: a row past it loads zeros and its store is
     // dropped by the hardware, so a view's last, partial tile runs the same branch-free code as a full one (no per-element row tests, no
-    // 64-bit addresses).  A lane of a padded output channel uses an offset beyond any descriptor.  (exp_flags bit 0, a tuning experiment:
-    // a zero-sized output descriptor drops every store.)
+    // 64-bit addresses).  A lane of a padded output channel uses an offset beyond any descriptor.
     // gathered rows (ConvArgs::gather): row m goes to its own pixel of the full tensor -- the descriptors span the whole view, and a row
     // past the view's count gets the out-of-range offset instead
     const unsigned long long vb64 = (unsigned long long)(GATHER ? Ho * Wo : Mv) * (unsigned)row_b;
     const unsigned valid_b = vb64 < 0x7FFE0000ull ? (unsigned)vb64 : 0x7FFE0000u;
-    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc((void*)out_v, 0, (a.exp_flags & 1) ? 0 : valid_b, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsO = __builtin_amdgcn_make_buffer_rsrc((void*)out_v, 0, valid_b, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI != 0 ? ex_v : out_v), 0, EPI == 1 ? valid_b : 0x7FFE0000, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc((void*)mask_v, 0, valid_b, 0x00020000);
     // FPN top-down (EPI 2): the nearest-neighbour source pixel of each of the tile's 128 rows is computed ONCE (one thread per
@@ -89,8 +87,8 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
         }
     };
     // The FPN output convs of P2 / P3 under the certified RPN pruning also leave (i) the split-fp16 copy of their output (h16.h) for the
-    // look-ahead conv and (ii) per pixel the sum of squares over this wave's 64 channels for the bound -- what prune_energy_kernel did in a
-    // second pass over the tensor.  Compiled into the plain (EPI 0, no mask) kernels only; wave-uniform branches elsewhere.
+    // look-ahead conv and (ii) per pixel the sum of squares over this wave's 64 channels for the bound, so the pruning needs no second pass
+    // over the tensor.  Compiled into the plain (EPI 0, no mask) kernels only; wave-uniform branches elsewhere.
     constexpr bool EXTRA = EPI == 0 && !MASK && !GATHER;
     const bool want16 = EXTRA && a.out16 != nullptr, wantE = EXTRA && TN == 2 && a.energy4 != nullptr;      // energy4 has four slots: 2 n-tiles of 128 x 2 wave columns (Cout = 256)
     unsigned char* const out16_v = want16 ? reinterpret_cast<unsigned char*>(a.out16) + so.pix_off * (long long)out_ld * 4 : nullptr;
@@ -638,14 +636,11 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             float ex[2][16];
 #pragma unroll
             for (int i = 0; i < 2; i++) vo3[i] = ((m0 + wm * 64 + i * 32 + 4 * kh_lane) * ld3 + n3) * 4;
-            const bool late = (b.exp_flags & 2) != 0;           // tuning experiment (CALD_P4_FUSE_LATE=1): load them after the MFMAs instead
-            if (!late) {
 #pragma unroll
-                for (int i = 0; i < 2; i++)
+            for (int i = 0; i < 2; i++)
 #pragma unroll
-                    for (int r = 0; r < 16; r++)
-                        ex[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX3, vo3[i], ((r & 3) + 8 * (r >> 2)) * ld3 * 4, 0));
-            }
+                for (int r = 0; r < 16; r++)
+                    ex[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX3, vo3[i], ((r & 3) + 8 * (r >> 2)) * ld3 * 4, 0));
             __builtin_amdgcn_sched_barrier(0);                  // keep the scheduler from sinking them to their first use
             f32x16 acc2[2][1];
 #pragma unroll
@@ -675,13 +670,6 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             // the rows of a partial tile need no per-element test (loads beyond the end return 0, stores are dropped)
             {
                 const float sc3 = b.scale[n3], sh3 = b.shift[n3];
-                if (late) {
-#pragma unroll
-                    for (int i = 0; i < 2; i++)
-#pragma unroll
-                        for (int r = 0; r < 16; r++)
-                            ex[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX3, vo3[i], ((r & 3) + 8 * (r >> 2)) * ld3 * 4, 0));
-                }
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
 #pragma unroll
@@ -716,13 +704,9 @@ __global__ __launch_bounds__(256, 3) void conv_p4_group_kernel(const ConvGroup g
 // bottleneck conv2 + conv3 in one launch (the two problems of a ConvGroup: p[0] = conv2, p[1] = conv3); 48 KB of LDS -> 3 workgroups / CU
 __global__ __launch_bounds__(256, 3) void conv_p4_fused_kernel(const ConvGroup g) { conv_p4_body<8, false, 1, 9>(g.p[0], blockIdx.x, &g.p[1]); }
 
-// CALD_P4_EXP: kernel-tuning experiments (tools/bench_conv.py): bit 0 = drop the output stores
-static inline int p4_exp_env() { static const int e = getenv("CALD_P4_EXP") ? atoi(getenv("CALD_P4_EXP")) : 0; return e; }
-
 // filter shape -> k-loop variant
 static inline int p4_taps(const ConvArgs& a) {
-    static const int unroll_env = getenv("CALD_P4_UNROLL") ? atoi(getenv("CALD_P4_UNROLL")) : 1;      // 0: generic rolled loop everywhere
-    if (!unroll_env || a.Cin % 16 != 0) return 0;
+    if (a.Cin % 16 != 0) return 0;
     if (a.KH == 3 && a.KW == 3) return 9;
     if (a.KH == 1 && a.KW == 1) return 1;
     return 0;
@@ -749,8 +733,8 @@ static inline bool p4_tile_ok(const ConvArgs& a, const bool wide, const ConvForc
 
 #define P4_NAME(K, EPIV, C4V, TNV, TAPSV) K "<" #EPIV "," #C4V "," #TNV "," #TAPSV ">"
 template <int EPI, bool C4, int TN, int TAPS>
-static const char* p4_go(const dim3 grid, const int lds, hipStream_t stream, const ConvArgs& a, const char* name) {
-    hipLaunchKernelGGL((conv_p4_kernel<EPI, C4, TN, TAPS>), grid, dim3(256), lds, stream, a);
+static const char* p4_go(const dim3 grid, hipStream_t stream, const ConvArgs& a, const char* name) {
+    hipLaunchKernelGGL((conv_p4_kernel<EPI, C4, TN, TAPS>), grid, dim3(256), 0, stream, a);
     return name;
 }
 template <int EPI, int TN, int TAPS>
@@ -770,7 +754,7 @@ const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, C
         if (a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return nullptr;
         if ((a.mask != nullptr) != (p[0].mask != nullptr)) return nullptr;
         if (a.mask && (a.out16 || a.energy4)) return nullptr;
-        g.blk0[i] = blk; blk += p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a; g.p[i].exp_flags = 0;
+        g.blk0[i] = blk; blk += p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a;
     }
     g.blk0[n] = blk;
     const int taps = p4_taps(p[0]);
@@ -788,42 +772,35 @@ const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, C
 // conv2 (3 x 3, stride 1, 64 -> 64, BN + ReLU) followed by conv3 (1 x 1, 64 -> 128 k channels, BN + residual + ReLU) on the same pixels:
 // the kernel if the fused kernel took both (same bits as the two separate launches), else nullptr
 const char* launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStream_t stream) {
-    static const int on = getenv("CALD_P4_FUSE") ? atoi(getenv("CALD_P4_FUSE")) : 1;
-    if (!on || !c2.w4 || !c3.w4 || c2.w16 || c3.w16) return nullptr;
+    if (!c2.w4 || !c3.w4 || c2.w16 || c3.w16) return nullptr;
     if (c2.KH != 3 || c2.KW != 3 || c2.stride != 1 || c2.pad != 1 || c2.Cin % 16 || c2.Cout != 64 || c2.CoutPad != 64 || c2.out_ld != 64) return nullptr;
     if (c2.residual || c2.up || c2.mask || c2.dyn_rows || c2.in_relu || c2.gather || c3.gather || p4_taps(c2) != 9) return nullptr;
     if (c3.KH != 1 || c3.KW != 1 || c3.stride != 1 || c3.pad != 0 || c3.Cin != 64 || c3.Kpad != 64 || c3.CoutPad % 64 || c3.Cout != c3.CoutPad) return nullptr;
     if (!c3.residual || !c3.scale || c3.bias || c3.out_ld != c3.Cout || c3.up || c3.mask || c3.dyn_rows || c3.in_relu || c3.in != c2.out || c3.total_mtiles != c2.total_mtiles || c3.V != c2.V) return nullptr;
     if (c2.row_map || c3.row_map || c2.in16 || c3.in16 || c2.out16 || c3.out16 || c2.energy4 || c3.energy4 || c2.ex16 || c3.ex16 || !c3.out) return nullptr;
-    ConvGroup g; g.n = 2; g.blk0[0] = 0; g.p[0] = c2; g.p[1] = c3; g.p[0].exp_flags = 0;
-    static const int late_env = getenv("CALD_P4_FUSE_LATE") ? atoi(getenv("CALD_P4_FUSE_LATE")) : 0;
-    g.p[1].exp_flags = late_env ? 2 : 0;
+    ConvGroup g; g.n = 2; g.blk0[0] = 0; g.p[0] = c2; g.p[1] = c3;
     const unsigned grid = (unsigned)p4_grid_mtiles(c2);          // one workgroup per 128-row tile (conv2's only N tile)
     hipLaunchKernelGGL(conv_p4_fused_kernel, dim3(grid), dim3(256), 0, stream, g);
     return "conv_p4_fused_kernel";
 }
 
 // the kernel if this variant handled the launch, else nullptr
-const char* launch_conv_p4(const ConvArgs& a_in, hipStream_t stream, ConvForce f) {
-    if (p4_refuses(a_in)) return nullptr;
-    const int exp_env = p4_exp_env();
-    static const int pad_lds = getenv("CALD_P4_PADLDS") ? atoi(getenv("CALD_P4_PADLDS")) : 0;    // extra dynamic LDS: caps workgroups per CU
-    ConvArgs a = a_in; a.exp_flags = exp_env;
+const char* launch_conv_p4(const ConvArgs& a, hipStream_t stream, ConvForce f) {
+    if (p4_refuses(a)) return nullptr;
     bool wide = a.CoutPad % 128 == 0;
     if (wide) {
         // tail quantisation: a launch of B equal workgroups on 768 slots (256 CUs x 3) runs at B / (ceil(B / 768) * 768); the
         // 128 x 64 tile doubles B at ~0.88 of the 128 x 128 tile's per-workgroup efficiency -- use it where that wins (never with
         // energy4: only the wide tile writes it)
-        static const int narrow_env = getenv("CALD_CONV_NARROW") ? atoi(getenv("CALD_CONV_NARROW")) : 1;
         const long long b2 = (long long)a.total_mtiles * (a.CoutPad / 128), b1 = 2 * b2;
         const double e2 = (double)b2 / (double)(((b2 + 767) / 768) * 768), e1 = 0.88 * (double)b1 / (double)(((b1 + 767) / 768) * 768);
-        if (narrow_env && e1 > e2 && !a.dyn_rows && !a.energy4) wide = false;
+        if (e1 > e2 && !a.dyn_rows && !a.energy4) wide = false;
     }
     if (f.tile == TILE_NARROW) wide = false;
     else if (f.tile == TILE_WIDE) wide = a.CoutPad % 128 == 0;
     if (!p4_tile_ok(a, wide, f)) return nullptr;
     const dim3 grid((unsigned)(p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64))));
-#define P4_ONE(EPIV, C4V, TNV, TAPSV) p4_go<EPIV, C4V, TNV, TAPSV>(grid, pad_lds, stream, a, P4_NAME("conv_p4_kernel", EPIV, C4V, TNV, TAPSV))
+#define P4_ONE(EPIV, C4V, TNV, TAPSV) p4_go<EPIV, C4V, TNV, TAPSV>(grid, stream, a, P4_NAME("conv_p4_kernel", EPIV, C4V, TNV, TAPSV))
     if (a.gather) {      // gathered rows: the unrolled 1 x 1 / 3 x 3 kernels, BN (+ residual) epilogue
         const int taps = p4_taps(a);
         if (a.Cin == 4 || a.up || a.mask || a.in_relu || a.dyn_rows || a.row_map || (taps != 1 && taps != 9)) return nullptr;
@@ -834,8 +811,7 @@ const char* launch_conv_p4(const ConvArgs& a_in, hipStream_t stream, ConvForce f
     }
     if (a.Cin == 4) {
         if (a.residual || a.up || a.in_relu || a.mask) return nullptr;
-        static const int stem_env = getenv("CALD_P4_UNROLL") ? atoi(getenv("CALD_P4_UNROLL")) : 1;
-        if (stem_env && a.KH == 7 && a.KW == 7 && a.Kpad == 208)       // unrolled stem: per-k-tile tap offsets precomputed
+        if (a.KH == 7 && a.KW == 7 && a.Kpad == 208)       // unrolled stem: per-k-tile tap offsets precomputed
             return wide ? P4_ONE(0, true, 2, 13) : P4_ONE(0, true, 1, 13);
         return wide ? P4_ONE(0, true, 2, 0) : P4_ONE(0, true, 1, 0);
     }

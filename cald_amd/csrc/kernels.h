@@ -147,17 +147,13 @@ void launch_cls_corr(const DetBuffers& det, const int* ref_sel, const int* ref_n
 
 // rpn_prune.hip -- certified pruning of the RPN head on P2 / P3 in the exact sweep (the file's header has the argument)
 struct RpnPruneArgs {
-    const float* feat[2];        // P2, P3: fp32 [pixel][256]
-    const LevelSeg* seg[2];
-    float* energy[2];            // [pixel][energy_parts] scratch: sum of squares over the 256 channels (4 partial sums of 64 channels each when the FPN
-                                 // output conv's epilogue wrote them, ConvArgs::energy4; 1 when prune_energy_kernel did)
-    unsigned* split[2];          // optional [pixel][256] words: the split-fp16 form of P2 / P3 (h16.h) written by the energy kernel for the look-ahead conv
+    const LevelSeg* seg[2];      // P2, P3
+    float* energy[2];            // [pixel][4]: sums of squares over the 256 channels, 64 channels each (the FPN output conv's epilogue, ConvArgs::energy4)
     float* pnorm[2];             // [pixel] scratch: |3 x 3 patch|_2 (select kernel -> scatter kernel)
     const float* head[2];        // approximate head maps [pixel][head_ld] (logits = channels 0..2)
     float* head_out[2];          // the same buffers: unselected pixels get logit -FLT_MAX, selected ones their exact rows
     // Two selection stages (rpn_prune.hip): stage 0 = the pixels holding an anchor whose LOWER bound reaches tau (at least k anchors: their exact
-    // logits give a sharper threshold), stage 1 = the remaining pixels with an upper bound at or above that threshold.  Single-stage mode
-    // (stages == 1, round 5's rule) uses the stage-0 arrays only.
+    // logits give a sharper threshold), stage 1 = the remaining pixels with an upper bound at or above that threshold.
     const float* head_rows[2][2];   // [stage][level] exact head rows of the selected pixels, compact [n_selected][head_ld] per view (at the view's pixel offset)
     int* row_map[2][2];          // [stage][level]: [pixel] -> selected pixel index, compact per view
     int* nsel[2];                // [stage]: [2][V] selected pixels per (level, view): the dyn_rows of the gathered launches
@@ -166,10 +162,9 @@ struct RpnPruneArgs {
     unsigned long long* log[2];  // optional, per stage [4]: the same counts of THIS forward's stage only (cald_profile_dump books the gathered launches with them), or null
     float* check;                // [2]: running max of |look-ahead - exact| / bound over the selected anchors (must stay <= 1); 1.0f once an activation left the split's range
     float c1[3], c0[3];          // bound per anchor: c1 * |patch|_2 + c0
-    int head_ld, pre_n, V, energy_parts, stages;
+    int head_ld, pre_n, V;
 };
-void launch_rpn_prune_energy(const RpnPruneArgs& a, hipStream_t st);       // before the look-ahead conv (writes its split-form input)
-void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipStream_t st);   // stage 0 (or the only one), then -- after stage 0's exact rows exist -- stage 1
+void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipStream_t st);   // stage 0, then -- after stage 0's exact rows exist -- stage 1
 void launch_rpn_prune_scatter(const RpnPruneArgs& a, hipStream_t st);
 
 // audit.hip -- decision margins of one Faster R-CNN forward (cascade mode: which images may differ from the exact mode by more than

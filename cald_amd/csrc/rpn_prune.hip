@@ -38,38 +38,13 @@
 // (tests: test_rpn_pruning_bound_holds_on_every_anchor) evaluates the bound on every anchor of P2 / P3, pruned ones included.
 #include "common.h"
 #include "kernels.h"
-#include "h16.h"
 #include <cfloat>
 
 namespace {
-// per pixel: sum over the 256 channels of P^2 -- and, on the way, the split-fp16 form of the pixel (h16.h) for the look-ahead conv: with it
-// the look-ahead runs on conv_h4 (operands HBM -> LDS by DMA, no split arithmetic in its k-loop) instead of conv_h3's fp32 loader; the
-// tensor is being read here anyway.  One wavefront per pixel (float4 per lane), 4 pixels per workgroup.
-__global__ __launch_bounds__(256) void prune_energy_kernel(RpnPruneArgs a, int l) {
-    const int v = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const LevelSeg sg = a.seg[l][v];
-    const int n = sg.H * sg.W;
-    const float4* f = reinterpret_cast<const float4*>(a.feat[l] + sg.pix_off * 256ll);
-    for (int p = blockIdx.x * 4 + wave; p < n; p += gridDim.x * 4) {
-        const float4 x = f[(long long)p * 64 + lane];
-        if (a.split[l]) h16_store4(reinterpret_cast<unsigned char*>(a.split[l]) + (sg.pix_off + p) * 1024ll, 4 * lane, x);
-        float s = (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s = s + __shfl_xor(s, off, 64);
-        if (lane == 0) {
-            a.energy[l][sg.pix_off + p] = s;
-            // |x| >= 4094 would leave fp16's range after the split's 2^4 scale (the look-ahead's hi half becomes inf) and a non-finite activation
-            // voids every bound: either is visible in the pixel's energy (|x| >= 4094 => s >= 4094^2).  Flag it: the sweep then repeats itself with
-            // the dense head (api.hip) -- a pruned anchor is never evaluated both ways, so this cannot be left to the check on the selected ones.
-            if (!(s < 16760836.0f) && a.check) atomicMax(reinterpret_cast<unsigned*>(a.check) + 1, __float_as_uint(1.0f));
-        }
-    }
-}
-
 // per (level, view): tau by radix select over the lower bounds, the pixel mask, the ordered list of selected pixels.
 // grid = (2, V), block = 1024, dynamic LDS = one bit per pixel.
 // (the 1.0001 covers the fp32 rounding of the 9 x 256 squares' sum in whatever order: <= 2 304 u = 1.4e-4 relative, half of it after the root)
-__device__ __forceinline__ float prune_patch_norm(const float* e, int parts, int y, int x, int H, int W) {
+__device__ __forceinline__ float prune_patch_norm(const float* e, int y, int x, int H, int W) {
     float s = 0.0f;
 #pragma unroll
     for (int dy = -1; dy <= 1; dy++)
@@ -77,15 +52,14 @@ __device__ __forceinline__ float prune_patch_norm(const float* e, int parts, int
         for (int dx = -1; dx <= 1; dx++) {
             const int yy = y + dy, xx = x + dx;
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const float* q = e + (yy * W + xx) * parts;
-                s = s + (parts == 4 ? (q[0] + q[1]) + (q[2] + q[3]) : q[0]);
+                const float* q = e + (yy * W + xx) * 4;
+                s = s + ((q[0] + q[1]) + (q[2] + q[3]));
             }
         }
     return sqrtf(s) * 1.0001f;
 }
-// MODE 0: the single-stage rule (round 5): select every pixel holding an anchor whose upper bound reaches tau, park the rest.
-// MODE 1: stage 0 of the two-stage rule: tau as above (kept in a.tau_key), select the pixels holding an anchor whose LOWER bound reaches tau -- at
-//         least k anchors, the ones that are certainly good.  Nothing is parked yet.
+// MODE 1: stage 0: tau = the k-th largest lower bound (kept in a.tau_key), select the pixels holding an anchor whose LOWER bound reaches tau --
+//         at least k anchors, the ones that are certainly good.  Nothing is parked yet.
 // MODE 2: stage 1: the exact logits of stage 0's pixels are known now (a.head_rows[0]); tau' = the k-th largest of them is a threshold that k
 //         real anchors reach, so an anchor with upper bound < max(tau, tau') cannot be among the k largest.  Select the remaining pixels whose
 //         upper bound reaches it, park everything selected by neither stage.  The band of "maybe" anchors below the threshold is one bound wide
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
     const int k = n < a.pre_n ? n : a.pre_n;
     const int ld = a.head_ld;
     const float* head = a.head[l] + sg.pix_off * (long long)ld;
-    const float* en = a.energy[l] + sg.pix_off * a.energy_parts;
+    const float* en = a.energy[l] + sg.pix_off * 4;
     float* pnv = a.pnorm[l] + sg.pix_off;           // |patch|_2 per pixel: written once below, re-read by the SAME thread in every pass (and by the scatter kernel)
     constexpr int ST = MODE == 2 ? 1 : 0;           // which stage's row list this launch writes
     int* rmap = a.row_map[ST][l] + sg.pix_off;
@@ -113,14 +87,16 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
     auto bound = [&](int an, float pn) { return a.c1[an] * pn + a.c0[an]; };
     if (MODE != 2) {
         for (int p = tid; p < npx; p += 1024) {
-            const float pn = prune_patch_norm(en, a.energy_parts, p / W, p % W, H, W);
+            const float pn = prune_patch_norm(en, p / W, p % W, H, W);
             pnv[p] = pn;
-            // the range of the split (see prune_energy_kernel): a patch norm below 4094 means every |x| in the patch is; anything else -- a large
-            // activation, inf, NaN -- sends the sweep back to the dense head
+            // the range of the split: |x| >= 4094 would leave fp16's range after the split's 2^4 scale (the look-ahead's hi half becomes inf),
+            // and a non-finite activation voids every bound.  A patch norm below 4094 means every |x| in the patch is below it; anything else --
+            // a large activation, inf, NaN -- sends the sweep back to the dense head (a pruned anchor is never evaluated both ways, so this
+            // cannot be left to the check on the selected ones)
             if (!(pn < 4094.0f) && a.check) atomicMax(reinterpret_cast<unsigned*>(a.check) + 1, __float_as_uint(1.0f));
         }
     }
-    // ---- the k-th largest of: the lower bounds over all anchors (MODE 0, 1) / the exact logits of stage 0's pixels (MODE 2) ----
+    // ---- the k-th largest of: the lower bounds over all anchors (MODE 1) / the exact logits of stage 0's pixels (MODE 2) ----
     const int ns0 = MODE == 2 ? a.nsel[0][l * a.V + v] : 0;
     const float* rows0 = MODE == 2 ? a.head_rows[0][l] + sg.pix_off * (long long)ld : nullptr;
     const bool all_kept = n <= k;
@@ -171,7 +147,6 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
             const float lg = head[(long long)p * ld + an];
             const float B = bound(an, pn);
             const float ub = lg + B, lb = lg - B;
-            if (MODE == 0) keep = keep || !(ub == ub) || det_orderable(ub) >= tau;             // NaN: never pruned
             if (MODE == 1) keep = keep || !(lb == lb) || det_orderable(lb) >= tau;
             if (MODE == 2) { first = first || !(lb == lb) || det_orderable(lb) >= tau_lb; keep = keep || !(ub == ub) || det_orderable(ub) >= tau; }
         }
@@ -209,18 +184,12 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
         if (a.stat) { atomicAdd(a.stat + 2 * l, (unsigned long long)base); if (MODE != 2) atomicAdd(a.stat + 2 * l + 1, (unsigned long long)npx); }
         if (a.log[ST]) { atomicAdd(a.log[ST] + 2 * l, (unsigned long long)base); atomicAdd(a.log[ST] + 2 * l + 1, (unsigned long long)npx); }
     }
-    if (MODE == 0) {
-        // unselected pixels: their three logits can never reach the top-k -- park them below every real logit
-        float* headw = a.head_out[l] + sg.pix_off * (long long)ld;
-        for (int p = tid; p < npx; p += 1024)
-            if (!((mask[p >> 5] >> (p & 31)) & 1u)) { headw[(long long)p * ld] = -FLT_MAX; headw[(long long)p * ld + 1] = -FLT_MAX; headw[(long long)p * ld + 2] = -FLT_MAX; }
-    }
 }
 
 // the exact head rows of the selected pixels back into the dense [pixel][head_ld] map -- and the bound put to the test: every selected anchor
 // has both values, the look-ahead's L~ (still in the map) and the exact L; max |L~ - L| / B over all of them goes to a.check[0]
 // (non-negative floats order like their bit patterns).  A ratio above 1 means the bound does not hold on this data: the sweep then repeats
-// itself with the dense head (api.hip).  grid = (blocks, V, 2 * stages): z = level + 2 * stage
+// itself with the dense head (api.hip).  grid = (blocks, V, 4): z = level + 2 * stage
 __global__ __launch_bounds__(256) void prune_scatter_kernel(RpnPruneArgs a) {
     const int l = blockIdx.z & 1, st = blockIdx.z >> 1, v = blockIdx.y;
     const LevelSeg sg = a.seg[l][v];
@@ -248,16 +217,12 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(RpnPruneArgs a) {
 }
 }   // namespace
 
-void launch_rpn_prune_energy(const RpnPruneArgs& a, hipStream_t st) {
-    for (int l = 0; l < 2; l++) hipLaunchKernelGGL(prune_energy_kernel, dim3(256, a.V), dim3(256), 0, st, a, l);
-}
 void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipStream_t st) {
     const size_t lds = (size_t)((max_pix + 31) / 32) * 4;
-    static PerDeviceOnce once0, once1, once2;
-    if (a.stages == 1) { allow_big_lds(once0, prune_select_kernel<0>); hipLaunchKernelGGL(prune_select_kernel<0>, dim3(2, a.V), dim3(1024), lds, st, a); }
-    else if (stage == 0) { allow_big_lds(once1, prune_select_kernel<1>); hipLaunchKernelGGL(prune_select_kernel<1>, dim3(2, a.V), dim3(1024), lds, st, a); }
+    static PerDeviceOnce once1, once2;
+    if (stage == 0) { allow_big_lds(once1, prune_select_kernel<1>); hipLaunchKernelGGL(prune_select_kernel<1>, dim3(2, a.V), dim3(1024), lds, st, a); }
     else { allow_big_lds(once2, prune_select_kernel<2>); hipLaunchKernelGGL(prune_select_kernel<2>, dim3(2, a.V), dim3(1024), lds, st, a); }
 }
 void launch_rpn_prune_scatter(const RpnPruneArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(prune_scatter_kernel, dim3(64, a.V, 2 * a.stages), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(prune_scatter_kernel, dim3(64, a.V, 4), dim3(256), 0, st, a);
 }

@@ -1,5 +1,5 @@
 """Times individual conv / linear layer shapes of the configs[1] forward on the MI355X (cald_op_conv_bench): the tuning loop
-for the GEMM kernels.  Usage: python tools/bench_conv.py [tag]   (env vars select kernel variants, see conv_p4.hip)"""
+for the GEMM kernels.  Usage: python tools/bench_conv.py [tag]   (launch_conv picks the kernel as in the product)"""
 import ctypes as C
 import json
 import os
