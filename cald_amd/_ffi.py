@@ -82,6 +82,13 @@ class ConvProbe(C.Structure):
                 ("energy4", c_f), ("energy4_n", C.c_int64)]
 
 
+class WgradPlan(C.Structure):
+    """cald_wgrad_plan (include/cald_hip.h): what cald_train_wgrad_plan answers."""
+    _fields_ = [("variant", C.c_int), ("reduce", C.c_int), ("MT", C.c_int), ("JT", C.c_int), ("S", C.c_longlong), ("chunk", C.c_longlong),
+                ("csplit", C.c_longlong), ("rows_per_block", C.c_longlong), ("scratch_bytes", C.c_longlong),
+                ("kernel", C.c_char * 48), ("reduce_kernel", C.c_char * 32)]
+
+
 # name -> (restype, argtypes): must list every symbol of include/cald_hip.h
 SIGNATURES = {
     "cald_last_error": (C.c_char_p, []),
@@ -145,6 +152,7 @@ SIGNATURES = {
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cald_train_linear_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p, C.c_int]),
+    "cald_train_wgrad_plan": (C.c_int, [C.c_longlong] + [C.c_int] * 12 + [C.POINTER(WgradPlan)]),
     "cald_train_relu_bwd": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cald_train_add": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cald_train_dilate": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),

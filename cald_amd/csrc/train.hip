@@ -762,19 +762,18 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* partial,
     }
 }
 
-// x [N][H][W][ldx] (Cin channels used, Cin % 4 == 0), g [N][Ho][Wo][ldg] (Cout channels used; ldg % 4 == 0 and the pad channels
-// readable).  dw: torch layout [Cout][Cin][KH][KW]; for a tap-major linear layer pass KH*KW = taps, H = W = 1 and x rows
-// [R][taps * Cin] as N = R... (see cald_train_linear_wgrad).  db: [Cout] or null.
-static int wgrad_impl(cald_ctx* c, long long Q, int N, int H, int W, const float* x, int Cin, int ldx, int Ho, int Wo, const float* g,
-                      int Cout, int ldg, int KH, int KW, int stride, int pad, int red_taps, int red_cin, float* dw, float* db, int accumulate,
-                      const float* row_scale) {
-    if (Cin % 4 || ldx % 4 || ldg % 4) TFAIL(CALD_ERR_INVALID, "Cin and the row strides must be multiples of 4");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipStream_t st = cald_internal_stream(c);
-    WgradArgs a; memset(&a, 0, sizeof(a));
-    a.x = x; a.g = g; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ldx = ldx; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.ldg = ldg;
-    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.J = KH * KW * Cin; a.JT = (a.J + 127) / 128; a.MT = (Cout + 127) / 128; a.Q = Q;
-    const long long tiles = (long long)a.MT * a.JT;
+// The launch plan of one weight gradient: which wgrad_kernel instantiation, how many splits of how many pixels, which reduction,
+// how the bias column sum is split, how much scratch.  wgrad_impl launches exactly what this returns; tests query it to pin the variant a
+// shape reaches.  Host arithmetic only.
+extern "C" int cald_train_wgrad_plan(long long Q, int N, int H, int W, int Cin, int ldx, int Cout, int ldg, int KH, int KW, int stride, int pad,
+                                     int red_taps, cald_wgrad_plan* out) {
+    if (!out) TFAIL(CALD_ERR_INVALID, "null argument");
+    if (Q < 1 || N < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 || stride < 1 || pad < 0 || red_taps < 1) TFAIL(CALD_ERR_INVALID, "bad geometry");
+    if (Cin % 4 || ldx % 4 || ldg % 4 || ldx < Cin || ldg < Cout) TFAIL(CALD_ERR_INVALID, "Cin and the row strides must be multiples of 4 (and cover the channels)");
+    memset(out, 0, sizeof(*out));
+    const long long J = (long long)KH * KW * Cin;
+    out->JT = (int)((J + 127) / 128); out->MT = (Cout + 127) / 128;
+    const long long tiles = (long long)out->MT * out->JT;
     const long long tile_floats = tiles * 128 * 128;
     // workgroups aimed at per launch: one resident round (2 per CU).  Measured on the whole step (the kernel shares the chip with the
     // data-gradient stream): 512 -> 34.6 / 33.8 ms (Faster R-CNN / RetinaNet), 384 -> 34.3 / 34.7, 1024 -> 34.9, 2048 -> 35.0 / 35.5
@@ -783,27 +782,57 @@ static int wgrad_impl(cald_ctx* c, long long Q, int N, int H, int W, const float
     const bool fast = bytesG < 0x7FFE0000ll && bytesX < 0x7FFE0000ll;
     static const bool pw_env = !(getenv("CALD_WGRAD_PW") && atoi(getenv("CALD_WGRAD_PW")) == 0);
     static const bool tab_env = !(getenv("CALD_WGRAD_TAB") && atoi(getenv("CALD_WGRAD_TAB")) == 0);
+    static const int bk_env = getenv("CALD_WGRAD_BK") ? atoi(getenv("CALD_WGRAD_BK")) : 16;     // 32-pixel stages measured slower (109 vs 115 TFLOP/s on the largest layer)
     // pointwise: every pixel row q of g pairs with row q of x (chunks are multiples of 32 pixels, so only the last split runs past Q)
-    const bool pw = fast && pw_env && KH == 1 && KW == 1 && stride == 1 && pad == 0 && Ho == H && Wo == W && Q == (long long)N * H * W;
+    const bool pw = fast && pw_env && KH == 1 && KW == 1 && stride == 1 && pad == 0 && Q == (long long)N * H * W;
     const bool tabm = fast && tab_env && !pw && Cin % 128 == 0;
     long long S = target / tiles;                         // rounded down: one workgroup over the resident round costs a second round
     const long long maxS_rows = (Q + 255) / 256; if (S > maxS_rows) S = maxS_rows;
     const long long cap = (512ll << 20) / 4 / tile_floats; if (S > cap) S = cap;
     if (S < 1) S = 1;
-    a.chunk = ((Q + S - 1) / S + 31) / 32 * 32;
-    S = (Q + a.chunk - 1) / a.chunk;
-    const long long csplit = (Q + 255) / 256 > 1024 ? 1024 : (Q + 255) / 256;
+    out->chunk = ((Q + S - 1) / S + 31) / 32 * 32;
+    out->S = (Q + out->chunk - 1) / out->chunk;
+    out->csplit = (Q + 255) / 256 > 1024 ? 1024 : (Q + 255) / 256;
+    out->rows_per_block = (Q + out->csplit - 1) / out->csplit;
+    out->scratch_bytes = (out->S * tile_floats + out->csplit * Cout + 64) * 4;
+    out->variant = pw ? CALD_WGRAD_POINTWISE : tabm ? CALD_WGRAD_TABLE : (fast && bk_env == 32) ? CALD_WGRAD_GENERAL32 : fast ? CALD_WGRAD_GENERAL : CALD_WGRAD_WIDE;
+    out->reduce = red_taps > 1 && red_taps <= 64 ? CALD_WGRAD_REDUCE_TAPS : CALD_WGRAD_REDUCE_FLAT;
+    static const char* const names[] = {"wgrad_kernel<true,16,1>", "wgrad_kernel<true,16,2>", "wgrad_kernel<true,16>", "wgrad_kernel<true,32>", "wgrad_kernel<false,16>"};
+    strcpy(out->kernel, names[out->variant]);          // (both fit: the struct was zeroed above)
+    strcpy(out->reduce_kernel, out->reduce == CALD_WGRAD_REDUCE_TAPS ? "wgrad_reduce_taps_kernel" : "wgrad_reduce_kernel");
+    return 0;
+}
+
+// x [N][H][W][ldx] (Cin channels used, Cin % 4 == 0), g [N][Ho][Wo][ldg] (Cout channels used; ldg % 4 == 0 and the pad channels
+// readable).  dw: torch layout [Cout][Cin][KH][KW]; for a tap-major linear layer pass KH*KW = taps, H = W = 1 and x rows
+// [R][taps * Cin] as N = R... (see cald_train_linear_wgrad).  db: [Cout] or null.
+static int wgrad_impl(cald_ctx* c, long long Q, int N, int H, int W, const float* x, int Cin, int ldx, int Ho, int Wo, const float* g,
+                      int Cout, int ldg, int KH, int KW, int stride, int pad, int red_taps, int red_cin, float* dw, float* db, int accumulate,
+                      const float* row_scale) {
+    if (Cin % 4 || ldx % 4 || ldg % 4) TFAIL(CALD_ERR_INVALID, "Cin and the row strides must be multiples of 4");
+    if (ldx < Cin || ldg < Cout) TFAIL(CALD_ERR_INVALID, "a row stride is smaller than the channel count");
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipStream_t st = cald_internal_stream(c);
+    WgradArgs a; memset(&a, 0, sizeof(a));
+    a.x = x; a.g = g; a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.ldx = ldx; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.ldg = ldg;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.J = KH * KW * Cin; a.JT = (a.J + 127) / 128; a.MT = (Cout + 127) / 128; a.Q = Q;
+    cald_wgrad_plan pl;
+    if (int rc = cald_train_wgrad_plan(Q, N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad, red_taps, &pl)) return rc;
+    const long long tiles = (long long)a.MT * a.JT, tile_floats = tiles * 128 * 128;
+    const long long S = pl.S, csplit = pl.csplit;
+    a.chunk = pl.chunk;
     void* scratch = nullptr;
-    if (int rc = cald_internal_scratch(c, (size_t)(S * tile_floats + csplit * Cout + 64) * 4, &scratch)) return rc;
+    if (int rc = cald_internal_scratch(c, (size_t)pl.scratch_bytes, &scratch)) return rc;
     a.partial = (float*)scratch;
-    static const int bk_env = getenv("CALD_WGRAD_BK") ? atoi(getenv("CALD_WGRAD_BK")) : 16;     // 32-pixel stages measured slower (109 vs 115 TFLOP/s on the largest layer)
-    if (pw) hipLaunchKernelGGL((wgrad_kernel<true, 16, 1>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a);
-    else if (tabm) hipLaunchKernelGGL((wgrad_kernel<true, 16, 2>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a);
-    else if (fast && bk_env == 32) hipLaunchKernelGGL((wgrad_kernel<true, 32>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a);
-    else if (fast) hipLaunchKernelGGL((wgrad_kernel<true, 16>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wgrad_kernel<false, 16>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a);
+    switch (pl.variant) {
+        case CALD_WGRAD_POINTWISE: hipLaunchKernelGGL((wgrad_kernel<true, 16, 1>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a); break;
+        case CALD_WGRAD_TABLE: hipLaunchKernelGGL((wgrad_kernel<true, 16, 2>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a); break;
+        case CALD_WGRAD_GENERAL32: hipLaunchKernelGGL((wgrad_kernel<true, 32>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a); break;
+        case CALD_WGRAD_GENERAL: hipLaunchKernelGGL((wgrad_kernel<true, 16>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a); break;
+        default: hipLaunchKernelGGL((wgrad_kernel<false, 16>), dim3((unsigned)tiles, (unsigned)S), dim3(256), 0, st, a); break;
+    }
     const long long nred = (long long)Cout * a.J;
-    if (red_taps > 1 && red_taps <= 64)
+    if (pl.reduce == CALD_WGRAD_REDUCE_TAPS)
         hipLaunchKernelGGL(wgrad_reduce_taps_kernel, dim3((unsigned)((red_cin + 63) / 64), (unsigned)Cout), dim3(256), (size_t)red_taps * 64 * 4, st,
                            a.partial, (int)S, tile_floats, (long long)a.JT * 128, red_cin, red_taps, dw, accumulate, row_scale);
     else
@@ -811,7 +840,7 @@ static int wgrad_impl(cald_ctx* c, long long Q, int N, int H, int W, const float
                            (long long)a.JT * 128, Cout, red_cin, red_taps, dw, accumulate, row_scale);
     if (db) {
         float* cp = a.partial + S * tile_floats;
-        const long long rpb = (Q + csplit - 1) / csplit;
+        const long long rpb = pl.rows_per_block;
         hipLaunchKernelGGL(colsum_partial_kernel, dim3((Cout + 127) / 128, (unsigned)csplit), dim3(256), 0, st, g, Q, Cout, ldg, rpb, cp);
         hipLaunchKernelGGL(colsum_final_kernel, dim3((Cout + 15) / 16), dim3(256), 0, st, cp, (int)csplit, Cout, db, accumulate);
     }
@@ -1354,7 +1383,7 @@ extern "C" int cald_train_roi_align(cald_ctx* c, const float* const* feats, cons
 __global__ void absmax_kernel(const float* x, long long n, unsigned* out_bits) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     float m = 0.0f;
-    for (long long j = i; j < n; j += (long long)gridDim.x * blockDim.x) { const float v = fabsf(x[j]); if (v > m) m = v; }   // NaN never wins
+    for (long long j = i; j < n; j += (long long)gridDim.x * blockDim.x) { const float v = fabsf(x[j]); if (v > m && v != INFINITY) m = v; }   // NaN and Inf never win
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
     if ((threadIdx.x & 63) == 0 && m > 0.0f) atomicMax(out_bits, __float_as_uint(m));
 }

@@ -211,6 +211,21 @@ def linear_wgrad(x, g, Cout, dw, db=None, taps=1, accumulate=False):
     return dw
 
 
+def conv_wgrad_plan(N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad):
+    """The launch plan conv_wgrad takes for this shape (kernel variant, splits, reduction): a host query, nothing runs."""
+    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    pl = _ffi.WgradPlan()
+    _ffi.check(_ffi.lib().cald_train_wgrad_plan(N * Ho * Wo, N, H, W, Cin, ldx, Cout, ldg, KH, KW, stride, pad, KH * KW, C.byref(pl)))
+    return pl
+
+
+def linear_wgrad_plan(R, K, Cout, ldg, taps=1):
+    """The launch plan linear_wgrad takes for this shape."""
+    pl = _ffi.WgradPlan()
+    _ffi.check(_ffi.lib().cald_train_wgrad_plan(R, 1, 1, R, K, K, Cout, ldg, 1, 1, 1, 0, taps, C.byref(pl)))
+    return pl
+
+
 def relu_bwd_(g, act=None, scale=None):
     Cc = g.shape[-1]
     _ffi.check(_ffi.lib().cald_train_relu_bwd(_wctx(g), g.numel() // Cc, Cc, _p(g), _p(act), _p(scale)))

@@ -374,6 +374,25 @@ int cald_train_conv_wgrad(cald_ctx* ctx, int N, int H, int W, const float* x, in
 /* linear layer: x [R][K], g [R][ldg] -> dw [Cout][K]; taps > 1: x rows are [tap][K / taps], dw is [Cout][K / taps][taps] */
 int cald_train_linear_wgrad(cald_ctx* ctx, int R, const float* x, int K, const float* g, int Cout, int ldg, int taps,
                             float* dw, float* db, int accumulate);
+/* The launch plan of the two calls above, as a host-only query (nothing is launched, no context needed): cald_train_conv_wgrad /
+ * cald_train_linear_wgrad launch exactly what it returns.  Q = output pixels (N * Ho * Wo; a linear layer: Q = R, N = H = 1, W = R, KH = KW
+ * = 1, Cin = ldx = K, red_taps = taps); red_taps = KH * KW for a conv.  `variant`: the wgrad_kernel instantiation -- pointwise (1 x 1,
+ * stride 1: both operands plain matrices), offset table (Cin % 128 == 0), general, general with 32-pixel stages (CALD_WGRAD_BK=32 only),
+ * wide (a tensor of 0x7FFE0000 bytes or more: 64-bit addressing).  The pixels are cut into S splits of `chunk` (a multiple of 32; the last
+ * one may be ragged), reduced in split order by `reduce`; the bias gradient sums `csplit` blocks of `rows_per_block` rows.
+ * Pad channels (Cout..ldg of g, Cin..ldx of x) may hold anything finite: they are read and never reach dw / db. */
+enum { CALD_WGRAD_POINTWISE = 0, CALD_WGRAD_TABLE = 1, CALD_WGRAD_GENERAL = 2, CALD_WGRAD_GENERAL32 = 3, CALD_WGRAD_WIDE = 4 };
+enum { CALD_WGRAD_REDUCE_FLAT = 0, CALD_WGRAD_REDUCE_TAPS = 1 };
+typedef struct cald_wgrad_plan {
+    int variant, reduce;                   /* CALD_WGRAD_*, CALD_WGRAD_REDUCE_* */
+    int MT, JT;                            /* 128 x 128 tiles over Cout and over KH * KW * Cin */
+    long long S, chunk;                    /* splits and pixels per split */
+    long long csplit, rows_per_block;      /* bias gradient: row blocks and rows per block */
+    long long scratch_bytes;
+    char kernel[48], reduce_kernel[32];    /* the same as names */
+} cald_wgrad_plan;
+int cald_train_wgrad_plan(long long Q, int N, int H, int W, int Cin, int ldx, int Cout, int ldg, int KH, int KW, int stride, int pad,
+                          int red_taps, cald_wgrad_plan* out);
 /* g = (act > 0 ? g : 0) * scale[c]  (ReLU backward on the layer's output + FrozenBatchNorm scale); act / scale may be null */
 int cald_train_relu_bwd(cald_ctx* ctx, long long rows, int C, float* g, const float* act, const float* scale);
 /* dst = a + b (b null: copy); n floats, multiple of 4 */
