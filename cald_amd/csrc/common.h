@@ -38,7 +38,7 @@ struct BatchPlan {
     LevelSeg seg[CALD_MAX_LEVELS][CALD_MAX_VIEWS + 1];
 };
 
-// Gathered rows of one view (conv_p4.hip, the cut_out view's backbone under api.hip's activation reuse): row m of the launch is a pixel
+// Gathered rows of one view (conv_p4.hip, the cut_out view's backbone under sweep.hip's activation reuse): row m of the launch is a pixel
 // of one of nr disjoint rectangles of the view's OUTPUT grid -- rectangle k holds rows [cum[k], cum[k + 1]) in row-major order, starting
 // at pixel (y0, x0), w pixels wide.  Rows are computed at that pixel and stored (and a residual read) at that pixel of the full tensor.
 #define CALD_GATHER_RECTS 8
@@ -57,7 +57,7 @@ __device__ __forceinline__ int gather_pixel(const GatherSet& g, const int m, con
 struct ConvArgs {
     const float* in;
     float* out;
-    const float* w;        // [Kpad][CoutPad], rows in chain order (api.hip conv_k_index: (16-channel chunk, kh, kw, channel) or (kh, kw, cin))
+    const float* w;        // [Kpad][CoutPad], rows in chain order (model.hip pack_conv, conv_k_index: (16-channel chunk, kh, kw, channel) or (kh, kw, cin))
     const float* w4;       // same weights packed [Kpad/16][2][CoutPad][2][4] for conv_p4.hip (k = 16 kt + 8 kq + 2 j + h), or null
     const void* w16;       // fp16 hi/lo split of the same weights * 2^S, [Kpad/16][2 (hi, lo)][CoutPad][16] (conv_h3.hip), or null
     float w16_unscale;     // 2^-(S + 4): undoes the weight scale 2^S and conv_h3's activation scale 2^4 (exact powers of two)

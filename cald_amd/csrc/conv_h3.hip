@@ -12,7 +12,7 @@
 // split -- weights by 2^S per layer at finalize (max |w| * 2^S <= 2^14), activations by 2^4 while staging -- and the
 // accumulator is multiplied by 2^-(S+4) first thing in the epilogue (exact).  Range: |activation| < 4094.
 //
-// k order: the same (16-channel chunk, kh, kw) k-tile walk as the exact kernels (api.hip conv_k_index): all nine taps of a
+// k order: the same (16-channel chunk, kh, kw) k-tile walk as the exact kernels (common.h conv_k_index): all nine taps of a
 // chunk are consecutive k-tiles, the three kw taps of a row read the same 64-byte pixel segments shifted by one pixel (L1
 // hits) and the three rows stay in L2 -- the kernel is L2-bandwidth-bound otherwise (at 128 x 128 tiles the 3x3 256->256
 // layer on P2 moves 74 GB per launch from L2, 10.6 TB/s).

@@ -5,7 +5,7 @@
 // detection/frcnn_la.py:258, :261, :113-114).
 //
 //   GEMM view:  M = output pixels of all views of the ragged batch (each view padded to a multiple
-//               of the 128-row tile), N = Cout, K = KH*KW*Cin in the contract's chain order (api.hip conv_k_index).
+//               of the 128-row tile), N = Cout, K = KH*KW*Cin in the contract's chain order (common.h conv_k_index).
 //   MFMA:       v_mfma_f32_32x32x2_f32 -- exact fp32, one k-ordered fma chain per output, so the
 //               result is bit-identical to the CPU oracle's fmaf chain (DESIGN.md contract).
 //   Tile:       128 x BN x 16, 256 threads = 4 waves; each wave owns TM x TN 32x32 accumulators.

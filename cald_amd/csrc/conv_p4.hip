@@ -359,7 +359,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
         rb0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, bvoff0, soffB, 0));     \
         if (TN == 2) rb1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, bvoff1, soffB, 0)); \
         u_kt++;                                                                                            \
-        /* k-tile order (16-channel chunk, kh, kw): api.hip conv_k_index */                                \
+        /* k-tile order (16-channel chunk, kh, kw): common.h conv_k_index */                                \
         u_kw++; if (u_kw == KW) { u_kw = 0; u_kh++; if (u_kh == KH) { u_kh = 0; u_ci += BK; } }            \
     }
 #define P4_STORE(BUF)                                                                                      \

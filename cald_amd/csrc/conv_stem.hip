@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256, 3) void conv_stem_kernel(const ConvArgs a, con
     }
 }
 
-// the kernel if it handled the launch (7 x 7 / 2 stem with packed stem weights -- api.hip sets them only when every view is an exact grid
+// the kernel if it handled the launch (7 x 7 / 2 stem with packed stem weights -- forward.hip fill_conv_args sets them only when every view is an exact grid
 // of 8 x 16 blocks), else nullptr
 const char* launch_conv_stem(const ConvArgs& a, hipStream_t stream) {
     if (!a.wstem || !a.out || a.KH != 7 || a.KW != 7 || a.stride != 2 || a.pad != 3 || a.Cin != 4 || a.Cout != 64 || a.out_ld != 64) return nullptr;

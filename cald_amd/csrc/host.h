@@ -1,0 +1,205 @@
+// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, model.hip, forward.hip, sweep.hip) share: the context and the model behind
+// the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those five files
+// alone: train.hip, jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
+#pragma once
+#include "../../include/cald_hip.h"
+#include "common.h"
+#include "kernels.h"
+#include "host_logic.h"
+
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
+
+// Everything but the two handle types lives in this namespace, so the library's cald_* symbols stay the C ABI plus cald_internal_*.
+namespace cald_host {
+int fail(int code, const char* fmt, ...);      // ctx.hip: sets the thread's cald_last_error() text, returns `code`
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(CALD_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+struct PilCoef { int ksize; int* d_bounds; int* d_kk; };
+struct PilKey { int in, out, fid; bool operator<(const PilKey& o) const { return in != o.in ? in < o.in : (out != o.out ? out < o.out : fid < o.fid); } };
+// one timed launch of the event profile (prof_begin / prof_end)
+struct ProfLaunch {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double flops = 0.0;
+    int tag = 0;            // 0: the model's own arithmetic; 1: the split-fp16 look-ahead pass of rpn_prune.hip (booked apart)
+    std::string desc;
+};
+}  // namespace cald_host
+using namespace cald_host;      // the five host files work inside it
+
+#define CALD_PRUNE_LOG 4096     // profiled forwards whose selected-pixel counts are kept per forward (cald_profile_dump)
+struct cald_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    char* arena = nullptr; size_t arena_cap = 0, arena_off = 0;
+    BatchPlan* d_plan = nullptr;
+    ViewDesc* d_views = nullptr;
+    float* d_zeros = nullptr;
+    // pinned host staging ring for the per-forward plan + view descriptors (keeps the source of the
+    // stream-ordered H2D copies alive without a host sync)
+    static const int NSTAGE = 8;
+    char* h_stage[NSTAGE] = {nullptr}; hipEvent_t stage_ev[NSTAGE] = {nullptr}; int stage_i = 0;
+    bool prof = false;
+    std::vector<ProfLaunch> prof_launches;
+    double prof_flops = 0.0; int64_t prof_extra_launches = 0;
+    int prof_tag_now = 0;                           // set around the look-ahead launches of rpn_prune.hip (per context: ADVICE r5)
+    double prof_prune_flops_cap[2] = {0.0, 0.0};    // FLOPs the gathered P2 / P3 launches are booked with (every pixel, once per selection stage; rescaled to the selected rows at read time)
+    hipEvent_t tot0 = nullptr, tot1 = nullptr; bool tot_open = false; double tot_ms = 0.0;
+    // RoI-head GEMMs run on a device-side row count (proposals after NMS): the profile counts their algorithmic FLOPs on the
+    // MEASURED rows, accumulated on the device while profiling (no host sync inside a forward)
+    float prune_worst = 0.0f;                     // largest ratio any sweep of this context has seen (cald_profile_prune)
+    long long prune_fallbacks = 0;                // sweeps repeated with the dense head (bound exceeded / activation outside the split's range)
+    float* d_prune_check = nullptr;               // rpn_prune.hip: running max of |look-ahead - exact| / bound (reset by every sweep call)
+    unsigned long long* d_prune_stat = nullptr;   // rpn_prune.hip: selected / total pixels of P2, P3 while profiling
+    // per profiled forward [sel P2, total P2, sel P3, total P3]: lets cald_profile_dump book each gathered launch on the rows it really computed
+    unsigned long long* d_prune_log = nullptr; int prune_log_n = 0;
+    struct GatherNote { int log; double cap[2]; };
+    std::map<size_t, GatherNote> prof_gather;     // launch index -> which log slot, and the FLOPs its P2 / P3 problems would cost on every pixel
+    unsigned long long* d_roi_rows = nullptr; double prof_roi_rows_cap = 0.0, prof_roi_flops_cap = 0.0; long long prof_roi_views = 0;
+    std::map<PilKey, PilCoef> pil;
+    char* train_scratch = nullptr; size_t train_scratch_cap = 0;   // train.hip: split-K partial tiles of the weight gradients
+    // cut_out reuse (cald_profile_cutout): per reused stage the conv output rows the cut_out forwards computed and what the dense forwards
+    // would have; batches whose cut_out views reused the reference forward, batches that could not (the retention did not fit)
+    double cut_rows[3] = {0.0, 0.0, 0.0}, cut_dense[3] = {0.0, 0.0, 0.0};
+    long long cut_batches = 0, cut_fallbacks = 0;
+};
+
+namespace cald_host {
+// device scratch that lives for one API call: everything is released when the call returns, on every path
+struct ScopedDev {
+    std::vector<void*> ptrs;
+    hipStream_t st;
+    explicit ScopedDev(hipStream_t s) : st(s) {}
+    ~ScopedDev() { if (!ptrs.empty()) { hipStreamSynchronize(st); for (void* p : ptrs) hipFree(p); } }
+    template <typename T> int alloc(T** out, size_t bytes) {
+        HIPCHK(hipMalloc((void**)out, bytes ? bytes : 1));
+        ptrs.push_back(*out);
+        return 0;
+    }
+};
+struct Bump {
+    char* base; size_t off = 0; bool dry;
+    explicit Bump(char* b, bool d) : base(b), dry(d) {}
+    template <typename T> T* get(size_t count) {
+        size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
+        T* p = dry ? nullptr : reinterpret_cast<T*>(base + off);
+        off += bytes;
+        return p;
+    }
+};
+
+struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
+struct ConvLayer {
+    float *w = nullptr, *w4 = nullptr, *bias = nullptr, *scale = nullptr, *shift = nullptr;
+    float* wstem = nullptr;                              // conv_stem.hip packing (the 7 x 7 / 2, 3 -> 64 stem only)
+    uint16_t* w16 = nullptr; float w16_unscale = 1.0f;   // CALD_PRECISION_F16X3 only
+    int Cin = 0, Cout = 0, CoutPad = 0, K = 0, Kpad = 0, KH = 1, KW = 1, stride = 1, pad = 0;
+    int CinTrue = 0;   // un-padded input channels (algorithmic FLOP accounting)
+};
+struct Bottleneck { ConvLayer c1, c2, c3, down; bool has_down = false; bool layer_end = false; };
+struct DebugEntry { const float* ptr; int level; int C; int kind; };  // kind 0: level tensor, 1: roi rows [cap][C]
+}  // namespace cald_host
+
+struct cald_model {
+    cald_ctx* ctx = nullptr;
+    cald_model_cfg cfg;
+    std::map<std::string, HostTensor> sd;
+    bool finalized = false;
+    ConvLayer conv1; std::vector<Bottleneck> blocks;
+    ConvLayer fpn_inner[4], fpn_layer[4], rpn_conv, rpn_head, fc6, fc7, pred;
+    // certified RPN pruning of the exact sweep (rpn_prune.hip): the 3 x 3 RPN conv once more with split-fp16 weights, the bound's constants
+    ConvLayer rpn_conv16; bool prune = false; float prune_c1[3] = {0, 0, 0}, prune_c0[3] = {0, 0, 0};
+    bool prune_allowed = false;     // finalize's verdict: the look-ahead layer exists and the bound's constants are finite (cald_model_set_rpn_prune* AND it in)
+    bool prune_capture = false;     // test hook: cald_forward takes the pruned path too and keeps the look-ahead's logit map (cald_model_set_rpn_prune_capture)
+    ConvLayer p6, p7, cls_tower[4], reg_tower[4], cls_out, reg_out;   // RetinaNet
+    int det_cap() const { return cfg.arch == CALD_ARCH_RETINANET ? cfg.num_classes * cfg.detections_per_img : cfg.detections_per_img; }
+    float* d_anchors = nullptr;
+    std::vector<void*> owned;
+    std::map<std::string, DebugEntry> dbg;
+    BatchPlan plan; int last_V = 0;
+    // CALD_PRECISION_F16X3: activation tensors that also (or only) exist in conv_h3.hip's split form (ConvArgs::in16 / out16), keyed by
+    // the fp32 buffer of the running forward.  fp32_dead: every consumer is a conv_h3 layer -- the fp32 tensor is not written at all
+    // and the split words live in the same buffer.
+    struct SplitFmt { unsigned* s16; bool fp32_dead; };
+    std::map<const float*, SplitFmt> split;
+    std::vector<ViewDesc> last_views;
+    // batch-level detection buffers used by the sweeps (cald_sweep alternates between the two sets: batch k + 1's reference forward
+    // is in flight while batch k's views are being scored)
+    DetBuffers sweep_det; int sweep_det_views = 0;
+    DetBuffers sweep_det2; int sweep_det2_views = 0;
+    // cald_sweep's scratch lives with the model, grown on demand, never freed between calls (round 3 allocated and freed six device
+    // buffers per call -- each hipFree an implicit device synchronisation -- and copied through pageable host memory)
+    struct SweepScratch {
+        size_t dev_bytes = 0, pin_bytes = 0, aug_cap = 0;
+        char* dev = nullptr; char* pin = nullptr; uint8_t* d_aug = nullptr;
+        hipEvent_t ev_ref[2] = {nullptr, nullptr}, ev_score[2] = {nullptr, nullptr};
+    } ss;
+    int key_cap = 32768;   // FRCNN candidate (proposal, class) list capacity per view, sized from box_score_thresh at create
+    // cut_out reuse (sweep.hip SweepRun): the reference forward's block outputs of the first three stages, one slot per batch parity (batch k + 1's
+    // reference forward runs before batch k's cut_out forward), and the gather plans of the cut_out forwards (pinned by parity + device)
+    struct CutReuse {
+        int mode = -1;              // cald_model_set_cutout_reuse: -1 the process default (CALD_CUTOUT_REUSE), 0 off, 1 on, 2 on with every stage dense
+        char* slot[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0};
+        char* h_gp[2] = {nullptr, nullptr}; char* d_gp = nullptr;
+    } cr;
+};
+
+namespace cald_host {
+// Every weight packing the conv kernels read (model.hip pack_conv)
+struct ConvPack {
+    std::vector<float> w, w4, wstem;
+    std::vector<uint16_t> w16; float w16_unscale = 1.0f;
+    int Cout = 0, CoutPad = 0, K = 0, Kpad = 0;
+};
+// independent convolutions (bias / BN / ReLU epilogue only) issued as ONE launch when they fit the same tiled kernel (forward.hip conv_group_on)
+struct ConvSpec { const ConvLayer* L; const float* in; float* out; int level; bool relu; const int* dyn = nullptr; const int* row_map = nullptr; const unsigned* in16 = nullptr;
+                  unsigned* out16 = nullptr; float* energy4 = nullptr; };      // out16 / energy4: conv_p4.hip's pruning extras (P2 / P3 of the FPN output convs)
+
+// ---- cut_out reuse: the cut_out views of a sweep batch run as a forward of their own, in the reference forward's image order (same plan),
+// and their first three stages recompute only the pixels the filled rectangles reach (host_logic.h cut_geometry), patching the reference
+// forward's retained block outputs in place ----
+#define CUT_MAX_BLOCKS 32          // blocks of the first three stages (ResNet-101: 3 + 4 + 23)
+struct FwdReuse {
+    int mode = 0;                  // 1: reference forward, the block outputs of the first nblk blocks go to out[]; 2: the cut_out forward
+    int nblk = 0;
+    float* out[CUT_MAX_BLOCKS] = {};
+    // mode 2: per stage gathered launches or dense ones (also written over out[]); the device gather plan (cut_plan_set_bytes): per block b and
+    // set k (0: the block output's dirty set -- downsample conv, conv2, conv3; 1: conv1's compute set) LevelSeg[V + 1] (the level's
+    // geometry, tile_start counting the set's tiles) then GatherSet[V]
+    bool gather[3] = {false, false, false};
+    const char* d_gp = nullptr;
+    int tiles[CUT_MAX_BLOCKS][2] = {};
+    double rows[CUT_MAX_BLOCKS][2] = {};
+};
+inline size_t cut_plan_set_bytes(int V) { return (size_t)(V + 1) * sizeof(LevelSeg) + (size_t)V * sizeof(GatherSet); }
+inline long long level_pix(const BatchPlan& P, int l, int V) { return P.seg[l][V].pix_off; }
+
+// ctx.hip
+int arena_reserve(cald_ctx* c, size_t bytes);
+int prof_begin(cald_ctx* c, ProfLaunch& t);                                                  // no-ops while the profile is off
+int prof_end(cald_ctx* c, ProfLaunch& t, double flops, int tag, const char* fmt, ...);
+int conv_refused(const ConvArgs& a);
+int run_conv(cald_ctx* c, const ConvArgs& a, double flops);
+// ops.hip
+int pil_resize(cald_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, int oh, int ow, uint8_t* tmp, int fid = 0);
+// model.hip
+std::vector<float> pack_w4(const std::vector<float>& w, int Kpad, int CoutPad);
+void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& couts, int cin, int cinp, int kh, int kw, int stride, int pad,
+               bool want16, ConvPack* P);
+// forward.hip
+void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], bool retina);
+bool stem_grid_exact(const LevelSeg* seg, int V);
+int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
+                  const FwdReuse* ru = nullptr);
+// sweep.hip
+void free_det(DetBuffers& d);
+int alloc_det(DetBuffers& d, int V, int cap, int C);
+}  // namespace cald_host

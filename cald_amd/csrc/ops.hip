@@ -1,0 +1,552 @@
+// ops.hip -- the stand-alone operators of the C ABI (cald_op_*): parity hooks of the tests and tools, outside any model.  Host-side
+// restatements used here (host_logic.h, no device work): cutout rectangle selection (cald/cald_helper.py:88-132), Pillow's resampling
+// coefficients (cald_helper.py:47-53), the detector-transform size rule (torchvision GeneralizedRCNNTransform).
+#include "host.h"
+
+// =============================================================================================
+// host-side restatements
+// =============================================================================================
+extern "C" int cald_op_transform_size(int H, int W, int min_size, int max_size, int* Hr, int* Wr, int* Hp, int* Wp) {
+    if (H <= 0 || W <= 0 || min_size <= 0 || max_size <= 0) return fail(CALD_ERR_INVALID, "bad sizes");
+    transform_size(H, W, min_size, max_size, Hr, Wr, Hp, Wp);
+    return 0;
+}
+
+extern "C" int cald_op_cutout_rects(uint64_t seed, int H, int W, int N, const float* boxes, int cut_num, int* rects_out, int* n_out) {
+    if (cut_num < 0 || cut_num > CALD_MAX_CUT) return fail(CALD_ERR_INVALID, "cut_num must be 0..%d", CALD_MAX_CUT);
+    *n_out = cutout_rects(seed, H, W, N, boxes, cut_num, rects_out);
+    return 0;
+}
+
+extern "C" int cald_op_cutout_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out) {
+    if (H < 1 || W < 1 || nrect < 0 || nrect > CALD_MAX_CUT || (nrect && !rects) || nblk < 0 || nblk > 64 || (nblk && !strides) || !out)
+        return fail(CALD_ERR_INVALID, "bad argument");
+    int Hr, Wr, Hp, Wp;
+    transform_size(H, W, min_size, max_size, &Hr, &Wr, &Hp, &Wp);
+    std::vector<CutSet> o(nblk + 1), t(nblk + 1);
+    cut_geometry(H, W, Hr, Wr, Hp, Wp, nrect, rects, nblk, strides, &o[0], o.data() + 1, t.data() + 1);
+    t[0].n = 0;
+    for (int e = 0; e <= nblk; e++)
+        for (int k = 0; k < 2; k++) {
+            const CutSet& sset = k ? t[e] : o[e];
+            int* q = out + (size_t)(2 * e + k) * (1 + 4 * CUT_SET_MAX);
+            memset(q, 0, sizeof(int) * (1 + 4 * CUT_SET_MAX));
+            q[0] = sset.n;
+            for (int i = 0; i < sset.n; i++) { q[1 + 4 * i] = sset.r[i].x0; q[2 + 4 * i] = sset.r[i].y0; q[3 + 4 * i] = sset.r[i].x1; q[4 + 4 * i] = sset.r[i].y1; }
+        }
+    return 0;
+}
+static int get_pil(cald_ctx* c, int inSize, int outSize, int fid, PilCoef* out) {
+    PilKey key{inSize, outSize, fid};
+    auto it = c->pil.find(key);
+    if (it == c->pil.end()) {
+        std::vector<int> b, k;
+        PilCoef pc; pc.ksize = pil_coeffs(inSize, outSize, fid, b, k);
+        HIPCHK(hipMalloc((void**)&pc.d_bounds, b.size() * sizeof(int)));
+        HIPCHK(hipMalloc((void**)&pc.d_kk, k.size() * sizeof(int)));
+        HIPCHK(hipMemcpy(pc.d_bounds, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(pc.d_kk, k.data(), k.size() * sizeof(int), hipMemcpyHostToDevice));
+        it = c->pil.insert(std::make_pair(key, pc)).first;
+    }
+    *out = it->second;
+    return 0;
+}
+// dst [oh][ow][3]; tmp must hold H*ow*3 bytes
+int cald_host::pil_resize(cald_ctx* c, const uint8_t* src, int H, int W, uint8_t* dst, int oh, int ow, uint8_t* tmp, int fid) {
+    const uint8_t* cur = src;
+    if (ow != W) {
+        PilCoef pc; int rc = get_pil(c, W, ow, fid, &pc); if (rc) return rc;
+        uint8_t* hdst = (oh != H) ? tmp : dst;
+        launch_pil_horizontal(src, H, W, hdst, ow, pc.d_bounds, pc.d_kk, pc.ksize, c->stream);
+        cur = hdst;
+    }
+    if (oh != H) {
+        PilCoef pc; int rc = get_pil(c, H, oh, fid, &pc); if (rc) return rc;
+        launch_pil_vertical(cur, H, ow, dst, oh, pc.d_bounds, pc.d_kk, pc.ksize, c->stream);
+    } else if (ow == W) {
+        HIPCHK(hipMemcpyAsync(dst, src, (size_t)H * W * 3, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+}
+extern "C" int cald_op_pil_resize(cald_ctx* c, const uint8_t* src_dev, int H, int W, uint8_t* dst_dev, int oh, int ow) {
+    if (!c || !src_dev || !dst_dev || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return fail(CALD_ERR_INVALID, "bad arguments");
+    uint8_t* tmp = nullptr;
+    HIPCHK(hipMalloc((void**)&tmp, (size_t)H * ow * 3));
+    int rc = pil_resize(c, src_dev, H, W, dst_dev, oh, ow, tmp);
+    hipStreamSynchronize(c->stream);
+    hipFree(tmp);
+    return rc;
+}
+
+// One augmented view of one image, outside the sweep (the helper API of cald/cald_helper.py and the parity tests).
+// A fresh generator is seeded with `seed` (torch's for GAUSS / SALT_PEPPER, Python's for COLOR_SWAP).
+extern "C" int cald_op_augment(cald_ctx* c, int kind, double param, uint64_t seed, const uint8_t* src_dev, int H, int W,
+                               int n_boxes, const float* boxes, void* dst_dev, float* boxes_out, int* aux_out) {
+    if (!c || H <= 0 || W <= 0) return fail(CALD_ERR_INVALID, "bad arguments");
+    if (kind == CALD_AUG_COLOR_SWAP) {
+        if (!aux_out) return fail(CALD_ERR_INVALID, "color_swap: aux_out is null");
+        PyRandom r; r.seed(seed);
+        aux_out[0] = r.randbelow(6);
+        return CALD_OK;
+    }
+    if (!src_dev || !dst_dev) return fail(CALD_ERR_INVALID, "null image pointer");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t nbytes = (size_t)H * W * 3;
+    if (kind == CALD_AUG_GAUSS || kind == CALD_AUG_SALT_PEPPER) {
+        NoiseJob nj; memset(&nj, 0, sizeof(nj));
+        nj.seed = seed; nj.src = src_dev; nj.H = H; nj.W = W; nj.nseg = 1; nj.seg[0].dst = dst_dev;
+        if (kind == CALD_AUG_GAUSS) { nj.seg[0].kind = 0; nj.seg[0].p0 = (float)param; }
+        else { nj.seg[0].kind = 1; nj.seg[0].p0 = (float)(param / 2.0); nj.seg[0].p1 = (float)(1.0 - param / 2.0); }
+        NoiseJob* d = nullptr;
+        HIPCHK(hipMalloc((void**)&d, sizeof(NoiseJob)));
+        hipError_t e = hipMemcpyAsync(d, &nj, sizeof(nj), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) { launch_noise_stream(d, 1, c->stream); e = hipStreamSynchronize(c->stream); }
+        hipFree(d);
+        if (e != hipSuccess) return fail(CALD_ERR_HIP, "noise stream failed: %s", hipGetErrorString(e));
+        return CALD_OK;
+    }
+    if (kind == CALD_AUG_COLOR_ADJUST) {
+        uint8_t* tmp = nullptr;
+        HIPCHK(hipMalloc((void**)&tmp, nbytes + 256));
+        unsigned long long* lsum = reinterpret_cast<unsigned long long*>(tmp + ((nbytes + 7) & ~(size_t)7));
+        launch_color_adjust(src_dev, H, W, (float)param, tmp, lsum, reinterpret_cast<uint8_t*>(dst_dev), c->stream);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        hipFree(tmp);
+        if (e != hipSuccess) return fail(CALD_ERR_HIP, "color adjust failed: %s", hipGetErrorString(e));
+        return CALD_OK;
+    }
+    if (kind == CALD_AUG_ROTATE) {
+        if (n_boxes < 0 || (n_boxes && (!boxes || !boxes_out))) return fail(CALD_ERR_INVALID, "rotate: null boxes");
+        int fx[6], nh, nw; pil_rotate_setup(H, W, param, fx, &nh, &nw);
+        uint8_t* ws = nullptr;
+        const size_t a = ((size_t)nh * nw * 3 + 255) & ~(size_t)255;
+        HIPCHK(hipMalloc((void**)&ws, a + (size_t)nh * W * 3));
+        launch_affine_nearest(src_dev, H, W, ws, nh, nw, fx, c->stream);
+        int rc = pil_resize(c, ws, nh, nw, reinterpret_cast<uint8_t*>(dst_dev), H, W, ws + a, 1);
+        hipError_t e = hipStreamSynchronize(c->stream);
+        hipFree(ws);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail(CALD_ERR_HIP, "rotate failed: %s", hipGetErrorString(e));
+        float par[12]; rotate_box_params(H, W, param, nw, nh, par);
+        rotate_boxes_host(par, boxes, n_boxes, boxes_out);
+        return CALD_OK;
+    }
+    return fail(CALD_ERR_INVALID, "cald_op_augment: kind %d has its own entry point or needs no device work", kind);
+}
+
+// =============================================================================================
+// operator-level entry points
+// =============================================================================================
+static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
+                     int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
+                     const float* residual, int relu, float* out) {
+    if (!c || !in || !weight || !out) return fail(CALD_ERR_INVALID, "null argument");
+    if (Cin % 4) return fail(CALD_ERR_INVALID, "Cin must be a multiple of 4");
+    HIPCHK(hipSetDevice(c->device));
+    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    ConvPack pk;
+    pack_conv({weight}, {Cout}, Cin, Cin, KH, KW, stride, pad, precision == CALD_PRECISION_F16X3, &pk);
+    const int CoutPad = pk.CoutPad, Kpad = pk.Kpad;
+    const std::vector<float>& w = pk.w;
+    std::vector<float> b(CoutPad, 0.0f), sc(CoutPad, 0.0f), sh(CoutPad, 0.0f);
+    for (int i = 0; i < Cout; i++) { if (bias) b[i] = bias[i]; if (bn_scale) { sc[i] = bn_scale[i]; sh[i] = bn_shift[i]; } }
+    BatchPlan P; memset(&P, 0, sizeof(P));
+    P.seg[0][0].H = H; P.seg[0][0].W = W; P.seg[0][1].pix_off = (long long)H * W; P.seg[0][1].tile_start = (H * W + 127) / 128;
+    P.seg[1][0].H = Ho; P.seg[1][0].W = Wo; P.seg[1][1].pix_off = (long long)Ho * Wo; P.seg[1][1].tile_start = (Ho * Wo + 127) / 128;
+    float *d_in, *d_out, *d_w, *d_b, *d_sc, *d_sh, *d_res = nullptr; BatchPlan* d_p;
+    HIPCHK(hipMalloc((void**)&d_in, (size_t)H * W * Cin * 4)); HIPCHK(hipMalloc((void**)&d_out, (size_t)Ho * Wo * Cout * 4));
+    HIPCHK(hipMalloc((void**)&d_w, w.size() * 4)); HIPCHK(hipMalloc((void**)&d_b, b.size() * 4));
+    HIPCHK(hipMalloc((void**)&d_sc, sc.size() * 4)); HIPCHK(hipMalloc((void**)&d_sh, sh.size() * 4));
+    HIPCHK(hipMalloc((void**)&d_p, sizeof(BatchPlan)));
+    HIPCHK(hipMemcpy(d_in, in, (size_t)H * W * Cin * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    float* d_w4 = nullptr;
+    if (!pk.w4.empty()) {
+        HIPCHK(hipMalloc((void**)&d_w4, pk.w4.size() * 4));
+        HIPCHK(hipMemcpy(d_w4, pk.w4.data(), pk.w4.size() * 4, hipMemcpyHostToDevice));
+    }
+    uint16_t* d_w16 = nullptr; const float w16_unscale = pk.w16_unscale;
+    if (!pk.w16.empty()) {
+        HIPCHK(hipMalloc((void**)&d_w16, pk.w16.size() * 2));
+        HIPCHK(hipMemcpy(d_w16, pk.w16.data(), pk.w16.size() * 2, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_sc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_sh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
+    if (residual) { HIPCHK(hipMalloc((void**)&d_res, (size_t)Ho * Wo * Cout * 4)); HIPCHK(hipMemcpy(d_res, residual, (size_t)Ho * Wo * Cout * 4, hipMemcpyHostToDevice)); }
+    ConvArgs a; memset(&a, 0, sizeof(a));
+    a.in = d_in; a.out = d_out; a.w = d_w; a.w4 = d_w4; a.w16 = d_w16; a.w16_unscale = w16_unscale; a.bias = bias ? d_b : nullptr; a.scale = bn_scale ? d_sc : nullptr; a.shift = bn_scale ? d_sh : nullptr;
+    a.residual = d_res; a.up = nullptr; a.seg_in = d_p->seg[0]; a.seg_out = d_p->seg[1]; a.seg_up = d_p->seg[1]; a.dyn_rows = nullptr;
+    a.V = 1; a.Cin = Cin; a.Cout = Cout; a.CoutPad = CoutPad; a.Kpad = Kpad; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.relu = relu; a.total_mtiles = (Ho * Wo + 127) / 128; a.out_ld = Cout; a.in_relu = 0; a.zeros = c->d_zeros;
+    const bool launched = launch_conv(a, c->stream) != nullptr;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, d_out, (size_t)Ho * Wo * Cout * 4, hipMemcpyDeviceToHost));
+    if (d_w4) hipFree(d_w4);
+    if (d_w16) hipFree(d_w16);
+    hipFree(d_in); hipFree(d_out); hipFree(d_w); hipFree(d_b); hipFree(d_sc); hipFree(d_sh); hipFree(d_p); if (d_res) hipFree(d_res);
+    return launched ? 0 : conv_refused(a);
+}
+extern "C" int cald_op_conv2d(cald_ctx* c, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
+                              int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
+                              const float* residual, int relu, float* out) {
+    return op_conv2d(c, CALD_PRECISION_FP32, in, H, W, Cin, weight, Cout, KH, KW, stride, pad, bias, bn_scale, bn_shift, residual, relu, out);
+}
+// ---------------------------------------------------------------------------------------------
+// test-only conv probe (tests/test_gpu_conv_variants.py): one launch of the product's launchers on a ragged batch the caller describes,
+// under a forced kernel choice, with the product's own weight packing.  Output buffers are the caller's, copied whole to the device and
+// back, so whatever the caller put beyond the rows / channels a kernel may write (its guard words) comes back for inspection.
+// ---------------------------------------------------------------------------------------------
+extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* pr, int n, int path, int tile, char* kernel, int kernel_cap) {
+    if (!c || !pr || n < 1 || n > CALD_MAX_GROUP || !kernel || kernel_cap < 1) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: bad arguments");
+    if (path < CONV_AUTO || path > CONV_H4_GROUP || tile < TILE_AUTO || tile > TILE_WIDE) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: bad path / tile");
+    if (path == CONV_P4_FUSED && n != 2) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: the fused mode takes two problems (conv2, conv3)");
+    HIPCHK(hipSetDevice(c->device));
+    kernel[0] = 0;
+    ScopedDev sd(c->stream);
+    ConvArgs a[CALD_MAX_GROUP];
+    struct Back { void* dev; void* host; size_t bytes; };
+    std::vector<Back> back;
+    int rc;
+    auto up = [&](const void* h, size_t bytes, void** d) -> int {       // device copy of a host array (null stays null)
+        *d = nullptr;
+        if (!h) return 0;
+        if ((rc = sd.alloc(d, bytes))) return rc;
+        HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    for (int i = 0; i < n; i++) {
+        const cald_conv_probe& p = pr[i];
+        if (p.V < 1 || p.V > CALD_PROBE_MAX_VIEWS || p.Cin < 4 || p.Cin % 4 || p.Cout < 1 || p.KH < 1 || p.KW < 1 || p.stride < 1 || p.pad < 0 ||
+            p.out_ld < p.Cout || !p.weight || !p.in)
+            return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: bad layer", i);
+        // geometry: level 0 input, 1 output, 2 the coarser level of `up`
+        std::vector<LevelSeg> seg(3 * (CALD_PROBE_MAX_VIEWS + 1));
+        memset(seg.data(), 0, seg.size() * sizeof(LevelSeg));
+        LevelSeg* si = &seg[0]; LevelSeg* so = &seg[CALD_PROBE_MAX_VIEWS + 1]; LevelSeg* su = &seg[2 * (CALD_PROBE_MAX_VIEWS + 1)];
+        std::vector<GatherSet> gs(p.V);
+        long long rows_out = 0;
+        for (int v = 0; v < p.V; v++) {
+            const int H = p.in_hw[v][0], W = p.in_hw[v][1];
+            if (H < 0 || W < 0) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: negative view size");
+            const int Ho = H && W ? (H + 2 * p.pad - p.KH) / p.stride + 1 : 0, Wo = H && W ? (W + 2 * p.pad - p.KW) / p.stride + 1 : 0;
+            if (Ho < 0 || Wo < 0 || (H && W && (Ho < 1 || Wo < 1))) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: view %d smaller than the filter", v);
+            si[v].H = H; si[v].W = W; so[v].H = Ho; so[v].W = Wo; su[v].H = p.up_hw[v][0]; su[v].W = p.up_hw[v][1];
+            long long m = (long long)Ho * Wo;
+            if (p.gather) {
+                GatherSet& g = gs[v]; memset(&g, 0, sizeof(g));
+                if (p.nrect[v] < 0 || p.nrect[v] > CALD_GATHER_RECTS) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: 0..%d rectangles", CALD_GATHER_RECTS);
+                g.nr = p.nrect[v];
+                for (int k = 0; k < g.nr; k++) {
+                    const int* r = p.rect[v][k];
+                    if (r[0] < 0 || r[1] < 0 || r[2] < 1 || r[3] < 1 || r[0] + r[2] > Wo || r[1] + r[3] > Ho)
+                        return fail(CALD_ERR_INVALID, "cald_op_conv_probe: rectangle outside view %d", v);
+                    g.x0[k] = r[0]; g.y0[k] = r[1]; g.w[k] = r[2]; g.cum[k + 1] = g.cum[k] + r[2] * r[3];
+                }
+                m = g.cum[g.nr];
+            }
+            si[v + 1].pix_off = si[v].pix_off + (long long)H * W;
+            so[v + 1].pix_off = so[v].pix_off + (long long)Ho * Wo;
+            su[v + 1].pix_off = su[v].pix_off + (long long)su[v].H * su[v].W;
+            so[v + 1].tile_start = so[v].tile_start + (int)((m + 127) / 128);
+            si[v + 1].tile_start = si[v].tile_start + (H * W + 127) / 128;
+            rows_out = so[v + 1].pix_off;
+        }
+        const long long pix_in = si[p.V].pix_off, pix_up = su[p.V].pix_off;
+        if ((p.out && p.out_n < rows_out * p.out_ld) || (p.out16 && p.out16_n < rows_out * p.out_ld) || (p.energy4 && p.energy4_n < rows_out * 4))
+            return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: an output buffer is smaller than the output", i);
+        ConvPack pk;
+        const int cin_true = p.cin_true > 0 ? p.cin_true : p.Cin;
+        if (cin_true > p.Cin) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: cin_true > Cin");
+        pack_conv({p.weight}, {p.Cout}, cin_true, p.Cin, p.KH, p.KW, p.stride, p.pad, precision == CALD_PRECISION_F16X3, &pk);
+        std::vector<float> vb(pk.CoutPad, 0.0f), vs(pk.CoutPad, 0.0f), vh(pk.CoutPad, 0.0f);
+        for (int k = 0; k < p.Cout; k++) { if (p.bias) vb[k] = p.bias[k]; if (p.bn_scale) { vs[k] = p.bn_scale[k]; vh[k] = p.bn_shift[k]; } }
+        ConvArgs& A = a[i]; memset(&A, 0, sizeof(A));
+        void* d;
+        const size_t out_b = (size_t)p.out_ld * 4;
+        if ((rc = up(pk.w.data(), pk.w.size() * 4, &d))) return rc; A.w = (const float*)d;
+        if ((rc = up(pk.w4.empty() ? nullptr : pk.w4.data(), pk.w4.size() * 4, &d))) return rc; A.w4 = (const float*)d;
+        if ((rc = up(pk.w16.empty() ? nullptr : pk.w16.data(), pk.w16.size() * 2, &d))) return rc; A.w16 = d; A.w16_unscale = pk.w16_unscale;
+        if ((rc = up(pk.wstem.empty() || !stem_grid_exact(so, p.V) ? nullptr : pk.wstem.data(), pk.wstem.size() * 4, &d))) return rc; A.wstem = (const float*)d;
+        if ((rc = up(p.bias ? vb.data() : nullptr, vb.size() * 4, &d))) return rc; A.bias = (const float*)d;
+        if ((rc = up(p.bn_scale ? vs.data() : nullptr, vs.size() * 4, &d))) return rc; A.scale = (const float*)d;
+        if ((rc = up(p.bn_scale ? vh.data() : nullptr, vh.size() * 4, &d))) return rc; A.shift = (const float*)d;
+        if ((rc = up(p.in, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in = (const float*)d;
+        if ((rc = up(p.in16, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in16 = (const unsigned*)d;
+        if ((rc = up(p.residual, (size_t)rows_out * out_b, &d))) return rc; A.residual = (const float*)d;
+        if ((rc = up(p.up, (size_t)pix_up * out_b, &d))) return rc; A.up = (const float*)d;
+        if ((rc = up(p.mask, (size_t)rows_out * out_b, &d))) return rc; A.mask = (const float*)d;
+        if ((rc = up(p.row_map, (size_t)rows_out * 4, &d))) return rc; A.row_map = (const int*)d;
+        if ((rc = up(p.has_dyn ? p.dyn_rows : nullptr, (size_t)p.V * 4, &d))) return rc; A.dyn_rows = (const int*)d;
+        if ((rc = up(p.gather ? gs.data() : nullptr, gs.size() * sizeof(GatherSet), &d))) return rc; A.gather = (const GatherSet*)d;
+        if ((rc = up(seg.data(), seg.size() * sizeof(LevelSeg), &d))) return rc;
+        A.seg_in = (const LevelSeg*)d; A.seg_out = A.seg_in + CALD_PROBE_MAX_VIEWS + 1; A.seg_up = A.seg_in + 2 * (CALD_PROBE_MAX_VIEWS + 1);
+        if ((rc = up(p.out, (size_t)p.out_n * 4, &d))) return rc; A.out = (float*)d;
+        if (p.out) back.push_back({d, p.out, (size_t)p.out_n * 4});
+        if ((rc = up(p.out16, (size_t)p.out16_n * 4, &d))) return rc; A.out16 = (unsigned*)d;
+        if (p.out16) back.push_back({d, p.out16, (size_t)p.out16_n * 4});
+        if ((rc = up(p.energy4, (size_t)p.energy4_n * 4, &d))) return rc; A.energy4 = (float*)d;
+        if (p.energy4) back.push_back({d, p.energy4, (size_t)p.energy4_n * 4});
+        A.ex16 = p.ex16 ? 1 : 0;
+        A.V = p.V; A.Cin = p.Cin; A.Cout = p.Cout; A.CoutPad = pk.CoutPad; A.Kpad = pk.Kpad;
+        A.KH = p.KH; A.KW = p.KW; A.stride = p.stride; A.pad = p.pad; A.relu = p.relu ? 1 : 0; A.in_relu = p.in_relu ? 1 : 0;
+        A.total_mtiles = so[p.V].tile_start; A.out_ld = p.out_ld; A.zeros = c->d_zeros;
+    }
+    if (path == CONV_P4_FUSED) a[1].in = a[0].out;       // conv3 reads conv2's output (which the fused kernel keeps on chip)
+    const ConvForce f{path, tile};
+    const char* names[CALD_MAX_GROUP] = {nullptr};
+    if (path == CONV_P4_FUSED) names[0] = names[1] = launch_conv_p4_fused(a[0], a[1], c->stream);
+    else if (n > 1 || path == CONV_P4_GROUP || path == CONV_H3_GROUP || path == CONV_H4_GROUP) launch_conv_group(a, n, c->stream, names, f);
+    else names[0] = launch_conv(a[0], c->stream, f);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::string all;
+    for (int i = 0; i < n; i++) {
+        if (!names[i]) return fail(CALD_ERR_UNSUPPORTED, "cald_op_conv_probe: problem %d refused under path %d tile %d", i, path, tile);
+        if (all.find(names[i]) == std::string::npos) { if (!all.empty()) all += ";"; all += names[i]; }
+    }
+    for (const Back& b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
+    snprintf(kernel, (size_t)kernel_cap, "%s", all.c_str());
+    return 0;
+}
+void launch_mfma_f16_probe(const unsigned short* A, const unsigned short* B, const unsigned* C, unsigned* D, long long n, hipStream_t stream);   // conv_h3.hip
+extern "C" int cald_op_mfma_f16(cald_ctx* c, const uint16_t* A, const uint16_t* B, const uint32_t* C, uint32_t* D, int64_t n) {
+    if (!c || !A || !B || !C || !D || n < 1) return fail(CALD_ERR_INVALID, "cald_op_mfma_f16: null argument or n < 1");
+    HIPCHK(hipSetDevice(c->device));
+    struct Bufs {       // freed on every exit path
+        void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
+    } d;
+    HIPCHK(hipMalloc(&d.p[0], (size_t)n * 32)); HIPCHK(hipMalloc(&d.p[1], (size_t)n * 32));
+    HIPCHK(hipMalloc(&d.p[2], (size_t)n * 4)); HIPCHK(hipMalloc(&d.p[3], (size_t)n * 4));
+    HIPCHK(hipMemcpyAsync(d.p[0], A, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d.p[1], B, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d.p[2], C, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    launch_mfma_f16_probe((const unsigned short*)d.p[0], (const unsigned short*)d.p[1], (const unsigned*)d.p[2], (unsigned*)d.p[3], (long long)n, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(D, d.p[3], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+extern "C" int cald_op_conv2d_f16x3(cald_ctx* c, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
+                                    int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
+                                    const float* residual, int relu, float* out) {
+    return op_conv2d(c, CALD_PRECISION_F16X3, in, H, W, Cin, weight, Cout, KH, KW, stride, pad, bias, bn_scale, bn_shift, residual, relu, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// kernel-tuning aid (tools/bench_conv.py): times ONE conv layer shape on a ragged batch of V equal views with
+// pseudo-random data (MFMA power, hence the sustained clock, depends on the operand values: never bench on zeros)
+// ---------------------------------------------------------------------------------------------
+__global__ void fill_random_kernel(float* p, long long n, unsigned seed) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        unsigned x = (unsigned)i * 2654435761u ^ seed; x ^= x >> 15; x *= 2246822519u; x ^= x >> 13; x *= 3266489917u; x ^= x >> 16;
+        p[i] = ((float)(x >> 8) * (1.0f / 8388608.0f) - 1.0f) * ((x & 7u) ? 1.0f : 0.0f);      // ~U(-1, 1), 1/8 zeros (post-ReLU-like)
+    }
+}
+extern "C" int cald_op_conv_bench(cald_ctx* c, int V, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int residual,
+                                  int relu, int iters, int group, double* ms_out, double* tflops_out) {
+    if (!c || V < 1 || V > CALD_MAX_VIEWS || iters < 1 || !ms_out || group < 1 || group > CALD_MAX_GROUP) return fail(CALD_ERR_INVALID, "bad arguments");
+    if (Cin % 4) return fail(CALD_ERR_INVALID, "Cin must be a multiple of 4");
+    HIPCHK(hipSetDevice(c->device));
+    const int KW = KH, Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+    const int CoutPad = cout_pad(Cout), K = KH * KW * Cin, Kpad = round_up(K, 16);
+    std::vector<float> w((size_t)Kpad * CoutPad, 0.0f), b(CoutPad, 0.1f), sc(CoutPad, 1.0f), sh(CoutPad, 0.01f);
+    unsigned r = 12345u;
+    for (int k = 0; k < K; k++) for (int n = 0; n < Cout; n++) { r = r * 1664525u + 1013904223u; w[(size_t)k * CoutPad + n] = ((float)(r >> 8) / 8388608.0f - 1.0f) * 0.05f; }
+    BatchPlan P; memset(&P, 0, sizeof(P));
+    for (int v = 0; v <= V; v++) {
+        P.seg[0][v].pix_off = (long long)v * H * W; P.seg[0][v].tile_start = v * ((H * W + 127) / 128); P.seg[0][v].H = H; P.seg[0][v].W = W;
+        P.seg[1][v].pix_off = (long long)v * Ho * Wo; P.seg[1][v].tile_start = v * ((Ho * Wo + 127) / 128); P.seg[1][v].H = Ho; P.seg[1][v].W = Wo;
+    }
+    ScopedDev sd(c->stream);
+    float *d_in, *d_out, *d_w, *d_w4 = nullptr, *d_b, *d_sc, *d_sh, *d_res = nullptr; BatchPlan* d_p;
+    const size_t n_in = (size_t)V * H * W * Cin, n_out = (size_t)V * Ho * Wo * Cout;
+    int rc;
+    if ((rc = sd.alloc(&d_in, n_in * 4)) || (rc = sd.alloc(&d_out, n_out * 4 * group)) || (rc = sd.alloc(&d_w, w.size() * 4)) || (rc = sd.alloc(&d_b, b.size() * 4)) ||
+        (rc = sd.alloc(&d_sc, sc.size() * 4)) || (rc = sd.alloc(&d_sh, sh.size() * 4)) || (rc = sd.alloc(&d_p, sizeof(BatchPlan)))) return rc;
+    if (residual && (rc = sd.alloc(&d_res, n_out * 4))) return rc;
+    hipLaunchKernelGGL(fill_random_kernel, dim3(4096), dim3(256), 0, c->stream, d_in, (long long)n_in, 1u);
+    if (d_res) hipLaunchKernelGGL(fill_random_kernel, dim3(4096), dim3(256), 0, c->stream, d_res, (long long)n_out, 2u);
+    HIPCHK(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+    if (CoutPad % 64 == 0 && ((Cin % 16 == 0 && KH * KW <= 32) || Cin == 4)) {
+        std::vector<float> w4 = pack_w4(w, Kpad, CoutPad);
+        if ((rc = sd.alloc(&d_w4, w4.size() * 4))) return rc;
+        HIPCHK(hipMemcpy(d_w4, w4.data(), w4.size() * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_sc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_sh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
+    ConvArgs a[CALD_MAX_GROUP];
+    for (int gi = 0; gi < group; gi++) {
+        memset(&a[gi], 0, sizeof(ConvArgs));
+        a[gi].in = d_in; a[gi].out = d_out + (size_t)gi * n_out; a[gi].w = d_w; a[gi].w4 = d_w4; a[gi].bias = d_b; a[gi].scale = d_sc; a[gi].shift = d_sh; a[gi].residual = d_res;
+        a[gi].seg_in = d_p->seg[0]; a[gi].seg_out = d_p->seg[1]; a[gi].seg_up = d_p->seg[1]; a[gi].V = V; a[gi].Cin = Cin; a[gi].Cout = Cout; a[gi].CoutPad = CoutPad; a[gi].Kpad = Kpad;
+        a[gi].KH = KH; a[gi].KW = KW; a[gi].stride = stride; a[gi].pad = pad; a[gi].relu = relu; a[gi].total_mtiles = V * ((Ho * Wo + 127) / 128); a[gi].out_ld = Cout; a[gi].zeros = c->d_zeros;
+    }
+    auto launch = [&]() { if (group > 1) launch_conv_group(a, group, c->stream); else launch_conv(a[0], c->stream); };
+    launch(); launch();
+    HIPCHK(hipGetLastError());
+    hipEvent_t e0, e1; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, c->stream));
+    for (int i = 0; i < iters; i++) launch();
+    HIPCHK(hipEventRecord(e1, c->stream));
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (const char* tp = getenv("CALD_CONV_TRACE")) {       // one more launch with the per-workgroup timeline recorded (conv_p4.hip), dumped raw
+        const size_t nblk = 1u << 17;
+        unsigned long long* d_tr;
+        if ((rc = sd.alloc(&d_tr, nblk * 64))) return rc;
+        HIPCHK(hipMemsetAsync(d_tr, 0, nblk * 64, c->stream));
+        for (int gi = 0; gi < group; gi++) a[gi].trace = d_tr;
+        launch();
+        HIPCHK(hipStreamSynchronize(c->stream));
+        std::vector<unsigned long long> h(nblk * 8);
+        HIPCHK(hipMemcpy(h.data(), d_tr, nblk * 64, hipMemcpyDeviceToHost));
+        size_t used = nblk; while (used > 0 && h[(used - 1) * 8] == 0) used--;
+        if (FILE* f = fopen(tp, "wb")) { fwrite(h.data(), 64, used, f); fclose(f); }
+        for (int gi = 0; gi < group; gi++) a[gi].trace = nullptr;
+    }
+    *ms_out = (double)ms / iters;
+    if (tflops_out) *tflops_out = 2.0 * (double)V * Ho * Wo * Cout * (double)K * group / (*ms_out * 1e-3) / 1e12;
+    return 0;
+}
+
+extern "C" int cald_op_consistency(cald_ctx* c, int N, const float* aug_box, const float* ref_scores_cls, const float* ref_pm,
+                                   int M, const float* boxes, const float* scores_cls, const float* pm, int C, float bp,
+                                   float* consistency_out) {
+    if (!c || !consistency_out || N < 0 || M < 0 || C < 2 || C > 256) return fail(CALD_ERR_INVALID, "bad arguments");
+    if (N > 50) return fail(CALD_ERR_INVALID, "at most 50 reference boxes (cald_train.py:110-113)");
+    HIPCHK(hipSetDevice(c->device));
+    const int cap = (N > M ? N : M) > 0 ? (N > M ? N : M) : 1;
+    DetBuffers d; int rc = alloc_det(d, 2, cap, C); if (rc) return rc;
+    if (N) {
+        HIPCHK(hipMemcpy(d.boxes, aug_box, (size_t)N * 16, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d.scores_cls, ref_scores_cls, (size_t)N * C * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d.prob_max, ref_pm, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    if (M) {
+        HIPCHK(hipMemcpy(d.boxes + (size_t)cap * 4, boxes, (size_t)M * 16, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d.scores_cls + (size_t)cap * C, scores_cls, (size_t)M * C * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d.prob_max + cap, pm, (size_t)M * 4, hipMemcpyHostToDevice));
+    }
+    int counts[2] = {N, M};
+    HIPCHK(hipMemcpy(d.count, counts, 8, hipMemcpyHostToDevice));
+    int h[4 + 50 + 1] = {0};   // ref_view, aug_view, kind, pair_img | ref_sel[50] | ref_n
+    h[0] = 0; h[1] = 1; h[2] = 0; h[3] = 0;
+    for (int i = 0; i < 50; i++) h[4 + i] = i;
+    h[54] = N;
+    int* dh; float* dpar; float* dcons;
+    HIPCHK(hipMalloc((void**)&dh, sizeof(h))); HIPCHK(hipMalloc((void**)&dpar, 48)); HIPCHK(hipMalloc((void**)&dcons, 4));
+    HIPCHK(hipMemcpy(dh, h, sizeof(h), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(dpar, 0, 48));
+    ScoreArgs a; a.det = d; a.ref_view = dh; a.aug_view = dh + 1; a.aug_kind = dh + 2; a.pair_img = dh + 3; a.ref_sel = dh + 4; a.ref_n = dh + 54;
+    a.aug_param = dpar; a.P = 1; a.bp = bp; a.cons = dcons;
+    launch_consistency(a, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(consistency_out, dcons, 4, hipMemcpyDeviceToHost));
+    hipFree(dh); hipFree(dpar); hipFree(dcons); free_det(d);
+    return 0;
+}
+
+// RoIHeads.postprocess_detections + transform.postprocess of ONE view on the kernels of the forward (roi.hip post_softmax_kernel /
+// post_nms_kernel): host arrays in, host arrays out.  Parity hook for detection/frcnn_la.py:32-87, :292-315.
+extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float* logits, const float* deltas, const float* proposals,
+                                         int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max,
+                                         float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
+                                         float* scores_cls_out, int* n_out) {
+    if (!c || !logits || !deltas || !proposals || !boxes_out || !scores_out || !labels_out || !props_out || !prob_max_out || !scores_cls_out || !n_out)
+        return fail(CALD_ERR_INVALID, "null argument");
+    if (R < 0 || R > CALD_ROI_CAP || C < 2 || C > 256 || det_max < 1 || det_max > 512) return fail(CALD_ERR_INVALID, "bad geometry (R <= %d, 2 <= C <= 256, det_max <= 512)", CALD_ROI_CAP);
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    const int ld = 5 * C;
+    int key_cap = 1024; while (key_cap < R * (C - 1)) key_cap <<= 1;
+    std::vector<float> pred((size_t)CALD_ROI_CAP * ld, 0.0f);
+    for (int r = 0; r < R; r++) {
+        memcpy(&pred[(size_t)r * ld], logits + (size_t)r * C, (size_t)C * 4);
+        memcpy(&pred[(size_t)r * ld + C], deltas + (size_t)r * 4 * C, (size_t)4 * C * 4);
+    }
+    ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
+    PostArgs pa; float *d_pred, *d_props, *d_prob, *d_pmax, *d_cbox; unsigned long long* d_keys; int *d_kc, *d_pc; ViewDesc* d_vd;
+    int rc;
+    if ((rc = sd.alloc(&d_pred, pred.size() * 4)) || (rc = sd.alloc(&d_props, (size_t)CALD_ROI_CAP * 16)) || (rc = sd.alloc(&d_prob, (size_t)CALD_ROI_CAP * C * 4)) ||
+        (rc = sd.alloc(&d_pmax, (size_t)CALD_ROI_CAP * 4)) || (rc = sd.alloc(&d_cbox, (size_t)2 * key_cap * 16)) || (rc = sd.alloc(&d_keys, (size_t)key_cap * 8)) ||
+        (rc = sd.alloc(&d_kc, 4)) || (rc = sd.alloc(&d_pc, 4)) || (rc = sd.alloc(&d_vd, sizeof(ViewDesc)))) return rc;
+    DetBuffers det; if ((rc = alloc_det(det, 1, det_max, C))) return rc;
+    HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_props, 0, (size_t)CALD_ROI_CAP * 16));
+    if (R) HIPCHK(hipMemcpy(d_props, proposals, (size_t)R * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pc, &R, 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+    pa.pred = d_pred; pa.pred_ld = ld; pa.C = C; pa.V = 1; pa.proposals = d_props; pa.prop_count = d_pc; pa.views = d_vd;
+    pa.score_thr = score_thr; pa.nms_thr = nms_thr; pa.prob = d_prob; pa.pmax = d_pmax; pa.keys = d_keys; pa.cbox = d_cbox; pa.key_count = d_kc;
+    pa.key_cap = key_cap; pa.det = det;
+    launch_frcnn_postprocess(pa, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, det.count, 4, hipMemcpyDeviceToHost));
+    *n_out = n;
+    if (n) {
+        HIPCHK(hipMemcpy(boxes_out, det.boxes, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(scores_out, det.scores, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(labels_out, det.labels, (size_t)n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(props_out, det.props, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(prob_max_out, det.prob_max, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(scores_cls_out, det.scores_cls, (size_t)n * C * 4, hipMemcpyDeviceToHost));
+    }
+    free_det(det);
+    return 0;
+}
+
+// MultiScaleRoIAlign(7, sampling_ratio 2) of ONE view on the inference kernels (roi.hip): feats[l] = host [H_l][W_l][C] for the four
+// levels P2..P5 (level_hw = {H0, W0, ..., H3, W3}), rois [R][4] in image coordinates, out [R][49][C] (host).  C == 256 runs the
+// row-walk kernel, other C (multiple of 4) the gather kernel.  Parity hook for detection/frcnn_la.py:205-209.
+extern "C" int cald_op_roi_align(cald_ctx* c, const float* const* feats, const int* level_hw, int C, int R, const float* rois, float* out) {
+    if (!c || !feats || !level_hw || !rois || !out) return fail(CALD_ERR_INVALID, "null argument");
+    if (R < 1 || R > CALD_ROI_CAP || C < 4 || C % 4) return fail(CALD_ERR_INVALID, "bad geometry (1 <= R <= %d, C a positive multiple of 4)", CALD_ROI_CAP);
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    BatchPlan P; memset(&P, 0, sizeof(P));
+    RoiArgs ro; float* d_f[4]; BatchPlan* d_p; float *d_rois, *d_out; int *d_pc, *d_order;
+    int rc;
+    for (int l = 0; l < 4; l++) {
+        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
+        if (H < 1 || W < 1 || !feats[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
+        P.seg[2 + l][0].H = H; P.seg[2 + l][0].W = W; P.seg[2 + l][1].pix_off = (long long)H * W;
+        if ((rc = sd.alloc(&d_f[l], (size_t)H * W * C * 4))) return rc;
+        HIPCHK(hipMemcpy(d_f[l], feats[l], (size_t)H * W * C * 4, hipMemcpyHostToDevice));
+    }
+    if ((rc = sd.alloc(&d_p, sizeof(BatchPlan))) || (rc = sd.alloc(&d_rois, (size_t)CALD_ROI_CAP * 16)) || (rc = sd.alloc(&d_out, (size_t)CALD_ROI_CAP * 49 * C * 4)) ||
+        (rc = sd.alloc(&d_pc, 4)) || (rc = sd.alloc(&d_order, 1024 * 4))) return rc;
+    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_rois, 0, (size_t)CALD_ROI_CAP * 16));
+    HIPCHK(hipMemcpy(d_rois, rois, (size_t)R * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_pc, &R, 4, hipMemcpyHostToDevice));
+    for (int l = 0; l < 4; l++) { ro.feat[l] = d_f[l]; ro.seg[l] = d_p->seg[2 + l]; }
+    ro.C = C; ro.V = 1; ro.proposals = d_rois; ro.prop_count = d_pc; ro.out = d_out; ro.order = d_order; ro.out16 = 0;
+    launch_roi_align(ro, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, d_out, (size_t)R * 49 * C * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int cald_op_cls_corr(cald_ctx* c, int n, const float* scores, const int64_t* labels, int C, float* out) {
+    if (!c || !out || n < 0 || C < 2 || C > 256) return fail(CALD_ERR_INVALID, "bad arguments");
+    HIPCHK(hipSetDevice(c->device));
+    DetBuffers d; int rc = alloc_det(d, 1, n > 0 ? n : 1, C); if (rc) return rc;
+    if (n) { HIPCHK(hipMemcpy(d.scores, scores, (size_t)n * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d.labels, labels, (size_t)n * 8, hipMemcpyHostToDevice)); }
+    HIPCHK(hipMemcpy(d.count, &n, 4, hipMemcpyHostToDevice));
+    int h[2] = {0, 0}; int* dh; float* dout;
+    HIPCHK(hipMalloc((void**)&dh, 8)); HIPCHK(hipMalloc((void**)&dout, (size_t)(C - 1) * 4));
+    HIPCHK(hipMemcpy(dh, h, 8, hipMemcpyHostToDevice));
+    launch_cls_corr(d, nullptr, nullptr, dh, dh + 1, 1, dout, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, dout, (size_t)(C - 1) * 4, hipMemcpyDeviceToHost));
+    hipFree(dh); hipFree(dout); free_det(d);
+    return 0;
+}

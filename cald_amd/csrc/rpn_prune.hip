@@ -24,7 +24,7 @@
 // rounding (and aligning) once at <= 2^-23 of the running magnitude: term j is carried by 3 (K - j) / 16 + 3 of them.  ReLU is 1-Lipschitz; the
 // bias add rounds once on each side.  The 1 x 1 head is evaluated by the SAME exact kernel on both hidden vectors:
 // |L~ - L| <= sum_c |v_ac| |h_e - h_f| + 2 g_h sum_c |v_ac| max(|h_e|, |h_f|), g_h = 256 u / (1 - 256 u), |h| <= |patch|_2 |w_c|_2 + |b_c|.
-// Per anchor a this is  B_a(p) = c1_a |patch(p)|_2 + c0_a  with two constants fixed at model finalize (api.hip, in double; inflated by 2 % for
+// Per anchor a this is  B_a(p) = c1_a |patch(p)|_2 + c0_a  with two constants fixed at model finalize (model.hip cald_model_finalize, in double; inflated by 2 % for
 // the float32 evaluation of the bound itself).
 // What is a theorem and what is a model: g_e and g_h are the textbook bounds of the fp32 chains the exact mode IS; the split error of the
 // operands is exact arithmetic on the formats; "one rounding of relative size 2^-23 per MFMA instruction" is a MODEL of
@@ -34,7 +34,7 @@
 // both ways, prune_scatter_kernel keeps max |L~ - L| / B over all of them (10 - 35 % of all anchors of the two levels, hundreds of thousands
 // per forward), and cald_sweep repeats itself with the dense head if the ratio ever exceeds 1 (observed: 5e-5, cald_profile_prune).
 // Round 6: the instruction IS now stated bit for bit (oracle/mfma_f16_model.h, pinned to the hardware on > 10^7 dot products), and the
-// constants in api.hip are derived from that statement -- a theorem about the model instead of a guess about the pipe; the all-anchor test
+// constants in model.hip are derived from that statement -- a theorem about the model instead of a guess about the pipe; the all-anchor test
 // (tests: test_rpn_pruning_bound_holds_on_every_anchor) evaluates the bound on every anchor of P2 / P3, pruned ones included.
 #include "common.h"
 #include "kernels.h"
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
 // the exact head rows of the selected pixels back into the dense [pixel][head_ld] map -- and the bound put to the test: every selected anchor
 // has both values, the look-ahead's L~ (still in the map) and the exact L; max |L~ - L| / B over all of them goes to a.check[0]
 // (non-negative floats order like their bit patterns).  A ratio above 1 means the bound does not hold on this data: the sweep then repeats
-// itself with the dense head (api.hip).  grid = (blocks, V, 4): z = level + 2 * stage
+// itself with the dense head (sweep.hip sweep_checked).  grid = (blocks, V, 4): z = level + 2 * stage
 __global__ __launch_bounds__(256) void prune_scatter_kernel(RpnPruneArgs a) {
     const int l = blockIdx.z & 1, st = blockIdx.z >> 1, v = blockIdx.y;
     const LevelSeg sg = a.seg[l][v];

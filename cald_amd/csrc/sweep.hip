@@ -1,0 +1,748 @@
+// sweep.hip -- the sweeps of the C ABI on the detector forward: cald_sweep / cald_sweep_audit as a pipeline of named stages (SweepRun), and
+// the baselines cald_sweep_ltc / cald_sweep_lsc.  Host-side restatements used here (host_logic.h): Python `random` (MT19937) + cutout
+// rectangle selection (cald/cald_helper.py:88-132), np.linspace sub-sampling (cald_train.py:110-113), the float64 means of cald_train.py:225-228.
+#include "host.h"
+
+// helper: device detection buffers
+void cald_host::free_det(DetBuffers& d) {
+    hipFree(d.boxes); hipFree(d.scores); hipFree(d.labels); hipFree(d.props); hipFree(d.prob_max); hipFree(d.scores_cls); hipFree(d.count);
+    memset(&d, 0, sizeof(d));
+}
+// all-or-nothing: on any failed hipMalloc everything already allocated is released and `d` is left zeroed
+int cald_host::alloc_det(DetBuffers& d, int V, int cap, int C) {
+    memset(&d, 0, sizeof(d));
+    d.cap = cap; d.C = C;
+    hipError_t e = hipMalloc((void**)&d.boxes, (size_t)V * cap * 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.scores, (size_t)V * cap * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.labels, (size_t)V * cap * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.props, (size_t)V * cap * 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.prob_max, (size_t)V * cap * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.scores_cls, (size_t)V * cap * C * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d.count, (size_t)V * 4);
+    if (e != hipSuccess) {
+        free_det(d);
+        return fail(CALD_ERR_HIP, "hipMalloc of detection buffers (%d views x %d rows x %d classes) failed: %s", V, cap, C, hipGetErrorString(e));
+    }
+    return 0;
+}
+// one of the model's batch-level detection-buffer sets (`views`: how many views it holds) holds at least VT views; after a failed growth
+// the model owns none
+static int ensure_det(cald_model* m, DetBuffers& set, int& views, int VT) {
+    if (views >= VT) return 0;
+    if (views) {
+        HIPCHK(hipStreamSynchronize(m->ctx->stream));
+        free_det(set);
+        views = 0;
+    }
+    int rc = alloc_det(set, VT, m->det_cap(), m->cfg.num_classes);
+    if (rc) return rc;
+    views = VT;
+    return 0;
+}
+// the buffers of D from view `o` on
+static DetBuffers det_at(const DetBuffers& D, size_t o) {
+    DetBuffers d2 = D;
+    const int cap = D.cap, C = D.C;
+    d2.boxes += o * cap * 4; d2.scores += o * cap; d2.labels += o * cap; d2.props += o * cap * 4;
+    d2.prob_max += o * cap; d2.scores_cls += o * cap * C; d2.count += o;
+    return d2;
+}
+// the untouched view of one image, and the reference views of images [i0, i0 + nb)
+static ViewDesc plain_view(const uint8_t* src, int H, int W) {
+    ViewDesc d; memset(&d, 0, sizeof(d));
+    d.src = src; d.H = H; d.W = W;
+    return d;
+}
+static std::vector<ViewDesc> ref_views(const uint8_t* const* images_dev, const int* H, const int* W, int i0, int nb) {
+    std::vector<ViewDesc> views(nb);
+    for (int i = 0; i < nb; i++) views[i] = plain_view(images_dev[i0 + i], H[i0 + i], W[i0 + i]);
+    return views;
+}
+
+// views per augmented forward: 96 fills whole rounds of the 768 workgroup slots in the mid-size layers and fc6 (CALD_FWD_VIEWS overrides)
+static int sweep_fwd_views() {
+    static const int env = getenv("CALD_FWD_VIEWS") ? atoi(getenv("CALD_FWD_VIEWS")) : 96;
+    return env < 1 ? 1 : (env > CALD_MAX_VIEWS ? CALD_MAX_VIEWS : env);
+}
+// n augmented views run in forwards of <= sweep_fwd_views() views, evenly sized (159 views run as 80 + 79, not 96 + 63: a short last forward
+// leaves most of its launches under-filled; results do not depend on the split).  96 views per forward: the mid-size layers and fc6 then
+// fill whole rounds of the 768 workgroup slots (measured +1.0 % on the sweep).  Forward f of the fwd_count(n) takes views [a0, a0 + nv).
+static int fwd_count(int n) { return (n + sweep_fwd_views() - 1) / sweep_fwd_views(); }
+static void fwd_span(int n, int f, int* a0, int* nv) {
+    const int n_fw = fwd_count(n);
+    *a0 = (int)(((long long)n * f) / n_fw); *nv = (int)(((long long)n * (f + 1)) / n_fw) - *a0;
+}
+// cut_out reuse on by default in the exact sweeps; CALD_CUTOUT_REUSE=0 turns it off for the process (A/B, escape hatch)
+static bool cut_reuse_env() {
+    static const bool on = !(getenv("CALD_CUTOUT_REUSE") && atoi(getenv("CALD_CUTOUT_REUSE")) == 0);
+    return on;
+}
+#define CUT_GATHER_MAX_COST 0.7    // a stage runs gathered while its tiles cost at most this fraction of the dense stage
+
+namespace {
+// The `ints` block of a scoring stage, the same words on the host and on the device: per pair ref_view | aug_view | aug_kind | pair_img
+// (P_MAX each), ref_sel [B][50], ref_n [B], then per view view_img | view_isref (VT each; VT = 0: no per-view tail -- ls_c has no cls_corr).
+struct PairLayout {
+    int P_MAX, B, VT;
+    struct Ptrs { int *ref_view, *aug_view, *aug_kind, *pair_img, *ref_sel, *ref_n, *view_img, *view_isref; };
+    size_t n_ints() const { return (size_t)P_MAX * 4 + (size_t)B * 51 + (size_t)VT * 2; }
+    Ptrs at(int* base) const {
+        Ptrs p;
+        p.ref_view = base; p.aug_view = p.ref_view + P_MAX; p.aug_kind = p.aug_view + P_MAX; p.pair_img = p.aug_kind + P_MAX;
+        p.ref_sel = p.pair_img + P_MAX; p.ref_n = p.ref_sel + (size_t)B * 50; p.view_img = p.ref_n + B; p.view_isref = p.view_img + VT;
+        return p;
+    }
+    // the scoring kernels' arguments over the device copy of the block
+    ScoreArgs score_args(int* d_base, const DetBuffers& D, const float* d_par, int P, float bp, float* cons) const {
+        const Ptrs p = at(d_base);
+        ScoreArgs sa; sa.det = D;
+        sa.ref_view = p.ref_view; sa.aug_view = p.aug_view; sa.aug_kind = p.aug_kind; sa.pair_img = p.pair_img;
+        sa.ref_sel = p.ref_sel; sa.ref_n = p.ref_n; sa.aug_param = d_par; sa.P = P; sa.bp = bp; sa.cons = cons;
+        return sa;
+    }
+};
+
+// =============================================================================================
+// the sweep (get_uncertainty, cald_train.py:91-231)
+// =============================================================================================
+// Host state of one batch from its reference forward to its float64 means.  Two live at a time: while the host builds the augmented
+// views of batch k (cutout needs the reference boxes on the host) the GPU already runs the reference forward of batch k + 1, and the
+// scores of batch k come back while batch k + 1 is being built -- the stream never waits for the host (round 3 stopped twice per batch).
+struct SweepBatch {
+    int i0 = 0, nb = 0, P = 0, VV = 0; bool live = false;
+    int* h_count; float* h_boxes; int* h_ints; float* h_par; NoiseJob* h_jobs; float* h_cons; float* h_clsc; float* h_vm; float* h_pm;   // pinned
+    std::vector<int> ref_n, pair_img, view_img, pair_aug, view_aug;   // pair_img: the pair's image slot = the view index of its reference view
+    std::vector<char> view_inert;     // cut_out reuse: a stand-in view of an image without detections (its results are not used)
+    std::vector<float> cut_margin;
+    bool kept = false;                // the reference forward retained its first three stages (retention slot k & 1)
+    // what build_aug_views hands to enqueue_aug_forwards and enqueue_scoring
+    std::vector<int> ref_sel, pair_kind, view_isref;
+    std::vector<float> pair_par;
+    std::vector<ViewDesc> aviews;
+};
+
+// One pass of cald_sweep[_audit] over the images.  force_dense: the RPN head runs dense even where the model prunes it (the repeat after a
+// pruning tripwire fired)
+struct SweepRun {
+    cald_model* m; int n_images; const uint8_t* const* images_dev; const int* H; const int* W; const int64_t* pool_pos;
+    const cald_sweep_cfg* cfg; double* consistency_out; double* cls_corr_out; float* margins_out; bool force_dense;
+    // ---- filled by setup() ----
+    cald_ctx* c = nullptr;
+    bool audit = false, prune_ok = false, retina = false, reuse = false;
+    int C = 0, cap = 0, A = 0, B = 0, VT = 0, NB = 0, P_MAX = 0, cut_a = -1;
+    PairLayout lay{0, 0, 0}; size_t n_ints = 0;
+    DetBuffers* DS[2] = {nullptr, nullptr};
+    int* d_ints = nullptr; float *d_par = nullptr, *d_cons = nullptr, *d_clsc = nullptr; NoiseJob* d_jobs = nullptr; unsigned long long* d_lsum = nullptr;
+    float *d_vm[2] = {nullptr, nullptr}, *d_pm = nullptr;     // decision-margin audit: per-view records of the two detection-buffer sets, per-pair records
+    SweepBatch bt[2];
+    // blocks of the first three stages (cut_out reuse), and the plan scratch of the reuse
+    int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
+    std::vector<BatchPlan> rplan;
+
+    static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+    // argument checks, detection buffers, the model-owned scratch and how this run carves it
+    int setup() {
+        if (!m || !images_dev || !H || !W || !pool_pos || !cfg || !consistency_out || !cls_corr_out) return fail(CALD_ERR_INVALID, "null argument");
+        audit = margins_out != nullptr;
+        prune_ok = !audit && !force_dense;      // the audit wants every anchor's own logit: dense RPN head
+        if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+        c = m->ctx;
+        HIPCHK(hipSetDevice(c->device));
+        C = m->cfg.num_classes; cap = m->det_cap();
+        A = cfg->n_augs;
+        if (A < 0 || A > CALD_MAX_AUGS) return fail(CALD_ERR_INVALID, "n_augs %d outside [0, %d]", A, CALD_MAX_AUGS);
+        int n_noise = 0;
+        for (int a = 0; a < A; a++) {
+            const int k = cfg->augs[a].kind;
+            if (k < CALD_AUG_FLIP || k > CALD_AUG_ROTATE) return fail(CALD_ERR_INVALID, "augmentation %d: unknown kind %d", a, k);
+            if (k == CALD_AUG_CUTOUT && (cfg->augs[a].param < 1.0 || cfg->augs[a].param > (double)CALD_MAX_CUT))
+                return fail(CALD_ERR_INVALID, "cutout: cut_num must be in [1, %d]", CALD_MAX_CUT);
+            if (k == CALD_AUG_RESIZE && !(cfg->augs[a].param > 0.0)) return fail(CALD_ERR_INVALID, "resize: ratio must be positive");
+            n_noise += (k == CALD_AUG_GAUSS || k == CALD_AUG_SALT_PEPPER);
+        }
+        if (n_noise > CALD_MAX_NOISE_SEG) return fail(CALD_ERR_INVALID, "at most %d GaussianNoise / SaltPepperNoise views per image", CALD_MAX_NOISE_SEG);
+        B = cfg->batch_images > 0 ? cfg->batch_images : 64;
+        if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+        VT = B * (1 + A);
+        NB = (n_images + B - 1) / B;
+        // the second set of detection buffers exists only when two batches are really in flight (a one-batch shard would pay VT x cap x C
+        // floats of HBM for nothing)
+        const bool two_sets = NB > 1;
+        { int rc0 = ensure_det(m, m->sweep_det, m->sweep_det_views, VT); if (rc0) return rc0; }
+        if (two_sets) { int rc0 = ensure_det(m, m->sweep_det2, m->sweep_det2_views, VT); if (rc0) return rc0; }
+        DS[0] = &m->sweep_det; DS[1] = two_sets ? &m->sweep_det2 : &m->sweep_det;
+        P_MAX = B * (A > 0 ? A : 1);
+        lay = PairLayout{P_MAX, B, VT}; n_ints = lay.n_ints();
+        // ---- persistent scratch (model-owned): device buffers of the scoring stage, pinned host staging in two sets (batch parity) ----
+        cald_model::SweepScratch& S = m->ss;
+        const size_t dev_need = al(n_ints * 4) + al((size_t)P_MAX * 12 * 4) + al((size_t)P_MAX * 4) + al((size_t)VT * (C - 1) * 4) + al(sizeof(NoiseJob) * B) +
+                                al(sizeof(unsigned long long) * P_MAX) + 2 * al((size_t)VT * CALD_VM * 4) + al((size_t)P_MAX * 2 * 4);
+        const size_t pin_set = al((size_t)VT * 4) + al((size_t)B * cap * 16) + al(n_ints * 4) + al((size_t)P_MAX * 12 * 4) + al(sizeof(NoiseJob) * B) +
+                               al((size_t)P_MAX * 4) + al((size_t)VT * (C - 1) * 4) + al((size_t)VT * CALD_VM * 4) + al((size_t)P_MAX * 2 * 4);
+        if (dev_need > S.dev_bytes || 2 * pin_set > S.pin_bytes) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (S.dev) { hipFree(S.dev); S.dev = nullptr; S.dev_bytes = 0; }
+            if (S.pin) { hipHostFree(S.pin); S.pin = nullptr; S.pin_bytes = 0; }
+            HIPCHK(hipMalloc((void**)&S.dev, dev_need)); S.dev_bytes = dev_need;
+            HIPCHK(hipHostMalloc((void**)&S.pin, 2 * pin_set)); S.pin_bytes = 2 * pin_set;
+        }
+        for (int i = 0; i < 2; i++) {
+            if (!S.ev_ref[i]) HIPCHK(hipEventCreateWithFlags(&S.ev_ref[i], hipEventDisableTiming));
+            if (!S.ev_score[i]) HIPCHK(hipEventCreateWithFlags(&S.ev_score[i], hipEventDisableTiming));
+        }
+        { Bump b(S.dev, false); d_ints = b.get<int>(n_ints); d_par = b.get<float>((size_t)P_MAX * 12); d_cons = b.get<float>(P_MAX);
+          d_clsc = b.get<float>((size_t)VT * (C - 1)); d_jobs = b.get<NoiseJob>(B); d_lsum = b.get<unsigned long long>(P_MAX);
+          d_vm[0] = b.get<float>((size_t)VT * CALD_VM); d_vm[1] = b.get<float>((size_t)VT * CALD_VM); d_pm = b.get<float>((size_t)P_MAX * 2); }
+        for (int q = 0; q < 2; q++) {
+            Bump b(S.pin + (size_t)q * pin_set, false);
+            bt[q].h_count = b.get<int>(VT); bt[q].h_boxes = b.get<float>((size_t)B * cap * 4); bt[q].h_ints = b.get<int>(n_ints);
+            bt[q].h_par = b.get<float>((size_t)P_MAX * 12); bt[q].h_jobs = b.get<NoiseJob>(B); bt[q].h_cons = b.get<float>(P_MAX);
+            bt[q].h_clsc = b.get<float>((size_t)VT * (C - 1));
+            bt[q].h_vm = b.get<float>((size_t)VT * CALD_VM); bt[q].h_pm = b.get<float>((size_t)P_MAX * 2);
+        }
+        if (m->prune && prune_ok) HIPCHK(hipMemsetAsync(c->d_prune_check, 0, 8, c->stream));
+        // ---- cut_out reuse (exact fp32, conv_p4.hip's gathered rows): the reference forward keeps the block outputs of the first three stages,
+        // and the batch's first cut_out augmentation recomputes only its dirty pixels over them ----
+        retina = m->cfg.arch == CALD_ARCH_RETINANET;
+        for (int a = 0; a < A && cut_a < 0; a++) if (cfg->augs[a].kind == CALD_AUG_CUTOUT) cut_a = a;
+        for (int b = 0, layer = 0, l = 2; b < (int)m->blocks.size() && layer < 3 && nblk < CUT_MAX_BLOCKS; b++) {
+            const Bottleneck& Bk = m->blocks[b];
+            blk_stride[nblk] = Bk.c2.stride; blk_lin[nblk] = l; l += Bk.c2.stride == 2 ? 1 : 0; blk_lout[nblk] = l; blk_stage[nblk] = layer;
+            nblk++;
+            if (Bk.layer_end) layer++;
+        }
+        reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
+        rplan.resize(reuse ? 1 : 0);
+        return 0;
+    }
+
+    void plan_of(int nv, const ViewDesc* vs, BatchPlan& P) const {
+        int hp[CALD_MAX_VIEWS][2];
+        for (int v = 0; v < nv; v++) { int Hr, Wr; transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &hp[v][0], &hp[v][1]); }
+        build_plan(P, nv, vs, hp, retina);
+    }
+    // retained block outputs of a plan, back to back in one slot
+    size_t retain_layout(const BatchPlan& P, int nv, char* base, float** out) const {
+        size_t off = 0;
+        for (int b = 0; b < nblk; b++) {
+            if (out) out[b] = reinterpret_cast<float*>(base + off);
+            off += al((size_t)level_pix(P, blk_lout[b], nv) * (size_t)m->blocks[b].c3.Cout * 4);
+        }
+        return off;
+    }
+
+    // reference views of batch k -> detections into set k & 1, counts + boxes to the pinned host set, event
+    int enqueue_ref(int k) {
+        SweepBatch& b = bt[k & 1];
+        b.i0 = k * B; b.nb = (n_images - b.i0 < B) ? n_images - b.i0 : B; b.live = true; b.P = 0; b.VV = b.nb;
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, b.i0, b.nb);
+        const DetBuffers& D = *DS[k & 1];
+        FwdReuse ru; b.kept = false;
+        if (reuse) {
+            plan_of(b.nb, views.data(), rplan[0]);
+            const size_t need = retain_layout(rplan[0], b.nb, nullptr, nullptr);
+            cald_model::CutReuse& R = m->cr;
+            const int q = k & 1;
+            if (need > R.cap[q]) {         // grown on demand; the slot's last reader (batch k - 2's cut_out forward) is in the stream ahead
+                HIPCHK(hipStreamSynchronize(c->stream));
+                if (R.slot[q]) hipFree(R.slot[q]);
+                R.slot[q] = nullptr; R.cap[q] = 0;
+                if (hipMalloc((void**)&R.slot[q], need + (need >> 3)) != hipSuccess) { (void)hipGetLastError(); R.slot[q] = nullptr; }
+                else R.cap[q] = need + (need >> 3);
+            }
+            if (R.slot[q]) { ru.mode = 1; ru.nblk = nblk; retain_layout(rplan[0], b.nb, R.slot[q], ru.out); b.kept = true; }
+            else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
+        }
+        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, prune_ok, b.kept ? &ru : nullptr);
+        if (r) return r;
+        if (hipMemcpyAsync(b.h_count, D.count, (size_t)b.nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipMemcpyAsync(b.h_boxes, D.boxes, (size_t)b.nb * cap * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(m->ss.ev_ref[k & 1], c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "D2H of reference detections failed");
+        return 0;
+    }
+
+    // augmented views of batch k, built on the host in the reference's order (cald_train.py:124-183; needs the batch's reference detections
+    // on the host), with the augmentation launches they need
+    int build_aug_views(int k) {
+        SweepBatch& b = bt[k & 1];
+        cald_model::SweepScratch& S = m->ss;
+        const int nb = b.nb, i0 = b.i0;
+        if (hipEventSynchronize(S.ev_ref[k & 1]) != hipSuccess) return fail(CALD_ERR_HIP, "reference forward failed: %s", hipGetErrorString(hipGetLastError()));
+        const int* h_count = b.h_count; const float* h_boxes = b.h_boxes;
+        b.ref_sel.assign((size_t)B * 50, 0); b.pair_aug.clear(); b.pair_kind.clear(); b.view_isref.assign(VT, 0);
+        b.ref_n.assign(B, 0); b.pair_img.clear(); b.view_img.assign(VT, 0); b.cut_margin.assign(B, INFINITY);
+        b.view_aug.assign(VT, 0); b.view_inert.assign(VT, 0);
+        b.pair_par.clear(); b.aviews.clear();
+        int njobs = 0;
+        size_t need = 0;
+        for (int i = 0; i < nb; i++) {
+            if (h_count[i] == 0) continue;
+            const int Hi = H[i0 + i], Wi = W[i0 + i];
+            for (int a = 0; a < A; a++) {
+                const int kd = cfg->augs[a].kind; const double prm = cfg->augs[a].param;
+                if (kd == CALD_AUG_SALT_PEPPER) need += al((size_t)Hi * Wi * 3);
+                else if (kd == CALD_AUG_GAUSS) need += al((size_t)Hi * Wi * 3 * sizeof(float));
+                else if (kd == CALD_AUG_COLOR_ADJUST) need += 2 * al((size_t)Hi * Wi * 3);
+                else if (kd == CALD_AUG_RESIZE) {
+                    const int ow = (int)((double)Wi * prm), oh = (int)((double)Hi * prm);
+                    if (ow < 1 || oh < 1) return fail(CALD_ERR_INVALID, "resize ratio %g empties a %dx%d image", prm, Hi, Wi);
+                    need += al((size_t)oh * ow * 3) + al((size_t)Hi * ow * 3);
+                } else if (kd == CALD_AUG_ROTATE) {
+                    int fx[6], nh, nw; pil_rotate_setup(Hi, Wi, prm, fx, &nh, &nw);
+                    need += al((size_t)nh * nw * 3) + al((size_t)nh * Wi * 3) + al((size_t)Hi * Wi * 3);
+                }
+            }
+        }
+        if (need > S.aug_cap) {      // the arena of augmented images is reused batch after batch in stream order; growing it drains the stream
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (S.d_aug) hipFree(S.d_aug);
+            S.d_aug = nullptr; S.aug_cap = 0;
+            if (hipMalloc((void**)&S.d_aug, need + (need >> 2)) != hipSuccess) return fail(CALD_ERR_HIP, "hipMalloc of the augmentation arena failed");
+            S.aug_cap = need + (need >> 2);
+        }
+        size_t aug_off = 0;
+        auto take = [&](size_t bytes) { uint8_t* p = S.d_aug + aug_off; aug_off += al(bytes); return p; };
+        int r = 0;
+        for (int i = 0; i < nb; i++) {
+            b.view_img[i] = i; b.view_isref[i] = 1;
+            const int n = h_count[i];
+            b.ref_n[i] = subsample_indices(n, &b.ref_sel[(size_t)i * 50]);
+            if (n == 0) continue;
+            const int Hi = H[i0 + i], Wi = W[i0 + i];
+            const uint64_t seed = (uint64_t)cfg->base_seed * 1000003ull + (uint64_t)pool_pos[i0 + i];
+            float sub[50 * 4];
+            for (int q = 0; q < b.ref_n[i]; q++) memcpy(sub + 4 * q, &h_boxes[((size_t)i * cap + b.ref_sel[(size_t)i * 50 + q]) * 4], 16);
+            int cur_a = 0;
+            auto add_view = [&](const ViewDesc& vd, int kind, const float* par) {
+                const int vidx = nb + (int)b.aviews.size();
+                b.aviews.push_back(vd); b.view_img[vidx] = i; b.view_isref[vidx] = 0; b.view_aug[vidx] = cur_a;
+                b.pair_img.push_back(i); b.pair_aug.push_back(vidx); b.pair_kind.push_back(kind);
+                for (int q = 0; q < 12; q++) b.pair_par.push_back(par ? par[q] : 0.0f);
+            };
+            const ViewDesc base = plain_view(images_dev[i0 + i], Hi, Wi);
+            PyRandom pyrng; pyrng.seed(seed);          // ColorSwap's randint and every cutout of this image, in call order
+            NoiseJob nj; memset(&nj, 0, sizeof(nj)); nj.seed = seed; nj.src = images_dev[i0 + i]; nj.H = Hi; nj.W = Wi;
+            for (int a = 0; a < A && !r; a++) {
+                const int kd = cfg->augs[a].kind; const double prm = cfg->augs[a].param;
+                float par[12] = {0};
+                cur_a = a;
+                if (kd == CALD_AUG_FLIP) { ViewDesc v = base; v.flip = 1; par[0] = (float)Wi; add_view(v, 1, par); }
+                else if (kd == CALD_AUG_GAUSS) {            // image + torch.randn(size) * std / 255.0
+                    NoiseSeg& sg = nj.seg[nj.nseg++]; sg.kind = 0; sg.p0 = (float)prm; sg.p1 = 0.0f;
+                    sg.dst = take((size_t)Hi * Wi * 3 * sizeof(float));
+                    ViewDesc v = base; v.noise = reinterpret_cast<const float*>(sg.dst); add_view(v, 0, nullptr);
+                } else if (kd == CALD_AUG_SALT_PEPPER) {    // noise = torch.rand(size); < prob/2 -> max, > 1 - prob/2 -> min
+                    NoiseSeg& sg = nj.seg[nj.nseg++]; sg.kind = 1; sg.p0 = (float)(prm / 2.0); sg.p1 = (float)(1.0 - prm / 2.0);
+                    sg.dst = take((size_t)Hi * Wi * 3);
+                    ViewDesc v = base; v.src = reinterpret_cast<const uint8_t*>(sg.dst); add_view(v, 0, nullptr);
+                } else if (kd == CALD_AUG_COLOR_ADJUST) {
+                    uint8_t* tmp = take((size_t)Hi * Wi * 3); uint8_t* dst = take((size_t)Hi * Wi * 3);
+                    launch_color_adjust(images_dev[i0 + i], Hi, Wi, (float)prm, tmp, d_lsum + b.pair_img.size(), dst, c->stream);
+                    ViewDesc v = base; v.src = dst; add_view(v, 0, nullptr);
+                } else if (kd == CALD_AUG_COLOR_SWAP) {
+                    ViewDesc v = base; v.swap = pyrng.randbelow(6); add_view(v, 0, nullptr);
+                } else if (kd == CALD_AUG_CUTOUT) {
+                    ViewDesc v = base;
+                    float cm = INFINITY;
+                    v.nrect = cutout_rects(pyrng, Hi, Wi, b.ref_n[i], sub, (int)prm, v.rects, &cm);
+                    if (cm < b.cut_margin[i]) b.cut_margin[i] = cm;
+                    add_view(v, 0, nullptr);
+                } else if (kd == CALD_AUG_RESIZE) {
+                    const int ow = (int)((double)Wi * prm), oh = (int)((double)Hi * prm);
+                    uint8_t* dst = take((size_t)oh * ow * 3); uint8_t* tmp = take((size_t)Hi * ow * 3);
+                    if ((r = pil_resize(c, images_dev[i0 + i], Hi, Wi, dst, oh, ow, tmp, 0))) break;
+                    par[0] = (float)prm; add_view(plain_view(dst, oh, ow), 2, par);          // boxes * ratio: float32 tensor times the scalar
+                } else if (kd == CALD_AUG_ROTATE) {
+                    int fx[6], nh, nw; pil_rotate_setup(Hi, Wi, prm, fx, &nh, &nw);
+                    uint8_t* rot = take((size_t)nh * nw * 3); uint8_t* tmp = take((size_t)nh * Wi * 3); uint8_t* dst = take((size_t)Hi * Wi * 3);
+                    launch_affine_nearest(images_dev[i0 + i], Hi, Wi, rot, nh, nw, fx, c->stream);
+                    if ((r = pil_resize(c, rot, nh, nw, dst, Hi, Wi, tmp, 1))) break;      // new_image.resize((w, h)): BICUBIC default
+                    ViewDesc v = base; v.src = dst;
+                    rotate_box_params(Hi, Wi, prm, nw, nh, par);
+                    add_view(v, 3, par);
+                }
+            }
+            if (r) return r;
+            if (nj.nseg) b.h_jobs[njobs++] = nj;
+        }
+        if (njobs) {
+            if (hipMemcpyAsync(d_jobs, b.h_jobs, sizeof(NoiseJob) * njobs, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of noise jobs failed");
+            launch_noise_stream(d_jobs, njobs, c->stream);
+        }
+        return 0;
+    }
+
+    // gather plan of batch k's cut_out forward (V views in the reference forward's order) into the pinned set k & 1, one H2D, and `ru`
+    int cut_plan(int k, int V, const ViewDesc* vs, FwdReuse& ru) {
+        cald_model::CutReuse& R = m->cr;
+        const size_t per = cut_plan_set_bytes(V), total = per * 2 * (size_t)nblk;
+        if (!R.d_gp) {
+            const size_t cap = cut_plan_set_bytes(CALD_MAX_VIEWS) * 2 * CUT_MAX_BLOCKS;
+            HIPCHK(hipMalloc((void**)&R.d_gp, cap));
+            HIPCHK(hipHostMalloc((void**)&R.h_gp[0], cap)); HIPCHK(hipHostMalloc((void**)&R.h_gp[1], cap));
+        }
+        plan_of(V, vs, rplan[0]);
+        const BatchPlan& P = rplan[0];
+        char* const h = R.h_gp[k & 1];
+        std::vector<CutSet> g_out((size_t)V * nblk), g_t1((size_t)V * nblk);
+        for (int v = 0; v < V; v++) {
+            int Hr, Wr, Hp, Wp; CutSet pool1;
+            transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &Hp, &Wp);
+            cut_geometry(vs[v].H, vs[v].W, Hr, Wr, Hp, Wp, vs[v].nrect, vs[v].rects, nblk, blk_stride, &pool1, &g_out[(size_t)v * nblk], &g_t1[(size_t)v * nblk]);
+        }
+        auto kf = [](const ConvLayer& L) { return (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue); };
+        double cost_g[3] = {0, 0, 0}, cost_d[3] = {0, 0, 0}, rows_g[3] = {0, 0, 0}, rows_d[3] = {0, 0, 0};
+        for (int b = 0; b < nblk; b++)
+            for (int kind = 0; kind < 2; kind++) {
+                const int lvl = kind ? blk_lin[b] : blk_lout[b];
+                LevelSeg* sg = reinterpret_cast<LevelSeg*>(h + (size_t)(2 * b + kind) * per);
+                GatherSet* gs = reinterpret_cast<GatherSet*>(reinterpret_cast<char*>(sg) + (size_t)(V + 1) * sizeof(LevelSeg));
+                int tiles = 0; double rows = 0.0;
+                for (int v = 0; v < V; v++) {
+                    LevelSeg L = P.seg[lvl][v]; L.tile_start = tiles; sg[v] = L;
+                    CutRect rr[CALD_GATHER_RECTS];
+                    int n = cut_disjoint(kind ? g_t1[(size_t)v * nblk + b] : g_out[(size_t)v * nblk + b], rr, CALD_GATHER_RECTS);
+                    if (n < 0) { n = 1; rr[0] = {0, 0, L.W - 1, L.H - 1}; }       // too fragmented: the whole view
+                    GatherSet& G = gs[v]; memset(&G, 0, sizeof(G));
+                    G.nr = n;
+                    for (int q = 0; q < n; q++) {
+                        G.x0[q] = rr[q].x0; G.y0[q] = rr[q].y0; G.w[q] = rr[q].x1 - rr[q].x0 + 1;
+                        G.cum[q + 1] = G.cum[q] + G.w[q] * (rr[q].y1 - rr[q].y0 + 1);
+                    }
+                    tiles += (G.cum[n] + 127) / 128; rows += (double)G.cum[n];
+                }
+                sg[V] = P.seg[lvl][V]; sg[V].tile_start = tiles;
+                ru.tiles[b][kind] = tiles; ru.rows[b][kind] = rows;
+                const Bottleneck& Bk = m->blocks[b];
+                const double w = kind ? kf(Bk.c1) : kf(Bk.c2) + kf(Bk.c3) + (Bk.has_down ? kf(Bk.down) : 0.0);
+                const double nconv = kind ? 1.0 : (Bk.has_down ? 3.0 : 2.0), dense = (double)level_pix(P, lvl, V);
+                const int st = blk_stage[b];
+                cost_g[st] += 128.0 * tiles * w; cost_d[st] += dense * w;
+                rows_g[st] += rows * nconv; rows_d[st] += dense * nconv;
+            }
+        // a stage runs gathered while its tiles cost at most CUT_GATHER_MAX_COST of the dense stage (the rest pays the halo, the per-view
+        // tile tails and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
+        for (int st = 0; st < 3; st++) {
+            ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= CUT_GATHER_MAX_COST * cost_d[st];
+            c->cut_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_dense[st] += rows_d[st];
+        }
+        if (hipMemcpyAsync(R.d_gp, h, total, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of the cut_out gather plan failed");
+        ru.mode = 2; ru.nblk = nblk; ru.d_gp = R.d_gp;
+        retain_layout(P, V, m->cr.slot[k & 1], ru.out);
+        c->cut_batches++;
+        return 0;
+    }
+
+    // forwards of batch k's augmented views: with the cut_out reuse its cut_out views first, as one forward in the reference forward's
+    // image order; the others in evenly sized forwards (fwd_span)
+    int enqueue_aug_forwards(int k) {
+        SweepBatch& b = bt[k & 1];
+        const DetBuffers& D = *DS[k & 1];
+        const int nb = b.nb, na = (int)b.aviews.size();
+        int r, n_rest = na, rest_slot = nb;
+        ViewDesc* rest_views = b.aviews.data();
+        std::vector<ViewDesc> rest;
+        int n_cut = 0;
+        for (int j = 0; j < na; j++) n_cut += b.view_aug[nb + j] == cut_a;
+        b.VV = nb + na;
+        if (b.kept && n_cut > 0 && 2 * nb + (na - n_cut) <= VT) {
+            // cut_out reuse: image i's cut_out view takes slot nb + i (a stand-in copy of the reference view, no rectangle, for an image
+            // without detections: same plan as the reference forward), the other augmented views slots 2 nb + ... in their order
+            std::vector<ViewDesc> cutv(nb);
+            std::vector<int> slot(na), nimg(VT, 0), naug(VT, 0);
+            std::vector<char> has(nb, 0), ninert(VT, 0);
+            for (int i = 0; i < nb; i++) nimg[i] = i;
+            int nr2 = 0;
+            for (int j = 0; j < na; j++) {
+                const int img = b.view_img[nb + j];
+                if (b.view_aug[nb + j] == cut_a) { slot[j] = nb + img; cutv[img] = b.aviews[j]; has[img] = 1; }
+                else { slot[j] = 2 * nb + nr2++; rest.push_back(b.aviews[j]); }
+                nimg[slot[j]] = img; naug[slot[j]] = b.view_aug[nb + j];
+            }
+            for (int i = 0; i < nb; i++)
+                if (!has[i]) {
+                    cutv[i] = plain_view(images_dev[b.i0 + i], H[b.i0 + i], W[b.i0 + i]);
+                    nimg[nb + i] = i; naug[nb + i] = cut_a; ninert[nb + i] = 1;
+                }
+            for (size_t p = 0; p < b.pair_aug.size(); p++) b.pair_aug[p] = slot[b.pair_aug[p] - nb];
+            b.view_img = nimg; b.view_aug = naug; b.view_inert = ninert;
+            FwdReuse ru;
+            if ((r = cut_plan(k, nb, cutv.data(), ru))) return r;
+            if ((r = forward_model(m, nb, cutv.data(), det_at(D, (size_t)nb), nullptr, prune_ok, &ru))) return r;
+            b.VV = 2 * nb + nr2; n_rest = nr2; rest_slot = 2 * nb; rest_views = rest.data();
+        } else if (b.kept) {
+            c->cut_fallbacks++;
+        }
+        for (int f = 0; f < fwd_count(n_rest); f++) {
+            int a0, nv; fwd_span(n_rest, f, &a0, &nv);
+            const size_t o = (size_t)(rest_slot + a0);
+            if ((r = forward_model(m, nv, rest_views + a0, det_at(D, o), audit ? d_vm[k & 1] + o * CALD_VM : nullptr, prune_ok))) return r;
+        }
+        return 0;
+    }
+
+    // scoring stage of batch k: the pair / view tables to the device, consistency + cls_corr (+ the pair audit), scores to the host, event
+    int enqueue_scoring(int k) {
+        SweepBatch& b = bt[k & 1];
+        const DetBuffers& D = *DS[k & 1];
+        const int P = (int)b.pair_img.size(), VV = b.VV;
+        b.P = P;
+        memset(b.h_ints, 0, n_ints * 4);
+        const PairLayout::Ptrs hp = lay.at(b.h_ints), dp = lay.at(d_ints);
+        for (int p = 0; p < P; p++) { hp.ref_view[p] = hp.pair_img[p] = b.pair_img[p]; hp.aug_view[p] = b.pair_aug[p]; hp.aug_kind[p] = b.pair_kind[p]; }
+        memcpy(hp.ref_sel, b.ref_sel.data(), (size_t)B * 50 * 4); memcpy(hp.ref_n, b.ref_n.data(), (size_t)B * 4);
+        memcpy(hp.view_img, b.view_img.data(), (size_t)VT * 4); memcpy(hp.view_isref, b.view_isref.data(), (size_t)VT * 4);
+        if (P) memcpy(b.h_par, b.pair_par.data(), (size_t)P * 12 * 4);
+        if (hipMemcpyAsync(d_ints, b.h_ints, n_ints * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+            (P && hipMemcpyAsync(d_par, b.h_par, (size_t)P * 12 * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess)) return fail(CALD_ERR_HIP, "H2D failed");
+        const ScoreArgs sa = lay.score_args(d_ints, D, d_par, P, cfg->bp, d_cons);
+        launch_consistency(sa, c->stream);
+        launch_cls_corr(D, dp.ref_sel, dp.ref_n, dp.view_img, dp.view_isref, VV, d_clsc, c->stream);
+        if (audit) {
+            launch_pair_audit(sa, d_pm, c->stream);
+            if (hipMemcpyAsync(b.h_vm, d_vm[k & 1], (size_t)VV * CALD_VM * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                (P && hipMemcpyAsync(b.h_pm, d_pm, (size_t)P * 2 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return fail(CALD_ERR_HIP, "D2H of the audit records failed");
+        }
+        if ((P && hipMemcpyAsync(b.h_cons, d_cons, (size_t)P * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            hipMemcpyAsync(b.h_clsc, d_clsc, (size_t)VV * (C - 1) * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipEventRecord(m->ss.ev_score[k & 1], c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "scoring stage failed: %s", hipGetErrorString(hipGetLastError()));
+        return 0;
+    }
+
+    // float64 means of a scored batch (cald_train.py:225-228); waits for its scores
+    int finish(int k) {
+        SweepBatch& b = bt[k & 1];
+        if (!b.live) return 0;
+        if (hipEventSynchronize(m->ss.ev_score[k & 1]) != hipSuccess) return fail(CALD_ERR_HIP, "scoring stage failed: %s", hipGetErrorString(hipGetLastError()));
+        const int nb = b.nb, P = b.P, VV = b.VV;
+        std::vector<std::vector<int>> img_pairs(nb), img_views(nb);
+        for (int p = 0; p < P; p++) img_pairs[b.pair_img[p]].push_back(p);
+        for (int v = nb; v < VV; v++) if (!b.view_inert[v]) img_views[b.view_img[v]].push_back(v);
+        // float64 sums in augmentation order (the cut_out reuse stores a batch's cut_out views ahead of the others)
+        for (int i = 0; i < nb; i++)
+            std::stable_sort(img_views[i].begin(), img_views[i].end(), [&](int x, int y) { return b.view_aug[x] < b.view_aug[y]; });
+        for (int i = 0; i < nb; i++) {
+            double* cc = cls_corr_out + (size_t)(b.i0 + i) * (C - 1);
+            const int nvw = 1 + (int)img_views[i].size();
+            for (int k2 = 0; k2 < C - 1; k2++) {
+                double sm = (double)b.h_clsc[(size_t)i * (C - 1) + k2];
+                for (int v : img_views[i]) sm += (double)b.h_clsc[(size_t)v * (C - 1) + k2];
+                cc[k2] = sm / (double)nvw;
+            }
+            if (b.h_count[i] == 0 || img_pairs[i].empty()) { consistency_out[b.i0 + i] = 0.0; continue; }
+            std::vector<double> cs;
+            for (int p : img_pairs[i]) cs.push_back((double)b.h_cons[p]);
+            consistency_out[b.i0 + i] = np_sum(cs.data(), (int)cs.size()) / (double)cs.size();
+        }
+        if (audit) {
+            // per image: the smallest margin of each decision kind over its views / pairs (include/cald_hip.h CALD_MARGIN_*)
+            for (int i = 0; i < nb; i++) {
+                float* mg = margins_out + (size_t)(b.i0 + i) * CALD_N_MARGINS;
+                for (int q = 0; q < CALD_N_MARGINS; q++) mg[q] = INFINITY;
+                auto take_view = [&](int v) { for (int q = 0; q <= VM_POST_CAP; q++) { const float t = b.h_vm[(size_t)v * CALD_VM + q]; if (t < mg[q]) mg[q] = t; } };
+                take_view(i);
+                for (int v : img_views[i]) take_view(v);
+                mg[CALD_MARGIN_REF_SUBSAMPLE] = b.h_vm[(size_t)i * CALD_VM + VM_POST_SUBORDER];
+                for (int p : img_pairs[i]) {
+                    if (b.h_pm[2 * p] < mg[CALD_MARGIN_ARGMAX]) mg[CALD_MARGIN_ARGMAX] = b.h_pm[2 * p];
+                    if (b.h_pm[2 * p + 1] != 0.0f) {
+                        const float t = b.h_vm[(size_t)b.pair_aug[p] * CALD_VM + VM_POST_TOP2];
+                        if (t < mg[CALD_MARGIN_ZERO_ROW]) mg[CALD_MARGIN_ZERO_ROW] = t;
+                    }
+                }
+                mg[CALD_MARGIN_CUTOUT] = b.cut_margin[i];
+            }
+        }
+        b.live = false;
+        return 0;
+    }
+
+    int run() {
+        int rc = setup();
+        if (rc) return rc;
+        // stream order: ref(0), ref(1), aug(0), score(0), ref(2), aug(1), score(1), ... -- the host builds batch k's views while the GPU runs
+        // the reference forward of batch k + 1, and reads batch k's scores while batch k + 1 is on the GPU
+        if (NB > 0) rc = enqueue_ref(0);
+        for (int k = 0; k < NB && !rc; k++) {
+            if (k + 1 < NB) {
+                if ((rc = finish(k - 1))) break;              // set (k + 1) & 1 is batch k - 1's: its means first (its scores are long back)
+                if ((rc = enqueue_ref(k + 1))) break;
+            }
+            if ((rc = build_aug_views(k)) || (rc = enqueue_aug_forwards(k)) || (rc = enqueue_scoring(k))) break;
+        }
+        for (int k = (NB >= 2 ? NB - 2 : 0); k < NB && !rc; k++) rc = finish(k);
+        if (rc) hipStreamSynchronize(c->stream);
+        return rc;
+    }
+};
+}  // namespace
+
+static int sweep_checked(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                         const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out) {
+    SweepRun first{m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, false};
+    int rc = first.run();
+    if (rc || !(m->prune && first.prune_ok && first.NB > 0)) return rc;
+    // the certified pruning's two tripwires: the bound, checked on every anchor that was evaluated both ways (15 - 60 % of P2 / P3), and the
+    // range of the split (an activation of |x| >= 4094 or a non-finite one).  Either one voids the certificate on this data: the results
+    // just computed are discarded and the same sweep is run again with the dense head, which needs neither (it used to fail)
+    cald_ctx* c = m->ctx;
+    float chk[2] = {0.0f, 0.0f};
+    HIPCHK(hipMemcpy(chk, c->d_prune_check, 8, hipMemcpyDeviceToHost));
+    const bool range = chk[1] != 0.0f;
+    if (chk[0] == chk[0] && !range) c->prune_worst = chk[0] > c->prune_worst ? chk[0] : c->prune_worst;
+    if (!(chk[0] <= 1.0f) || range) {
+        c->prune_fallbacks++;
+        SweepRun dense{m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, true};
+        rc = dense.run();
+    }
+    return rc;
+}
+extern "C" int cald_sweep(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                          const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out) {
+    return sweep_checked(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, nullptr);
+}
+extern "C" int cald_sweep_audit(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                                const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out,
+                                float* margins_out) {
+    if (!margins_out) return fail(CALD_ERR_INVALID, "null argument");
+    return sweep_checked(m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out);
+}
+
+
+// =============================================================================================
+// baseline sweeps on the same detector forward
+// =============================================================================================
+// lt_c_train.py:105-121 get_uncertainty: one forward per image, min over detections of |IoU(box, prop) + prob_max - 1|
+extern "C" int cald_sweep_ltc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                              int batch_images, double* uncertainty_out) {
+    if (!m || !images_dev || !H || !W || !uncertainty_out) return fail(CALD_ERR_INVALID, "null argument");
+    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+    if (m->cfg.arch != CALD_ARCH_FRCNN) return fail(CALD_ERR_INVALID, "lt_c needs the Faster R-CNN outputs (props)");
+    cald_ctx* c = m->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    int B = batch_images > 0 ? batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    { int rc0 = ensure_det(m, m->sweep_det, m->sweep_det_views, B); if (rc0) return rc0; }
+    float* d_out = nullptr; HIPCHK(hipMalloc((void**)&d_out, (size_t)B * 4));
+    std::vector<float> h(B);
+    int rc = 0;
+    for (int i0 = 0; i0 < n_images && !rc; i0 += B) {
+        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
+        if ((rc = forward_model(m, nb, views.data(), m->sweep_det))) break;
+        launch_lt_uncertainty(m->sweep_det, nb, d_out, c->stream);
+        if (hipMemcpyAsync(h.data(), d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "lt_c scoring failed: %s", hipGetErrorString(hipGetLastError())); break; }
+        for (int i = 0; i < nb; i++) uncertainty_out[i0 + i] = (double)h[i];
+    }
+    hipStreamSynchronize(c->stream); hipFree(d_out);
+    return rc;
+}
+
+// ls_c_train.py:108-155 get_uncertainty: reference view + GaussianNoise(image, 8 i), i = 1..6 (six consecutive torch.randn
+// draws on the per-image re-seeded generator), top-30 reference boxes by prob_max, IoU stability weighted by prob_max, minus
+// U = max(1 - prob_max).
+extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                              const int64_t* pool_pos, uint64_t base_seed, int batch_images, double* stability_out) {
+    if (!m || !images_dev || !H || !W || !pool_pos || !stability_out) return fail(CALD_ERR_INVALID, "null argument");
+    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+    cald_ctx* c = m->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const int A = 6;
+    int B = batch_images > 0 ? batch_images : 32; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    const int cap = m->det_cap(), VT = B * (1 + A), P_MAX = B * A;
+    { int rc0 = ensure_det(m, m->sweep_det, m->sweep_det_views, VT); if (rc0) return rc0; }
+    DetBuffers& D = m->sweep_det;
+    int* d_ints = nullptr; float *d_par = nullptr, *d_rows = nullptr; NoiseJob* d_gjobs = nullptr; float* d_noise = nullptr; size_t noise_cap = 0;
+    const PairLayout L{P_MAX, B, 0};
+    const size_t n_ints = L.n_ints();
+    ScopedDev scratch(c->stream);
+    {
+        int rc0;
+        if ((rc0 = scratch.alloc(&d_ints, n_ints * 4)) || (rc0 = scratch.alloc(&d_par, (size_t)P_MAX * 12 * 4)) ||
+            (rc0 = scratch.alloc(&d_rows, (size_t)P_MAX * 50 * 4)) || (rc0 = scratch.alloc(&d_gjobs, sizeof(NoiseJob) * B))) return rc0;
+    }
+    HIPCHK(hipMemset(d_par, 0, (size_t)P_MAX * 12 * 4));
+    std::vector<int> h_count(VT); std::vector<float> h_pm((size_t)B * cap), h_rows((size_t)P_MAX * 50);
+    int rc = 0;
+    for (int i0 = 0; i0 < n_images && !rc; i0 += B) {
+        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
+        if ((rc = forward_model(m, nb, views.data(), D))) break;
+        if (hipMemcpyAsync(h_count.data(), D.count, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipMemcpyAsync(h_pm.data(), D.prob_max, (size_t)nb * cap * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "D2H of reference detections failed"); break; }
+        // host: top-30 by prob_max (value desc, index asc), noise jobs, views
+        std::vector<int> ref_sel((size_t)B * 50, 0), ref_n(B, 0), pair_aug, pair_img;
+        std::vector<ViewDesc> aviews; std::vector<NoiseJob> gjobs;
+        size_t need = 0;
+        for (int i = 0; i < nb; i++) if (h_count[i] > 0) need += ((size_t)H[i0 + i] * W[i0 + i] * 3 * A * 4 + 255) & ~(size_t)255;
+        if (need > noise_cap) { if (d_noise) hipFree(d_noise); d_noise = nullptr; noise_cap = 0;
+            if (hipMalloc((void**)&d_noise, need + (need >> 2)) != hipSuccess) { rc = fail(CALD_ERR_HIP, "hipMalloc of the noise arena failed"); break; } noise_cap = need + (need >> 2); }
+        size_t noff = 0;
+        for (int i = 0; i < nb; i++) {
+            const int n = h_count[i];
+            if (n == 0) continue;
+            const float* pm = &h_pm[(size_t)i * cap];
+            std::vector<int> idx(n); for (int k = 0; k < n; k++) idx[k] = k;
+            if (n > 30) {
+                std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return pm[x] > pm[y]; });
+                idx.resize(30);
+            }
+            ref_n[i] = (int)idx.size();
+            for (size_t k = 0; k < idx.size(); k++) ref_sel[(size_t)i * 50 + k] = idx[k];
+            const int Hi = H[i0 + i], Wi = W[i0 + i], ne = Hi * Wi * 3;
+            float* nbase = reinterpret_cast<float*>(reinterpret_cast<char*>(d_noise) + noff); noff += ((size_t)ne * A * 4 + 255) & ~(size_t)255;
+            NoiseJob gj; memset(&gj, 0, sizeof(gj));
+            gj.src = images_dev[i0 + i]; gj.H = Hi; gj.W = Wi; gj.nseg = A; gj.seed = (uint64_t)base_seed * 1000003ull + (uint64_t)pool_pos[i0 + i];
+            for (int k = 0; k < A; k++) { gj.seg[k].kind = 0; gj.seg[k].p0 = 8.0f * (float)(k + 1); gj.seg[k].dst = nbase + (size_t)k * ne; }
+            gjobs.push_back(gj);
+            for (int k = 0; k < A; k++) {
+                ViewDesc v = plain_view(images_dev[i0 + i], Hi, Wi); v.noise = nbase + (size_t)k * ne;
+                pair_img.push_back(i); pair_aug.push_back(nb + (int)aviews.size());
+                aviews.push_back(v);
+            }
+        }
+        if (!gjobs.empty()) {
+            if (hipMemcpyAsync(d_gjobs, gjobs.data(), sizeof(NoiseJob) * gjobs.size(), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "H2D of gaussian-noise jobs failed"); break; }
+            launch_noise_stream(d_gjobs, (int)gjobs.size(), c->stream);
+        }
+        const int na = (int)aviews.size();
+        // evenly sized forwards, as cald_sweep issues them (192 views run 96 + 96, not 128 + 64; CALD_MAX_VIEWS is the hard cap)
+        for (int f = 0; f < fwd_count(na) && !rc; f++) {
+            int a0, nv; fwd_span(na, f, &a0, &nv);
+            rc = forward_model(m, nv, aviews.data() + a0, det_at(D, (size_t)(nb + a0)));
+        }
+        if (rc) break;
+        const int P = (int)pair_img.size();
+        std::vector<int> ints(n_ints, 0);
+        const PairLayout::Ptrs hp = L.at(ints.data());
+        for (int p = 0; p < P; p++) { hp.ref_view[p] = hp.pair_img[p] = pair_img[p]; hp.aug_view[p] = pair_aug[p]; hp.aug_kind[p] = 0; }
+        memcpy(hp.ref_sel, ref_sel.data(), (size_t)B * 50 * 4); memcpy(hp.ref_n, ref_n.data(), (size_t)B * 4);
+        if (hipMemcpyAsync(d_ints, ints.data(), n_ints * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "H2D failed"); break; }
+        launch_max_iou(L.score_args(d_ints, D, d_par, P, 0.f, nullptr), d_rows, c->stream);
+        if ((P && hipMemcpyAsync(h_rows.data(), d_rows, (size_t)P * 50 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+            hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "ls_c scoring failed: %s", hipGetErrorString(hipGetLastError())); break; }
+        // host: float64 / float32 numpy arithmetic of ls_c_train.py:151-153
+        std::vector<std::vector<int>> img_pairs(nb);
+        for (int p = 0; p < P; p++) img_pairs[pair_img[p]].push_back(p);
+        for (int i = 0; i < nb; i++) {
+            if (h_count[i] == 0) { stability_out[i0 + i] = 0.0; continue; }
+            const int N = ref_n[i];
+            std::vector<float> pm(N); std::vector<double> st(N, 0.0), prod(N);
+            float U = 0.0f;
+            for (int k = 0; k < N; k++) {
+                pm[k] = h_pm[(size_t)i * cap + ref_sel[(size_t)i * 50 + k]];
+                const float u = 1.0f - pm[k];
+                if (k == 0 || u > U) U = u;
+            }
+            for (int p : img_pairs[i]) for (int k = 0; k < N; k++) st[k] += (double)h_rows[(size_t)p * 50 + k];
+            for (int k = 0; k < N; k++) { st[k] = st[k] / 6.0; prod[k] = (double)pm[k] * st[k]; }
+            stability_out[i0 + i] = np_sum(prod.data(), N) / (double)np_sum_f32(pm.data(), N) - (double)U;
+        }
+    }
+    hipStreamSynchronize(c->stream);
+    if (d_noise) hipFree(d_noise);          // the fixed scratch belongs to `scratch`
+    return rc;
+}

@@ -4,7 +4,7 @@
  * product's own arithmetic contract for that mode, down to the matrix instruction:
  *
  *   operands   x -> (hi, lo) fp16 with 16 x = hi + lo (activations; cald_amd/csrc/common.h split16_word), w 2^S = hi + lo (weights, S per
- *              layer: cald_amd/csrc/api.hip pack_w16);
+ *              layer: cald_amd/csrc/model.hip pack_w16);
  *   k order    the exact mode's chain order (16-channel chunk, kh, kw, channel) / (kh, kw, cin), cut into k-tiles of 16;
  *   per k-tile acc = mfma(a_lo, b_hi, acc); acc = mfma(a_hi, b_lo, acc); acc = mfma(a_hi, b_hi, acc)   (conv_h3.hip H3_TILE, conv_h4.hip);
  *   mfma       one output element of v_mfma_f32_32x32x16_f16 = mfma_f16_model.h, identified from the hardware and pinned to it by
@@ -240,7 +240,7 @@ ORC_API void orc_mfma_f16_dot16(const uint16_t* A, const uint16_t* B, const uint
 /* -------------------------------------------------------------------------------------------------------------------------------
  * Weights of one layer, prepared once: K-major [K][N] floats (rows in chain order, as orc_conv2d_nhwc takes them) ->
  *   vh / vl [Kpad][Npad] float (values of the hi / lo halves of w 2^S), eh / el [Kpad][Npad] int16 (alignment exponents), *unscale = 2^-(S+4).
- * cald_amd/csrc/api.hip pack_w16: S = 14 - frexp-exponent of max |w| over the layer, clamped to +-40.
+ * cald_amd/csrc/model.hip pack_w16: S = 14 - frexp-exponent of max |w| over the layer, clamped to +-40.
  * ------------------------------------------------------------------------------------------------------------------------------- */
 ORC_API int orc_f16x3_weights(const float* wk, int KH, int KW, int Cin, int N, int Kpad, int Npad,
                               float* vh, float* vl, int16_t* eh, int16_t* el, float* unscale) {

@@ -279,14 +279,14 @@ def mfma_f16_dot16(A, B, Cin, fast=None):
 
 
 def uses_f16x3(Cin, Cout, KH, KW):
-    """Which layers of a CALD_PRECISION_F16X3 model run on the fp16 matrix pipe (cald_amd/csrc/api.hip make_conv: w16 is packed iff ...);
+    """Which layers of a CALD_PRECISION_F16X3 model run on the fp16 matrix pipe (cald_amd/csrc/model.hip make_conv: w16 is packed iff ...);
     the others (the 15-channel RPN head) run the exact fp32 chain in that mode too."""
     coutpad = -(-Cout // 128) * 128 if Cout >= 128 else (-(-Cout // 64) * 64 if Cout >= 64 else -(-Cout // 32) * 32)
     return coutpad % 64 == 0 and ((Cin % 16 == 0 and KH * KW <= 32) or Cin == 4)
 
 
 def f16x3_weights(wk, KH, KW, Cin):
-    """Split weights of one layer (api.hip pack_w16): wk K-major [(kh, kw, cin)][Cout] -> prepared arrays in chain order."""
+    """Split weights of one layer (model.hip pack_w16): wk K-major [(kh, kw, cin)][Cout] -> prepared arrays in chain order."""
     wk = f32(wk); K, N = wk.shape
     assert K == KH * KW * Cin
     Kpad = -(-K // 16) * 16; Npad = -(-N // 16) * 16
@@ -472,7 +472,7 @@ def _f16x3_layer(P, name, wk, KH, KW, Cin):
 def _conv(P, name, x, wk, KH, KW, stride, pad, in_relu=False, **kw):
     """A conv layer of the model.  precision "fp32": the exact fp32 chain.  precision "f16x3" (CALD_PRECISION_F16X3): the layers the
     library runs on the fp16 matrix pipe (uses_f16x3) follow conv2d_f16x3; a residual / top-down operand is then read back from a tensor
-    the mode keeps in split form only (api.hip fwd_layout `only(...)`: block outputs, the downsample branch, the FPN laterals), i.e. as
+    the mode keeps in split form only (forward.hip fwd_layout `only(...)`: block outputs, the downsample branch, the FPN laterals), i.e. as
     h16_join(split16_word(value))."""
     Cin, Cout = x.shape[2], wk.shape[1]
     if P.get("precision", "fp32") == "f16x3" and uses_f16x3(Cin, Cout, KH, KW):
