@@ -130,6 +130,9 @@ SIGNATURES = {
     "cald_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_f, C.c_int64, c_i64]),
     "cald_jpeg_info": (C.c_int, [C.c_void_p, C.c_size_t, c_i, c_i, c_i]),
     "cald_jpeg_decode_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p)]),
+    "cald_jpeg_probe": (C.c_int, [C.c_void_p, C.c_size_t, c_i, c_i, c_i, c_i]),
+    "cald_jpeg_decode_batch_any": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p)]),
+    "cald_jpeg_decode_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "cald_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "cald_profile_read": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_d]),
     "cald_profile_prune": (C.c_int, [C.c_void_p, c_d, c_d, c_d, c_d, c_d]),

@@ -116,7 +116,9 @@ class Subset(object):
 
 
 def device_pool(dataset, indices=None):
-    """JPEG files decoded once on the GPU into an HBM-resident pool (cald_amd.pool.DevicePool); ``pool.loader()`` feeds get_uncertainty."""
+    """Image files decoded once into an HBM-resident pool (cald_amd.pool.DevicePool); ``pool.loader()`` feeds get_uncertainty.
+    Baseline and progressive JPEGs are decoded on the GPU; any other file (CMYK, arithmetic-coded, not a JPEG, ...) is decoded
+    by Pillow on the host, file by file -- see ``DevicePool.from_files``; ``pool.decode_counts`` tells the routes taken."""
     from .pool import DevicePool
     idx = range(len(dataset)) if indices is None else indices
     return DevicePool.from_files([dataset.path(int(i)) for i in idx])

@@ -134,8 +134,10 @@ class VOCDetection(object):
         return convert(None, dict(image_id=idx, annotations=self.annotation(idx)))[1]
 
     def device_pool(self, indices=None):
-        """The JPEG files of `indices` (default: all) decoded once on the GPU into an HBM-resident pool (bit-identical to
-        Image.open(path).convert('RGB')); ``pool.loader()`` is what get_uncertainty takes."""
+        """The image files of `indices` (default: all) decoded once into an HBM-resident pool (bit-identical to
+        Image.open(path).convert('RGB')); ``pool.loader()`` is what get_uncertainty takes.  Baseline and progressive
+        JPEGs are decoded on the GPU; any other file (CMYK, arithmetic-coded, not a JPEG, ...) is decoded by Pillow on
+        the host, file by file -- see ``DevicePool.from_files``; ``pool.decode_counts`` tells the routes taken."""
         from .pool import DevicePool
         idx = range(len(self)) if indices is None else indices
         return DevicePool.from_files([self.images[int(i)] for i in idx])

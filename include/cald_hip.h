@@ -30,7 +30,7 @@ typedef struct cald_model cald_model;
 #define CALD_ERR_HIP (-2)
 #define CALD_ERR_STATE (-3)
 #define CALD_ERR_MISSING_WEIGHT (-4)
-#define CALD_ERR_UNSUPPORTED (-5)   /* input outside the supported set (e.g. progressive JPEG) */
+#define CALD_ERR_UNSUPPORTED (-5)   /* input outside the supported set (e.g. a CMYK JPEG) */
 
 /* arithmetic of the conv / linear GEMMs.
  *   FP32   exact: one k-ordered fp32 fma chain per output (v_mfma_f32_32x32x2_f32), bit-identical to the oracle.
@@ -286,13 +286,35 @@ int cald_debug_tensor(cald_model* m, const char* name, int view, float* host_out
 
 /* ---- input side: PIL.Image.open(path).convert('RGB') of torchvision's VOCDetection /
  * CocoDetection __getitem__ (detection/voc_utils.py:47-58, detection/coco_utils.py; DataLoader at cald_train.py:434).
- * Bit-identical to Pillow / libjpeg-turbo defaults (ISLOW IDCT, fancy upsampling) for 8-bit baseline Huffman JPEGs:
- * grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan, restart intervals allowed.  Other flavours
- * (progressive, CMYK, ...) return CALD_ERR_UNSUPPORTED -- nothing is decoded on the CPU. ---- */
+ * Bit-identical to Pillow / libjpeg-turbo defaults (ISLOW IDCT, fancy upsampling).  Three kinds of file:
+ *   BASELINE      8-bit sequential Huffman (SOF0 / SOF1), grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan,
+ *                 restart intervals allowed.  This is the strict set of cald_jpeg_info / cald_jpeg_decode_batch: they
+ *                 return CALD_ERR_UNSUPPORTED for anything else and decode nothing on the CPU.
+ *   GPU_EXTENDED  decoded on the GPU by cald_jpeg_decode_batch_any only: 8-bit progressive Huffman (SOF2), same colour
+ *                 and sampling set, whose scan script follows T.81 G.1.1.1 and brings every coefficient of every
+ *                 component to Al = 0 (DC scans interleaved over all components or single-component; restart intervals
+ *                 allowed; tables may change between scans); and 3-component files coded as R, G, B (Adobe transform 0,
+ *                 or component ids 'R','G','B' without JFIF), sequential or progressive.
+ *   HOST_ONLY     a JPEG the GPU path does not decode; the caller decodes it on the host (cald_amd.pool falls back to
+ *                 Pillow): 4-component CMYK / YCCK, arithmetic coding, lossless, hierarchical, 12-bit, other sampling
+ *                 factors, sequential files with more than one scan, and progressive files that are truncated, whose
+ *                 script is incomplete (libjpeg smooths what is missing) or breaks the progression rules. ---- */
+#define CALD_JPEG_BASELINE 0
+#define CALD_JPEG_GPU_EXTENDED 1
+#define CALD_JPEG_HOST_ONLY 2
 /* host-only header parse: image size and component count */
 int cald_jpeg_info(const uint8_t* data, size_t size, int* H, int* W, int* ncomp);
 /* decodes n JPEG files (host bytes) into caller-allocated device images out_dev[i] = uint8 [H][W][3] (RGB) */
 int cald_jpeg_decode_batch(cald_ctx* ctx, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* const* out_dev);
+/* host-only classification.  CALD_OK with *kind = one of CALD_JPEG_*; CALD_ERR_INVALID for bytes that are not a JPEG.
+ * H, W and ncomp are filled whenever a frame header was read (also for HOST_ONLY). */
+int cald_jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* ncomp, int* kind);
+/* cald_jpeg_decode_batch for BASELINE and GPU_EXTENDED files mixed in one call; CALD_ERR_UNSUPPORTED (naming the image
+ * index) for a HOST_ONLY file.  A batch of BASELINE files runs exactly the launches of cald_jpeg_decode_batch. */
+int cald_jpeg_decode_batch_any(cald_ctx* ctx, int n, const uint8_t* const* data, const size_t* sizes, uint8_t* const* out_dev);
+/* CPU restatement: decodes one BASELINE or GPU_EXTENDED file into host memory [H][W][3] by driving the kernels' own
+ * __host__ __device__ functions from plain loops.  Needs no GPU. */
+int cald_jpeg_decode_host(const uint8_t* data, size_t size, uint8_t* out_host);
 
 /* ---- measurement: HIP-event timing of every conv/linear launch on the context stream ---- */
 int cald_profile_enable(cald_ctx* ctx, int on);
