@@ -60,6 +60,11 @@ class PackJob(C.Structure):
                 ("packed", C.c_void_p)]
 
 
+class LLCfg(C.Structure):
+    """cald_ll_cfg of include/cald_hip.h."""
+    _fields_ = [("batch_views", C.c_int), ("levels", C.c_int * 4)]
+
+
 class SweepCfg(C.Structure):
     _fields_ = [("base_seed", C.c_uint64), ("bp", C.c_float), ("batch_images", C.c_int), ("n_augs", C.c_int),
                 ("augs", AugSpec * MAX_AUGS)]
@@ -109,6 +114,13 @@ SIGNATURES = {
     "cald_sweep_audit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d, c_f]),
     "cald_sweep_ltc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, c_d]),
     "cald_sweep_lsc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.c_uint64, C.c_int, c_d]),
+    "cald_lossnet_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cald_lossnet_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, c_f, c_i64, C.c_int]),
+    "cald_lossnet_finalize": (C.c_int, [C.c_void_p]),
+    "cald_lossnet_destroy": (C.c_int, [C.c_void_p]),
+    "cald_sweep_ll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i, C.POINTER(LLCfg), c_d, c_f]),
+    "cald_op_gap": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f]),
+    "cald_op_lossnet": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
     "cald_op_consistency": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f, c_f, C.c_int, c_f, c_f, c_f, C.c_int, C.c_float, c_f]),
     "cald_op_cls_corr": (C.c_int, [C.c_void_p, C.c_int, c_f, c_i64, C.c_int, c_f]),
     "cald_op_pil_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),

@@ -171,7 +171,8 @@ static int gconv_on(cald_model* m, const ConvLayer& L, const float* in, float* o
     return run_conv(m->ctx, a, 2.0 * ru.rows[b][kind] * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue));
 }
 
-static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V) {
+// feat_only: the features-only forward (FwdFeatures) -- nothing behind the pyramid is laid out
+static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V, bool feat_only = false) {
     const BatchPlan& P = m->plan;
     const long long px[8] = {level_pix(P, 0, V), level_pix(P, 1, V), level_pix(P, 2, V), level_pix(P, 3, V),
                              level_pix(P, 4, V), level_pix(P, 5, V), level_pix(P, 6, V), level_pix(P, 7, V)};
@@ -198,11 +199,12 @@ static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V) {
         const int K = m->cfg.num_classes, per = m->cfg.detections_per_img;
         for (int i = 0; i < 3; i++) F.inner[i] = B.get<float>(px[3 + i] * 256);
         for (int i = 0; i < 5; i++) F.Pf[i] = B.get<float>(px[3 + i] * 256);
-        for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) F.ret_t[h][q][i] = B.get<float>(px[3 + i] * 256);
+        if (!feat_only) for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) F.ret_t[h][q][i] = B.get<float>(px[3 + i] * 256);
         // RetinaNet: laterals, P3..P5 and P7 feed conv_h3 / conv_h4 layers only; P6 is also read through a ReLU by p7 (fp32 input path of
         // conv_h3); the tower tensors go from matrix-pipe layer to matrix-pipe layer.
         for (int i = 0; i < 3; i++) only(F.inner[i]);
         only(F.Pf[0]); only(F.Pf[1]); only(F.Pf[2]); both(F.Pf[3], F.Pf16[3], px[6] * 256); only(F.Pf[4]);
+        if (feat_only) return;
         for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) only(F.ret_t[h][q][i]);
         for (int i = 0; i < 5; i++) { F.cls_h[i] = B.get<float>(px[3 + i] * m->cls_out.Cout); F.reg_h[i] = B.get<float>(px[3 + i] * 36); }
         int maxa = 0;
@@ -220,13 +222,14 @@ static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V) {
     }
     for (int i = 0; i < 4; i++) F.inner[i] = B.get<float>(px[2 + i] * 256);
     for (int i = 0; i < 5; i++) F.Pf[i] = B.get<float>(px[2 + i] * 256);
-    for (int i = 0; i < 5; i++) F.rpn_tl[i] = B.get<float>(px[2 + i] * 256);
+    if (!feat_only) for (int i = 0; i < 5; i++) F.rpn_tl[i] = B.get<float>(px[2 + i] * 256);
     // Faster R-CNN: P2..P5 -> RPN conv (split form) + RoIAlign (fp32): both forms, written by the MFMA-bound 3 x 3 output convs.  P6 is a
     // strided pixel copy of P5 -- a pixel's 1 KB is copied whole, so the copy of the split twin IS the split form of P6 (only the RPN
     // conv reads it).  Laterals: split form only.
     for (int i = 0; i < 4; i++) only(F.inner[i]);
     for (int i = 0; i < 4; i++) both(F.Pf[i], F.Pf16[i], px[2 + i] * 256);
     only(F.Pf[4]);
+    if (feat_only) return;
     for (int i = 0; i < 5; i++) F.rpn_h[i] = B.get<float>(px[2 + i] * 15);
     const int pre = m->cfg.rpn_pre_nms_top_n;
     F.cand_key = B.get<unsigned long long>((size_t)V * 5 * pre);
@@ -268,12 +271,15 @@ __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, un
     if (threadIdx.x == 0) atomicAdd(acc, s);
 }
 
-// views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled here.
-int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru) {
+// views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled here.  feat (host.h FwdFeatures): the forward stops after
+// the FPN and hands out the pyramid; `det` is then not used, and pruning, cut_out reuse and the audit do not apply.
+int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
+                             FwdFeatures* feat) {
     cald_ctx* c = m->ctx;
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
     if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
-    if (det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
+    if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
+    if (!feat && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
     HIPCHK(hipSetDevice(c->device));
     int hp[CALD_MAX_VIEWS][2];
     int max_pix0 = 0, max_pix2 = 0, max_pix6 = 0;
@@ -283,6 +289,12 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
         int Hp, Wp;
         transform_size(d.H, d.W, m->cfg.min_size, m->cfg.max_size, &d.Hr, &d.Wr, &Hp, &Wp);
         d.Ho = d.H; d.Wo = d.W;
+        if (feat && feat->pad_to) {      // the loader batch's common size (torchvision's ImageList): Hr / Wr stay the view's own, the rest is zero
+            const int Hq = feat->pad_to[v][0], Wq = feat->pad_to[v][1];
+            if (Hq % 32 || Wq % 32 || Hq < Hp || Wq < Wp)
+                return fail(CALD_ERR_INVALID, "view %d: pad_to %d x %d must be a multiple of 32 and at least the view's own %d x %d", v, Hq, Wq, Hp, Wp);
+            Hp = Hq; Wp = Wq;
+        }
         hp[v][0] = Hp; hp[v][1] = Wp;
         if (Hp * Wp > max_pix0) max_pix0 = Hp * Wp;
     }
@@ -296,8 +308,8 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
         int p6 = m->plan.seg[6][v].H * m->plan.seg[6][v].W; if (p6 > max_pix6) max_pix6 = p6;
     }
     FwdBufs F;
-    { Bump dry(nullptr, true); fwd_layout(m, dry, F, V); int rc = arena_reserve(c, dry.off); if (rc) return rc; }
-    { Bump real(c->arena, false); fwd_layout(m, real, F, V); }
+    { Bump dry(nullptr, true); fwd_layout(m, dry, F, V, feat != nullptr); int rc = arena_reserve(c, dry.off); if (rc) return rc; }
+    { Bump real(c->arena, false); fwd_layout(m, real, F, V, feat != nullptr); }
     {
         const int si = c->stage_i; c->stage_i = (si + 1) % cald_ctx::NSTAGE;
         HIPCHK(hipEventSynchronize(c->stage_ev[si]));
@@ -355,8 +367,19 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
             if ((rc = conv_group_on(m, sp, 3, V))) return rc;
         }
         if ((rc = conv_on(m, m->p6, F.Pf[2], F.Pf[3], 5, 6, V, false))) return rc;
-        if ((rc = conv_on(m, m->p7, F.Pf[3], F.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true))) return rc;
         const char* pn[5] = {"P3", "P4", "P5", "P6", "P7"};
+        if (feat) {                  // P3..P6, and P7 where the caller pools it
+            const int np = feat->p7 ? 5 : 4;
+            if (feat->p7 && (rc = conv_on(m, m->p7, F.Pf[3], F.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true))) return rc;
+            for (int i = 0; i < np; i++) {
+                m->dbg[pn[i]] = {F.Pf[i], 3 + i, 256, 0};
+                auto sp = m->split.find(F.Pf[i]);
+                feat->P[i] = F.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = 3 + i;
+            }
+            HIPCHK(hipGetLastError());
+            return 0;
+        }
+        if ((rc = conv_on(m, m->p7, F.Pf[3], F.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true))) return rc;
         const char* cnm[5] = {"cls0", "cls1", "cls2", "cls3", "cls4"};
         const char* rnm[5] = {"reg0", "reg1", "reg2", "reg3", "reg4"};
         for (int i = 0; i < 5; i++) m->dbg[pn[i]] = {F.Pf[i], 3 + i, 256, 0};
@@ -402,6 +425,16 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
         if (prune)                // the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
             for (int i = 0; i < 2; i++) { sp[i].out16 = F.prune_p16[i]; sp[i].energy4 = F.prune_energy[i]; }
         if ((rc = conv_group_on(m, sp, 4, V))) return rc;
+    }
+    if (feat) {                      // P2..P5: neither LastLevelMaxPool nor the RPN runs
+        const char* fn[4] = {"P2", "P3", "P4", "P5"};
+        for (int i = 0; i < 4; i++) {
+            m->dbg[fn[i]] = {F.Pf[i], 2 + i, 256, 0};
+            auto sp = m->split.find(F.Pf[i]);
+            feat->P[i] = F.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = 2 + i;
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
     }
     {   // LastLevelMaxPool: max_pool2d(P5, 1, 2) = every other pixel of every other row; in F16X3 the copy runs on P5's split twin
         auto tw = m->split.find(F.Pf[3]);

@@ -1,6 +1,6 @@
-// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, model.hip, forward.hip, sweep.hip) share: the context and the model behind
-// the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those five files
-// alone: train.hip, jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
+// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, model.hip, forward.hip, sweep.hip, lossnet.hip) share: the context and the model
+// behind the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those six
+// files alone: train.hip, jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
 #pragma once
 #include "../../include/cald_hip.h"
 #include "common.h"
@@ -32,7 +32,7 @@ struct ProfLaunch {
     std::string desc;
 };
 }  // namespace cald_host
-using namespace cald_host;      // the five host files work inside it
+using namespace cald_host;      // the host files work inside it
 
 #define CALD_PRUNE_LOG 4096     // profiled forwards whose selected-pixel counts are kept per forward (cald_profile_dump)
 struct cald_ctx {
@@ -179,6 +179,16 @@ struct FwdReuse {
     int tiles[CUT_MAX_BLOCKS][2] = {};
     double rows[CUT_MAX_BLOCKS][2] = {};
 };
+// ---- features-only forward (the learning-loss sweep, lossnet.hip): the forward stops after the FPN -- Faster R-CNN after the grouped output
+// convs (P2..P5), RetinaNet after P6 (P3..P6; P7 too when p7 is set) ----
+struct FwdFeatures {
+    const int (*pad_to)[2] = nullptr;   // per view {Hp, Wp}, multiples of 32 and >= the view's own padded size, which they replace (null: the view's own).
+                                        // Hr / Wr stay the view's own; the area beyond the resized image is zero
+    bool p7 = false;
+    // filled by forward_model, per pyramid index: the level tensor in the arena (valid until the context's next forward), whether it exists in
+    // split form only (h16.h), and its level in the plan
+    const float* P[5] = {}; bool split_only[5] = {}; int plan_level[5] = {};
+};
 inline size_t cut_plan_set_bytes(int V) { return (size_t)(V + 1) * sizeof(LevelSeg) + (size_t)V * sizeof(GatherSet); }
 inline long long level_pix(const BatchPlan& P, int l, int V) { return P.seg[l][V].pix_off; }
 
@@ -198,7 +208,7 @@ void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& cout
 void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], bool retina);
 bool stem_grid_exact(const LevelSeg* seg, int V);
 int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
-                  const FwdReuse* ru = nullptr);
+                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr);
 // sweep.hip
 void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);

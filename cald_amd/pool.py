@@ -14,7 +14,7 @@ progressive with an incomplete or rule-breaking scan script, truncated, or not a
 Pillow on the host (``fallback="pillow"``, the default), so one odd file never fails a pool.  ``jpeg_info`` and
 ``decode_jpeg_batch`` are the strict entry points: baseline only, no host decode, ever.
 
-``pool.loader(subset)`` yields ``([image], [None])`` batches of one, i.e. it can be passed wherever the reference
+``pool.loader(subset)`` yields ``([image], [None])`` batches of one (``batch_size=`` makes them larger), i.e. it can be passed wherever the reference
 passes ``unlabeled_loader`` (``cald_amd.sweep.get_uncertainty`` takes uint8 HWC CUDA tensors as they are).
 """
 import ctypes as C
@@ -221,10 +221,13 @@ class DevicePool:
             pool[i].copy_(torch.from_numpy(a), non_blocking=True)
         return pool
 
-    def loader(self, subset=None, rank=0, world_size=1):
-        """Iterable with the reference loader's batch shape: (images: list of 1, targets: list of 1).  With
-        world_size > 1 only this rank's strided shard subset[rank::world_size] is yielded (pass
-        ``loader_is_sharded=True`` to get_uncertainty)."""
+    def loader(self, subset=None, rank=0, world_size=1, batch_size=1):
+        """Iterable with the reference loader's batch shape: (images: list of batch_size, targets: list of batch_size; the
+        last batch may be short).  With world_size > 1 only this rank's strided shard subset[rank::world_size] is yielded
+        (pass ``loader_is_sharded=True`` to get_uncertainty).  batch_size > 1 is what the learning-loss sweep's loader has
+        (ll_train.py:265-268; ``baselines.ll_get_uncertainty`` pads a batch's images to their common size)."""
         order = range(len(self)) if subset is None else subset
-        for i in list(order)[rank::world_size]:
-            yield [self[int(i)]], [None]
+        mine = list(order)[rank::world_size]
+        for s in range(0, len(mine), batch_size):
+            part = mine[s:s + batch_size]
+            yield [self[int(i)] for i in part], [None] * len(part)

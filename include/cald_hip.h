@@ -185,7 +185,33 @@ int cald_sweep_ltc(cald_model* m, int n_images, const uint8_t* const* images_dev
 int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                    const int64_t* pool_pos, uint64_t base_seed, int batch_images, double* stability_out);
 
+/* ---- the learning-loss baseline (ll_train.py, ll4al/models/lossnet.py): the detector's forward stops after the FPN, four pyramid levels
+ * are average-pooled over the whole PADDED map (AdaptiveAvgPool2d(1) of the batched ImageList tensor, frcnn_ll.py:601-602), and LossNet --
+ * relu(FC_i) 256 -> D per level, concatenation, linear 4 D -> 1 -- scores every image (lossnet.hip). ---- */
+typedef struct cald_lossnet cald_lossnet;
+int cald_lossnet_create(cald_ctx* ctx, cald_lossnet** out);
+/* LossNet.state_dict() keys: "FC1.weight" [D][256] ... "FC4.bias" [D], "linear.weight" [1][4*D], "linear.bias" [1]; D = interm_dim, 1..256 */
+int cald_lossnet_load_tensor(cald_lossnet* ln, const char* key, const float* data, const int64_t* shape, int ndim);
+/* CALD_ERR_MISSING_WEIGHT for a missing tensor, CALD_ERR_INVALID for a mis-shaped one */
+int cald_lossnet_finalize(cald_lossnet* ln);
+int cald_lossnet_destroy(cald_lossnet* ln);
+typedef struct cald_ll_cfg {
+    int batch_views;       /* views per launch sequence (0 = default 32; capped at 128); results do not depend on it */
+    int levels[4];         /* pyramid index per LossNet branch: Faster R-CNN 0..3 = P2..P5, RetinaNet 0..4 = P3..P7 */
+} cald_ll_cfg;
+/* ll_train.py:145-166 get_uncertainty(task_model, ll_model, unlabeled_loader).  group[i]: loader-batch id of image i (non-decreasing);
+ * an image is padded to its group's common size -- the per-dimension maximum of the members' resized sizes, rounded up to 32 -- so its
+ * score depends on its loader batch, as in the reference.  cfg NULL: batch_views 0 and the reference's levels as shipped: {0,1,2,3} for
+ * Faster R-CNN, {0,0,0,0} for RetinaNet (ll_train.py:155-161 feeds features[0] = P3 to all four branches).  A cfg's levels are taken as given.
+ * uncertainty_out [n] (the float32 value, widened); pooled_out: NULL or [n][4][256] float32, the four pooled vectors per image. */
+int cald_sweep_ll(cald_model* m, cald_lossnet* ln, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                  const int* group, const cald_ll_cfg* cfg, double* uncertainty_out, float* pooled_out);
+
 /* ---- operator-level entry points (used by the parity tests; same kernels as the paths above) ---- */
+/* the learning-loss sweep's pooling of one [H][W][C] tensor (C == 256) in its fixed order (lossnet.hip), and LossNet on n x [4][256] pooled
+ * vectors; host pointers */
+int cald_op_gap(cald_ctx* ctx, const float* x, int H, int W, int C, float* mean_out);
+int cald_op_lossnet(cald_lossnet* ln, int n, const float* pooled, float* out);
 /* scoring of ONE (reference, augmentation) pair, cald_train.py:189-224 */
 int cald_op_consistency(cald_ctx* ctx, int N, const float* aug_box, const float* ref_scores_cls, const float* ref_pm,
                         int M, const float* boxes, const float* scores_cls, const float* pm, int C, float bp,
