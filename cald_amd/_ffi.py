@@ -47,6 +47,7 @@ MARGIN_NAMES = ['rpn_topk', 'rpn_iou', 'rpn_order', 'rpn_trunc', 'rpn_small', 'r
 # (tools/cascade_margins.py, profiles/r5_cascade_margins.txt): about the 90th percentile of |margin_exact - margin_f16x3|.
 MARGIN_NOISE_F16X3 = [2e-5, 2e-6, 2e-5, 2e-5, 1e-5, 1e-6, 1e-4, 5e-6, 2e-6, 5e-6, 5e-6, 5e-6, 2e-6, 5e-6, 2e-6, 0.0]
 AUG_FLIP, AUG_GAUSS, AUG_COLOR_ADJUST, AUG_COLOR_SWAP, AUG_SALT_PEPPER, AUG_CUTOUT, AUG_RESIZE, AUG_ROTATE = range(1, 9)
+MAX_NOISE_SEG = 16    # CALD_MAX_NOISE_SEG: GaussianNoise / SaltPepperNoise views drawn from one generator
 
 
 class AugSpec(C.Structure):
@@ -128,6 +129,7 @@ SIGNATURES = {
     "cald_op_cutout_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i, C.c_int, c_i, c_i]),
     "cald_op_augment": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f,
                                   C.c_void_p, c_f, c_i]),
+    "cald_op_noise_stream": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i, c_d, C.POINTER(C.c_void_p)]),
     "cald_op_frcnn_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             C.c_int, c_f, c_f, c_i64, c_f, c_f, c_f, c_i]),
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),

@@ -172,6 +172,10 @@ static inline int pil_coeffs(int inSize, int outSize, int fid, std::vector<int>&
     return ksize;
 }
 
+// torch.randn(3, H, W) on fewer than 16 elements takes torch's scalar path (another draw pattern, double arithmetic) instead of the
+// 16-chunk Box-Muller fill noise_stream_kernel restates: every entry point that draws Gaussian noise refuses such an image.
+static inline bool randn_unsupported(int H, int W) { return (long long)H * W * 3 < 16; }
+
 // PIL Image.rotate(angle, expand=True): matrix arithmetic of Image.rotate (python floats, round(., 15)),
 // then the FIX()ed 16.16 coefficients of Geometry.c affine_fixed.  (cald_helper.py:153)
 static inline double py_round15(double v) { char buf[64]; snprintf(buf, sizeof(buf), "%.15f", v); return strtod(buf, nullptr); }
@@ -181,6 +185,16 @@ static inline void pil_rotate_setup(int H, int W, double angle_deg, int fix[6], 
     const double w = (double)W, h = (double)H, cx = w / 2.0, cy = h / 2.0;
     const double ang = -(angle * (3.141592653589793 / 180.0));
     double m[6] = {py_round15(std::cos(ang)), py_round15(std::sin(ang)), 0.0, py_round15(-std::sin(ang)), py_round15(std::cos(ang)), 0.0};
+    if (angle == 90.0 || angle == 270.0) {
+        // Image.rotate returns transpose(ROTATE_90 / ROTATE_270) for these two angles when expand is set: out[y][x] = in[x][W-1-y] resp.
+        // in[H-1-x][y], a W x H image.  The same index permutation as the exact affine map the nearest-neighbour loop evaluates.
+        if (angle == 90.0) { m[0] = 0; m[1] = -1; m[2] = w; m[3] = 1; m[4] = 0; m[5] = 0; }
+        else { m[0] = 0; m[1] = 1; m[2] = 0; m[3] = -1; m[4] = 0; m[5] = h; }
+        fix[0] = pil_fix(m[0]); fix[1] = pil_fix(m[1]); fix[3] = pil_fix(m[3]); fix[4] = pil_fix(m[4]);
+        fix[2] = pil_fix(m[2] + m[0] * 0.5 + m[1] * 0.5); fix[5] = pil_fix(m[5] + m[3] * 0.5 + m[4] * 0.5);
+        *nH = W; *nW = H;
+        return;
+    }
     double m2 = m[0] * -cx + m[1] * -cy + m[2], m5 = m[3] * -cx + m[4] * -cy + m[5];
     m[2] = m2 + cx; m[5] = m5 + cy;
     const double xs[4] = {0, w, w, 0}, ys[4] = {0, 0, h, h};

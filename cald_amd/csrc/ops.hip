@@ -78,6 +78,37 @@ extern "C" int cald_op_pil_resize(cald_ctx* c, const uint8_t* src_dev, int H, in
     return rc;
 }
 
+// One NoiseJob of up to CALD_MAX_NOISE_SEG views drawn in order from one generator, one launch of noise_stream_kernel: what the sweep
+// issues per image, without a model.  kinds[g] = CALD_AUG_GAUSS (params[g] = std, dsts[g] = float [3][H][W]) or CALD_AUG_SALT_PEPPER
+// (params[g] = prob, dsts[g] = uint8 [H][W][3]).
+extern "C" int cald_op_noise_stream(cald_ctx* c, uint64_t seed, const uint8_t* src_dev, int H, int W, int nseg, const int* kinds,
+                                    const double* params, void* const* dsts) {
+    if (!c || !src_dev || H <= 0 || W <= 0 || !kinds || !params || !dsts) return fail(CALD_ERR_INVALID, "cald_op_noise_stream: bad arguments");
+    if (nseg < 1 || nseg > CALD_MAX_NOISE_SEG) return fail(CALD_ERR_INVALID, "cald_op_noise_stream: 1..%d segments", CALD_MAX_NOISE_SEG);
+    NoiseJob nj; memset(&nj, 0, sizeof(nj));
+    nj.seed = seed; nj.src = src_dev; nj.H = H; nj.W = W; nj.nseg = nseg;
+    for (int g = 0; g < nseg; g++) {
+        NoiseSeg& sg = nj.seg[g];
+        if (!dsts[g]) return fail(CALD_ERR_INVALID, "cald_op_noise_stream: segment %d has no destination", g);
+        sg.dst = dsts[g];
+        if (kinds[g] == CALD_AUG_GAUSS) {
+            if (randn_unsupported(H, W))
+                return fail(CALD_ERR_UNSUPPORTED, "GaussianNoise on a %dx%d image: torch.randn of fewer than 16 elements takes torch's scalar path, which is not implemented", H, W);
+            sg.kind = 0; sg.p0 = (float)params[g]; sg.p1 = 0.0f;
+        } else if (kinds[g] == CALD_AUG_SALT_PEPPER) {
+            sg.kind = 1; sg.p0 = (float)(params[g] / 2.0); sg.p1 = (float)(1.0 - params[g] / 2.0);
+        } else return fail(CALD_ERR_INVALID, "cald_op_noise_stream: segment %d: kind %d is neither GAUSS nor SALT_PEPPER", g, kinds[g]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    NoiseJob* d = nullptr;
+    HIPCHK(hipMalloc((void**)&d, sizeof(NoiseJob)));
+    hipError_t e = hipMemcpyAsync(d, &nj, sizeof(nj), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) { launch_noise_stream(d, 1, c->stream); e = hipStreamSynchronize(c->stream); }
+    hipFree(d);
+    if (e != hipSuccess) return fail(CALD_ERR_HIP, "noise stream failed: %s", hipGetErrorString(e));
+    return CALD_OK;
+}
+
 // One augmented view of one image, outside the sweep (the helper API of cald/cald_helper.py and the parity tests).
 // A fresh generator is seeded with `seed` (torch's for GAUSS / SALT_PEPPER, Python's for COLOR_SWAP).
 extern "C" int cald_op_augment(cald_ctx* c, int kind, double param, uint64_t seed, const uint8_t* src_dev, int H, int W,
@@ -93,17 +124,8 @@ extern "C" int cald_op_augment(cald_ctx* c, int kind, double param, uint64_t see
     HIPCHK(hipSetDevice(c->device));
     const size_t nbytes = (size_t)H * W * 3;
     if (kind == CALD_AUG_GAUSS || kind == CALD_AUG_SALT_PEPPER) {
-        NoiseJob nj; memset(&nj, 0, sizeof(nj));
-        nj.seed = seed; nj.src = src_dev; nj.H = H; nj.W = W; nj.nseg = 1; nj.seg[0].dst = dst_dev;
-        if (kind == CALD_AUG_GAUSS) { nj.seg[0].kind = 0; nj.seg[0].p0 = (float)param; }
-        else { nj.seg[0].kind = 1; nj.seg[0].p0 = (float)(param / 2.0); nj.seg[0].p1 = (float)(1.0 - param / 2.0); }
-        NoiseJob* d = nullptr;
-        HIPCHK(hipMalloc((void**)&d, sizeof(NoiseJob)));
-        hipError_t e = hipMemcpyAsync(d, &nj, sizeof(nj), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) { launch_noise_stream(d, 1, c->stream); e = hipStreamSynchronize(c->stream); }
-        hipFree(d);
-        if (e != hipSuccess) return fail(CALD_ERR_HIP, "noise stream failed: %s", hipGetErrorString(e));
-        return CALD_OK;
+        void* dsts[1] = {dst_dev};
+        return cald_op_noise_stream(c, seed, src_dev, H, W, 1, &kind, &param, dsts);
     }
     if (kind == CALD_AUG_COLOR_ADJUST) {
         uint8_t* tmp = nullptr;

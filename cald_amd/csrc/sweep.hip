@@ -152,7 +152,7 @@ struct SweepRun {
         C = m->cfg.num_classes; cap = m->det_cap();
         A = cfg->n_augs;
         if (A < 0 || A > CALD_MAX_AUGS) return fail(CALD_ERR_INVALID, "n_augs %d outside [0, %d]", A, CALD_MAX_AUGS);
-        int n_noise = 0;
+        int n_noise = 0; bool any_gauss = false;
         for (int a = 0; a < A; a++) {
             const int k = cfg->augs[a].kind;
             if (k < CALD_AUG_FLIP || k > CALD_AUG_ROTATE) return fail(CALD_ERR_INVALID, "augmentation %d: unknown kind %d", a, k);
@@ -160,8 +160,13 @@ struct SweepRun {
                 return fail(CALD_ERR_INVALID, "cutout: cut_num must be in [1, %d]", CALD_MAX_CUT);
             if (k == CALD_AUG_RESIZE && !(cfg->augs[a].param > 0.0)) return fail(CALD_ERR_INVALID, "resize: ratio must be positive");
             n_noise += (k == CALD_AUG_GAUSS || k == CALD_AUG_SALT_PEPPER);
+            any_gauss |= k == CALD_AUG_GAUSS;
         }
         if (n_noise > CALD_MAX_NOISE_SEG) return fail(CALD_ERR_INVALID, "at most %d GaussianNoise / SaltPepperNoise views per image", CALD_MAX_NOISE_SEG);
+        if (any_gauss)
+            for (int i = 0; i < n_images; i++)
+                if (randn_unsupported(H[i], W[i]))
+                    return fail(CALD_ERR_UNSUPPORTED, "GaussianNoise on image %d (%dx%d): torch.randn of fewer than 16 elements takes torch's scalar path, which is not implemented", i, H[i], W[i]);
         B = cfg->batch_images > 0 ? cfg->batch_images : 64;
         if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
         VT = B * (1 + A);
@@ -646,6 +651,9 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
                               const int64_t* pool_pos, uint64_t base_seed, int batch_images, double* stability_out) {
     if (!m || !images_dev || !H || !W || !pool_pos || !stability_out) return fail(CALD_ERR_INVALID, "null argument");
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+    for (int i = 0; i < n_images; i++)
+        if (randn_unsupported(H[i], W[i]))
+            return fail(CALD_ERR_UNSUPPORTED, "GaussianNoise on image %d (%dx%d): torch.randn of fewer than 16 elements takes torch's scalar path, which is not implemented", i, H[i], W[i]);
     cald_ctx* c = m->ctx;
     HIPCHK(hipSetDevice(c->device));
     const int A = 6;

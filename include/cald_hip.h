@@ -234,9 +234,22 @@ int cald_op_cutout_geometry(int H, int W, int min_size, int max_size, int nrect,
  *   CALD_AUG_SALT_PEPPER  SaltPepperNoise :78-85  dst_dev = uint8 [H][W][3]
  *   CALD_AUG_COLOR_ADJUST ColorAdjust :65-69      dst_dev = uint8 [H][W][3]
  *   CALD_AUG_COLOR_SWAP   ColorSwap :56-62        aux_out[0] = index of the drawn channel permutation (no device work)
- *   CALD_AUG_ROTATE       rotate :135-223         dst_dev = uint8 [H][W][3], boxes_out[n_boxes][4] (host) */
+ *   CALD_AUG_ROTATE       rotate :135-223         dst_dev = uint8 [H][W][3], boxes_out[n_boxes][4] (host)
+ * Two edges of the Pillow / torch calls behind these:
+ *   - GAUSS needs 3 * H * W >= 16.  Below that torch.randn takes its scalar path (another draw pattern), which is not implemented:
+ *     cald_op_augment, cald_op_noise_stream, cald_sweep (with a GAUSS augmentation) and cald_sweep_lsc return CALD_ERR_UNSUPPORTED
+ *     for such an image and write nothing.  A 1 x 6 image is the smallest accepted.  SALT_PEPPER has no such limit.
+ *   - ROTATE by 90 or 270 degrees (mod 360) follows Pillow's short-cut: Image.rotate(expand=True) returns the exact transpose
+ *     (a W x H image) instead of running the affine loop, whose expanded canvas would be one pixel larger each way.  Every other
+ *     angle, 0 and 180 included, takes the affine path, which equals Pillow's result there. */
 int cald_op_augment(cald_ctx* ctx, int kind, double param, uint64_t seed, const uint8_t* src_dev, int H, int W,
                     int n_boxes, const float* boxes, void* dst_dev, float* boxes_out, int* aux_out);
+/* parity hook of the noise kernel: nseg (1..16) GaussianNoise / SaltPepperNoise views of ONE image drawn in order from ONE generator
+ * seeded with `seed`, in one launch -- what cald_sweep issues per image ('multi_ga', 'multi_sp', cald_sweep_lsc), without a model.
+ * kinds[g] = CALD_AUG_GAUSS or CALD_AUG_SALT_PEPPER, params[g] and the layout of the device buffer dsts[g] as in cald_op_augment
+ * (kinds, params and the pointer array dsts are host memory). */
+int cald_op_noise_stream(cald_ctx* ctx, uint64_t seed, const uint8_t* src_dev, int H, int W, int nseg, const int* kinds,
+                         const double* params, void* const* dsts);
 /* RoIHeads.postprocess_detections + GeneralizedRCNNTransform.postprocess of one view (detection/frcnn_la.py:32-87, :292-315) on the
  * forward's own kernels: logits [R][C], deltas [R][4C] (class-major), proposals [R][4] in resized-image coordinates (host); outputs
  * (host, det_max rows each; scores_cls [det_max][C]) and the number of detections.  R <= 1000. */

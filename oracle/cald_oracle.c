@@ -859,6 +859,10 @@ ORC_API void orc_pil_rotate_matrix(int H, int W, double angle_deg, double* m /*6
     double angle = fmod(angle_deg, 360.0); if (angle < 0) angle += 360.0;
     double w = (double)W, h = (double)H, cx = w / 2.0, cy = h / 2.0;
     double ang = -(angle * (3.141592653589793 / 180.0));
+    /* Image.rotate returns transpose(ROTATE_90 / ROTATE_270) for these two angles when expand is set: a pure index permutation
+     * (out[y][x] = in[x][W-1-y] resp. in[H-1-x][y]), written here as the exact affine map the nearest-neighbour loop evaluates */
+    if (angle == 90.0) { m[0] = 0; m[1] = -1; m[2] = w; m[3] = 1; m[4] = 0; m[5] = 0; *nH = W; *nW = H; return; }
+    if (angle == 270.0) { m[0] = 0; m[1] = 1; m[2] = 0; m[3] = -1; m[4] = 0; m[5] = h; *nH = W; *nW = H; return; }
     m[0] = py_round15(cos(ang)); m[1] = py_round15(sin(ang)); m[2] = 0.0;
     m[3] = py_round15(-sin(ang)); m[4] = py_round15(cos(ang)); m[5] = 0.0;
     double tx = -cx, ty = -cy;
@@ -969,7 +973,10 @@ static void normal_fill_16(const float* u, float* o, float std) {
         o[j + 8] = ((radius * sn) * std) / 255.0f;
     }
 }
-ORC_API void orc_gaussian_noise(uint64_t seed, int n, float std, float* out) {
+/* Fewer than 16 elements: torch.randn takes its scalar path (another draw pattern, double arithmetic), which nothing here restates.
+ * Every Gaussian entry point returns -1 for it and writes nothing; 0 otherwise. */
+ORC_API int orc_gaussian_noise(uint64_t seed, int n, float std, float* out) {
+    if (n < 16) return -1;
     orc_mt s; mt_init_genrand(&s, (uint32_t)(seed & 0xffffffffu));
     float* u = (float*)malloc(sizeof(float) * ((size_t)n + 16));
     for (int i = 0; i < n; i++) u[i] = (float)((double)(mt_next(&s) & 0xffffffu) * (1.0 / 16777216.0));
@@ -980,6 +987,7 @@ ORC_API void orc_gaussian_noise(uint64_t seed, int n, float std, float* out) {
         normal_fill_16(v, out + n - 16, std);
     }
     free(u);
+    return 0;
 }
 
 
@@ -1022,7 +1030,8 @@ ORC_API void orc_max_iou_rows(int N, const float* ref_boxes, int M, const float*
 
 /* torch.randn called nseg times in a row on the same generator (ls_c_train.py:129-131: GaussianNoise(image, i*8),
  * i = 1..6): the MT19937 stream simply continues from one call to the next. */
-ORC_API void orc_gaussian_noise_seq(uint64_t seed, int n, int nseg, const float* stds, float* out /*[nseg][n]*/) {
+ORC_API int orc_gaussian_noise_seq(uint64_t seed, int n, int nseg, const float* stds, float* out /*[nseg][n]*/) {
+    if (n < 16 && nseg > 0) return -1;
     orc_mt s; mt_init_genrand(&s, (uint32_t)(seed & 0xffffffffu));
     float* u = (float*)malloc(sizeof(float) * ((size_t)n + 16));
     for (int g = 0; g < nseg; g++) {
@@ -1036,13 +1045,15 @@ ORC_API void orc_gaussian_noise_seq(uint64_t seed, int n, int nseg, const float*
         }
     }
     free(u);
+    return 0;
 }
 
 
 /* One torch CPU generator consumed by a sequence of torch.randn(n) (kind 0, scaled: * std / 255) and
  * torch.rand(n) (kind 1) calls: get_uncertainty draws GaussianNoise and SaltPepperNoise views of one image from
  * the same global generator, in call order (cald_train.py:127-157). */
-ORC_API void orc_torch_stream(uint64_t seed, int nops, const int* kinds, int n, const float* stds, float* out /*[nops][n]*/) {
+ORC_API int orc_torch_stream(uint64_t seed, int nops, const int* kinds, int n, const float* stds, float* out /*[nops][n]*/) {
+    if (n < 16) for (int g = 0; g < nops; g++) if (kinds[g] != 1) return -1;
     orc_mt s; mt_init_genrand(&s, (uint32_t)(seed & 0xffffffffu));
     float* u = (float*)malloc(sizeof(float) * ((size_t)n + 16));
     for (int g = 0; g < nops; g++) {
@@ -1060,6 +1071,7 @@ ORC_API void orc_torch_stream(uint64_t seed, int nops, const int* kinds, int n, 
         }
     }
     free(u);
+    return 0;
 }
 
 /* cald_helper.ColorAdjust (cald_helper.py:65-69): torchvision F.adjust_brightness / _contrast / _saturation on a

@@ -201,8 +201,14 @@ def rotate_aug(img, boxes, angle):
 def gaussian_noise(seed, H, W, std=16):
     """cald_helper.py:72-75: the additive term torch.randn(3, H, W) * std / 255.0 (CHW float32)."""
     out = np.empty(3 * H * W, np.float32)
-    lib().orc_gaussian_noise(C.c_uint64(seed), C.c_int(3 * H * W), C.c_float(std), _p(out))
+    _randn_supported(lib().orc_gaussian_noise(C.c_uint64(seed), C.c_int(3 * H * W), C.c_float(std), _p(out)), 3 * H * W)
     return out.reshape(3, H, W)
+
+
+def _randn_supported(rc, n):
+    """torch.randn on fewer than 16 elements takes torch's scalar path; the oracle (like the kernel) refuses it."""
+    if rc != 0:
+        raise NotImplementedError("torch.randn of %d elements (< 16) follows torch's scalar path, which is not restated" % n)
 
 
 def resize_aug(img, ratio):
@@ -715,7 +721,7 @@ def torch_stream(seed, n, ops):
     stds = f32([p for _, p in ops])
     out = np.empty((len(ops), n), np.float32)
     if len(ops):
-        lib().orc_torch_stream(C.c_uint64(seed), C.c_int(len(ops)), _p(kinds, c_i), C.c_int(n), _p(stds), _p(out))
+        _randn_supported(lib().orc_torch_stream(C.c_uint64(seed), C.c_int(len(ops)), _p(kinds, c_i), C.c_int(n), _p(stds), _p(out)), n)
     return out
 
 
@@ -823,7 +829,7 @@ def lt_get_uncertainty(P, images, min_size=600, max_size=1000):
 def gaussian_noise_seq(seed, H, W, stds):
     stds = f32(stds)
     out = np.empty((len(stds), 3 * H * W), np.float32)
-    lib().orc_gaussian_noise_seq(C.c_uint64(seed), C.c_int(3 * H * W), C.c_int(len(stds)), _p(stds), _p(out))
+    _randn_supported(lib().orc_gaussian_noise_seq(C.c_uint64(seed), C.c_int(3 * H * W), C.c_int(len(stds)), _p(stds), _p(out)), 3 * H * W)
     return out.reshape(len(stds), 3, H, W)
 
 
