@@ -66,6 +66,11 @@ class LLCfg(C.Structure):
     _fields_ = [("batch_views", C.c_int), ("levels", C.c_int * 4)]
 
 
+class LossNetTensors(C.Structure):
+    """cald_lossnet_tensors of include/cald_hip.h: LossNet's parameters (or gradients) as device pointers in state_dict() layout."""
+    _fields_ = [("fc_w", C.c_void_p * 4), ("fc_b", C.c_void_p * 4), ("lin_w", C.c_void_p), ("lin_b", C.c_void_p)]
+
+
 class SweepCfg(C.Structure):
     _fields_ = [("base_seed", C.c_uint64), ("bp", C.c_float), ("batch_images", C.c_int), ("n_augs", C.c_int),
                 ("augs", AugSpec * MAX_AUGS)]
@@ -120,6 +125,11 @@ SIGNATURES = {
     "cald_lossnet_finalize": (C.c_int, [C.c_void_p]),
     "cald_lossnet_destroy": (C.c_int, [C.c_void_p]),
     "cald_sweep_ll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i, C.POINTER(LLCfg), c_d, c_f]),
+    "cald_train_gap": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, C.c_void_p]),
+    "cald_lossnet_train_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossNetTensors), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cald_lossnet_train_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossNetTensors), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(LossNetTensors), C.c_int, C.c_void_p]),
+    "cald_loss_pred_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cald_op_gap": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f]),
     "cald_op_lossnet": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
     "cald_op_consistency": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f, c_f, C.c_int, c_f, c_f, c_f, C.c_int, C.c_float, c_f]),
@@ -191,6 +201,11 @@ SIGNATURES = {
     "cald_train_focal_loss": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "cald_train_bce_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "cald_train_softmax_ce_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cald_train_smooth_l1_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, c_f, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "cald_train_bce_logits_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cald_train_add_bcast": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]),
     "cald_train_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i, C.c_int, C.c_int, C.c_void_p]),
     "cald_train_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "cald_train_subsample2": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

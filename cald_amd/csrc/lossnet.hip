@@ -240,6 +240,47 @@ extern "C" int cald_op_lossnet(cald_lossnet* ln, int n, const float* pooled, flo
 }
 
 // =============================================================================================
+// pooling in the training forward (ll_train.py:77 task_model(images, targets) -> features; frcnn_ll.py:601-602)
+// =============================================================================================
+int cald_internal_scratch(cald_ctx* c, size_t bytes, void** out);   // ctx.hip: grow-only per-context device scratch (stream-ordered reuse)
+
+// the geometry of four dense levels, written on the device (no host table has to outlive the call): seg [4][N], LevelSeg.pix_off = n H W
+struct DenseHW { int H[4], W[4]; };
+__global__ void dense_seg_fill_kernel(LevelSeg* seg, const int N, const DenseHW g) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 4 * N) return;
+    const int l = i / N, n = i % N, H = g.H[l], W = g.W[l];
+    LevelSeg s; s.pix_off = (long long)n * H * W; s.H = H; s.W = W; s.tile_start = n * ((H * W + 127) / 128); s.pad_ = 0;
+    seg[i] = s;
+}
+
+extern "C" int cald_train_gap(cald_ctx* c, int N, const float* const* maps, const int* level_hw, float* pooled) {
+    if (!c || !maps || !level_hw || !pooled) return fail(CALD_ERR_INVALID, "null argument");
+    if (N < 1 || N > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "batch of %d images outside [1, %d]", N, CALD_MAX_VIEWS);
+    DenseHW g; int max_chunks = 1; long long bytes = 0;
+    for (int l = 0; l < 4; l++) {
+        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
+        if (!maps[l] || H < 1 || W < 1 || (long long)H * W > (1ll << 22)) return fail(CALD_ERR_INVALID, "level %d: bad map (%d x %d)", l, H, W);
+        g.H[l] = H; g.W[l] = W;
+        const int ch = (H * W + GAP_CHUNK - 1) / GAP_CHUNK;
+        if (ch > max_chunks) max_chunks = ch;
+        bytes += (long long)N * H * W * LL_C * 4;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    const size_t seg_bytes = ((size_t)4 * N * sizeof(LevelSeg) + 255) / 256 * 256;
+    void* scratch = nullptr; int rc;
+    if ((rc = cald_internal_scratch(c, seg_bytes + (size_t)N * 4 * max_chunks * LL_C * 4, &scratch))) return rc;
+    LevelSeg* d_seg = reinterpret_cast<LevelSeg*>(scratch);
+    hipLaunchKernelGGL(dense_seg_fill_kernel, dim3((4 * N + 255) / 256), dim3(256), 0, c->stream, d_seg, N, g);
+    GapArgs a; memset(&a, 0, sizeof(a));
+    for (int l = 0; l < 4; l++) { a.feat[l] = maps[l]; a.seg[l] = d_seg + (size_t)l * N; }
+    a.nslot = 4; a.V = N; a.chunk_stride = max_chunks; a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + seg_bytes);
+    GapFinishArgs fa; for (int j = 0; j < 4; j++) fa.branch_slot[j] = j;
+    fa.pooled = pooled;
+    return run_gap(c, a, fa, 4, max_chunks, bytes);
+}
+
+// =============================================================================================
 // the sweep (ll_train.py:145-166)
 // =============================================================================================
 extern "C" int cald_sweep_ll(cald_model* m, cald_lossnet* ln, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,

@@ -15,7 +15,9 @@
 //                              index is the MFMA row / column, the pixel index is k: no transposes), staged through LDS,
 //                              pixels split over workgroups, partial tiles summed in a fixed order (deterministic)
 //   RoIAlign forward/backward  roi_align_train_kernel / roi_align_bwd_kernel (bilinear weights scattered with atomics)
-//   losses                     softmax cross-entropy, smooth-L1, binary cross-entropy with logits: value + gradient in one pass
+//   losses                     softmax cross-entropy, smooth-L1, binary cross-entropy with logits: value + gradient in one pass; the
+//                              same three per IMAGE (*_seg_kernel) for the learning-loss baseline's task model, whose LossNet gradient
+//                              joins the pyramid's in add_bcast_kernel (lossnet_train.hip, cald_amd/ll_train.py)
 //   optimizer                  sgd_kernel: torch.optim.SGD (weight decay, momentum, no dampening / nesterov) over the flat
 //                              parameter buffer
 #include "common.h"
@@ -900,6 +902,28 @@ extern "C" int cald_train_add(cald_ctx* c, long long n, float* dst, const float*
     THIP(hipGetLastError());
     return 0;
 }
+// dst[n][p][c] = (a + b) + g[n][c] / (float)HW: where the RPN branch's and the box head's gradients of a pyramid level are joined, the
+// gradient of LossNet's global average pooling of that level (the same for every pixel) rides along -- no further pass over the maps.
+// grid (float4s of one image / 256, N); the quotient is one IEEE division per float4 lane, HBM-bound like add_kernel (12 bytes per float).
+__global__ void add_bcast_kernel(float* dst, const float* a, const float* b, const float* g, long long g_stride, unsigned per4, unsigned C4, float hw) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per4) return;
+    const long long o = (long long)blockIdx.y * per4 + i;
+    float4 v = reinterpret_cast<const float4*>(a)[o];
+    const float4 w = reinterpret_cast<const float4*>(b)[o];
+    const float4 q = reinterpret_cast<const float4*>(g + (long long)blockIdx.y * g_stride)[i % C4];
+    v.x = (v.x + w.x) + q.x / hw; v.y = (v.y + w.y) + q.y / hw; v.z = (v.z + w.z) + q.z / hw; v.w = (v.w + w.w) + q.w / hw;
+    reinterpret_cast<float4*>(dst)[o] = v;
+}
+extern "C" int cald_train_add_bcast(cald_ctx* c, int N, long long HW, int C, float* dst, const float* a, const float* b, const float* g, long long g_stride) {
+    if (!c || !dst || !a || !b || !g || N < 1 || N > 65535 || HW < 1 || C < 4 || C % 4 || g_stride % 4 || g_stride < 0) TFAIL(CALD_ERR_INVALID, "bad arguments (C and g_stride must be multiples of 4)");
+    if (HW > (1ll << 24) || HW * (C / 4) >= (1ll << 31)) TFAIL(CALD_ERR_INVALID, "map of %lld pixels x %d channels is too large", HW, C);
+    THIP(hipSetDevice(cald_internal_device(c)));
+    const unsigned per4 = (unsigned)(HW * (C / 4));
+    hipLaunchKernelGGL(add_bcast_kernel, dim3((per4 + 255) / 256, N), dim3(256), 0, cald_internal_stream(c), dst, a, b, g, g_stride, per4, (unsigned)(C / 4), (float)HW);
+    THIP(hipGetLastError());
+    return 0;
+}
 // stride-s data gradient, step 1: scatter g [N][Ho][Wo][C] onto the stride-1 grid [N][Hd][Wd][C] (zeros elsewhere), Hd = (Ho-1)*s+1 + extra
 __global__ void dilate_kernel(const float* g, float* out, int N, int Ho, int Wo, int Hd, int Wd, int C4, int s) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1628,6 +1652,114 @@ extern "C" int cald_train_bce_logits(cald_ctx* c, int n, const float* logits, co
     if (!c || !loss_out || n < 1 || !logits || !idx || !labels) TFAIL(CALD_ERR_INVALID, "bad arguments");
     THIP(hipSetDevice(cald_internal_device(c)));
     hipLaunchKernelGGL(bce_logits_kernel, dim3(1), dim3(256), 0, cald_internal_stream(c), logits, (const long long*)idx, labels, n, gscale, loss_out, grad);
+    THIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// the same three losses per IMAGE (the learning-loss baseline's task losses, frcnn_ll.py:29-64 and :243-276; ll_train.py:77-85): segment i
+// = rows / gathered entries [off[i], off[i + 1]), ONE workgroup per image running the kernel above on its segment -- the same
+// thread-strided sum and block_sum_256, so a single segment returns the unsegmented kernel's bits -- loss[i], and image i's gradient
+// scaled by gscale[i] (device; null = 1).  The segments are the TRUE per-image sample counts: the reference's view(len(labels), -1, C)
+// presumes equal counts per image, and with equal counts the two agree.  The table travels in the kernel arguments.
+// ---------------------------------------------------------------------------------------------------------------------
+#define TRAIN_MAX_SEG 64
+struct SegTable { int off[TRAIN_MAX_SEG + 1]; float denom[TRAIN_MAX_SEG]; };
+static int seg_table(int N, const int* seg_off, const float* denom, SegTable& t) {
+    if (N < 1 || N > TRAIN_MAX_SEG || !seg_off) TFAIL(CALD_ERR_INVALID, "%d segments outside [1, %d]", N, TRAIN_MAX_SEG);
+    if (seg_off[0] < 0) TFAIL(CALD_ERR_INVALID, "negative segment offset");
+    memset(&t, 0, sizeof(t));
+    for (int i = 0; i <= N; i++) {
+        if (i && seg_off[i] < seg_off[i - 1]) TFAIL(CALD_ERR_INVALID, "segment offsets must be non-decreasing (segment %d)", i - 1);
+        t.off[i] = seg_off[i];
+    }
+    for (int i = 0; i < N; i++) {
+        t.denom[i] = denom ? denom[i] : 1.0f;
+        if (!(t.denom[i] > 0.0f)) TFAIL(CALD_ERR_INVALID, "denominator of segment %d is not positive", i);
+    }
+    return 0;
+}
+__global__ __launch_bounds__(256) void softmax_ce_seg_kernel(const SegTable t, const float* logits, const long long* labels, int C, int ld,
+                                                             const float* gscale, float* loss, float* grad) {
+    __shared__ float red[256];
+    const int img = blockIdx.x, r0 = t.off[img], R = t.off[img + 1] - r0;
+    const float gs = gscale ? gscale[img] : 1.0f;
+    float local = 0.0f;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        const float* z = logits + (long long)(r0 + r) * ld;
+        float m = z[0];
+        for (int k = 1; k < C; k++) m = fmaxf(m, z[k]);
+        float s = 0.0f;
+        for (int k = 0; k < C; k++) s += det_expf(z[k] - m);
+        const int y = (int)labels[r0 + r];
+        local += (det_logf(s) + m) - z[y];
+        if (grad) {
+            float* g = grad + (long long)(r0 + r) * ld;
+            const float inv = gs / (float)R;
+            for (int k = 0; k < C; k++) g[k] = (det_expf(z[k] - m) / s - (k == y ? 1.0f : 0.0f)) * inv;
+        }
+    }
+    const float tot = block_sum_256(local, red);
+    if (threadIdx.x == 0) loss[img] = R > 0 ? tot / (float)R : 0.0f;
+}
+__global__ __launch_bounds__(256) void smooth_l1_seg_kernel(const SegTable t, const float* pred, const long long* idx, const float* target, float beta,
+                                                            const float* gscale, float* loss, float* grad) {
+    __shared__ float red[256];
+    const int img = blockIdx.x, e0 = 4 * t.off[img], n = t.off[img + 1] - t.off[img];
+    const float gs = gscale ? gscale[img] : 1.0f, denom = t.denom[img];
+    float local = 0.0f;
+    for (int e = threadIdx.x; e < 4 * n; e += 256) {
+        const long long o = idx[(e0 + e) >> 2] + (e & 3);
+        const float d = pred[o] - target[e0 + e], ad = fabsf(d);
+        local += 1.0f * (ad < beta ? 0.5f * d * d / beta : ad - 0.5f * beta);
+        if (grad) grad[o] = (ad < beta ? d / beta : (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f))) * (1.0f * gs / denom);
+    }
+    const float tot = block_sum_256(local, red);
+    if (threadIdx.x == 0) loss[img] = tot / denom;           // no foreground row: 0 / denom = 0, and no gradient was written
+}
+__global__ __launch_bounds__(256) void bce_logits_seg_kernel(const SegTable t, const float* x, const long long* idx, const float* y, const float* gscale,
+                                                             float* loss, float* grad) {
+    __shared__ float red[256];
+    const int img = blockIdx.x, e0 = t.off[img], n = t.off[img + 1] - e0;
+    const float gs = gscale ? gscale[img] : 1.0f;
+    float local = 0.0f;
+    for (int e = threadIdx.x; e < n; e += 256) {
+        const long long o = idx[e0 + e];
+        const float z = x[o], tt = y[e0 + e];
+        local += ((z > 0.0f ? z : 0.0f) - z * tt) + det_logf(1.0f + det_expf(-fabsf(z)));
+        if (grad) grad[o] = (det_sigmoidf(z) - tt) * (gs / (float)n);
+    }
+    const float tot = block_sum_256(local, red);
+    if (threadIdx.x == 0) loss[img] = n > 0 ? tot / (float)n : 0.0f;
+}
+extern "C" int cald_train_softmax_ce_seg(cald_ctx* c, int N, const int* seg_off, int C, int ld, const float* logits, const int64_t* labels,
+                                         const float* gscale, float* loss_out, float* grad_out) {
+    if (!c || !logits || !labels || !loss_out || C < 1 || ld < C) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    SegTable t; int rc;
+    if ((rc = seg_table(N, seg_off, nullptr, t))) return rc;
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(softmax_ce_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)labels, C, ld, gscale, loss_out, grad_out);
+    THIP(hipGetLastError());
+    return 0;
+}
+extern "C" int cald_train_smooth_l1_seg(cald_ctx* c, int N, const int* seg_off, const float* pred, const int64_t* idx, const float* target, float beta,
+                                        const float* denom, const float* gscale, float* loss_out, float* grad) {
+    if (!c || !loss_out || !denom) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    SegTable t; int rc;
+    if ((rc = seg_table(N, seg_off, denom, t))) return rc;
+    if (t.off[N] > 0 && (!pred || !idx || !target)) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(smooth_l1_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, pred, (const long long*)idx, target, beta, gscale, loss_out, grad);
+    THIP(hipGetLastError());
+    return 0;
+}
+extern "C" int cald_train_bce_logits_seg(cald_ctx* c, int N, const int* seg_off, const float* logits, const int64_t* idx, const float* labels,
+                                         const float* gscale, float* loss_out, float* grad) {
+    if (!c || !loss_out || !logits || !idx || !labels) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    SegTable t; int rc;
+    if ((rc = seg_table(N, seg_off, nullptr, t))) return rc;
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(bce_logits_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)idx, labels, gscale, loss_out, grad);
     THIP(hipGetLastError());
     return 0;
 }

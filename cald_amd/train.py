@@ -521,7 +521,12 @@ class FasterRCNNTrainer(_TrainerBase):
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
                  rpn_pre_nms_top_n=2000, rpn_post_nms_top_n=2000, rpn_nms_thresh=0.7, rpn_fg_iou=0.7, rpn_bg_iou=0.3,
                  rpn_batch=256, rpn_pos_fraction=0.5, box_fg_iou=0.5, box_bg_iou=0.5, box_batch=512, box_pos_fraction=0.25,
-                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k"):
+                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k", loss_mode=None):
+        if loss_mode not in (None, "ll"):
+            raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
+        # "ll": the learning-loss baseline's task model (detection/frcnn_ll.py): one loss per IMAGE (frcnn_ll.py:29-64, :243-276) and the
+        # four pooled pyramid vectors LossNet reads (ll_train.py:77); None launches exactly what it always launched
+        self.loss_mode = loss_mode
         self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler)
         self.cfg = dict(pre_n=rpn_pre_nms_top_n, post_n=rpn_post_nms_top_n, nms=rpn_nms_thresh, rpn_fg=rpn_fg_iou, rpn_bg=rpn_bg_iou,
                         rpn_batch=rpn_batch, rpn_pos=rpn_pos_fraction, box_fg=box_fg_iou, box_bg=box_bg_iou, box_batch=box_batch,
@@ -543,8 +548,10 @@ class FasterRCNNTrainer(_TrainerBase):
         self._spec_grads = None
 
     def forward(self, images, targets, proposals_override=None):
-        """Training forward.  Returns the four losses as 1-element device tensors (no autograd) and keeps what backward needs."""
+        """Training forward.  Returns the four losses as 1-element device tensors (no autograd) and keeps what backward needs.
+        loss_mode "ll": returns ({name: [N] per-image losses}, pooled [N, 4, 256])."""
         cfg, N, Ccls = self.cfg, len(images), self.C
+        ll = self.loss_mode == "ll"
         mark = self._mark
         mark("start")
         self._begin_step()
@@ -632,7 +639,7 @@ class FasterRCNNTrainer(_TrainerBase):
         props_ready = None
         if proposals_override is None:
             props, counts = ops.rpn_proposals(heads, Hp, Wp, img_sizes, cfg["pre_n"], cfg["post_n"], cfg["nms"], 1e-3)
-            if self.speculate and aux is not None and self.grad_wanted:
+            if self.speculate and aux is not None and self.grad_wanted and not ll:
                 # The host now needs the proposals (counts, then the match results) to draw the RoI samples: ~1 ms during which the main
                 # stream would sit empty.  The RPN branch of the backward pass depends on nothing that comes later, so its first half
                 # (loss gradients, the head's gradients, the 3x3 conv's weight gradients) is enqueued here, behind the proposal
@@ -745,6 +752,7 @@ class FasterRCNNTrainer(_TrainerBase):
                         gtsel_all.append(gt_off[i] + np.maximum(m[keep], 0) if n_gt[i] else np.full(len(keep), gt_off[-1], np.int64))
                         img_col.append(np.full(len(keep), float(i), np.float32))
                     roi_labels_np = np.concatenate(lab_all).astype(np.int64)
+                    per_img = [len(l) for l in lab_all]
                     R = len(roi_labels_np)
                     pos_rows = np.flatnonzero(roi_labels_np > 0)
                     n_posrows = len(pos_rows)
@@ -779,6 +787,18 @@ class FasterRCNNTrainer(_TrainerBase):
                          samples=_LazyDict({"box": box_samples_fn} if box_samples_fn is not None else {}, rpn=rpn_samples,
                                            **({} if box_samples_fn is not None else {"box": box_samples})), spec=spec)
         mark("box head")
+        if ll:
+            # per-image segments of the index lists (they are built image by image) and the reference's normalisers
+            L = self.last
+            L["rpn_cnt"] = [len(sp) + len(sn) for sp, sn in rpn_samples]
+            L["rpn_pos_cnt"] = [len(sp) for sp, _ in rpn_samples]
+            L["roi_cnt"] = [int(v) for v in per_img]
+            edges = np.cumsum([0] + L["roi_cnt"])
+            L["roi_pos_cnt"] = [int((roi_labels_np[edges[i]:edges[i + 1]] > 0).sum()) for i in range(N)]
+            losses = self._ll_losses(L)
+            L["pooled"] = ops.train_gap(P[:4])          # the batch's PADDED maps, as frcnn_ll.py:601-602 pools them
+            mark("losses")
+            return losses, L["pooled"]
         losses = {
             "loss_classifier": ops.softmax_ce(pred.view(R, -1), labels_dev, Ccls),
             "loss_box_reg": ops.smooth_l1(pred, pred_idx, box_tgt, 1.0 / 9, R),
@@ -787,6 +807,24 @@ class FasterRCNNTrainer(_TrainerBase):
         }
         mark("losses")
         return losses
+
+    def _ll_losses(self, L, gs=None, gpred=None, ghead=None, which=(0, 1, 2, 3)):
+        """The per-image task losses of loss_mode "ll" in the reference's dict order: cross entropy = mean over image i's sampled rows,
+        box loss = smooth_l1(beta 1, sum) / R_i (frcnn_ll.py:48-61), objectness = BCE mean over image i's sampled anchors, RPN box loss
+        = L1 sum / (sampled anchors of image i) (frcnn_ll.py:267-273).  gs [4, N] (device): per-image gradient scales, with gpred /
+        ghead the zeroed gradient buffers the kernels write into."""
+        g = (lambda i: None) if gs is None else (lambda i: gs[i])
+        R = L["R"]
+        out = {}
+        if 0 in which:
+            out["loss_classifier"] = ops.softmax_ce_seg(L["pred"].view(R, -1), L["labels"], self.C, L["roi_cnt"], grad=gpred, gscale=g(0))
+        if 1 in which:
+            out["loss_box_reg"] = ops.smooth_l1_seg(L["pred"], L["pred_idx"], L["box_tgt"], 1.0, L["roi_pos_cnt"], L["roi_cnt"], grad=gpred, gscale=g(1))
+        if 2 in which:
+            out["loss_objectness"] = ops.bce_logits_seg(L["head_flat"], L["obj_idx"], L["obj_lab"], L["rpn_cnt"], grad=ghead, gscale=g(2))
+        if 3 in which:
+            out["loss_rpn_box_reg"] = ops.smooth_l1_seg(L["head_flat"], L["box_idx"], L["rpn_tgt"], 0.0, L["rpn_pos_cnt"], L["rpn_cnt"], grad=ghead, gscale=g(3))
+        return out
 
     def relu_decisions(self):
         """{name: bool NCHW / [R, C] CPU tensor}: which side every ReLU of the last forward's differentiated part took (for
@@ -814,8 +852,11 @@ class FasterRCNNTrainer(_TrainerBase):
         acc_saved, self.accumulate_grads = self.accumulate_grads, (False if speculative else self.accumulate_grads)
         try:
             ghead_flat = torch.zeros_like(L["head_flat"])
-            ops.bce_logits(L["head_flat"], L["obj_idx"], L["obj_lab"], grad=ghead_flat, gscale=g_obj)
-            ops.smooth_l1(L["head_flat"], L["box_idx"], L["rpn_tgt"], 1.0 / 9, L["obj_idx"].numel(), grad=ghead_flat, gscale=g_reg)
+            if self.loss_mode == "ll":                       # g_obj: the [4, N] per-image scales
+                self._ll_losses(L, gs=g_obj, ghead=ghead_flat, which=(2, 3))
+            else:
+                ops.bce_logits(L["head_flat"], L["obj_idx"], L["obj_lab"], grad=ghead_flat, gscale=g_obj)
+                ops.smooth_l1(L["head_flat"], L["box_idx"], L["rpn_tgt"], 1.0 / 9, L["obj_idx"].numel(), grad=ghead_flat, gscale=g_reg)
             o, ghs = 0, []
             for i, (h, w) in enumerate(level_hw):
                 ghs.append(ghead_flat[o:o + L["head_sizes"][i]].view(N, h, w, 16)); o += L["head_sizes"][i]
@@ -853,9 +894,24 @@ class FasterRCNNTrainer(_TrainerBase):
                         dst.copy_(src)
 
     # ---- backward ----
-    def backward(self, gscale=(1.0, 1.0, 1.0, 1.0)):
-        """Gradients of sum_i gscale[i] * loss_i (order: classifier, box_reg, objectness, rpn_box_reg) into the flat gradient buffer."""
+    def backward(self, gscale=(1.0, 1.0, 1.0, 1.0), g_pooled=None):
+        """Gradients of sum_i gscale[i] * loss_i (order: classifier, box_reg, objectness, rpn_box_reg) into the flat gradient buffer.
+        loss_mode "ll": gscale is [4][N] (a float or a sequence per loss, or a device tensor) -- one scale per loss and image -- and
+        g_pooled (optional, [N, 4, 256]) the gradient LossNet sends into the pooled pyramid vectors; it joins the pyramid's gradient
+        inside the kernel that adds the RPN branch's and the box head's maps, so the maps are not passed over again."""
         L = self.last
+        ll = self.loss_mode == "ll"
+        if ll:
+            if not torch.is_tensor(gscale):
+                gscale = torch.tensor([[float(v)] * L["N"] if not hasattr(v, "__len__") else [float(x) for x in v] for v in gscale],
+                                      dtype=torch.float32)
+            gscale = gscale.to(self.dev, torch.float32).contiguous()
+            assert tuple(gscale.shape) == (4, L["N"]), "gscale must be [4][N] in loss_mode 'll'"
+            if g_pooled is not None:
+                g_pooled = g_pooled.to(torch.float32).contiguous()
+                assert tuple(g_pooled.shape) == tuple(L["pooled"].shape)
+        elif g_pooled is not None:
+            raise ValueError("g_pooled belongs to loss_mode 'll'")
         N, R, P, level_hw = L["N"], L["R"], L["P"], L["level_hw"]
         # The box-head branch (predictor -> fc7 -> fc6 -> RoIAlign backward) and the RPN branch meet only at the FPN outputs: the former
         # is issued on the batch-only stream (idle during the backward pass), the latter on the main stream.
@@ -869,8 +925,11 @@ class FasterRCNNTrainer(_TrainerBase):
                 ops._WGRAD_CTX[0] = aux[1]
             try:
                 gpred = torch.zeros_like(L["pred"])
-                ops.softmax_ce(L["pred"].view(R, -1), L["labels"], self.C, grad=gpred, gscale=gscale[0])
-                ops.smooth_l1(L["pred"], L["pred_idx"], L["box_tgt"], 1.0 / 9, R, grad=gpred, gscale=gscale[1])
+                if ll:
+                    self._ll_losses(L, gs=gscale, gpred=gpred.view(R, -1), which=(0, 1))
+                else:
+                    ops.softmax_ce(L["pred"].view(R, -1), L["labels"], self.C, grad=gpred, gscale=gscale[0])
+                    ops.smooth_l1(L["pred"], L["pred_idx"], L["box_tgt"], 1.0 / 9, R, grad=gpred, gscale=gscale[1])
                 g7 = self.pred.bwd(gpred, mask=L["f7"])
                 g6 = self.fc7.bwd(g7, mask=L["f6"])
                 groi = self.fc6.bwd(g6)
@@ -880,7 +939,9 @@ class FasterRCNNTrainer(_TrainerBase):
             finally:
                 ops._WGRAD_CTX[0] = prev
         spec = L.get("spec")
-        if spec is not None and float(gscale[2]) == 1.0 and float(gscale[3]) == 1.0:
+        if ll:
+            gts_ = self._rpn_branch_weights(L, gscale, None)
+        elif spec is not None and float(gscale[2]) == 1.0 and float(gscale[3]) == 1.0:
             self._commit_speculative()
             gts_ = spec
         else:
@@ -892,7 +953,11 @@ class FasterRCNNTrainer(_TrainerBase):
             main.wait_stream(aux[0])
             for t in gP_roi:
                 t.record_stream(main)
-        gP = [ops.add(gP[i], gP_roi[i]) for i in range(4)]
+        if g_pooled is not None:
+            # LossNet's gradient of level l is g_pooled[n][l][c] / (H_l W_l) at every pixel: it rides in the join of the two branches
+            gP = [ops.add_bcast(gP[i], gP_roi[i], g_pooled[:, i, :]) for i in range(4)]
+        else:
+            gP = [ops.add(gP[i], gP_roi[i]) for i in range(4)]
         gP[3] = ops.add(gP[3], ops.dilate(gpool, 2, P[3].shape[1], P[3].shape[2]))          # LastLevelMaxPool (kernel 1, stride 2)
         # FPN
         ginner = self._fpn_out_bwd(gP[:4])
@@ -918,7 +983,11 @@ class RetinaNetTrainer(_TrainerBase):
     ANCHOR_KIND = 1
 
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
-                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None):
+                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None):
+        if loss_mode is not None:
+            raise NotImplementedError("loss_mode=%r: training LossNet beside a RetinaNet (ll_train.py:97-120, retina_ll.py's per-image "
+                                      "losses) is outside the scope of the learning-loss training step, which covers Faster R-CNN" % (loss_mode,))
+        self.loss_mode = None
         self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator)
         self.cfg = dict(fg=fg_iou_thresh, bg=bg_iou_thresh)
         cin = [None, 0, 1, 2]                                    # body layer index -> FPN block index (returned_layers = [2, 3, 4])
@@ -1128,8 +1197,54 @@ class _LossFn(torch.autograd.Function):
         return None, None, None, None
 
 
+class _LossFnLL(torch.autograd.Function):
+    """_LossFn for a ``loss_mode="ll"`` trainer: four [N] loss vectors and the pooled pyramid vectors [N, 4, 256] leave the forward; the
+    backward takes one gradient per loss and image and -- unless the features were detached (ll_train.py:90-95) -- LossNet's gradient
+    of the pooled vectors."""
+
+    @staticmethod
+    def forward(ctx, anchor, net, images, targets):
+        ctx.net = net
+        ctx.set_materialize_grads(False)                   # detached features reach backward() as None, not as a tensor of zeros
+        d, pooled = net.forward(images, targets)
+        net.forward_serial = ctx.serial = getattr(net, "forward_serial", 0) + 1
+        return tuple(d[k] for k in net.LOSS_NAMES) + (pooled,)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        net = ctx.net
+        if net.forward_serial != ctx.serial:
+            raise RuntimeError("backward() of a training forward after a later forward of the same model: its saved activations "
+                               "were replaced; call backward() before the next model(images, targets)")
+        N = net.last["N"]
+        zero = None
+        rows = []
+        for g in gs[:4]:
+            if g is None:
+                zero = torch.zeros(N, dtype=torch.float32, device=net.dev) if zero is None else zero
+                g = zero
+            rows.append(g.reshape(N).to(torch.float32))
+        mine = [p.grad is not None and p.grad.data_ptr() == net.grads[k].data_ptr() for k, p in net.params.items()]
+        foreign = [k for k, p in net.params.items() if p.grad is not None and p.grad.data_ptr() != net.grads[k].data_ptr()]
+        if foreign:
+            raise RuntimeError("parameter .grad was replaced by another tensor (%s ...): use zero_grad() between steps" % foreign[0])
+        if any(mine) and not all(mine):
+            raise RuntimeError("some parameters carry a gradient and some do not: call zero_grad() on all of them")
+        net.accumulate_grads = all(mine)
+        try:
+            net.backward(torch.stack(rows), g_pooled=gs[4])
+        finally:
+            net.accumulate_grads = False
+        for k in net.names:
+            if net.params[k].grad is None:
+                net.params[k].grad = net.grads[k]
+        return None, None, None, None
+
+
 class TrainableDetector(object):
-    """``task_model`` in train mode: ``model(images, targets) -> {loss name: scalar tensor}`` whose sum can be ``.backward()``-ed."""
+    """``task_model`` in train mode: ``model(images, targets) -> {loss name: scalar tensor}`` whose sum can be ``.backward()``-ed.
+    Over a ``loss_mode="ll"`` trainer: ``-> (features, {loss name: [N] tensor})`` as detection/frcnn_ll.py returns them, ``features``
+    = {'0'..'3'}: [N, 256] views of the pooled pyramid vectors (one autograd tensor), ready for ll_train.LossNet."""
 
     def __init__(self, net):
         self.net = net
@@ -1141,8 +1256,16 @@ class TrainableDetector(object):
 
     def __call__(self, images, targets):
         self.net.grad_wanted = torch.is_grad_enabled()
+        if getattr(self.net, "loss_mode", None) == "ll":
+            out = _LossFnLL.apply(self._anchor, self.net, images, targets)
+            pooled = out[4]
+            return {str(k): pooled[:, k, :] for k in range(4)}, dict(zip(self.net.LOSS_NAMES, out[:4]))
         out = _LossFn.apply(self._anchor, self.net, images, targets)
         return dict(zip(self.net.LOSS_NAMES, out))
+
+    def train(self, mode=True):
+        self.training = bool(mode)
+        return self
 
 
 class SGD(torch.optim.Optimizer):

@@ -376,6 +376,106 @@ def bce_logits(logits, idx, labels, grad=None, gscale=1.0):
     return loss
 
 
+def _seg_off(counts):
+    off = [0]
+    for n in counts:
+        off.append(off[-1] + int(n))
+    return off
+
+
+def softmax_ce_seg(logits, labels, Ccls, counts, grad=None, gscale=None):
+    """softmax_ce per image: image i owns the next counts[i] rows.  gscale: None or a float32 device tensor [N].  Returns the losses [N]."""
+    N = len(counts)
+    loss = torch.empty(N, dtype=torch.float32, device=logits.device)
+    _ffi.check(_ffi.lib().cald_train_softmax_ce_seg(_wctx(logits), N, _int_array(_seg_off(counts)), Ccls, logits.shape[1], _p(logits), _p(labels),
+                                                    _p(gscale), _p(loss), _p(grad)))
+    return loss
+
+
+def smooth_l1_seg(pred, idx, target, beta, counts, denoms, grad=None, gscale=None):
+    """smooth_l1 per image: image i owns the next counts[i] gathered 4-vectors and divides its sum by denoms[i].  Returns the losses [N]."""
+    N = len(counts)
+    loss = torch.empty(N, dtype=torch.float32, device=pred.device)
+    den = (C.c_float * N)(*[float(d) for d in denoms])
+    _ffi.check(_ffi.lib().cald_train_smooth_l1_seg(_wctx(pred), N, _int_array(_seg_off(counts)), _p(pred), _p(idx), _p(target), beta, den,
+                                                   _p(gscale), _p(loss), _p(grad)))
+    return loss
+
+
+def bce_logits_seg(logits, idx, labels, counts, grad=None, gscale=None):
+    """bce_logits per image: image i owns the next counts[i] gathered logits.  Returns the losses [N]."""
+    N = len(counts)
+    loss = torch.empty(N, dtype=torch.float32, device=logits.device)
+    _ffi.check(_ffi.lib().cald_train_bce_logits_seg(_wctx(logits), N, _int_array(_seg_off(counts)), _p(logits), _p(idx), _p(labels), _p(gscale),
+                                                    _p(loss), _p(grad)))
+    return loss
+
+
+def add_bcast(a, b, g, out=None):
+    """(a + b) + g[n][c] / (H W) on [N, H, W, C] maps; g: [N, C] float32 view whose rows may be strided (a level of pooled [N, 4, C])."""
+    _chk(a, "a"); _chk(b, "b")
+    N, H, W, Cc = a.shape
+    assert g.dtype == torch.float32 and g.shape == (N, Cc) and g.stride(1) == 1 and b.shape == a.shape
+    out = out if out is not None else torch.empty_like(a)
+    _ffi.check(_ffi.lib().cald_train_add_bcast(_wctx(a), N, H * W, Cc, _p(out), _p(a), _p(b), _p(g), g.stride(0) if N > 1 else Cc))
+    return out
+
+
+def train_gap(maps, out=None):
+    """Global average pooling of four dense NHWC maps [N, H_l, W_l, 256] in the learning-loss sweep's summation order -> [N, 4, 256]."""
+    N = maps[0].shape[0]
+    for m in maps:
+        _chk(m, "map"); assert m.shape[0] == N and m.shape[3] == 256
+    out = out if out is not None else torch.empty((N, 4, 256), dtype=torch.float32, device=maps[0].device)
+    hw = [v for m in maps for v in (m.shape[1], m.shape[2])]
+    _ffi.check(_ffi.lib().cald_train_gap(_wctx(maps[0]), N, _ptr_array(maps), _int_array(hw), _p(out)))
+    return out
+
+
+def _lossnet_tensors(ts):
+    """ts: the ten tensors in LossNet.state_dict() order (FC1.weight, FC1.bias, ..., linear.weight, linear.bias)."""
+    t = _ffi.LossNetTensors()
+    for j in range(4):
+        t.fc_w[j], t.fc_b[j] = ts[2 * j].data_ptr(), ts[2 * j + 1].data_ptr()
+    t.lin_w, t.lin_b = ts[8].data_ptr(), ts[9].data_ptr()
+    return t
+
+
+def lossnet_fwd(params, pooled, D):
+    """pooled [B, 4, 256] -> (pred [B], hidden [B, 4, D])."""
+    _chk(pooled, "pooled")
+    B = pooled.shape[0]
+    hidden = torch.empty((B, 4, D), dtype=torch.float32, device=pooled.device)
+    pred = torch.empty(B, dtype=torch.float32, device=pooled.device)
+    t = _lossnet_tensors(params)
+    _ffi.check(_ffi.lib().cald_lossnet_train_fwd(_wctx(pooled), B, D, C.byref(t), _p(pooled), _p(hidden), _p(pred)))
+    return pred, hidden
+
+
+def lossnet_bwd(params, grads, pooled, hidden, g_pred, accumulate=False, need_g_pooled=False):
+    """Gradients of LossNet's ten tensors into `grads`; returns g_pooled [B, 4, 256] or None."""
+    _chk(pooled, "pooled"); _chk(hidden, "hidden"); _chk(g_pred, "g_pred")
+    B, D = pooled.shape[0], hidden.shape[2]
+    gh = torch.empty((B, 4 * D), dtype=torch.float32, device=pooled.device)
+    g_pooled = torch.empty_like(pooled) if need_g_pooled else None
+    tp, tg = _lossnet_tensors(params), _lossnet_tensors(grads)
+    _ffi.check(_ffi.lib().cald_lossnet_train_bwd(_wctx(pooled), B, D, C.byref(tp), _p(pooled), _p(hidden), _p(g_pred), _p(gh), C.byref(tg),
+                                                 int(accumulate), _p(g_pooled)))
+    return g_pooled
+
+
+def loss_pred_loss(inp, target, margin, g_up=None, want_terms=False, want_grad=True, per_pair=False):
+    """LossPredLoss value [1] (+ the pair terms [B/2]) and d loss / d input [B] scaled by the device scalar g_up (None: 1); per_pair: the
+    gradient of the pair terms (reduction='none') under the upstream gradients g_up [B/2]."""
+    _chk(inp, "input"); _chk(target, "target")
+    B = inp.numel()
+    loss = torch.empty(1, dtype=torch.float32, device=inp.device)
+    terms = torch.empty(B // 2, dtype=torch.float32, device=inp.device) if want_terms else None
+    grad = torch.empty(B, dtype=torch.float32, device=inp.device) if want_grad else None
+    _ffi.check(_ffi.lib().cald_loss_pred_loss(_wctx(inp), B, _p(inp), _p(target), float(margin), int(per_pair), _p(g_up), _p(loss), _p(terms), _p(grad)))
+    return loss, terms, grad
+
+
 def preprocess(images_u8, sizes, Hp, Wp, remainders=None):
     """images_u8: list of uint8 [H, W, 3] cuda tensors; sizes: list of (Hr, Wr).  Returns [N, Hp, Wp, 4] float32."""
     N = len(images_u8)

@@ -207,6 +207,35 @@ typedef struct cald_ll_cfg {
 int cald_sweep_ll(cald_model* m, cald_lossnet* ln, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                   const int* group, const cald_ll_cfg* cfg, double* uncertainty_out, float* pooled_out);
 
+/* ---- training the loss-prediction module (ll_train.py:55-142, ll4al/models/lossnet.py, ll4al/main.py:64-83; lossnet_train.hip).  All
+ * pointers are DEVICE pointers unless said otherwise; everything is enqueued on the context's stream; every sum has a fixed order. ---- */
+/* The training forward's pooling: maps[l] = dense [N][H_l][W_l][256] (level_hw = host {H_0, W_0, ..., H_3, W_3}), the batch's PADDED maps
+ * (frcnn_ll.py:601-602) -> pooled [N][4][256], with the sweep's two pooling kernels, hence cald_op_gap's summation order and bits. */
+int cald_train_gap(cald_ctx* ctx, int N, const float* const* maps, const int* level_hw, float* pooled);
+/* LossNet parameters (or their gradients) in LossNet.state_dict() layout */
+typedef struct cald_lossnet_tensors {
+    float* fc_w[4];        /* FCj.weight [D][256] */
+    float* fc_b[4];        /* FCj.bias [D] */
+    float* lin_w;          /* linear.weight [1][4 D] */
+    float* lin_b;          /* linear.bias [1] */
+} cald_lossnet_tensors;
+/* pooled [B][4][256] -> hidden [B][4][D] = relu(FCj), pred [B]: the arithmetic of cald_op_lossnet (one k-ordered fmaf chain from +0 per FC
+ * output, + bias, ReLU; one chain over 4 D, + bias), so pred carries cald_op_lossnet's bits.  D = 1..256. */
+int cald_lossnet_train_fwd(cald_ctx* ctx, int B, int D, const cald_lossnet_tensors* params, const float* pooled, float* hidden, float* pred);
+/* g_pred [B] = d loss / d pred.  grads (same layout as params): g linear.weight[i] = sum_b g_b * hidden[b][i] and g linear.bias = sum_b g_b,
+ * b ascending from +0; g_h = hidden > 0 ? g_b * lw[i] : 0; g FCj.weight[d][c] = sum_b g_h[b][j][d] * pooled[b][j][c] and g FCj.bias[d] =
+ * sum_b g_h[b][j][d], b ascending; accumulate != 0 adds to what grads holds.  g_pooled [B][4][256] (null when the features are detached):
+ * one d-ordered fmaf chain from +0 per element.  gh_scratch [B][4 D]. */
+int cald_lossnet_train_bwd(cald_ctx* ctx, int B, int D, const cald_lossnet_tensors* params, const float* pooled, const float* hidden,
+                           const float* g_pred, float* gh_scratch, const cald_lossnet_tensors* grads, int accumulate, float* g_pooled);
+/* ll4al/main.py:64-83 LossPredLoss(input, target, margin): pairs (i, B-1-i), i < B/2; one = t_i - t_(B-1-i) > 0 ? +1 : -1 (a tie is -1);
+ * term_i = max(0, margin - one * (p_i - p_(B-1-i))); loss_out [1] = (sum of the terms, i ascending from +0) / (B/2); terms_out (or null)
+ * [B/2] = reduction='none'.  grad_out (or null) [B]: per_pair == 0 (reduction='mean') g_up / (B/2) * d sum / d input with g_up = *g_up_dev
+ * (null: 1); per_pair != 0 (reduction='none') pair i's upstream gradient is g_up_dev[i] (null: 1) and nothing is divided.  At term == 0
+ * exactly the gradient passes (torch.clamp's backward).  B odd or > 2048: CALD_ERR_INVALID before any launch. */
+int cald_loss_pred_loss(cald_ctx* ctx, int B, const float* input, const float* target, float margin, int per_pair, const float* g_up_dev,
+                        float* loss_out, float* terms_out, float* grad_out);
+
 /* ---- operator-level entry points (used by the parity tests; same kernels as the paths above) ---- */
 /* the learning-loss sweep's pooling of one [H][W][C] tensor (C == 256) in its fixed order (lossnet.hip), and LossNet on n x [4][256] pooled
  * vectors; host pointers */
@@ -524,6 +553,22 @@ int cald_train_focal_loss(cald_ctx* ctx, int N, const int* level_pix, int A, int
 /* F.binary_cross_entropy_with_logits over n logits at float offsets idx[i] (mean) */
 int cald_train_bce_logits(cald_ctx* ctx, int n, const float* logits, const int64_t* idx, const float* labels, float gscale,
                           float* loss_out, float* grad);
+/* The three losses above per IMAGE (frcnn_ll.py:29-64, :243-276): N <= 64 segments, segment i = rows / gathered entries
+ * [seg_off[i], seg_off[i + 1]) (seg_off: HOST, N + 1 non-decreasing entries), loss_out [N], image i's gradient scaled by gscale[i] (DEVICE,
+ * N floats; null = 1).  One workgroup per image with the single-segment kernel's thread-strided sum, so N = 1 returns that kernel's bits.
+ * Segments are the TRUE per-image sample counts; the reference's view(len(labels), -1, C) presumes equal counts, where the two agree.
+ * softmax_ce: mean over the image's rows.  smooth_l1: sum / denom[i] (denom: HOST, N floats > 0); an empty segment gives 0 and no
+ * gradient.  bce_logits: mean over the image's entries.  An empty cross-entropy / BCE segment gives loss 0. */
+int cald_train_softmax_ce_seg(cald_ctx* ctx, int N, const int* seg_off, int C, int ld, const float* logits, const int64_t* labels,
+                              const float* gscale, float* loss_out, float* grad_out);
+int cald_train_smooth_l1_seg(cald_ctx* ctx, int N, const int* seg_off, const float* pred, const int64_t* idx, const float* target, float beta,
+                             const float* denom, const float* gscale, float* loss_out, float* grad);
+int cald_train_bce_logits_seg(cald_ctx* ctx, int N, const int* seg_off, const float* logits, const int64_t* idx, const float* labels,
+                              const float* gscale, float* loss_out, float* grad);
+/* dst[n][p][c] = (a[n][p][c] + b[n][p][c]) + g[n * g_stride + c] / (float)HW: the join of two gradient maps [N][HW][C] (C a multiple of 4)
+ * with the gradient of a global average pooling of the same map (IEEE division), in one pass */
+int cald_train_add_bcast(cald_ctx* ctx, int N, long long HW, int C, float* dst, const float* a, const float* b, const float* g,
+                         long long g_stride);
 /* GeneralizedRCNNTransform of a training batch: images[i] = device uint8 [H_i][W_i][3]; hw = host {H_i, W_i, Hr_i, Wr_i} per image
  * (source and resized sizes); remainders[i] (or null) = device float [3][H_i][W_i] added to image / 255.  out [N][Hp][Wp][4]:
  * normalized, bilinearly resized, zero-padded; channel 3 is zero. */
