@@ -14,10 +14,11 @@
 //                              on v_mfma_f32_32x32x2_f32; both operands are read in their natural NHWC order (the channel
 //                              index is the MFMA row / column, the pixel index is k: no transposes), staged through LDS,
 //                              pixels split over workgroups, partial tiles summed in a fixed order (deterministic)
-//   RoIAlign forward/backward  roi_align_train_kernel / roi_align_bwd_kernel (bilinear weights scattered with atomics)
-//   losses                     softmax cross-entropy, smooth-L1, binary cross-entropy with logits: value + gradient in one pass; the
-//                              same three per IMAGE (*_seg_kernel) for the learning-loss baseline's task model, whose LossNet gradient
-//                              joins the pyramid's in add_bcast_kernel (lossnet_train.hip, cald_amd/ll_train.py)
+//   RoIAlign forward/backward  roi_align_train_kernel / roi_align_bwd_fixed*_kernel (bilinear weights scattered with fixed-point
+//                              integer atomics: deterministic)
+//   losses                     softmax cross-entropy, smooth-L1, binary cross-entropy with logits: value + gradient in one pass, one workgroup
+//                              per segment -- the whole batch, or one IMAGE (*_seg entry points) for the learning-loss baseline's task
+//                              model, whose LossNet gradient joins the pyramid's in add_bcast_kernel (lossnet_train.hip, cald_amd/ll_train.py)
 //   optimizer                  sgd_kernel: torch.optim.SGD (weight decay, momentum, no dampening / nesterov) over the flat
 //                              parameter buffer
 #include "common.h"
@@ -943,34 +944,6 @@ extern "C" int cald_train_dilate(cald_ctx* c, int N, int Ho, int Wo, int C, int 
     THIP(hipGetLastError());
     return 0;
 }
-// stride-2 data gradient, last step: the four phase results (output pixels (2m + a, 2n + b) depend on disjoint filter taps) are woven
-// into dX [N][H][W][C]; phase (a, b) lives in ph[2a + b] = [N][Hp_ab][Wp_ab][C] and its pixel (m + off, n + off) belongs to (2m + a, 2n + b).
-// mask (optional, same shape as dX): ReLU backward of the layer dX flows into.
-struct WeaveArgs { const float* ph[4]; int Hp[4], Wp[4], off[4]; };
-__global__ void weave2_kernel(WeaveArgs a, const float* mask, float* out, int N, int H, int W, int C4) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long n4 = (long long)N * H * W * C4;
-    if (i >= n4) return;
-    const int c = (int)(i % C4); long long p = i / C4;
-    const int x = (int)(p % W); p /= W; const int y = (int)(p % H); const int n = (int)(p / H);
-    const int k = 2 * (y & 1) + (x & 1);
-    const int py = (y >> 1) + a.off[k], px = (x >> 1) + a.off[k];
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (py < a.Hp[k] && px < a.Wp[k]) v = reinterpret_cast<const float4*>(a.ph[k])[(((long long)n * a.Hp[k] + py) * a.Wp[k] + px) * C4 + c];
-    if (mask) { const float4 m = reinterpret_cast<const float4*>(mask)[i]; if (!(m.x > 0.f)) v.x = 0.f; if (!(m.y > 0.f)) v.y = 0.f; if (!(m.z > 0.f)) v.z = 0.f; if (!(m.w > 0.f)) v.w = 0.f; }
-    reinterpret_cast<float4*>(out)[i] = v;
-}
-extern "C" int cald_train_weave2(cald_ctx* c, int N, int H, int W, int C, const float* const* phases, const int* phase_hw, const int* phase_off,
-                                 const float* mask, float* out) {
-    if (!c || !phases || !phase_hw || !phase_off || !out || C % 4) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    WeaveArgs a;
-    for (int k = 0; k < 4; k++) { a.ph[k] = phases[k]; a.Hp[k] = phase_hw[2 * k]; a.Wp[k] = phase_hw[2 * k + 1]; a.off[k] = phase_off[k]; if (!phases[k]) TFAIL(CALD_ERR_INVALID, "null phase"); }
-    const long long n4 = (long long)N * H * W * (C / 4);
-    hipLaunchKernelGGL(weave2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, cald_internal_stream(c), a, mask, out, N, H, W, C / 4);
-    THIP(hipGetLastError());
-    return 0;
-}
 // FPN top-down backward: coarse[n][yc][xc][c] += sum of fine[n][yf][xf][c] over the fine pixels whose nearest source is (yc, xc)
 // (F.interpolate(size=fine, mode='nearest'): source = floor(dst * coarse / fine))
 __global__ void upsample_bwd_kernel(const float* fine, float* coarse, int N, int Hf, int Wf, int Hc, int Wc, int C4) {
@@ -1357,34 +1330,6 @@ __global__ __launch_bounds__(256) void roi_align_train_kernel(RoiTrainArgs a) {
         reinterpret_cast<float4*>(a.out)[(long long)r * 49 * Cq + idx] = make_float4(acc.x / 4.0f, acc.y / 4.0f, acc.z / 4.0f, acc.w / 4.0f);
     }
 }
-// backward: a thread owns (bin, ONE channel), consecutive lanes = consecutive channels, so that every atomic instruction of a
-// wavefront lands on 256 contiguous bytes (two cache lines) of one feature pixel
-__global__ __launch_bounds__(256) void roi_align_bwd_kernel(RoiTrainArgs a) {
-    __shared__ RoiSample sy[14], sx[14];
-    const int r = blockIdx.x, tid = threadIdx.x;
-    int n, l;
-    roi_setup(a, r, sy, sx, &n, &l);
-    const int Hf = a.H[l], Wf = a.W[l], C = a.C;
-    float* gf = a.gfeat[l] + (long long)n * Hf * Wf * C;
-    for (int idx = tid; idx < 49 * C; idx += 256) {
-        const int bin = idx / C, c = idx - bin * C;
-        const int ph = bin / 7, pw = bin - ph * 7;
-        const float go = a.gout[(long long)r * 49 * C + idx] * 0.25f;
-#pragma unroll
-        for (int iy = 0; iy < 2; iy++) {
-            const RoiSample Y = sy[ph * 2 + iy];
-#pragma unroll
-            for (int ix = 0; ix < 2; ix++) {
-                const RoiSample X = sx[pw * 2 + ix];
-                if (!(Y.valid && X.valid)) continue;
-                unsafeAtomicAdd(gf + (long long)(Y.lo * Wf + X.lo) * C + c, Y.h * X.h * go);
-                unsafeAtomicAdd(gf + (long long)(Y.lo * Wf + X.hi) * C + c, Y.h * X.l * go);
-                unsafeAtomicAdd(gf + (long long)(Y.hi * Wf + X.lo) * C + c, Y.l * X.h * go);
-                unsafeAtomicAdd(gf + (long long)(Y.hi * Wf + X.hi) * C + c, Y.l * X.l * go);
-            }
-        }
-    }
-}
 static int roi_args(RoiTrainArgs& a, const float* const* feats, float* const* gfeats, const int* level_hw, int C, int R, const float* rois) {
     if (C % 4 || R < 1 || !rois || !level_hw) return cald_internal_fail(CALD_ERR_INVALID, "bad RoIAlign arguments");
     memset(&a, 0, sizeof(a));
@@ -1416,6 +1361,8 @@ __device__ inline double fixed_scale(unsigned max_bits) {
     return max_bits ? ldexp(1.0, 40 - (e + 1)) : 1.0;
 }
 struct RoiAccPtrs { long long* p[4]; };
+// backward: a thread owns (bin, ONE channel), consecutive lanes = consecutive channels, so that every atomic instruction of a
+// wavefront lands on 256 contiguous bytes (two cache lines) of one feature pixel
 __global__ __launch_bounds__(256) void roi_align_bwd_fixed_kernel(RoiTrainArgs a, RoiAccPtrs acc, const unsigned* max_bits) {
     __shared__ RoiSample sy[14], sx[14];
     const int r = blockIdx.x, tid = threadIdx.x;
@@ -1533,20 +1480,13 @@ __global__ void fixed_to_float_kernel(const long long* acc, float* g, long long 
         if (v) g[i] = g[i] + (float)((double)v * inv);
     }
 }
-/* gfeats[l] += scatter of gout through the bilinear weights.  Deterministic (fixed-point accumulation, see above); CALD_ROI_BWD_FLOAT=1
- * selects plain float atomics (summation in arrival order). */
+/* gfeats[l] += scatter of gout through the bilinear weights.  Deterministic (fixed-point accumulation, see above). */
 extern "C" int cald_train_roi_align_bwd(cald_ctx* c, int N, float* const* gfeats, const int* level_hw, int C, int R, const float* rois, const float* gout) {
     if (!c || !gfeats || !gout || N < 1) TFAIL(CALD_ERR_INVALID, "bad arguments");
     THIP(hipSetDevice(cald_internal_device(c)));
     hipStream_t st = cald_internal_stream(c);
     RoiTrainArgs a; if (int rc = roi_args(a, (const float* const*)gfeats, gfeats, level_hw, C, R, rois)) return rc;
     a.gout = gout;
-    static const bool float_atomics = getenv("CALD_ROI_BWD_FLOAT") && atoi(getenv("CALD_ROI_BWD_FLOAT")) != 0;
-    if (float_atomics) {
-        hipLaunchKernelGGL(roi_align_bwd_kernel, dim3(R), dim3(256), 0, st, a);
-        THIP(hipGetLastError());
-        return 0;
-    }
     long long n[4], total = 0;
     for (int l = 0; l < 4; l++) { n[l] = (long long)N * a.H[l] * a.W[l] * C; total += (n[l] + 1) & ~1ll; }
     void* scratch = nullptr;
@@ -1568,100 +1508,14 @@ extern "C" int cald_train_roi_align_bwd(cald_ctx* c, int N, float* const* gfeats
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// losses: value and gradient in one pass.  Each kernel is ONE workgroup (the row counts are a few thousand), so the sums are
-// taken in a fixed order.  `gscale` multiplies the gradient (the upstream gradient of the scalar loss, normally 1).
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ inline float block_sum_256(float v, float* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v; __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-    const float r = red[0]; __syncthreads();
-    return r;
-}
-// F.cross_entropy(logits[R][C], labels) (mean over rows); grad[r][c] = (softmax - onehot) / R; rows have stride ld
-__global__ __launch_bounds__(256) void softmax_ce_kernel(const float* logits, const long long* labels, int R, int C, int ld, float gscale,
-                                                         float* loss, float* grad) {
-    __shared__ float red[256];
-    float local = 0.0f;
-    for (int r = threadIdx.x; r < R; r += 256) {
-        const float* z = logits + (long long)r * ld;
-        float m = z[0];
-        for (int k = 1; k < C; k++) m = fmaxf(m, z[k]);
-        float s = 0.0f;
-        for (int k = 0; k < C; k++) s += det_expf(z[k] - m);
-        const int y = (int)labels[r];
-        local += (det_logf(s) + m) - z[y];
-        if (grad) {
-            float* g = grad + (long long)r * ld;
-            const float inv = gscale / (float)R;
-            for (int k = 0; k < C; k++) g[k] = (det_expf(z[k] - m) / s - (k == y ? 1.0f : 0.0f)) * inv;
-        }
-    }
-    const float tot = block_sum_256(local, red);
-    if (threadIdx.x == 0) *loss = tot / (float)R;
-}
-extern "C" int cald_train_softmax_ce(cald_ctx* c, int R, int C, int ld, const float* logits, const int64_t* labels, float gscale, float* loss_out,
-                                     float* grad_out) {
-    if (!c || !logits || !labels || !loss_out || R < 1 || C < 1) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(softmax_ce_kernel, dim3(1), dim3(256), 0, cald_internal_stream(c), logits, (const long long*)labels, R, C, ld, gscale, loss_out, grad_out);
-    THIP(hipGetLastError());
-    return 0;
-}
-// det_utils.smooth_l1_loss(pred, target, beta, size_average=False) / denom over n gathered 4-vectors: pred 4-vector i starts at
-// float offset idx[i] of `pred` (and of `grad`, which the caller has zeroed).  beta = 0 is the plain L1 loss (retinanet_cal.py:217);
-// weights (optional, one per 4-vector) multiply each vector's term (per-image 1 / num_foreground of RetinaNet).
-__global__ __launch_bounds__(256) void smooth_l1_kernel(const float* pred, const long long* idx, const float* target, int n, float beta, float denom,
-                                                        const float* weights, float gscale, float* loss, float* grad) {
-    __shared__ float red[256];
-    float local = 0.0f;
-    for (int e = threadIdx.x; e < 4 * n; e += 256) {
-        const long long o = idx[e >> 2] + (e & 3);
-        const float d = pred[o] - target[e], ad = fabsf(d);
-        const float w = weights ? weights[e >> 2] : 1.0f;
-        local += w * (ad < beta ? 0.5f * d * d / beta : ad - 0.5f * beta);
-        if (grad) grad[o] = (ad < beta ? d / beta : (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f))) * (w * gscale / denom);
-    }
-    const float tot = block_sum_256(local, red);
-    if (threadIdx.x == 0) *loss = tot / denom;
-}
-extern "C" int cald_train_smooth_l1(cald_ctx* c, int n, const float* pred, const int64_t* idx, const float* target, float beta, float denom,
-                                    const float* weights, float gscale, float* loss_out, float* grad) {
-    if (!c || !loss_out || (n > 0 && (!pred || !idx || !target))) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(smooth_l1_kernel, dim3(1), dim3(256), 0, cald_internal_stream(c), pred, (const long long*)idx, target, n, beta, denom, weights, gscale, loss_out, grad);
-    THIP(hipGetLastError());
-    return 0;
-}
-// F.binary_cross_entropy_with_logits(x[idx], y) (mean over n gathered logits)
-__global__ __launch_bounds__(256) void bce_logits_kernel(const float* x, const long long* idx, const float* y, int n, float gscale, float* loss, float* grad) {
-    __shared__ float red[256];
-    float local = 0.0f;
-    for (int e = threadIdx.x; e < n; e += 256) {
-        const long long o = idx[e];
-        const float z = x[o], t = y[e];
-        // max(z, 0) - z * t + log(1 + exp(-|z|))
-        local += ((z > 0.0f ? z : 0.0f) - z * t) + det_logf(1.0f + det_expf(-fabsf(z)));
-        if (grad) grad[o] = (det_sigmoidf(z) - t) * (gscale / (float)n);
-    }
-    const float tot = block_sum_256(local, red);
-    if (threadIdx.x == 0) *loss = tot / (float)n;
-}
-extern "C" int cald_train_bce_logits(cald_ctx* c, int n, const float* logits, const int64_t* idx, const float* labels, float gscale, float* loss_out,
-                                     float* grad) {
-    if (!c || !loss_out || n < 1 || !logits || !idx || !labels) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(bce_logits_kernel, dim3(1), dim3(256), 0, cald_internal_stream(c), logits, (const long long*)idx, labels, n, gscale, loss_out, grad);
-    THIP(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// the same three losses per IMAGE (the learning-loss baseline's task losses, frcnn_ll.py:29-64 and :243-276; ll_train.py:77-85): segment i
-// = rows / gathered entries [off[i], off[i + 1]), ONE workgroup per image running the kernel above on its segment -- the same
-// thread-strided sum and block_sum_256, so a single segment returns the unsegmented kernel's bits -- loss[i], and image i's gradient
-// scaled by gscale[i] (device; null = 1).  The segments are the TRUE per-image sample counts: the reference's view(len(labels), -1, C)
-// presumes equal counts per image, and with equal counts the two agree.  The table travels in the kernel arguments.
+// losses: value and gradient in one pass, ONE workgroup per segment (the row counts are a few thousand), so the sums are taken in a
+// fixed order.  Segment i = rows / gathered entries [off[i], off[i + 1]).  The plain entry points launch one segment over everything
+// with a host `gscale` (the upstream gradient of the scalar loss, normally 1); the *_seg entry points launch one segment per IMAGE
+// (the learning-loss baseline's task losses, frcnn_ll.py:29-64 and :243-276; ll_train.py:77-85): loss[i], and image i's gradient
+// scaled by seg_gscale[i] (device; null = the host gscale).  Same kernel, same thread-strided sum and block_sum_256, so a single
+// segment returns the plain entry point's bits.  The segments are the TRUE per-image sample counts: the reference's
+// view(len(labels), -1, C) presumes equal counts per image, and with equal counts the two agree.  The table travels in the kernel
+// arguments.
 // ---------------------------------------------------------------------------------------------------------------------
 #define TRAIN_MAX_SEG 64
 struct SegTable { int off[TRAIN_MAX_SEG + 1]; float denom[TRAIN_MAX_SEG]; };
@@ -1679,11 +1533,26 @@ static int seg_table(int N, const int* seg_off, const float* denom, SegTable& t)
     }
     return 0;
 }
-__global__ __launch_bounds__(256) void softmax_ce_seg_kernel(const SegTable t, const float* logits, const long long* labels, int C, int ld,
-                                                             const float* gscale, float* loss, float* grad) {
+// the plain entry points' table: everything in one segment; their arguments are checked by the entry point, not by seg_table
+static SegTable one_segment(int n, float denom) {
+    SegTable t;
+    memset(&t, 0, sizeof(t));
+    t.off[1] = n; t.denom[0] = denom;
+    return t;
+}
+__device__ inline float block_sum_256(float v, float* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v; __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+    const float r = red[0]; __syncthreads();
+    return r;
+}
+// F.cross_entropy(logits[R][C], labels) (mean over the segment's rows); grad[r][c] = (softmax - onehot) / R; rows have stride ld
+__global__ __launch_bounds__(256) void softmax_ce_kernel(const SegTable t, const float* logits, const long long* labels, int C, int ld, float gscale,
+                                                         const float* seg_gscale, float* loss, float* grad) {
     __shared__ float red[256];
     const int img = blockIdx.x, r0 = t.off[img], R = t.off[img + 1] - r0;
-    const float gs = gscale ? gscale[img] : 1.0f;
+    const float gs = seg_gscale ? seg_gscale[img] : gscale;
     float local = 0.0f;
     for (int r = threadIdx.x; r < R; r += 256) {
         const float* z = logits + (long long)(r0 + r) * ld;
@@ -1702,66 +1571,102 @@ __global__ __launch_bounds__(256) void softmax_ce_seg_kernel(const SegTable t, c
     const float tot = block_sum_256(local, red);
     if (threadIdx.x == 0) loss[img] = R > 0 ? tot / (float)R : 0.0f;
 }
-__global__ __launch_bounds__(256) void smooth_l1_seg_kernel(const SegTable t, const float* pred, const long long* idx, const float* target, float beta,
-                                                            const float* gscale, float* loss, float* grad) {
+// det_utils.smooth_l1_loss(pred, target, beta, size_average=False) / denom over a segment's gathered 4-vectors: pred 4-vector i starts
+// at float offset idx[i] of `pred` (and of `grad`, which the caller has zeroed).  beta = 0 is the plain L1 loss (retinanet_cal.py:217);
+// weights (optional, one per 4-vector) multiply each vector's term (per-image 1 / num_foreground of RetinaNet).
+__global__ __launch_bounds__(256) void smooth_l1_kernel(const SegTable t, const float* pred, const long long* idx, const float* target, float beta,
+                                                        const float* weights, float gscale, const float* seg_gscale, float* loss, float* grad) {
     __shared__ float red[256];
     const int img = blockIdx.x, e0 = 4 * t.off[img], n = t.off[img + 1] - t.off[img];
-    const float gs = gscale ? gscale[img] : 1.0f, denom = t.denom[img];
+    const float gs = seg_gscale ? seg_gscale[img] : gscale, denom = t.denom[img];
     float local = 0.0f;
     for (int e = threadIdx.x; e < 4 * n; e += 256) {
         const long long o = idx[(e0 + e) >> 2] + (e & 3);
         const float d = pred[o] - target[e0 + e], ad = fabsf(d);
-        local += 1.0f * (ad < beta ? 0.5f * d * d / beta : ad - 0.5f * beta);
-        if (grad) grad[o] = (ad < beta ? d / beta : (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f))) * (1.0f * gs / denom);
+        const float w = weights ? weights[(e0 + e) >> 2] : 1.0f;
+        local += w * (ad < beta ? 0.5f * d * d / beta : ad - 0.5f * beta);
+        if (grad) grad[o] = (ad < beta ? d / beta : (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f))) * (w * gs / denom);
     }
     const float tot = block_sum_256(local, red);
     if (threadIdx.x == 0) loss[img] = tot / denom;           // no foreground row: 0 / denom = 0, and no gradient was written
 }
-__global__ __launch_bounds__(256) void bce_logits_seg_kernel(const SegTable t, const float* x, const long long* idx, const float* y, const float* gscale,
-                                                             float* loss, float* grad) {
+// F.binary_cross_entropy_with_logits(x[idx], y) (mean over a segment's gathered logits)
+__global__ __launch_bounds__(256) void bce_logits_kernel(const SegTable t, const float* x, const long long* idx, const float* y, float gscale,
+                                                         const float* seg_gscale, float* loss, float* grad) {
     __shared__ float red[256];
     const int img = blockIdx.x, e0 = t.off[img], n = t.off[img + 1] - e0;
-    const float gs = gscale ? gscale[img] : 1.0f;
+    const float gs = seg_gscale ? seg_gscale[img] : gscale;
     float local = 0.0f;
     for (int e = threadIdx.x; e < n; e += 256) {
         const long long o = idx[e0 + e];
         const float z = x[o], tt = y[e0 + e];
+        // max(z, 0) - z * t + log(1 + exp(-|z|))
         local += ((z > 0.0f ? z : 0.0f) - z * tt) + det_logf(1.0f + det_expf(-fabsf(z)));
         if (grad) grad[o] = (det_sigmoidf(z) - tt) * (gs / (float)n);
     }
     const float tot = block_sum_256(local, red);
     if (threadIdx.x == 0) loss[img] = n > 0 ? tot / (float)n : 0.0f;
 }
+static int launch_softmax_ce(cald_ctx* c, int N, const SegTable& t, int C, int ld, const float* logits, const int64_t* labels, float gscale,
+                             const float* seg_gscale, float* loss_out, float* grad_out) {
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(softmax_ce_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)labels, C, ld, gscale, seg_gscale,
+                       loss_out, grad_out);
+    THIP(hipGetLastError());
+    return 0;
+}
+static int launch_smooth_l1(cald_ctx* c, int N, const SegTable& t, const float* pred, const int64_t* idx, const float* target, float beta,
+                            const float* weights, float gscale, const float* seg_gscale, float* loss_out, float* grad) {
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(smooth_l1_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, pred, (const long long*)idx, target, beta, weights, gscale,
+                       seg_gscale, loss_out, grad);
+    THIP(hipGetLastError());
+    return 0;
+}
+static int launch_bce_logits(cald_ctx* c, int N, const SegTable& t, const float* logits, const int64_t* idx, const float* labels, float gscale,
+                             const float* seg_gscale, float* loss_out, float* grad) {
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(bce_logits_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)idx, labels, gscale, seg_gscale,
+                       loss_out, grad);
+    THIP(hipGetLastError());
+    return 0;
+}
+extern "C" int cald_train_softmax_ce(cald_ctx* c, int R, int C, int ld, const float* logits, const int64_t* labels, float gscale, float* loss_out,
+                                     float* grad_out) {
+    if (!c || !logits || !labels || !loss_out || R < 1 || C < 1) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    return launch_softmax_ce(c, 1, one_segment(R, 1.0f), C, ld, logits, labels, gscale, nullptr, loss_out, grad_out);
+}
+extern "C" int cald_train_smooth_l1(cald_ctx* c, int n, const float* pred, const int64_t* idx, const float* target, float beta, float denom,
+                                    const float* weights, float gscale, float* loss_out, float* grad) {
+    if (!c || !loss_out || (n > 0 && (!pred || !idx || !target))) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    return launch_smooth_l1(c, 1, one_segment(n, denom), pred, idx, target, beta, weights, gscale, nullptr, loss_out, grad);
+}
+extern "C" int cald_train_bce_logits(cald_ctx* c, int n, const float* logits, const int64_t* idx, const float* labels, float gscale, float* loss_out,
+                                     float* grad) {
+    if (!c || !loss_out || n < 1 || !logits || !idx || !labels) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    return launch_bce_logits(c, 1, one_segment(n, 1.0f), logits, idx, labels, gscale, nullptr, loss_out, grad);
+}
 extern "C" int cald_train_softmax_ce_seg(cald_ctx* c, int N, const int* seg_off, int C, int ld, const float* logits, const int64_t* labels,
                                          const float* gscale, float* loss_out, float* grad_out) {
     if (!c || !logits || !labels || !loss_out || C < 1 || ld < C) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    SegTable t; int rc;
-    if ((rc = seg_table(N, seg_off, nullptr, t))) return rc;
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(softmax_ce_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)labels, C, ld, gscale, loss_out, grad_out);
-    THIP(hipGetLastError());
-    return 0;
+    SegTable t;
+    if (int rc = seg_table(N, seg_off, nullptr, t)) return rc;
+    return launch_softmax_ce(c, N, t, C, ld, logits, labels, 1.0f, gscale, loss_out, grad_out);
 }
 extern "C" int cald_train_smooth_l1_seg(cald_ctx* c, int N, const int* seg_off, const float* pred, const int64_t* idx, const float* target, float beta,
                                         const float* denom, const float* gscale, float* loss_out, float* grad) {
     if (!c || !loss_out || !denom) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    SegTable t; int rc;
-    if ((rc = seg_table(N, seg_off, denom, t))) return rc;
+    SegTable t;
+    if (int rc = seg_table(N, seg_off, denom, t)) return rc;
     if (t.off[N] > 0 && (!pred || !idx || !target)) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(smooth_l1_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, pred, (const long long*)idx, target, beta, gscale, loss_out, grad);
-    THIP(hipGetLastError());
-    return 0;
+    return launch_smooth_l1(c, N, t, pred, idx, target, beta, nullptr, 1.0f, gscale, loss_out, grad);
 }
 extern "C" int cald_train_bce_logits_seg(cald_ctx* c, int N, const int* seg_off, const float* logits, const int64_t* idx, const float* labels,
                                          const float* gscale, float* loss_out, float* grad) {
     if (!c || !loss_out || !logits || !idx || !labels) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    SegTable t; int rc;
-    if ((rc = seg_table(N, seg_off, nullptr, t))) return rc;
-    THIP(hipSetDevice(cald_internal_device(c)));
-    hipLaunchKernelGGL(bce_logits_seg_kernel, dim3(N), dim3(256), 0, cald_internal_stream(c), t, logits, (const long long*)idx, labels, gscale, loss_out, grad);
-    THIP(hipGetLastError());
-    return 0;
+    SegTable t;
+    if (int rc = seg_table(N, seg_off, nullptr, t)) return rc;
+    return launch_bce_logits(c, N, t, logits, idx, labels, 1.0f, gscale, loss_out, grad);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1793,8 +1698,6 @@ extern "C" int cald_train_preprocess(cald_ctx* c, int N, const uint8_t* const* i
     launch_preprocess((const ViewDesc*)dv, s0, out, N, Hp * Wp, st);
     THIP(hipGetLastError());
     if (int rc = stage_consumed(c, slot, st)) return rc;
-    static const bool sync_env = getenv("CALD_TRAIN_PREPROCESS_SYNC") && atoi(getenv("CALD_TRAIN_PREPROCESS_SYNC"));   // A/B switch
-    if (sync_env) THIP(hipStreamSynchronize(st));
     return 0;
 }
 /* max_pool2d(3, 2, 1): in [N][H][W][C] -> out [N][(H-1)/2+1][(W-1)/2+1][C] */

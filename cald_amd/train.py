@@ -23,21 +23,23 @@ torchvision semantics restated here (0.8.2, "TV-mem" in SURVEY Appendix A; in-re
   * RoI heads: proposals + ground truth; Matcher(0.5, 0.5); sampler(512, 0.25); BoxCoder (10, 10, 5, 5); cross-entropy +
     smooth-L1 (beta 1/9) / #sampled                                                                     (frcnn_la.py:160-222)
 The samplers draw from torch's CPU generator (the reference draws ``torch.randperm`` on its CUDA device: a different stream of
-random numbers, the same distribution over subsets).  ``sampler="choose_k"`` (default) draws k distinct indices in O(k);
-``sampler="randperm"`` consumes ``torch.randperm(n, generator=g)[:k]`` for the positives, then for the negatives, image by
+random numbers, the same distribution over subsets).  ``sampler="choose_k"`` (default) keeps the k smallest of iid uniform keys, one per candidate: ``choose_k``
+below for the RPN anchors of an image, one ``torch.rand`` call and one host routine (``cald_train_roi_sample_host``) for the RoI
+candidates of the whole batch; ``sampler="randperm"`` consumes ``torch.randperm(n, generator=g)[:k]`` for the positives, then for the negatives, image by
 image, RPN before the RoI heads -- exactly the calls torchvision's BalancedPositiveNegativeSampler makes, so a seeded CPU
 generator reproduces torchvision's own samples (``tests/test_gpu_train.py::test_randperm_sampler_*``).
 """
+import contextlib
+import os
+import time
+
 import numpy as np
 import torch
 
 from . import train_ops as ops
 
 
-# 1: 3x3 stride-2 data gradients as four phase convolutions on the un-dilated dY (4x fewer FLOPs; measured SLOWER at batch 4 -- 100.4
-# vs 104.4 images/s on one box -- because the four small launches are latency-bound); default: one conv on the zero-stuffed grid
-_S2_PHASES = __import__("os").environ.get("CALD_TRAIN_S2_PHASES", "0") != "0"
-_PACK_PLAN = __import__("os").environ.get("CALD_TRAIN_PACK_PLAN", "1") != "0"      # all trainable layers re-packed in two launches per step
+_PACK_PLAN = os.environ.get("CALD_TRAIN_PACK_PLAN", "1") != "0"      # all trainable layers re-packed in two launches per step
 
 
 def _bn_fold(sd, prefix, eps=1e-5):
@@ -127,15 +129,7 @@ class _Conv(object):
             self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, pack=False)
         return [self._pk, self._pkd]
 
-    def _is_s2(self):
-        return _S2_PHASES and self.stride == 2 and self.K == 3 and self.pad == 1 and self.w.dim() == 4
-
     def _packed_grad(self):
-        if self._is_s2():                                   # four phase sub-filters instead of one filter on the zero-stuffed grid
-            if self._pkd is None or self._pkd_version != self.net.version:
-                self._pkd = ops.pack_s2_grads(self.w, scale=self.scale, CinK=self.out_ld, outs=self._pkd)
-                self._pkd_version = self.net.version
-            return self._pkd
         if self._pkd is None or self._pkd_version != self.net.version:
             buf = self._pkd.buf if self._pkd is not None else None
             # FrozenBatchNorm layers: the scale rides in the packed filter, so the incoming gradient is the one wrt the BN output
@@ -186,9 +180,6 @@ class _Conv(object):
         pkd = self._packed_grad()
         if self.mode == 2 or self.w.dim() == 2:
             return ops.conv(g, pkd, residual=residual, mask=mask)
-        if self._is_s2():
-            assert residual is None
-            return ops.conv_dgrad_s2(g, pkd, x.shape[1], x.shape[2], mask=mask)
         return ops.conv_dgrad(g, pkd, x.shape[1], x.shape[2], self.stride, self.pad, residual=residual, mask=mask)
 
 
@@ -304,7 +295,7 @@ class _TrainerBase(object):
         self.side = self.aux = None
         self._pack_plan = None
         self._roi_pin = None
-        if __import__("os").environ.get("CALD_TRAIN_SIDE_STREAM", "1") != "0":
+        if os.environ.get("CALD_TRAIN_SIDE_STREAM", "1") != "0":
             from .detector import get_side_ctx
             st = torch.cuda.Stream(device=self.dev)
             di = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
@@ -318,6 +309,18 @@ class _TrainerBase(object):
         if self.side is not None:
             torch.cuda.current_stream(self.dev).wait_stream(self.side[0])
 
+    @contextlib.contextmanager
+    def _aux_stream(self):
+        """What the block issues goes to the batch-only stream and its context (to the current stream where there is none)."""
+        if self.aux is None:
+            yield
+            return
+        prev, ops._WGRAD_CTX[0] = ops._WGRAD_CTX[0], self.aux[1]
+        try:
+            with torch.cuda.stream(self.aux[0]):
+                yield
+        finally:
+            ops._WGRAD_CTX[0] = prev
 
     # ---- parameter plumbing ----
     def _lookup(self, name):
@@ -399,7 +402,7 @@ class _TrainerBase(object):
 
     def _mark(self, name):
         if self.timing is not None:
-            torch.cuda.synchronize(self.dev); self.timing.append((name, __import__("time").time()))
+            torch.cuda.synchronize(self.dev); self.timing.append((name, time.time()))
 
     def _repack(self):
         """Forward and data-gradient forms of every trainable weight, packed on the side stream while the main stream runs the
@@ -410,8 +413,8 @@ class _TrainerBase(object):
         st.wait_stream(self._main)                          # the optimizer's update of the flat parameter buffer
         prev, ops._WGRAD_CTX[0] = ops._WGRAD_CTX[0], ctx
         try:
-            with torch.cuda.stream(st):                     # torch-side helpers of the packers (sub-filter gathers) run on this stream too
-                planned = [cv for cv in self.convs if cv.trainable and not cv._is_s2()] if _PACK_PLAN else []
+            with torch.cuda.stream(st):
+                planned = [cv for cv in self.convs if cv.trainable] if _PACK_PLAN else []
                 if planned:
                     # every layer's two forms in two launches: ~220 per-layer launches kept this stream busy for 1.5 ms, longer than
                     # the frozen layers cover (tools/train_event_timeline.py: layer 2 started 1.5 ms after the optimizer step)
@@ -477,12 +480,6 @@ class _TrainerBase(object):
         self._mark("body")
         return feats
 
-    def _inputs_and_body(self, images, targets):
-        self._begin_step()
-        u8, rem = self._prepare_images(images)
-        u8, rem, Hp, Wp, img_sizes, gts, gt_labels = self._inputs(u8, rem, targets)
-        return self._body(u8, rem, Hp, Wp, img_sizes), Hp, Wp, img_sizes, gts, gt_labels
-
     def _body_backward(self, gC):
         """gC[li]: gradient wrt the output of body layer li + 1 coming from the FPN laterals (None where there is none)."""
         g = None
@@ -508,6 +505,25 @@ class _TrainerBase(object):
                 if trainable:
                     out.update({"layer%d.%d.a1" % (li + 1, b): nchw(blk.a1), "layer%d.%d.a2" % (li + 1, b): nchw(blk.a2), "layer%d.%d.out" % (li + 1, b): nchw(blk.out)})
         return out
+
+
+class _Step(object):
+    """What the stages of one FasterRCNNTrainer.forward hand to each other, named by the stage that sets it.  KEPT: the fields that
+    become ``self.last`` (what backward(), the tests and the tools read of the last forward)."""
+    __slots__ = ("N", "u8", "rem",
+                 # RPN targets
+                 "Hp", "Wp", "img_sizes", "gts", "gt_labels", "n_gt", "gt_off", "gt_labels_cat", "gts_all", "level_hw", "head_sizes",
+                 "obj_idx", "obj_lab", "box_idx", "rpn_tgt", "rpn_samples",
+                 # FPN + RPN head
+                 "feats", "inner", "P", "tl", "heads", "head_flat",
+                 # proposals
+                 "props", "counts",
+                 # RoI sampling
+                 "R", "per_img", "rois", "labels", "pred_idx", "box_tgt", "roi_labels_np", "box_samples", "lazy",
+                 # box head
+                 "roi_rows", "f6", "f7", "pred")
+    KEPT = ("N", "R", "feats", "inner", "P", "tl", "heads", "head_flat", "head_sizes", "level_hw", "obj_idx", "obj_lab", "box_idx", "rpn_tgt",
+            "rois", "roi_rows", "f6", "f7", "pred", "labels", "pred_idx", "box_tgt")
 
 
 class FasterRCNNTrainer(_TrainerBase):
@@ -540,272 +556,230 @@ class FasterRCNNTrainer(_TrainerBase):
         self.pred_ld = ops.round_up(5 * num_classes, 4)
         self.pred = _Conv(self, self._merge_groups[2], self._merge_groups[3], out_ld=self.pred_ld)
         assert self.pred.Cout == 5 * num_classes, "box predictor does not match num_classes"
-        # CALD_TRAIN_SPECULATE=1: the first half of the backward's RPN branch is enqueued during the forward's RoI-sampling window (see
-        # forward).  Off by default: it paid (-0.8 ms) while the weight-gradient stream was the longer one of the backward; since that
-        # stream got faster the step is bound by the data-gradient chain, which wants the RPN branch beside the box-head branch: +0.7 ms
-        self.speculate = __import__("os").environ.get("CALD_TRAIN_SPECULATE", "0") != "0"
-        self.grad_wanted = True         # TrainableDetector clears it under torch.no_grad()
-        self._spec_grads = None
 
-    def forward(self, images, targets, proposals_override=None):
+    def forward(self, images, targets):
         """Training forward.  Returns the four losses as 1-element device tensors (no autograd) and keeps what backward needs.
         loss_mode "ll": returns ({name: [N] per-image losses}, pooled [N, 4, 256])."""
-        cfg, N, Ccls = self.cfg, len(images), self.C
-        ll = self.loss_mode == "ll"
-        mark = self._mark
-        mark("start")
+        s = _Step()
+        s.N = len(images)
+        self._mark("start")
         self._begin_step()
-        u8, rem = self._prepare_images(images)              # on the main stream: the images may have just been produced there
-        aux, prev = self.aux, ops._WGRAD_CTX[0]
-        import contextlib
-        with (torch.cuda.stream(aux[0]) if aux is not None else contextlib.nullcontext()):
-            if aux is not None:
-                ops._WGRAD_CTX[0] = aux[1]
-            try:
-                u8, rem, Hp, Wp, img_sizes, gts, gt_labels = self._inputs(u8, rem, targets)
-                # The RPN targets depend on the anchors and the ground truth only: match + sample them BEFORE the network is enqueued, so the
-                # device->host copy of the match results does not wait for (and the host-side sampling does not stall) the body's kernels.
-                level_hw = [(Hp // 4, Wp // 4), (Hp // 8, Wp // 8), (Hp // 16, Wp // 16), (Hp // 32, Wp // 32)]
-                level_hw.append(((level_hw[3][0] - 1) // 2 + 1, (level_hw[3][1] - 1) // 2 + 1))
-                head_sizes = [N * h * w * 16 for h, w in level_hw]
-                anchors = self.anchors(Hp, Wp, level_hw)
-                A_img = anchors.shape[0]
-                # ---- RPN targets and sampling (anchor order: level, y, x, anchor).  One device->host copy of all match results, host-side
-                # sampling (torch CPU generator), one host->device copy of every index the loss kernels need. ----
-                lvl_start = np.cumsum([0] + [h * w * 3 for h, w in level_hw])
-                head_off = np.cumsum([0] + head_sizes)
-                lvl_pix = np.array([h * w for h, w in level_hw])
-                def head_offsets(img, idx):                                  # float offset of anchor idx's objectness logit in head_flat
-                    l = np.searchsorted(lvl_start, idx, side="right") - 1
-                    rel = idx - lvl_start[l]
-                    pix, a = rel // 3, rel % 3
-                    return head_off[l] + (img * lvl_pix[l] + pix) * 16 + a, a
-                n_gt = [int(g.shape[0]) for g in gts]
-                gt_off = np.cumsum([0] + n_gt)
-                gt_labels_cat = np.ascontiguousarray(torch.cat(gt_labels).numpy()) if sum(n_gt) else np.zeros(1, np.int64)
-                gts_all = torch.cat(gts + [torch.zeros((1, 4), device=self.dev)])      # last row: the "matched box" of images without ground truth
-                matched_dev = torch.full((N, A_img), -1, dtype=torch.int32, device=self.dev)
-                for i in range(N):
-                    if n_gt[i]:
-                        ops.match(anchors, gts[i], cfg["rpn_fg"], cfg["rpn_bg"], True, out=matched_dev[i])
-                matched_all = matched_dev.cpu().numpy()
-                obj_idx, obj_lab, box_idx, anc_idx, gt_idx = [], [], [], [], []
-                rpn_samples, box_samples = [], []
-                for i in range(N):
-                    m = matched_all[i]
-                    pos, neg = torch.from_numpy(np.flatnonzero(m >= 0)), torch.from_numpy(np.flatnonzero(m == -1))
-                    sp, sn = self._sample(pos, neg, cfg["rpn_batch"], cfg["rpn_pos"])
-                    sp, sn = np.sort(sp.numpy()), np.sort(sn.numpy())
-                    rpn_samples.append((sp, sn))
-                    op_, ap_ = head_offsets(i, sp); on_, _ = head_offsets(i, sn)
-                    obj_idx += [op_, on_]; obj_lab += [np.ones(len(op_), np.float32), np.zeros(len(on_), np.float32)]
-                    box_idx.append(op_ - ap_ + 3 + 4 * ap_)                  # channel 3 + 4a of the same pixel
-                    anc_idx.append(sp); gt_idx.append(gt_off[i] + m[sp])
-                obj_idx, box_idx, anc_idx, gt_idx = [np.concatenate(v).astype(np.int64) for v in (obj_idx, box_idx, anc_idx, gt_idx)]
-                packed = torch.from_numpy(np.concatenate([obj_idx, box_idx, anc_idx, gt_idx])).to(self.dev)
-                n_obj, n_pos = len(obj_idx), len(box_idx)
-                obj_idx, box_idx = packed[:n_obj], packed[n_obj:n_obj + n_pos]
-                anc_sel, gt_sel = packed[n_obj + n_pos:n_obj + 2 * n_pos], packed[n_obj + 2 * n_pos:]
-                obj_lab = torch.from_numpy(np.concatenate(obj_lab)).to(self.dev)
-                rpn_tgt = ops.box_encode(gts_all[gt_sel], anchors[anc_sel], (1.0, 1.0, 1.0, 1.0))
-                mark("rpn targets")
-            finally:
-                ops._WGRAD_CTX[0] = prev
-        if aux is not None:                                 # what the main stream consumes from the batch-only stream
-            self._main.wait_stream(aux[0])
-            for t in list(gts) + [gts_all, packed, obj_lab, rpn_tgt]:
+        s.u8, s.rem = self._prepare_images(images)          # on the main stream: the images may have just been produced there
+        self._rpn_targets(s, targets)
+        self._fpn_rpn_head(s)
+        self._proposals(s)
+        self._roi_sampling(s)
+        self._box_head(s)
+        return self._losses(s)
+
+    def _rpn_targets(self, s, targets):
+        """Stage 1, on the batch-only stream: input sizes, ground truth, anchor matching, the RPN sampler, the RPN loss kernels' index lists."""
+        cfg, N = self.cfg, s.N
+        with self._aux_stream():
+            s.u8, s.rem, s.Hp, s.Wp, s.img_sizes, s.gts, s.gt_labels = self._inputs(s.u8, s.rem, targets)
+            Hp, Wp, gts = s.Hp, s.Wp, s.gts
+            # The RPN targets depend on the anchors and the ground truth only: match + sample them BEFORE the network is enqueued, so the
+            # device->host copy of the match results does not wait for (and the host-side sampling does not stall) the body's kernels.
+            level_hw = [(Hp // 4, Wp // 4), (Hp // 8, Wp // 8), (Hp // 16, Wp // 16), (Hp // 32, Wp // 32)]
+            level_hw.append(((level_hw[3][0] - 1) // 2 + 1, (level_hw[3][1] - 1) // 2 + 1))
+            head_sizes = [N * h * w * 16 for h, w in level_hw]
+            anchors = self.anchors(Hp, Wp, level_hw)
+            A_img = anchors.shape[0]
+            # ---- RPN targets and sampling (anchor order: level, y, x, anchor).  One device->host copy of all match results, host-side
+            # sampling (torch CPU generator), one host->device copy of every index the loss kernels need. ----
+            lvl_start = np.cumsum([0] + [h * w * 3 for h, w in level_hw])
+            head_off = np.cumsum([0] + head_sizes)
+            lvl_pix = np.array([h * w for h, w in level_hw])
+            def head_offsets(img, idx):                                  # float offset of anchor idx's objectness logit in head_flat
+                l = np.searchsorted(lvl_start, idx, side="right") - 1
+                rel = idx - lvl_start[l]
+                pix, a = rel // 3, rel % 3
+                return head_off[l] + (img * lvl_pix[l] + pix) * 16 + a, a
+            n_gt = [int(g.shape[0]) for g in gts]
+            gt_off = np.cumsum([0] + n_gt)
+            s.gt_labels_cat = np.ascontiguousarray(torch.cat(s.gt_labels).numpy()) if sum(n_gt) else np.zeros(1, np.int64)
+            s.gts_all = torch.cat(gts + [torch.zeros((1, 4), device=self.dev)])      # last row: the "matched box" of images without ground truth
+            matched_dev = torch.full((N, A_img), -1, dtype=torch.int32, device=self.dev)
+            for i in range(N):
+                if n_gt[i]:
+                    ops.match(anchors, gts[i], cfg["rpn_fg"], cfg["rpn_bg"], True, out=matched_dev[i])
+            matched_all = matched_dev.cpu().numpy()
+            obj_idx, obj_lab, box_idx, anc_idx, gt_idx = [], [], [], [], []
+            s.rpn_samples = []
+            for i in range(N):
+                m = matched_all[i]
+                pos, neg = torch.from_numpy(np.flatnonzero(m >= 0)), torch.from_numpy(np.flatnonzero(m == -1))
+                sp, sn = self._sample(pos, neg, cfg["rpn_batch"], cfg["rpn_pos"])
+                sp, sn = np.sort(sp.numpy()), np.sort(sn.numpy())
+                s.rpn_samples.append((sp, sn))
+                op_, ap_ = head_offsets(i, sp); on_, _ = head_offsets(i, sn)
+                obj_idx += [op_, on_]; obj_lab += [np.ones(len(op_), np.float32), np.zeros(len(on_), np.float32)]
+                box_idx.append(op_ - ap_ + 3 + 4 * ap_)                  # channel 3 + 4a of the same pixel
+                anc_idx.append(sp); gt_idx.append(gt_off[i] + m[sp])
+            obj_idx, box_idx, anc_idx, gt_idx = [np.concatenate(v).astype(np.int64) for v in (obj_idx, box_idx, anc_idx, gt_idx)]
+            packed = torch.from_numpy(np.concatenate([obj_idx, box_idx, anc_idx, gt_idx])).to(self.dev)
+            n_obj, n_pos = len(obj_idx), len(box_idx)
+            s.obj_idx, s.box_idx = packed[:n_obj], packed[n_obj:n_obj + n_pos]
+            anc_sel, gt_sel = packed[n_obj + n_pos:n_obj + 2 * n_pos], packed[n_obj + 2 * n_pos:]
+            s.obj_lab = torch.from_numpy(np.concatenate(obj_lab)).to(self.dev)
+            s.rpn_tgt = ops.box_encode(s.gts_all[gt_sel], anchors[anc_sel], (1.0, 1.0, 1.0, 1.0))
+            s.level_hw, s.head_sizes, s.n_gt, s.gt_off = level_hw, head_sizes, n_gt, gt_off
+            self._mark("rpn targets")
+        if self.aux is not None:                            # what the main stream consumes from the batch-only stream
+            self._main.wait_stream(self.aux[0])
+            for t in list(gts) + [s.gts_all, packed, s.obj_lab, s.rpn_tgt]:
                 t.record_stream(self._main)
-        feats = self._body(u8, rem, Hp, Wp, img_sizes)
-        # FPN (top-down), LastLevelMaxPool
-        inner = [None] * 4
+
+    def _fpn_rpn_head(self, s):
+        """Stage 2: body, FPN (top-down), LastLevelMaxPool, the RPN head on the five levels."""
+        N = s.N
+        s.feats = feats = self._body(s.u8, s.rem, s.Hp, s.Wp, s.img_sizes)
+        s.inner = inner = [None] * 4
         inner[3] = self.lat[3].fwd(feats[3])
         for i in (2, 1, 0):
             inner[i] = self.lat[i].fwd(feats[i], up=inner[i + 1])
-        P = self._fpn_out_fwd(inner)
+        s.P = P = self._fpn_out_fwd(inner)
         P.append(ops.subsample2(P[3]))
-        assert level_hw == [(p.shape[1], p.shape[2]) for p in P]
+        assert s.level_hw == [(p.shape[1], p.shape[2]) for p in P]
         # RPN head on the five levels: outputs in ONE buffer so that the loss kernels address (level, pixel, channel) by offset
-        head_flat = torch.zeros(sum(head_sizes), dtype=torch.float32, device=self.dev)
-        heads, o = [], 0
-        tl = ops.conv_group(P, self.rpn_conv._packed(), pad=1, relu=True)            # shared 3x3 conv on the five levels: one launch
-        for i, (h, w) in enumerate(level_hw):
-            heads.append(ops.conv(tl[i], self.rpn_head._packed(), out=head_flat[o:o + head_sizes[i]].view(N, h, w, 16), out_ld=16))
+        s.head_flat = torch.zeros(sum(s.head_sizes), dtype=torch.float32, device=self.dev)
+        s.heads, o = [], 0
+        s.tl = tl = ops.conv_group(P, self.rpn_conv._packed(), pad=1, relu=True)     # shared 3x3 conv on the five levels: one launch
+        for i, (h, w) in enumerate(s.level_hw):
+            s.heads.append(ops.conv(tl[i], self.rpn_head._packed(), out=s.head_flat[o:o + s.head_sizes[i]].view(N, h, w, 16), out_ld=16))
             self.rpn_conv._count(P[i], 1); self.rpn_head._count(tl[i], 1)
-            o += head_sizes[i]
-        mark("fpn+rpn head")
-        spec = None
-        rpn_state = dict(N=N, P=P, tl=tl, head_flat=head_flat, head_sizes=head_sizes, level_hw=level_hw, obj_idx=obj_idx, obj_lab=obj_lab,
-                         box_idx=box_idx, rpn_tgt=rpn_tgt)
-        props_ready = None
-        if proposals_override is None:
-            props, counts = ops.rpn_proposals(heads, Hp, Wp, img_sizes, cfg["pre_n"], cfg["post_n"], cfg["nms"], 1e-3)
-            if self.speculate and aux is not None and self.grad_wanted and not ll:
-                # The host now needs the proposals (counts, then the match results) to draw the RoI samples: ~1 ms during which the main
-                # stream would sit empty.  The RPN branch of the backward pass depends on nothing that comes later, so its first half
-                # (loss gradients, the head's gradients, the 3x3 conv's weight gradients) is enqueued here, behind the proposal
-                # kernels, for unit upstream gradients (losses.backward() of the plain sum, the reference's loop); backward() uses it
-                # when its upstream gradients are 1 and recomputes otherwise.  The second half (the 3x3 conv's data gradients, ~2 ms)
-                # stays in backward(): there it runs beside the box-head branch, which would otherwise be alone on the chip.
-                props.record_stream(aux[0])
-                counts_h = torch.empty(counts.shape, dtype=counts.dtype, pin_memory=True)
-                counts_h.copy_(counts, non_blocking=True)
-                props_ready = torch.cuda.Event(); props_ready.record(self._main)
-                spec = self._rpn_branch_weights(rpn_state, 1.0, 1.0, speculative=True)
-                props_ready.synchronize()
-                counts = counts_h.tolist()
-                proposals = [props[i, :counts[i]] for i in range(N)]
+            o += s.head_sizes[i]
+        self._mark("fpn+rpn head")
+
+    def _proposals(self, s):
+        """Stage 3: the RPN's proposals, a fixed [N, post_n, 4] block and the number of used rows per image, both left on the device."""
+        cfg = self.cfg
+        s.props, s.counts = ops.rpn_proposals(s.heads, s.Hp, s.Wp, s.img_sizes, cfg["pre_n"], cfg["post_n"], cfg["nms"], 1e-3)
+        self._mark("proposals")
+
+    def _roi_sampling(self, s):
+        """Stage 4: the RoI heads' candidates matched on the device, labelled and sampled on the host (the forward's ONE host stop after
+        the RPN's): RoIAlign's rows, their labels and regression targets, the loss kernels' index lists."""
+        cfg, N, n_gt, props = self.cfg, s.N, s.n_gt, s.props
+        # The proposal counts are not waited for.  The RoI candidates are matched in a fixed-row table (image i: its post_n proposal
+        # slots, used or not, then its ground truth) and the counts travel to the host in the same copy as the match results; unused
+        # slots are dropped there.
+        post = int(props.shape[1])
+        pr_off = np.cumsum([0] + [post + g for g in n_gt])
+        T = int(pr_off[-1])
+        pr_all = torch.cat([t for i in range(N) for t in ((props[i], s.gts[i]) if n_gt[i] else (props[i],))]).contiguous()
+        matched_dev = torch.full((T + N,), -1, dtype=torch.int32, device=self.dev)
+        for i in range(N):
+            if n_gt[i]:
+                ops.match(pr_all[pr_off[i]:pr_off[i + 1]], s.gts[i], cfg["box_fg"], cfg["box_bg"], False, out=matched_dev[pr_off[i]:pr_off[i + 1]])
+        matched_dev[T:] = s.counts.to(torch.int32)
+        matched_all = matched_dev.cpu().numpy()
+        # ---- the GPU waits from here to the host->device copy of the sampler: everything in between is host time on the step's critical path ----
+        counts = matched_all[T:]
+        sample = self._sample_rois_choose_k if self.sampler == "choose_k" else self._sample_rois_randperm
+        sample(s, pr_all, pr_off, matched_all, counts)
+        # what only tests and inspection read: the proposals as a list, the RoI labels on the host
+        s.lazy = {"proposals": lambda c=counts.copy(): [props[i, :int(c[i])] for i in range(N)],
+                  "roi_labels": lambda l=s.roi_labels_np: torch.from_numpy(np.ascontiguousarray(l))}
+        self._mark("roi sampling")
+
+    def _sample_rois_choose_k(self, s, pr_all, pr_off, matched_all, counts):
+        """One C call for the whole batch (cald_train_roi_sample_host): labels, the balanced sampler (the k smallest of iid uniform keys
+        per class -- one generator call for all images, one key per table row), every index list of the loss kernels, written into
+        pinned memory and uploaded as one block; one kernel (cald_train_roi_gather) then builds RoIAlign's rows and the regression
+        targets.  The numpy loop of the other sampler + eight small torch ops cost 0.6 ms of GPU idle per step."""
+        cfg, N, post = self.cfg, s.N, int(s.props.shape[1])
+        keys = torch.rand(sum(post + g for g in s.n_gt), generator=self.generator, dtype=torch.float64).numpy()
+        cap = N * cfg["box_batch"]
+        if self._roi_pin is None or self._roi_pin.numel() < 6 * cap:
+            self._roi_pin = torch.empty(6 * cap, dtype=torch.int64, pin_memory=True)
+        pin_np = self._roi_pin.numpy()
+        _, _, R, n_posrows, per_img = ops.roi_sample_host([post] * N, s.n_gt, counts, matched_all, s.gt_labels_cat, keys, cfg["box_batch"], cfg["box_pos"],
+                                                          self.pred_ld, self.C, out=pin_np)
+        packed2 = torch.empty(6 * cap, dtype=torch.int64, device=self.dev)
+        packed2.copy_(self._roi_pin[:6 * cap], non_blocking=True)       # the pinned block is rewritten only after the next step's stop
+        s.rois, s.box_tgt = ops.roi_gather(pr_all, s.gts_all, packed2, cap, R, n_posrows, cfg["w"])
+        s.R, s.per_img = R, per_img
+        s.labels, s.pred_idx = packed2[2 * cap:2 * cap + R], packed2[3 * cap:3 * cap + n_posrows]
+        keep_np, s.roi_labels_np = pin_np[:R].copy(), pin_np[2 * cap:2 * cap + R].copy()
+        def box_samples(keep=keep_np, lab=s.roi_labels_np, per_img=per_img, cn=counts.copy(), pr_off=pr_off.copy()):
+            out, o = [], 0
+            for i in range(N):                      # table row -> compact candidate number (used proposals, then the ground truth)
+                r = keep[o:o + per_img[i]] - pr_off[i]
+                c = np.where(r < post, r, r - post + int(cn[i]))
+                l = lab[o:o + per_img[i]]
+                out.append((c[l > 0], c[l == 0])); o += per_img[i]
+            return out
+        s.box_samples = box_samples
+
+    def _sample_rois_randperm(self, s, pr_all, pr_off, matched_all, counts):
+        """torchvision's own sampler calls image by image (_sample) on the compact candidate list of each image -- its used proposals,
+        then its ground truth -- with the index lists and targets put together by numpy and small torch ops."""
+        cfg, N, n_gt, post = self.cfg, s.N, s.n_gt, int(s.props.shape[1])
+        # compact candidate number -> row of the fixed-row table (the used proposal slots, then the ground truth)
+        rowmap = [np.concatenate([np.arange(int(counts[i])), post + np.arange(n_gt[i])]).astype(np.int64) for i in range(N)]
+        keep_all, lab_all, gtsel_all, img_col, box_samples = [], [], [], [], []
+        for i in range(N):
+            m = matched_all[pr_off[i]:pr_off[i + 1]][rowmap[i]]
+            if n_gt[i]:
+                labels = s.gt_labels[i].numpy()[np.maximum(m, 0)].copy()
+                labels[m == -1] = 0
+                labels[m == -2] = -1
             else:
-                # ONE host stop instead of two: the proposal counts are not waited for.  The RoI candidates are matched in a fixed-row
-                # table (image i: its post_n proposal slots, used or not, then its ground truth) and the counts travel to the host in
-                # the same copy as the match results; unused slots are dropped there.  Same candidates, same draws, same rows.
-                proposals = None
-        else:
-            proposals = [p.to(self.dev).float().contiguous() for p in proposals_override]
-        mark("proposals")
-        # ---- RoI sampling (on the batch-only stream when the main stream is busy with the speculative branch: the device->host copy
-        # of the match results then waits for the match kernels only) ----
-        on_aux = props_ready is not None
-        with (torch.cuda.stream(aux[0]) if on_aux else contextlib.nullcontext()):
-            if on_aux:
-                aux[0].wait_event(props_ready)
-                ops._WGRAD_CTX[0] = aux[1]
-            try:
-                fixed_rows = proposals is None
-                slots = [(int(props.shape[1]) if fixed_rows else int(proposals[i].shape[0])) for i in range(N)]
-                n_pr = [slots[i] + n_gt[i] for i in range(N)]
-                pr_off = np.cumsum([0] + n_pr)
-                src = [props[i] for i in range(N)] if fixed_rows else proposals
-                pr_all = torch.cat([t for i in range(N) for t in ((src[i], gts[i]) if n_gt[i] else (src[i],))]).contiguous()
-                matched_dev = torch.full((int(pr_off[-1]) + (N if fixed_rows else 0),), -1, dtype=torch.int32, device=self.dev)
-                for i in range(N):
-                    if n_gt[i]:
-                        ops.match(pr_all[pr_off[i]:pr_off[i + 1]], gts[i], cfg["box_fg"], cfg["box_bg"], False, out=matched_dev[pr_off[i]:pr_off[i + 1]])
-                if fixed_rows:
-                    matched_dev[int(pr_off[-1]):] = counts.to(torch.int32)
-                matched_all = matched_dev.cpu().numpy()
-                # ---- the GPU waits from here to the host->device copy below: everything in between is host time on the step's critical path ----
-                T = int(pr_off[-1])
-                if fixed_rows:
-                    counts_np = matched_all[T:]
-                    counts = None                           # as a list only where someone asks (self.last["proposals"], the randperm sampler)
-                else:
-                    counts_np, counts = None, list(slots)
-                lazy = {}
-                if fixed_rows:
-                    lazy["proposals"] = lambda props=props, c=counts_np.copy(): [props[i, :int(c[i])] for i in range(N)]
-                if self.sampler == "choose_k":
-                    # one C call for the whole batch (cald_train_roi_sample_host): labels, the balanced sampler (the k smallest of iid
-                    # uniform keys per class -- one generator call for all images), every index list of the loss kernels, written into
-                    # pinned memory and uploaded as one block; one kernel (cald_train_roi_gather) then builds RoIAlign's rows and the
-                    # regression targets.  The numpy loop of the other branch + eight small torch ops cost 0.6 ms of GPU idle per step.
-                    # Keys are drawn per (image, post_n proposal slots + ground truth) whatever the table's shape, so that the fixed-row and
-                    # the compact table (speculative path, proposals handed in) select the same candidates from the same generator state.
-                    post = cfg["post_n"]
-                    if all(sl <= post for sl in slots):
-                        keys = torch.rand(sum(post + g for g in n_gt), generator=self.generator, dtype=torch.float64).numpy()
-                        if any(sl != post for sl in slots):
-                            ko = np.cumsum([0] + [post + g for g in n_gt])
-                            keys = np.concatenate([keys[np.r_[ko[i]:ko[i] + slots[i], ko[i] + post:ko[i] + post + n_gt[i]]] for i in range(N)])
-                    else:
-                        keys = torch.rand(T, generator=self.generator, dtype=torch.float64).numpy()
-                    cap = N * cfg["box_batch"]
-                    if self._roi_pin is None or self._roi_pin.numel() < 6 * cap:
-                        self._roi_pin = torch.empty(6 * cap, dtype=torch.int64, pin_memory=True)
-                    pin_np = self._roi_pin.numpy()
-                    _, _, R, n_posrows, per_img = ops.roi_sample_host(slots, n_gt, counts_np, matched_all, gt_labels_cat, keys, cfg["box_batch"], cfg["box_pos"],
-                                                                      self.pred_ld, Ccls, out=pin_np)
-                    packed2 = torch.empty(6 * cap, dtype=torch.int64, device=self.dev)
-                    packed2.copy_(self._roi_pin[:6 * cap], non_blocking=True)       # the pinned block is rewritten only after the next step's stop
-                    rois, box_tgt = ops.roi_gather(pr_all, gts_all, packed2, cap, R, n_posrows, cfg["w"])
-                    keep_sel, labels_dev = packed2[:R], packed2[2 * cap:2 * cap + R]
-                    pred_idx = packed2[3 * cap:3 * cap + n_posrows]
-                    keep_np, roi_labels_np = pin_np[:R].copy(), pin_np[2 * cap:2 * cap + R].copy()
-                    def box_samples_fn(keep=keep_np, lab=roi_labels_np, per_img=per_img, cn=None if counts_np is None else counts_np.copy(), slots=list(slots),
-                                       pr_off=pr_off.copy()):
-                        out, o = [], 0
-                        for i in range(N):                      # table row -> compact candidate number (used proposals, then the ground truth)
-                            r = keep[o:o + per_img[i]] - pr_off[i]
-                            c = np.where(r < slots[i], r, r - slots[i] + (slots[i] if cn is None else int(cn[i])))
-                            l = lab[o:o + per_img[i]]
-                            out.append((c[l > 0], c[l == 0])); o += per_img[i]
-                        return out
-                    box_samples = None
-                else:
-                    if counts is None:
-                        counts = [int(v) for v in counts_np]
-                    # compact candidate number -> row of the fixed-row table (the used proposal slots, then the ground truth)
-                    rowmap = [np.concatenate([np.arange(counts[i]), slots[i] + np.arange(n_gt[i])]).astype(np.int64) for i in range(N)]
-                    keep_all, lab_all, gtsel_all, img_col = [], [], [], []
-                    for i in range(N):
-                        m = matched_all[pr_off[i]:pr_off[i + 1]][rowmap[i]]
-                        if n_gt[i]:
-                            labels = gt_labels[i].numpy()[np.maximum(m, 0)].copy()
-                            labels[m == -1] = 0
-                            labels[m == -2] = -1
-                        else:
-                            labels = np.zeros(len(m), np.int64)
-                        pos, neg = torch.from_numpy(np.flatnonzero(labels >= 1)), torch.from_numpy(np.flatnonzero(labels == 0))
-                        sp, sn = self._sample(pos, neg, cfg["box_batch"], cfg["box_pos"])
-                        box_samples.append((np.sort(sp.numpy()), np.sort(sn.numpy())))
-                        keep = np.sort(np.concatenate([sp.numpy(), sn.numpy()]))
-                        keep_all.append(pr_off[i] + rowmap[i][keep]); lab_all.append(labels[keep])
-                        gtsel_all.append(gt_off[i] + np.maximum(m[keep], 0) if n_gt[i] else np.full(len(keep), gt_off[-1], np.int64))
-                        img_col.append(np.full(len(keep), float(i), np.float32))
-                    roi_labels_np = np.concatenate(lab_all).astype(np.int64)
-                    per_img = [len(l) for l in lab_all]
-                    R = len(roi_labels_np)
-                    pos_rows = np.flatnonzero(roi_labels_np > 0)
-                    n_posrows = len(pos_rows)
-                    pred_idx_np = pos_rows * self.pred_ld + Ccls + 4 * roi_labels_np[pos_rows]
-                    packed2 = torch.from_numpy(np.concatenate([np.concatenate(keep_all), np.concatenate(gtsel_all), roi_labels_np, pred_idx_np, pos_rows]).astype(np.int64)).to(self.dev)
-                    img_col_dev = torch.from_numpy(np.concatenate(img_col)).to(self.dev)
-                    box_samples_fn = None
-                    keep_sel, gt_sel2, labels_dev = packed2[:R], packed2[R:2 * R], packed2[2 * R:3 * R]
-                    pred_idx, pos_sel = packed2[3 * R:3 * R + n_posrows], packed2[3 * R + n_posrows:3 * R + 2 * n_posrows]
-                    boxes = pr_all[keep_sel]
-                    rois = torch.cat([img_col_dev[:, None], boxes], dim=1).contiguous()
-                    roi_gt = gts_all[gt_sel2]
-                    box_tgt = ops.box_encode(roi_gt.contiguous(), boxes.contiguous(), cfg["w"])[pos_sel].contiguous()
-                lazy["roi_labels"] = lambda l=roi_labels_np: torch.from_numpy(np.ascontiguousarray(l))
-                if "proposals" not in lazy:
-                    lazy["proposals"] = lambda p=proposals: p
-            finally:
-                ops._WGRAD_CTX[0] = prev
-        if on_aux:
-            self._main.wait_stream(aux[0])
-            for t in (packed2, rois, box_tgt):
-                t.record_stream(self._main)
-        mark("roi sampling")
-        # ---- box head ----
-        roi_rows = ops.roi_align(P[:4], rois)
-        f6 = self.fc6.fwd(roi_rows.view(1, 1, R, -1), relu=True)
-        f7 = self.fc7.fwd(f6, relu=True)
-        pred = self.pred.fwd(f7)
-        self.last = _LazyDict(lazy, N=N, R=R, feats=feats, inner=inner, P=P, tl=tl, heads=heads, head_flat=head_flat, head_sizes=head_sizes, level_hw=level_hw,
-                         obj_idx=obj_idx, obj_lab=obj_lab, box_idx=box_idx, rpn_tgt=rpn_tgt, rois=rois, roi_rows=roi_rows, f6=f6, f7=f7, pred=pred,
-                         labels=labels_dev, pred_idx=pred_idx, box_tgt=box_tgt,
-                         samples=_LazyDict({"box": box_samples_fn} if box_samples_fn is not None else {}, rpn=rpn_samples,
-                                           **({} if box_samples_fn is not None else {"box": box_samples})), spec=spec)
-        mark("box head")
-        if ll:
+                labels = np.zeros(len(m), np.int64)
+            pos, neg = torch.from_numpy(np.flatnonzero(labels >= 1)), torch.from_numpy(np.flatnonzero(labels == 0))
+            sp, sn = self._sample(pos, neg, cfg["box_batch"], cfg["box_pos"])
+            box_samples.append((np.sort(sp.numpy()), np.sort(sn.numpy())))
+            keep = np.sort(np.concatenate([sp.numpy(), sn.numpy()]))
+            keep_all.append(pr_off[i] + rowmap[i][keep]); lab_all.append(labels[keep])
+            gtsel_all.append(s.gt_off[i] + np.maximum(m[keep], 0) if n_gt[i] else np.full(len(keep), s.gt_off[-1], np.int64))
+            img_col.append(np.full(len(keep), float(i), np.float32))
+        s.roi_labels_np = roi_labels_np = np.concatenate(lab_all).astype(np.int64)
+        s.per_img = [len(l) for l in lab_all]
+        s.R = R = len(roi_labels_np)
+        pos_rows = np.flatnonzero(roi_labels_np > 0)
+        n_posrows = len(pos_rows)
+        pred_idx_np = pos_rows * self.pred_ld + self.C + 4 * roi_labels_np[pos_rows]
+        packed2 = torch.from_numpy(np.concatenate([np.concatenate(keep_all), np.concatenate(gtsel_all), roi_labels_np, pred_idx_np, pos_rows]).astype(np.int64)).to(self.dev)
+        img_col_dev = torch.from_numpy(np.concatenate(img_col)).to(self.dev)
+        keep_sel, gt_sel2, s.labels = packed2[:R], packed2[R:2 * R], packed2[2 * R:3 * R]
+        s.pred_idx, pos_sel = packed2[3 * R:3 * R + n_posrows], packed2[3 * R + n_posrows:3 * R + 2 * n_posrows]
+        boxes = pr_all[keep_sel]
+        s.rois = torch.cat([img_col_dev[:, None], boxes], dim=1).contiguous()
+        roi_gt = s.gts_all[gt_sel2]
+        s.box_tgt = ops.box_encode(roi_gt.contiguous(), boxes.contiguous(), cfg["w"])[pos_sel].contiguous()
+        s.box_samples = lambda: box_samples
+
+    def _box_head(self, s):
+        """Stage 5: RoIAlign, the two-layer head, the predictor; the step's record for backward() and inspection."""
+        s.roi_rows = ops.roi_align(s.P[:4], s.rois)
+        s.f6 = self.fc6.fwd(s.roi_rows.view(1, 1, s.R, -1), relu=True)
+        s.f7 = self.fc7.fwd(s.f6, relu=True)
+        s.pred = self.pred.fwd(s.f7)
+        self.last = _LazyDict(s.lazy, samples=_LazyDict({"box": s.box_samples}, rpn=s.rpn_samples), **{k: getattr(s, k) for k in _Step.KEPT})
+        self._mark("box head")
+
+    def _losses(self, s):
+        """Stage 6: the four losses -- per batch, or per image with the pooled pyramid vectors in loss_mode "ll"."""
+        L, N = self.last, s.N
+        if self.loss_mode == "ll":
             # per-image segments of the index lists (they are built image by image) and the reference's normalisers
-            L = self.last
-            L["rpn_cnt"] = [len(sp) + len(sn) for sp, sn in rpn_samples]
-            L["rpn_pos_cnt"] = [len(sp) for sp, _ in rpn_samples]
-            L["roi_cnt"] = [int(v) for v in per_img]
+            L["rpn_cnt"] = [len(sp) + len(sn) for sp, sn in s.rpn_samples]
+            L["rpn_pos_cnt"] = [len(sp) for sp, _ in s.rpn_samples]
+            L["roi_cnt"] = [int(v) for v in s.per_img]
             edges = np.cumsum([0] + L["roi_cnt"])
-            L["roi_pos_cnt"] = [int((roi_labels_np[edges[i]:edges[i + 1]] > 0).sum()) for i in range(N)]
+            L["roi_pos_cnt"] = [int((s.roi_labels_np[edges[i]:edges[i + 1]] > 0).sum()) for i in range(N)]
             losses = self._ll_losses(L)
-            L["pooled"] = ops.train_gap(P[:4])          # the batch's PADDED maps, as frcnn_ll.py:601-602 pools them
-            mark("losses")
+            L["pooled"] = ops.train_gap(s.P[:4])        # the batch's PADDED maps, as frcnn_ll.py:601-602 pools them
+            self._mark("losses")
             return losses, L["pooled"]
         losses = {
-            "loss_classifier": ops.softmax_ce(pred.view(R, -1), labels_dev, Ccls),
-            "loss_box_reg": ops.smooth_l1(pred, pred_idx, box_tgt, 1.0 / 9, R),
-            "loss_objectness": ops.bce_logits(head_flat, obj_idx, obj_lab),
-            "loss_rpn_box_reg": ops.smooth_l1(head_flat, box_idx, rpn_tgt, 1.0 / 9, n_obj),
+            "loss_classifier": ops.softmax_ce(s.pred.view(s.R, -1), s.labels, self.C),
+            "loss_box_reg": ops.smooth_l1(s.pred, s.pred_idx, s.box_tgt, 1.0 / 9, s.R),
+            "loss_objectness": ops.bce_logits(s.head_flat, s.obj_idx, s.obj_lab),
+            "loss_rpn_box_reg": ops.smooth_l1(s.head_flat, s.box_idx, s.rpn_tgt, 1.0 / 9, s.obj_idx.numel()),
         }
-        mark("losses")
+        self._mark("losses")
         return losses
 
     def _ll_losses(self, L, gs=None, gpred=None, ghead=None, which=(0, 1, 2, 3)):
@@ -836,39 +810,25 @@ class FasterRCNNTrainer(_TrainerBase):
         out["fc6"] = (L["f6"] > 0).view(L["R"], -1).cpu(); out["fc7"] = (L["f7"] > 0).view(L["R"], -1).cpu()
         return out
 
-    def _rpn_branch_weights(self, L, g_obj, g_reg, speculative=False):
+    def _rpn_branch_weights(self, L, g_obj, g_reg):
         """First half of the RPN branch: RPN losses -> gradient of the 1x1 head's output -> the weight gradients of the head and of the
         3x3 conv (shared weights: they accumulate over the five levels) and the head's data gradient (with the conv's ReLU backward).
-        Returns that gradient per level -- what the 3x3 conv's data gradient (_rpn_branch_data) starts from.  speculative: the weight
-        gradients go to buffers of their own (whether backward() must overwrite or add to the flat buffer is not known yet)."""
+        Returns that gradient per level -- what the 3x3 conv's data gradient (_rpn_branch_data) starts from."""
         N, P, level_hw = L["N"], L["P"], L["level_hw"]
-        layers = (self.rpn_head, self.rpn_conv)
-        saved = [(c.gw, c.gb) for c in layers]
-        if speculative:
-            if self._spec_grads is None:
-                self._spec_grads = [(torch.zeros_like(c.gw), torch.zeros_like(c.gb)) for c in layers]
-            for c, (gw, gb) in zip(layers, self._spec_grads):
-                c.gw, c.gb = gw, gb
-        acc_saved, self.accumulate_grads = self.accumulate_grads, (False if speculative else self.accumulate_grads)
-        try:
-            ghead_flat = torch.zeros_like(L["head_flat"])
-            if self.loss_mode == "ll":                       # g_obj: the [4, N] per-image scales
-                self._ll_losses(L, gs=g_obj, ghead=ghead_flat, which=(2, 3))
-            else:
-                ops.bce_logits(L["head_flat"], L["obj_idx"], L["obj_lab"], grad=ghead_flat, gscale=g_obj)
-                ops.smooth_l1(L["head_flat"], L["box_idx"], L["rpn_tgt"], 1.0 / 9, L["obj_idx"].numel(), grad=ghead_flat, gscale=g_reg)
-            o, ghs = 0, []
-            for i, (h, w) in enumerate(level_hw):
-                ghs.append(ghead_flat[o:o + L["head_sizes"][i]].view(N, h, w, 16)); o += L["head_sizes"][i]
-                self.rpn_head.bwd(ghs[i], need_dx=False, accumulate=i > 0, x=L["tl"][i])
-                self.rpn_head._count(L["tl"][i], 1)
-            gts_ = ops.conv_group(ghs, self.rpn_head._packed_grad(), masks=L["tl"])       # 1x1 head: data gradient of the five levels + ReLU backward, one launch
-            for i in range(5):
-                self.rpn_conv.bwd(gts_[i], need_dx=False, accumulate=i > 0, x=P[i])
-        finally:
-            self.accumulate_grads = acc_saved
-            for c, (gw, gb) in zip(layers, saved):
-                c.gw, c.gb = gw, gb
+        ghead_flat = torch.zeros_like(L["head_flat"])
+        if self.loss_mode == "ll":                           # g_obj: the [4, N] per-image scales
+            self._ll_losses(L, gs=g_obj, ghead=ghead_flat, which=(2, 3))
+        else:
+            ops.bce_logits(L["head_flat"], L["obj_idx"], L["obj_lab"], grad=ghead_flat, gscale=g_obj)
+            ops.smooth_l1(L["head_flat"], L["box_idx"], L["rpn_tgt"], 1.0 / 9, L["obj_idx"].numel(), grad=ghead_flat, gscale=g_reg)
+        o, ghs = 0, []
+        for i, (h, w) in enumerate(level_hw):
+            ghs.append(ghead_flat[o:o + L["head_sizes"][i]].view(N, h, w, 16)); o += L["head_sizes"][i]
+            self.rpn_head.bwd(ghs[i], need_dx=False, accumulate=i > 0, x=L["tl"][i])
+            self.rpn_head._count(L["tl"][i], 1)
+        gts_ = ops.conv_group(ghs, self.rpn_head._packed_grad(), masks=L["tl"])       # 1x1 head: data gradient of the five levels + ReLU backward, one launch
+        for i in range(5):
+            self.rpn_conv.bwd(gts_[i], need_dx=False, accumulate=i > 0, x=P[i])
         return gts_
 
     def _rpn_branch_data(self, L, gts_):
@@ -878,20 +838,6 @@ class FasterRCNNTrainer(_TrainerBase):
             self.rpn_conv._count(P[i], 1)
         g = ops.conv_group(gts_, self.rpn_conv._packed_grad(), pad=1)       # the five levels in one launch, like the forward
         return g[:4], g[4]
-
-    def _commit_speculative(self):
-        """The speculative weight gradients of the RPN branch become the real ones: moved (or added) into the flat gradient buffer, on
-        the stream that computed them."""
-        st = self.side[0] if self.side is not None else torch.cuda.current_stream(self.dev)
-        with torch.cuda.stream(st):
-            for c, (gw, gb) in zip((self.rpn_head, self.rpn_conv), self._spec_grads):
-                for dst, src in ((c.gw, gw), (c.gb, gb)):
-                    if dst is None:
-                        continue
-                    if self.accumulate_grads:
-                        dst.add_(src)
-                    else:
-                        dst.copy_(src)
 
     # ---- backward ----
     def backward(self, gscale=(1.0, 1.0, 1.0, 1.0), g_pooled=None):
@@ -915,38 +861,24 @@ class FasterRCNNTrainer(_TrainerBase):
         N, R, P, level_hw = L["N"], L["R"], L["P"], L["level_hw"]
         # The box-head branch (predictor -> fc7 -> fc6 -> RoIAlign backward) and the RPN branch meet only at the FPN outputs: the former
         # is issued on the batch-only stream (idle during the backward pass), the latter on the main stream.
-        import contextlib
-        aux, prev = self.aux, ops._WGRAD_CTX[0]
+        aux = self.aux
         main = torch.cuda.current_stream(self.dev)
         if aux is not None:
             aux[0].wait_stream(main)
-        with (torch.cuda.stream(aux[0]) if aux is not None else contextlib.nullcontext()):
-            if aux is not None:
-                ops._WGRAD_CTX[0] = aux[1]
-            try:
-                gpred = torch.zeros_like(L["pred"])
-                if ll:
-                    self._ll_losses(L, gs=gscale, gpred=gpred.view(R, -1), which=(0, 1))
-                else:
-                    ops.softmax_ce(L["pred"].view(R, -1), L["labels"], self.C, grad=gpred, gscale=gscale[0])
-                    ops.smooth_l1(L["pred"], L["pred_idx"], L["box_tgt"], 1.0 / 9, R, grad=gpred, gscale=gscale[1])
-                g7 = self.pred.bwd(gpred, mask=L["f7"])
-                g6 = self.fc7.bwd(g7, mask=L["f6"])
-                groi = self.fc6.bwd(g6)
-                gP_roi = [torch.zeros_like(p) for p in P[:4]]
-                ops.roi_align_bwd_(gP_roi, L["rois"], groi.view(R, 49, -1))
-                self._mark("bwd box head (aux)")
-            finally:
-                ops._WGRAD_CTX[0] = prev
-        spec = L.get("spec")
-        if ll:
-            gts_ = self._rpn_branch_weights(L, gscale, None)
-        elif spec is not None and float(gscale[2]) == 1.0 and float(gscale[3]) == 1.0:
-            self._commit_speculative()
-            gts_ = spec
-        else:
-            gts_ = self._rpn_branch_weights(L, gscale[2], gscale[3])
-        L["spec"] = None
+        with self._aux_stream():
+            gpred = torch.zeros_like(L["pred"])
+            if ll:
+                self._ll_losses(L, gs=gscale, gpred=gpred.view(R, -1), which=(0, 1))
+            else:
+                ops.softmax_ce(L["pred"].view(R, -1), L["labels"], self.C, grad=gpred, gscale=gscale[0])
+                ops.smooth_l1(L["pred"], L["pred_idx"], L["box_tgt"], 1.0 / 9, R, grad=gpred, gscale=gscale[1])
+            g7 = self.pred.bwd(gpred, mask=L["f7"])
+            g6 = self.fc7.bwd(g7, mask=L["f6"])
+            groi = self.fc6.bwd(g6)
+            gP_roi = [torch.zeros_like(p) for p in P[:4]]
+            ops.roi_align_bwd_(gP_roi, L["rois"], groi.view(R, 49, -1))
+            self._mark("bwd box head (aux)")
+        gts_ = self._rpn_branch_weights(L, gscale, None) if ll else self._rpn_branch_weights(L, gscale[2], gscale[3])
         gP, gpool = self._rpn_branch_data(L, gts_)      # on the main stream, beside the box-head branch on the batch-only stream
         self._mark("bwd rpn branch")
         if aux is not None:
@@ -1010,55 +942,48 @@ class RetinaNetTrainer(_TrainerBase):
         u8, rem = self._prepare_images(images)              # on the main stream: the images may have just been produced there
         # Everything that depends on the batch only (ground-truth upload, anchor matching, regression targets) goes first, on its own
         # stream: the device->host copy of the match results then does not wait for the network's kernels.
-        aux, prev = self.aux, ops._WGRAD_CTX[0]
-        import contextlib
-        with (torch.cuda.stream(aux[0]) if aux is not None else contextlib.nullcontext()):
-            if aux is not None:
-                ops._WGRAD_CTX[0] = aux[1]
-            try:
-                u8, rem, Hp, Wp, img_sizes, gts, gt_labels = self._inputs(u8, rem, targets)
-                if any(g.shape[0] == 0 for g in gts):
-                    raise ValueError("RetinaNet training needs at least one ground-truth box per image (retinanet_cal.py:110-124)")
-                level_hw = [(Hp // 8, Wp // 8), (Hp // 16, Wp // 16), (Hp // 32, Wp // 32)]
-                for _ in range(2):                              # P6, P7: 3x3 stride-2 convs with padding 1
-                    level_hw.append(((level_hw[-1][0] - 1) // 2 + 1, (level_hw[-1][1] - 1) // 2 + 1))
-                level_pix = [h * w for h, w in level_hw]
-                cls_sizes, reg_sizes = [N * n * self.cls_ld for n in level_pix], [N * n * 36 for n in level_pix]
-                anchors = self.anchors(Hp, Wp, level_hw)
-                A_tot = anchors.shape[0]
-                matched_dev = torch.empty((N, A_tot), dtype=torch.int32, device=self.dev)
-                for i in range(N):
-                    ops.match(anchors, gts[i], self.cfg["fg"], self.cfg["bg"], True, out=matched_dev[i])
-                matched_all = matched_dev.cpu().numpy()
-                n_gt = [int(g.shape[0]) for g in gts]
-                gt_off = np.cumsum([0] + n_gt)
-                gts_all = torch.cat(gts)
-                lvl_start = np.cumsum([0] + [n * 9 for n in level_pix])
-                reg_off = np.cumsum([0] + reg_sizes)
-                lvl_pix = np.array(level_pix)
-                box_idx, anc_idx, gt_idx, wts, nfg = [], [], [], [], []
-                for i in range(N):
-                    m = matched_all[i]
-                    fg = np.flatnonzero(m >= 0)
-                    l = np.searchsorted(lvl_start, fg, side="right") - 1
-                    rel = fg - lvl_start[l]
-                    pix, a = rel // 9, rel % 9
-                    box_idx.append(reg_off[l] + (i * lvl_pix[l] + pix) * 36 + 4 * a)
-                    anc_idx.append(fg); gt_idx.append(gt_off[i] + m[fg])
-                    nfg.append(len(fg)); wts.append(np.full(len(fg), 1.0 / (max(1, len(fg)) * N), np.float32))
-                box_idx, anc_idx, gt_idx = [np.concatenate(v).astype(np.int64) for v in (box_idx, anc_idx, gt_idx)]
-                packed = torch.from_numpy(np.concatenate([box_idx, anc_idx, gt_idx])).to(self.dev)
-                nb = len(box_idx)
-                box_idx, anc_sel, gt_sel = packed[:nb], packed[nb:2 * nb], packed[2 * nb:]
-                fl = torch.from_numpy(np.concatenate([np.concatenate(wts), np.array([1.0 / (max(1, n) * N) for n in nfg], np.float32)])).to(self.dev)
-                box_w, img_w = fl[:nb], fl[nb:]
-                reg_tgt = ops.box_encode(gts_all[gt_sel], anchors[anc_sel], (1.0, 1.0, 1.0, 1.0))
-                gt_labels_dev = torch.cat(gt_labels).to(self.dev)
-                gt_off_dev = torch.from_numpy(gt_off.astype(np.int32)).to(self.dev)
-            finally:
-                ops._WGRAD_CTX[0] = prev
-        if aux is not None:
-            self._main.wait_stream(aux[0])
+        with self._aux_stream():
+            u8, rem, Hp, Wp, img_sizes, gts, gt_labels = self._inputs(u8, rem, targets)
+            if any(g.shape[0] == 0 for g in gts):
+                raise ValueError("RetinaNet training needs at least one ground-truth box per image (retinanet_cal.py:110-124)")
+            level_hw = [(Hp // 8, Wp // 8), (Hp // 16, Wp // 16), (Hp // 32, Wp // 32)]
+            for _ in range(2):                              # P6, P7: 3x3 stride-2 convs with padding 1
+                level_hw.append(((level_hw[-1][0] - 1) // 2 + 1, (level_hw[-1][1] - 1) // 2 + 1))
+            level_pix = [h * w for h, w in level_hw]
+            cls_sizes, reg_sizes = [N * n * self.cls_ld for n in level_pix], [N * n * 36 for n in level_pix]
+            anchors = self.anchors(Hp, Wp, level_hw)
+            A_tot = anchors.shape[0]
+            matched_dev = torch.empty((N, A_tot), dtype=torch.int32, device=self.dev)
+            for i in range(N):
+                ops.match(anchors, gts[i], self.cfg["fg"], self.cfg["bg"], True, out=matched_dev[i])
+            matched_all = matched_dev.cpu().numpy()
+            n_gt = [int(g.shape[0]) for g in gts]
+            gt_off = np.cumsum([0] + n_gt)
+            gts_all = torch.cat(gts)
+            lvl_start = np.cumsum([0] + [n * 9 for n in level_pix])
+            reg_off = np.cumsum([0] + reg_sizes)
+            lvl_pix = np.array(level_pix)
+            box_idx, anc_idx, gt_idx, wts, nfg = [], [], [], [], []
+            for i in range(N):
+                m = matched_all[i]
+                fg = np.flatnonzero(m >= 0)
+                l = np.searchsorted(lvl_start, fg, side="right") - 1
+                rel = fg - lvl_start[l]
+                pix, a = rel // 9, rel % 9
+                box_idx.append(reg_off[l] + (i * lvl_pix[l] + pix) * 36 + 4 * a)
+                anc_idx.append(fg); gt_idx.append(gt_off[i] + m[fg])
+                nfg.append(len(fg)); wts.append(np.full(len(fg), 1.0 / (max(1, len(fg)) * N), np.float32))
+            box_idx, anc_idx, gt_idx = [np.concatenate(v).astype(np.int64) for v in (box_idx, anc_idx, gt_idx)]
+            packed = torch.from_numpy(np.concatenate([box_idx, anc_idx, gt_idx])).to(self.dev)
+            nb = len(box_idx)
+            box_idx, anc_sel, gt_sel = packed[:nb], packed[nb:2 * nb], packed[2 * nb:]
+            fl = torch.from_numpy(np.concatenate([np.concatenate(wts), np.array([1.0 / (max(1, n) * N) for n in nfg], np.float32)])).to(self.dev)
+            box_w, img_w = fl[:nb], fl[nb:]
+            reg_tgt = ops.box_encode(gts_all[gt_sel], anchors[anc_sel], (1.0, 1.0, 1.0, 1.0))
+            gt_labels_dev = torch.cat(gt_labels).to(self.dev)
+            gt_off_dev = torch.from_numpy(gt_off.astype(np.int32)).to(self.dev)
+        if self.aux is not None:
+            self._main.wait_stream(self.aux[0])
             for t in list(gts) + [gts_all, packed, fl, reg_tgt, matched_dev, gt_labels_dev, gt_off_dev]:
                 t.record_stream(self._main)
         mark("targets")
@@ -1157,6 +1082,26 @@ class RetinaNetTrainer(_TrainerBase):
         return self.grads
 
 
+def _backward_into_grads(net, gscale, **kw):
+    """net.backward(gscale, **kw) under autograd's rules for ``.grad``: a parameter whose .grad is set (no zero_grad since the last
+    backward, or zero_grad(set_to_none=False)) accumulates.  The .grad tensors ARE views of the flat gradient buffer, so accumulation
+    happens inside the kernels; a .grad that is some other tensor, or set on some parameters only, is refused."""
+    mine = [p.grad is not None and p.grad.data_ptr() == net.grads[k].data_ptr() for k, p in net.params.items()]
+    foreign = [k for k, p in net.params.items() if p.grad is not None and p.grad.data_ptr() != net.grads[k].data_ptr()]
+    if foreign:
+        raise RuntimeError("parameter .grad was replaced by another tensor (%s ...): use zero_grad() between steps" % foreign[0])
+    if any(mine) and not all(mine):
+        raise RuntimeError("some parameters carry a gradient and some do not: call zero_grad() on all of them")
+    net.accumulate_grads = all(mine)
+    try:
+        net.backward(gscale, **kw)
+    finally:
+        net.accumulate_grads = False
+    for k in net.names:
+        if net.params[k].grad is None:
+            net.params[k].grad = net.grads[k]
+
+
 class _LossFn(torch.autograd.Function):
     """Bridges the hand-written backward into torch autograd so that the reference's ``losses.backward()`` works unchanged."""
 
@@ -1178,22 +1123,7 @@ class _LossFn(torch.autograd.Function):
             raise RuntimeError("backward() of a training forward after a later forward of the same model: its saved activations "
                                "were replaced; call backward() before the next model(images, targets)")
         gscale = [0.0 if g is None else float(g) for g in gs]
-        # autograd semantics: a parameter whose .grad is set (no zero_grad since the last backward, or zero_grad(set_to_none=False))
-        # accumulates.  The .grad tensors ARE views of the flat gradient buffer, so accumulation happens inside the kernels.
-        mine = [p.grad is not None and p.grad.data_ptr() == net.grads[k].data_ptr() for k, p in net.params.items()]
-        foreign = [k for k, p in net.params.items() if p.grad is not None and p.grad.data_ptr() != net.grads[k].data_ptr()]
-        if foreign:
-            raise RuntimeError("parameter .grad was replaced by another tensor (%s ...): use zero_grad() between steps" % foreign[0])
-        if any(mine) and not all(mine):
-            raise RuntimeError("some parameters carry a gradient and some do not: call zero_grad() on all of them")
-        net.accumulate_grads = all(mine)
-        try:
-            net.backward(gscale)                    # net.last IS this forward's record (the serial check above)
-        finally:
-            net.accumulate_grads = False
-        for k in net.names:
-            if net.params[k].grad is None:
-                net.params[k].grad = net.grads[k]
+        _backward_into_grads(net, gscale)           # net.last IS this forward's record (the serial check above)
         return None, None, None, None
 
 
@@ -1224,20 +1154,7 @@ class _LossFnLL(torch.autograd.Function):
                 zero = torch.zeros(N, dtype=torch.float32, device=net.dev) if zero is None else zero
                 g = zero
             rows.append(g.reshape(N).to(torch.float32))
-        mine = [p.grad is not None and p.grad.data_ptr() == net.grads[k].data_ptr() for k, p in net.params.items()]
-        foreign = [k for k, p in net.params.items() if p.grad is not None and p.grad.data_ptr() != net.grads[k].data_ptr()]
-        if foreign:
-            raise RuntimeError("parameter .grad was replaced by another tensor (%s ...): use zero_grad() between steps" % foreign[0])
-        if any(mine) and not all(mine):
-            raise RuntimeError("some parameters carry a gradient and some do not: call zero_grad() on all of them")
-        net.accumulate_grads = all(mine)
-        try:
-            net.backward(torch.stack(rows), g_pooled=gs[4])
-        finally:
-            net.accumulate_grads = False
-        for k in net.names:
-            if net.params[k].grad is None:
-                net.params[k].grad = net.grads[k]
+        _backward_into_grads(net, torch.stack(rows), g_pooled=gs[4])
         return None, None, None, None
 
 
@@ -1255,7 +1172,6 @@ class TrainableDetector(object):
         return self.net.parameters()
 
     def __call__(self, images, targets):
-        self.net.grad_wanted = torch.is_grad_enabled()
         if getattr(self.net, "loss_mode", None) == "ll":
             out = _LossFnLL.apply(self._anchor, self.net, images, targets)
             pooled = out[4]

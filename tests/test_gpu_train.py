@@ -80,9 +80,9 @@ def test_conv_forward_dgrad_wgrad_vs_autograd(T, case):
 
 
 @pytest.mark.parametrize("hw", [(18, 22), (17, 23), (9, 8)])
-def test_stride2_data_gradient_by_phases(T, hw):
-    """The 3x3 stride-2 data gradient as four phase convolutions on the un-dilated dY + weave (even and odd input sizes), with the
-    FrozenBN scale folded in and the next ReLU's mask applied in the weave == autograd."""
+def test_stride2_data_gradient_with_scale_and_mask(T, hw):
+    """The 3x3 stride-2 data gradient as one convolution on the zero-stuffed dY (even and odd input sizes), with the FrozenBN scale
+    folded into the packed filter and the next ReLU's mask applied in the epilogue == autograd."""
     torch, ops = T
     import torch.nn.functional as F
     H, W = hw
@@ -94,12 +94,12 @@ def test_stride2_data_gradient_by_phases(T, hw):
     y = F.conv2d(xd, w.double(), stride=2, padding=1) * sc.double().view(1, -1, 1, 1)
     gy = torch.randn(y.shape, generator=g)
     y.backward(gy.double())
-    packs = ops.pack_s2_grads(w.cuda(), scale=sc.cuda(), CinK=Cout)
+    pkd = ops.PackedConv(w.cuda(), scale=sc.cuda(), CinK=Cout, mode=1)
     nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().cuda()
-    got = ops.conv_dgrad_s2(nhwc(gy), packs, H, W, mask=nhwc(act))
-    _close(got.permute(0, 3, 1, 2), xd.grad * (act.double() > 0), 2e-5, "stride-2 data gradient by phases")
-    got = ops.conv_dgrad_s2(nhwc(gy), packs, H, W)
-    _close(got.permute(0, 3, 1, 2), xd.grad, 2e-5, "stride-2 data gradient by phases, no mask")
+    got = ops.conv_dgrad(nhwc(gy), pkd, H, W, 2, 1, mask=nhwc(act))
+    _close(got.permute(0, 3, 1, 2), xd.grad * (act.double() > 0), 2e-5, "stride-2 data gradient")
+    got = ops.conv_dgrad(nhwc(gy), pkd, H, W, 2, 1)
+    _close(got.permute(0, 3, 1, 2), xd.grad, 2e-5, "stride-2 data gradient, no mask")
 
 
 def test_epilogue_bn_relu_residual_and_relu_backward(T):
@@ -405,37 +405,6 @@ def test_drop_in_training_loop_updates_like_torch_sgd(T, oracle):
         w = rparams[k].detach()
         err = float((p.detach().double().cpu() - w).abs().max()) / float(w.abs().max())
         assert err <= 1e-5, (k, err)
-
-
-def test_speculative_rpn_branch_equals_the_plain_backward(T):
-    """The RPN branch of the backward pass is enqueued during the forward's RoI-sampling window for unit upstream gradients.  Same
-    losses and the same gradients, bit for bit, as with the speculation off; non-unit upstream gradients fall back to the plain path;
-    a forward under torch.no_grad() does not speculate."""
-    torch, ops = T
-    from cald_amd import train
-    sd, images, targets = _train_case(torch, n_images=3, seed=33)
-    out = {}
-    for spec in (True, False):
-        net = train.FasterRCNNTrainer(sd, 21, min_size=160, max_size=256, box_batch=64, generator=torch.Generator().manual_seed(4))
-        net.speculate = spec
-        losses = net.forward(images, targets)
-        assert (net.last["spec"] is not None) == spec
-        grads = net.backward()
-        torch.cuda.synchronize()
-        out[spec] = ({k: float(v) for k, v in losses.items()}, {k: v.clone() for k, v in grads.items()})
-        if spec:                                            # scaled losses: the speculative result is dropped, the plain path runs
-            net.forward(images, targets)
-            g2 = net.backward((1.0, 1.0, 0.5, 2.0))
-            torch.cuda.synchronize()
-            k = "rpn.head.conv.weight"
-            assert not torch.equal(g2[k], out[True][1][k]) and bool(torch.isfinite(g2[k]).all())
-            model = train.TrainableFasterRCNN(net)
-            with torch.no_grad():
-                model(images, targets)
-            assert net.last["spec"] is None
-    assert out[True][0] == out[False][0]
-    for k in out[True][1]:
-        assert torch.equal(out[True][1][k], out[False][1][k]), k
 
 
 def test_fused_sgd_launch_equals_the_per_tensor_launches(T):

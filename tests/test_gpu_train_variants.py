@@ -371,7 +371,7 @@ SMALL_MAPS = [(1, 1), (1, 2), (2, 3)]
 
 
 def test_conv_entry_points_exact_on_the_smallest_maps(T):
-    """ops.conv (forward with a power-of-two FrozenBN scale and bias), ops.conv_dgrad, ops.conv_dgrad_s2 and ops.conv_group with
+    """ops.conv (forward with a power-of-two FrozenBN scale and bias), ops.conv_dgrad (stride 1 and 2) and ops.conv_group with
     masks, each once per map smaller than its 3 x 3 filter, on exact-integer operands: |sum| <= 2 * 9 * 256 * 4, far inside 2^24."""
     torch, ops = T
     import torch.nn.functional as F
@@ -384,7 +384,7 @@ def test_conv_entry_points_exact_on_the_smallest_maps(T):
     pk = ops.PackedConv(w.cuda(), scale=sc.cuda(), shift=sh.cuda())
     pkb = ops.PackedConv(w.cuda(), bias=b.cuda())
     pkd = ops.PackedConv(w.cuda(), CinK=Cout, mode=1)
-    packs = ops.pack_s2_grads(w.cuda(), scale=sc.cuda(), CinK=Cout)
+    pkd2 = ops.PackedConv(w.cuda(), scale=sc.cuda(), CinK=Cout, mode=1)
     gys, acts = [], []
     for H, W in SMALL_MAPS:
         x = ti(-1, 1, N, Cin, H, W)
@@ -400,8 +400,8 @@ def test_conv_entry_points_exact_on_the_smallest_maps(T):
         g2 = ti(-2, 2, N, Cout, Ho, Wo)
         xd = torch.zeros(N, Cin, H, W, dtype=torch.float64, requires_grad=True)
         (F.conv2d(xd, w.double(), stride=2, padding=1) * sc.double().view(1, -1, 1, 1)).backward(g2.double())
-        _exact(_cpu(ops.conv_dgrad_s2(nhwc(g2), packs, H, W).permute(0, 3, 1, 2)), xd.grad.numpy(), "stride-2 data gradient %dx%d" % (H, W))
-        _exact(_cpu(ops.conv_dgrad_s2(nhwc(g2), packs, H, W, mask=nhwc(act)).permute(0, 3, 1, 2)), (xd.grad * (act > 0)).numpy(), "stride-2 data gradient + mask %dx%d" % (H, W))
+        _exact(_cpu(ops.conv_dgrad(nhwc(g2), pkd2, H, W, 2, 1).permute(0, 3, 1, 2)), xd.grad.numpy(), "stride-2 data gradient %dx%d" % (H, W))
+        _exact(_cpu(ops.conv_dgrad(nhwc(g2), pkd2, H, W, 2, 1, mask=nhwc(act)).permute(0, 3, 1, 2)), (xd.grad * (act > 0)).numpy(), "stride-2 data gradient + mask %dx%d" % (H, W))
     outs = ops.conv_group([nhwc(t) for t in gys], pkd, pad=1, masks=[nhwc(t) for t in acts])
     for o, gy, act, hw in zip(outs, gys, acts, SMALL_MAPS):
         _exact(_cpu(o.permute(0, 3, 1, 2)), (F.conv_transpose2d(gy.double(), w.double(), padding=1) * (act > 0)).numpy(), "grouped data gradient + mask %dx%d" % hw)
@@ -688,9 +688,9 @@ def test_roi_backward_drops_non_finite_gradients(T, roi_case):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. the paths behind the environment switches (read once per process): one fresh child process per setting
 # ---------------------------------------------------------------------------------------------------------------------
-SWITCH_ENV = ("CALD_WGRAD_PW", "CALD_WGRAD_TAB", "CALD_WGRAD_BK", "CALD_WGRAD_TARGET", "CALD_ROI_BWD_FLOAT", "CALD_ROI_BWD_MERGE")
+SWITCH_ENV = ("CALD_WGRAD_PW", "CALD_WGRAD_TAB", "CALD_WGRAD_BK", "CALD_WGRAD_TARGET", "CALD_ROI_BWD_MERGE")
 SWITCH_SETTINGS = [{}, {"CALD_WGRAD_PW": "0"}, {"CALD_WGRAD_TAB": "0"}, {"CALD_WGRAD_BK": "32"}, {"CALD_WGRAD_TARGET": "64"},
-                   {"CALD_WGRAD_TARGET": "4096"}, {"CALD_ROI_BWD_MERGE": "0"}, {"CALD_ROI_BWD_FLOAT": "1"}]
+                   {"CALD_WGRAD_TARGET": "4096"}, {"CALD_ROI_BWD_MERGE": "0"}]
 CHILD_CONV = ["pw_q1_cout1", "pw_ragged", "pw_q1793", "pw_seam", "tab_2x3_map", "tab_s2_odd", "tab_1x1_s2_odd", "tab_ragged_seam",
               "tab_fills_seam", "gen_1x2_map", "gen_j_tail", "gen_cin4_7x7", "gen_s2_odd", "gen_ragged_seam"]
 CHILD_LINEAR = [(513, 64, 256, 1), (200, 49 * 64, 128, 49)]
@@ -722,11 +722,11 @@ def child_main(out_prefix):
 
 
 def test_environment_switch_paths_in_child_processes(T, tmp_path):
-    """CALD_WGRAD_PW=0, CALD_WGRAD_TAB=0, CALD_WGRAD_BK=32, CALD_WGRAD_TARGET=64 / 4096, CALD_ROI_BWD_MERGE=0, CALD_ROI_BWD_FLOAT=1:
+    """CALD_WGRAD_PW=0, CALD_WGRAD_TAB=0, CALD_WGRAD_BK=32, CALD_WGRAD_TARGET=64 / 4096, CALD_ROI_BWD_MERGE=0:
     the library reads each once per process, so each setting gets a fresh child (one after another, stopping at the first failure).
     Every child asserts its exact-integer cases against the integer sums; here the results of every setting must be IDENTICAL to the
     default run's, the plans must show that the switch took effect, the un-merged fixed-point RoI backward must equal the merged one
-    bit for bit, and the float-atomics backward is held to float64 at the 1e-5 rule."""
+    bit for bit, and the default backward is held to float64 at the 1e-5 rule."""
     torch, ops = T
     base = {k: v for k, v in os.environ.items() if k not in SWITCH_ENV}
     res = []
@@ -756,7 +756,6 @@ def test_environment_switch_paths_in_child_processes(T, tmp_path):
     _, grads = _roi_autograd(torch, rois, [np.zeros((2, h, w, 256), np.float32) for h, w in ROI_DIMS], gout)
     off = 0
     for l, g in enumerate(grads):
-        _close(res[7][1][off:off + g.size].reshape(g.shape), g, 1e-5, "float-atomics RoI backward, level %d" % l)
         _close(roi0[off:off + g.size].reshape(g.shape), g, 1e-5, "default RoI backward in the child, level %d" % l)
         off += g.size
 
@@ -785,12 +784,10 @@ VEC_SIZES = [(1, 1), (15, 17), (16, 16), (1, 257)]         # H x W with C = 4, N
 
 
 @pytest.mark.parametrize("hw", VEC_SIZES, ids=str)
-def test_dilate_and_weave_exact(T, hw):
-    """dilate_kernel (stride-2 scatter onto the stride-1 grid, including the extra rows / columns of an even input size) and
-    weave2_kernel (the four phases of a stride-2 data gradient woven into dX, with and without the ReLU mask) against their index
-    rules in numpy, at float4 counts of 1, 255, 256, 257 and at odd and even H, W."""
+def test_dilate_exact(T, hw):
+    """dilate_kernel (stride-2 scatter onto the stride-1 grid, including the extra rows / columns of an even input size) against its
+    index rule in numpy, at float4 counts of 1, 255, 256, 257 and at odd and even H, W."""
     torch, ops = T
-    from cald_amd import _ffi
     for (H, W) in (hw, (hw[1], hw[0]), (hw[0] + 1, hw[1]), (6, 5)):
         rs = np.random.RandomState(H * 1000 + W)
         N, Cc = (1, 4) if (H, W) != (6, 5) else (2, 12)
@@ -799,22 +796,6 @@ def test_dilate_and_weave_exact(T, hw):
         want = np.zeros((N, H, W, Cc), np.float32)
         want[:, ::2, ::2] = g[:, :(H + 1) // 2, :(W + 1) // 2]
         _exact(_cpu(ops.dilate(torch.from_numpy(g).cuda(), 2, H, W)), want, "dilate to %dx%d" % (H, W))
-        # the phases of ops.conv_dgrad_s2: k = 2a + b is a (1 + a) x (1 + b) filter with pad (k > 0) on [Ho][Wo]
-        dims = [(Ho, Wo), (Ho + 2, Wo + 1), (Ho + 1, Wo + 2), (Ho + 1, Wo + 1)]; off = [0, 1, 1, 1]
-        ph = [rs.randint(-9, 10, (N, h, w, Cc)).astype(np.float32) for h, w in dims]
-        mask = rs.randint(-1, 2, (N, H, W, Cc)).astype(np.float32)
-        want = np.zeros((N, H, W, Cc), np.float32)
-        for y in range(H):
-            for x in range(W):
-                k = 2 * (y & 1) + (x & 1); py, px = (y >> 1) + off[k], (x >> 1) + off[k]
-                if py < dims[k][0] and px < dims[k][1]:
-                    want[:, y, x] = ph[k][:, py, px]
-        phc = [torch.from_numpy(p).cuda() for p in ph]
-        for m in (None, mask):
-            out = torch.full((N, H, W, Cc), float("nan"), device="cuda"); mc = torch.from_numpy(m).cuda() if m is not None else None
-            _ffi.check(_ffi.lib().cald_train_weave2(ops._wctx(out), N, H, W, Cc, ops._ptr_array(phc), ops._int_array([v for d in dims for v in d]),
-                                                    ops._int_array(off), ops._p(mc), ops._p(out)))
-            _exact(_cpu(out), want if m is None else want * (mask > 0), "weave2 %dx%d%s" % (H, W, " + mask" if m is not None else ""))
 
 
 @pytest.mark.parametrize("n4", [1, 255, 256, 257])
