@@ -142,6 +142,8 @@ SIGNATURES = {
     "cald_op_noise_stream": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i, c_d, C.POINTER(C.c_void_p)]),
     "cald_op_frcnn_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             C.c_int, c_f, c_f, c_i64, c_f, c_f, c_f, c_i]),
+    "cald_op_retina_postprocess": (C.c_int, [C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f] + [C.c_int] * 6
+                                   + [C.c_float, C.c_float, C.c_int, c_f, c_f, c_i64, c_f, c_f, c_i]),
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),
     "cald_op_conv2d": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),

@@ -523,6 +523,74 @@ extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float*
     return 0;
 }
 
+// RetinaNet.postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the forward (retina.hip
+// retina_cand_kernel / retina_class_nms_kernel / retina_emit_kernel): host arrays in, host arrays out.  The RetinaArgs are filled as
+// forward.hip fills them (cand_cap = power of two >= anchors, min_box 1e-2, det cap K * per_class).  Parity hook for
+// detection/retinanet_cal.py:402-490.
+extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                                          const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                                          float score_thr, float nms_thr, int per_class,
+                                          float* boxes_out, float* scores_out, int64_t* labels_out, float* prob_max_out,
+                                          float* scores_cls_out, int* n_out) {
+    if (!c || !cls || !reg || !level_hw || !base_anchors || !boxes_out || !scores_out || !labels_out || !prob_max_out || !scores_cls_out || !n_out)
+        return fail(CALD_ERR_INVALID, "null argument");
+    if (A < 1 || A > 64 || K < 1 || K > 256 || per_class < 1 || per_class > 1024 || Hp < 1 || Wp < 1 || Hr < 1 || Wr < 1 || Ho < 1 || Wo < 1)
+        return fail(CALD_ERR_INVALID, "bad geometry (1 <= A <= 64, 1 <= K <= 256, 1 <= per_class <= 1024, positive sizes)");
+    long long anchors = 0;
+    for (int l = 0; l < 5; l++) {
+        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
+        if (H < 1 || W < 1 || H > Hp || W > Wp || !cls[l] || !reg[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
+        anchors += (long long)H * W * A;
+    }
+    if (anchors > (1 << 20)) return fail(CALD_ERR_INVALID, "at most %d anchors", 1 << 20);
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    const int maxa = (int)anchors;
+    int cap = 1024; while (cap < maxa) cap <<= 1;
+    BatchPlan P; memset(&P, 0, sizeof(P));      // level 0: the padded input; levels 3..7: P3..P7
+    P.seg[0][0].H = Hp; P.seg[0][0].W = Wp; P.seg[0][1].pix_off = (long long)Hp * Wp;
+    ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
+    RetinaArgs ra; BatchPlan* d_p; ViewDesc* d_vd; float *d_cls[5], *d_reg[5], *d_base;
+    int rc;
+    for (int l = 0; l < 5; l++) {
+        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
+        P.seg[3 + l][0].H = H; P.seg[3 + l][0].W = W; P.seg[3 + l][1].pix_off = (long long)H * W;
+        if ((rc = sd.alloc(&d_cls[l], (size_t)H * W * A * K * 4)) || (rc = sd.alloc(&d_reg[l], (size_t)H * W * A * 16))) return rc;
+        HIPCHK(hipMemcpy(d_cls[l], cls[l], (size_t)H * W * A * K * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_reg[l], reg[l], (size_t)H * W * A * 16, hipMemcpyHostToDevice));
+    }
+    if ((rc = sd.alloc(&d_p, sizeof(BatchPlan))) || (rc = sd.alloc(&d_vd, sizeof(ViewDesc))) || (rc = sd.alloc(&d_base, (size_t)5 * A * 16)) ||
+        (rc = sd.alloc(&ra.cand_count, (size_t)K * 4)) || (rc = sd.alloc(&ra.cand_key, (size_t)K * cap * 8)) || (rc = sd.alloc(&ra.cand_box, (size_t)K * cap * 16)) ||
+        (rc = sd.alloc(&ra.cand_skip, (size_t)K * cap)) || (rc = sd.alloc(&ra.kept_anchor, (size_t)K * per_class * 4)) ||
+        (rc = sd.alloc(&ra.kept_box, (size_t)K * per_class * 16)) || (rc = sd.alloc(&ra.kept_count, (size_t)K * 4))) return rc;
+    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_base, base_anchors, (size_t)5 * A * 16, hipMemcpyHostToDevice));
+    DetBuffers det; if ((rc = alloc_det(det, 1, K * per_class, K))) return rc;
+    for (int l = 0; l < 5; l++) { ra.cls[l] = d_cls[l]; ra.reg[l] = d_reg[l]; ra.seg[l] = d_p->seg[3 + l]; }
+    ra.seg0 = d_p->seg[0]; ra.views = d_vd; ra.base_anchors = d_base;
+    ra.cls_ld = A * K; ra.reg_ld = A * 4; ra.A = A; ra.K = K; ra.V = 1;
+    ra.score_thr = score_thr; ra.nms_thr = nms_thr; ra.min_box = 1e-2f;
+    ra.per_class = per_class; ra.cand_cap = cap; ra.det = det;
+    launch_retina_postprocess(ra, maxa, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    int n = 0;
+    if (e == hipSuccess) e = hipMemcpy(&n, det.count, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (n < 0 || n > K * per_class)) { free_det(det); return fail(CALD_ERR_HIP, "retina postprocess returned %d detections (cap %d)", n, K * per_class); }
+    if (e == hipSuccess && n) {
+        e = hipMemcpy(boxes_out, det.boxes, (size_t)n * 16, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(scores_out, det.scores, (size_t)n * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(labels_out, det.labels, (size_t)n * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(prob_max_out, det.prob_max, (size_t)n * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(scores_cls_out, det.scores_cls, (size_t)n * K * 4, hipMemcpyDeviceToHost);
+    }
+    free_det(det);
+    if (e != hipSuccess) return fail(CALD_ERR_HIP, "retina postprocess failed: %s", hipGetErrorString(e));
+    *n_out = n;
+    return 0;
+}
+
 // MultiScaleRoIAlign(7, sampling_ratio 2) of ONE view on the inference kernels (roi.hip): feats[l] = host [H_l][W_l][C] for the four
 // levels P2..P5 (level_hw = {H0, W0, ..., H3, W3}), rois [R][4] in image coordinates, out [R][49][C] (host).  C == 256 runs the
 // row-walk kernel, other C (multiple of 4) the gather kernel.  Parity hook for detection/frcnn_la.py:205-209.

@@ -286,6 +286,16 @@ int cald_op_frcnn_postprocess(cald_ctx* ctx, int R, int C, const float* logits, 
                               int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max,
                               float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
                               float* scores_cls_out, int* n_out);
+/* RetinaNet.postprocess_detections + the stock GeneralizedRCNNTransform.postprocess of one view (detection/retinanet_cal.py:402-490) on
+ * the forward's own kernels: cls[l] = [H_l][W_l][A*K] logits (channel a*K + k), reg[l] = [H_l][W_l][A*4] deltas for the five levels
+ * P3..P7 (host), level_hw = {H0, W0, ..., H4, W4}, base_anchors [5][A][4], padded size Hp x Wp (anchor strides Hp / H_l, Wp / W_l),
+ * resized size Hr x Wr (clip), original size Ho x Wo.  Outputs (host, K * per_class rows each; scores_cls [K * per_class][K]) in class
+ * order and the number of detections.  per_class <= 1024, at most 2^20 anchors. */
+int cald_op_retina_postprocess(cald_ctx* ctx, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                               const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                               float score_thr, float nms_thr, int per_class,
+                               float* boxes_out, float* scores_out, int64_t* labels_out, float* prob_max_out,
+                               float* scores_cls_out, int* n_out);
 /* MultiScaleRoIAlign(output 7, sampling_ratio 2, aligned=False; detection/frcnn_la.py:205-209) of one view on the forward's own
  * kernels: feats[l] = [H_l][W_l][C] (host) for P2..P5, level_hw = {H0, W0, ..., H3, W3}, rois [R][4]; out [R][49][C] (host) */
 int cald_op_roi_align(cald_ctx* ctx, const float* const* feats, const int* level_hw, int C, int R, const float* rois, float* out);
