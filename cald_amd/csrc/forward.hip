@@ -1,5 +1,5 @@
-// forward.hip -- one forward of the detector over a ragged batch of views: the level plan, the arena layout, the conv launches of every
-// layer (single, fused pair, group, gathered rows of the cut_out reuse), forward_model, cald_forward and cald_debug_tensor.
+// forward.hip -- one forward of the detector over a ragged batch of views: the level plan, each stage's arena layout, the conv launches of every layer
+// (single, fused pair, group, gathered rows of the cut_out reuse), forward_model as a run of named stages (ForwardRun), cald_forward, cald_debug_tensor.
 #include "host.h"
 
 // =============================================================================================
@@ -33,22 +33,132 @@ void cald_host::build_plan(BatchPlan& P, int V, const ViewDesc* views, const int
 }
 static int level_tiles(const BatchPlan& P, int l, int V) { return P.seg[l][V].tile_start; }
 
-struct FwdBufs {
-    float *in0, *c1, *p1, *X[2], *T1, *T2, *D, *Cf[4], *inner[4], *Pf[5], *rpn_h[5];
-    unsigned long long* cand_key; float *cand_box, *sorted_box, *sorted_raw; int* sorted_count;
-    float* proposals; int* prop_count; int* roi_order;
-    float *roi, *f6, *f7, *pr, *prob, *pmax; unsigned long long* keys; float* cbox; int* key_count;
-    // RetinaNet
-    float *ret_t[2][2][5], *cls_h[5], *reg_h[5], *rcand_box, *kept_box; unsigned long long* rcand_key;   // ret_t[tower][ping-pong][level]
-    float* rpn_tl[5];
-    int *cand_count, *kept_anchor, *kept_count; int cand_cap; int max_anchors; unsigned char* cand_skip;
-    unsigned* Pf16[5];   // CALD_PRECISION_F16X3: split twins of the tensors that stay fp32 as well
-    // decision-margin audit (audit.hip): what the RPN / post-processing kernels leave behind for it
-    unsigned long long *next_key, *trunc_key, *kept_key; float* post_maxc;
-    // certified RPN pruning (rpn_prune.hip), levels P2 / P3
-    float *prune_energy[2], *prune_pn[2], *prune_rows[2][2]; int *prune_map[2][2], *prune_nsel[2]; unsigned* prune_p16[2]; unsigned* prune_tau;      // [stage][level] row lists of the two selection stages
-    float* prune_look[2];        // capture mode only: the look-ahead's head map before select / scatter overwrite it
+// ---- arena scratch, one struct per stage of ForwardRun; a stage that does not run is not laid out.  Bump::get rounds every buffer to 256
+// bytes on its own, so the arena's total does not depend on the order of the calls ----
+// split forms (F16X3, h16.h): every tensor whose readers are conv_h3 / conv_h4 layers lives in split form ONLY, in the buffer the fp32
+// tensor would have used (same 4 bytes per element): the pooled stem output, the inner tensors of a bottleneck, the block outputs
+// (read as a GEMM operand by the next block's conv1 / downsample conv / the FPN lateral, and as the residual by conv3's epilogue,
+// which joins hi + lo again), the downsample branch, the laterals (operand of the 3 x 3 output conv, top-down term of the next
+// lateral's epilogue).  22 significant bits instead of 24 on those tensors -- the precision every GEMM operand of this mode has.
+struct SplitReg {
+    cald_model* m; Bump& B; bool on;
+    void only(float* t) { if (on) m->split[t] = {reinterpret_cast<unsigned*>(t), true}; }
+    void both(float* t, unsigned*& twin, size_t n) { if (on) { twin = B.get<unsigned>(n); m->split[t] = {twin, false}; } }      // fp32 and a split twin
 };
+static const int CCH[4] = {256, 512, 1024, 2048};      // channels of C2..C5
+struct BodyBufs {
+    float *in0, *c1, *p1, *X[2], *T1, *T2, *D, *Cf[4];
+    void layout(Bump& B, SplitReg& S, const long long* px) {
+        in0 = B.get<float>(px[0] * 4); c1 = B.get<float>(px[1] * 64); p1 = B.get<float>(px[2] * 64);
+        X[0] = B.get<float>(px[2] * 256); X[1] = B.get<float>(px[2] * 256);
+        T1 = B.get<float>(px[2] * 128); T2 = B.get<float>(px[2] * 64); D = B.get<float>(px[2] * 256);
+        for (int i = 0; i < 4; i++) { Cf[i] = B.get<float>(px[2 + i] * CCH[i]); S.only(Cf[i]); }
+        S.only(p1); S.only(T1); S.only(T2); S.only(X[0]); S.only(X[1]); S.only(D);
+    }
+};
+// Faster R-CNN: four laterals and P2..P6 from level 2.  P2..P5 -> RPN conv (split form) + RoIAlign (fp32): both forms, written by the
+// MFMA-bound 3 x 3 output convs.  P6 is a strided pixel copy of P5 -- a pixel's 1 KB is copied whole, so the copy of the split twin IS the
+// split form of P6 (only the RPN conv reads it).  RetinaNet: three laterals and P3..P7 from level 3.  P3..P5 and P7 feed conv_h3 / conv_h4
+// layers only; P6 is also read through a ReLU by p7 (fp32 input path of conv_h3).  Laterals: split form only.
+struct PyramidBufs {
+    float *inner[4], *Pf[5]; unsigned* Pf16[5];   // CALD_PRECISION_F16X3: split twins of the tensors that stay fp32 as well
+    void layout(Bump& B, SplitReg& S, const long long* px, bool retina) {
+        const int first = retina ? 3 : 2, nl = retina ? 3 : 4;
+        for (int i = 0; i < nl; i++) { inner[i] = B.get<float>(px[first + i] * 256); S.only(inner[i]); }
+        for (int i = 0; i < 5; i++) {
+            Pf[i] = B.get<float>(px[first + i] * 256);
+            if (i == 4 || (retina && i < 3)) S.only(Pf[i]); else S.both(Pf[i], Pf16[i], px[first + i] * 256);
+        }
+    }
+};
+void cald_host::RetinaTailBufs::layout(Bump& B, int V, int K, int per_class, int maxa) {
+    max_anchors = maxa;
+    cand_cap = 1024; while (cand_cap < maxa) cand_cap <<= 1;       // a power of two at least the anchor count
+    cand_count = B.get<int>((size_t)V * K); cand_key = B.get<unsigned long long>((size_t)V * K * cand_cap);
+    cand_box = B.get<float>((size_t)V * K * cand_cap * 4); cand_skip = B.get<unsigned char>((size_t)V * K * cand_cap);
+    kept_anchor = B.get<int>((size_t)V * K * per_class); kept_box = B.get<float>((size_t)V * K * per_class * 4); kept_count = B.get<int>((size_t)V * K);
+}
+struct RetinaBufs {
+    float *ret_t[2][2][5], *cls_h[5], *reg_h[5]; RetinaTailBufs tail;   // ret_t[tower][ping-pong][level]: from matrix-pipe layer to matrix-pipe layer
+    void layout(Bump& B, SplitReg& S, const long long* px, int V, int cls_ld, int K, int per_class, int max_anchors) {
+        for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) { ret_t[h][q][i] = B.get<float>(px[3 + i] * 256); S.only(ret_t[h][q][i]); }
+        for (int i = 0; i < 5; i++) { cls_h[i] = B.get<float>(px[3 + i] * cls_ld); reg_h[i] = B.get<float>(px[3 + i] * 36); }
+        tail.layout(B, V, K, per_class, max_anchors);
+    }
+};
+void cald_host::ProposalBufs::layout(Bump& B, int V) { proposals = B.get<float>((size_t)V * CALD_ROI_CAP * 4); prop_count = B.get<int>(V); }
+struct RpnBufs {
+    float *rpn_tl[5], *rpn_h[5], *cand_box, *sorted_box, *sorted_raw; unsigned long long* cand_key; int* sorted_count; ProposalBufs prop;
+    void layout(Bump& B, const long long* px, int V, int pre) {
+        for (int i = 0; i < 5; i++) { rpn_tl[i] = B.get<float>(px[2 + i] * 256); rpn_h[i] = B.get<float>(px[2 + i] * 15); }
+        cand_key = B.get<unsigned long long>((size_t)V * 5 * pre); cand_box = B.get<float>((size_t)V * 5 * pre * 4);
+        sorted_box = B.get<float>((size_t)V * 5 * pre * 4); sorted_raw = B.get<float>((size_t)V * 5 * pre * 4); sorted_count = B.get<int>(V);
+        prop.layout(B, V);
+    }
+};
+// certified RPN pruning (rpn_prune.hip), levels P2 / P3: f16x3 / pruning-off models do not pay for the scratch
+struct PruneBufs {
+    float *energy[2] = {}, *pn[2] = {}, *rows[2][2] = {}; int *map[2][2] = {}, *nsel[2] = {}; unsigned* p16[2] = {}; unsigned* tau = nullptr;   // [stage][level] row lists of the two selection stages
+    float* look[2] = {};         // capture mode only: the look-ahead's head map before select / scatter overwrite it
+    void layout(Bump& B, const long long* px, int V, bool capture) {
+        for (int i = 0; i < 2; i++) {
+            energy[i] = B.get<float>(px[2 + i] * 4); pn[i] = B.get<float>(px[2 + i]); p16[i] = B.get<unsigned>(px[2 + i] * 256);
+            for (int s2 = 0; s2 < 2; s2++) { rows[s2][i] = B.get<float>(px[2 + i] * 15); map[s2][i] = B.get<int>(px[2 + i]); }
+            if (capture) look[i] = B.get<float>(px[2 + i] * 15);
+        }
+        for (int s2 = 0; s2 < 2; s2++) nsel[s2] = B.get<int>((size_t)2 * V);
+        tau = B.get<unsigned>((size_t)2 * V);
+    }
+};
+void cald_host::RoiBufs::layout(Bump& B, int V, int C) { order = B.get<int>((size_t)V * 1024); roi = B.get<float>((size_t)V * CALD_ROI_CAP * 49 * C); }
+void cald_host::PostBufs::layout(Bump& B, int V, int C, int cap) {
+    key_cap = cap;
+    prob = B.get<float>((size_t)V * CALD_ROI_CAP * C); pmax = B.get<float>((size_t)V * CALD_ROI_CAP);
+    keys = B.get<unsigned long long>((size_t)V * key_cap); cbox = B.get<float>((size_t)V * 2 * key_cap * 4); key_count = B.get<int>(V);
+}
+struct BoxBufs {
+    RoiBufs roi; float *f6, *f7, *pr; PostBufs post;
+    void layout(Bump& B, SplitReg& S, int V, int pred_ld, int C, int key_cap) {
+        roi.layout(B, V, 256);
+        f6 = B.get<float>((size_t)V * CALD_ROI_CAP * 1024); f7 = B.get<float>((size_t)V * CALD_ROI_CAP * 1024);
+        S.only(roi.roi); S.only(f6); S.only(f7);           // RoIAlign -> fc6 -> fc7 -> predictor: conv_h3 layers all the way
+        pr = B.get<float>((size_t)V * CALD_ROI_CAP * pred_ld);
+        post.layout(B, V, C, key_cap);
+    }
+};
+// decision-margin audit (audit.hip): what the RPN / post-processing kernels leave behind for it
+struct AuditBufs {
+    unsigned long long *next_key, *trunc_key, *kept_key; float* post_maxc;
+    void layout(Bump& B, int V, int det_cap) {
+        next_key = B.get<unsigned long long>((size_t)V * 10); trunc_key = B.get<unsigned long long>((size_t)V * 2);
+        kept_key = B.get<unsigned long long>((size_t)V * det_cap); post_maxc = B.get<float>(V);
+    }
+};
+
+RoiArgs cald_host::roi_args(const RoiBufs& S, const float* const* feat, const BatchPlan* plan, int C, int V, const ProposalBufs& P, bool out16) {
+    RoiArgs ro{};
+    for (int i = 0; i < 4; i++) { ro.feat[i] = feat[i]; ro.seg[i] = plan->seg[2 + i]; }
+    ro.C = C; ro.V = V; ro.proposals = P.proposals; ro.prop_count = P.prop_count; ro.out = S.roi; ro.order = S.order; ro.out16 = out16 ? 1 : 0;
+    return ro;
+}
+PostArgs cald_host::post_args(const PostBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views,
+                              float score_thr, float nms_thr, const DetBuffers& det) {
+    PostArgs pa{};
+    pa.pred = pred; pa.pred_ld = pred_ld; pa.C = C; pa.V = V; pa.proposals = P.proposals; pa.prop_count = P.prop_count; pa.views = views; pa.score_thr = score_thr; pa.nms_thr = nms_thr;
+    pa.prob = S.prob; pa.pmax = S.pmax; pa.keys = S.keys; pa.cbox = S.cbox; pa.key_count = S.key_count; pa.key_cap = S.key_cap; pa.det = det;
+    return pa;
+}
+RetinaArgs cald_host::retina_args(const RetinaTailBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
+                                  const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class, const DetBuffers& det) {
+    RetinaArgs ra{};
+    for (int i = 0; i < 5; i++) { ra.cls[i] = cls[i]; ra.reg[i] = reg[i]; ra.seg[i] = plan->seg[3 + i]; }
+    ra.seg0 = plan->seg[0]; ra.views = views; ra.base_anchors = base_anchors;
+    ra.cls_ld = A * K; ra.reg_ld = A * 4; ra.A = A; ra.K = K; ra.V = V; ra.score_thr = score_thr; ra.nms_thr = nms_thr; ra.min_box = 1e-2f;
+    ra.per_class = per_class; ra.cand_cap = S.cand_cap;
+    ra.cand_count = S.cand_count; ra.cand_key = S.cand_key; ra.cand_box = S.cand_box; ra.cand_skip = S.cand_skip;
+    ra.kept_anchor = S.kept_anchor; ra.kept_box = S.kept_box; ra.kept_count = S.kept_count; ra.det = det;
+    return ra;
+}
 
 // conv_stem.hip wants every view's output to be an exact grid of 8 x 16 pixel blocks (padded sizes are multiples of 32); seg: host copy,
 // V + 1 entries
@@ -171,99 +281,6 @@ static int gconv_on(cald_model* m, const ConvLayer& L, const float* in, float* o
     return run_conv(m->ctx, a, 2.0 * ru.rows[b][kind] * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue));
 }
 
-// feat_only: the features-only forward (FwdFeatures) -- nothing behind the pyramid is laid out
-static void fwd_layout(cald_model* m, Bump& B, FwdBufs& F, int V, bool feat_only = false) {
-    const BatchPlan& P = m->plan;
-    const long long px[8] = {level_pix(P, 0, V), level_pix(P, 1, V), level_pix(P, 2, V), level_pix(P, 3, V),
-                             level_pix(P, 4, V), level_pix(P, 5, V), level_pix(P, 6, V), level_pix(P, 7, V)};
-    m->split.clear();
-    static const bool split_on = !(getenv("CALD_H3_S16") && atoi(getenv("CALD_H3_S16")) == 0);
-    const bool sp16 = m->cfg.precision == CALD_PRECISION_F16X3 && split_on;
-    auto both = [&](float* t, unsigned*& twin, size_t n) { if (sp16) { twin = B.get<unsigned>(n); m->split[t] = {twin, false}; } };
-    auto only = [&](float* t) { if (sp16) m->split[t] = {reinterpret_cast<unsigned*>(t), true}; };
-    F.in0 = B.get<float>(px[0] * 4);
-    F.c1 = B.get<float>(px[1] * 64);
-    F.p1 = B.get<float>(px[2] * 64);
-    F.X[0] = B.get<float>(px[2] * 256); F.X[1] = B.get<float>(px[2] * 256);
-    F.T1 = B.get<float>(px[2] * 128); F.T2 = B.get<float>(px[2] * 64); F.D = B.get<float>(px[2] * 256);
-    const int cch[4] = {256, 512, 1024, 2048};
-    for (int i = 0; i < 4; i++) F.Cf[i] = B.get<float>(px[2 + i] * cch[i]);
-    // split forms (F16X3, h16.h): every tensor whose readers are conv_h3 / conv_h4 layers lives in split form ONLY, in the buffer the fp32
-    // tensor would have used (same 4 bytes per element): the pooled stem output, the inner tensors of a bottleneck, the block outputs
-    // (read as a GEMM operand by the next block's conv1 / downsample conv / the FPN lateral, and as the residual by conv3's epilogue,
-    // which joins hi + lo again), the downsample branch, the laterals (operand of the 3 x 3 output conv, top-down term of the next
-    // lateral's epilogue).  22 significant bits instead of 24 on those tensors -- the precision every GEMM operand of this mode has.
-    only(F.p1); only(F.T1); only(F.T2); only(F.X[0]); only(F.X[1]); only(F.D);
-    for (int i = 0; i < 4; i++) only(F.Cf[i]);
-    if (m->cfg.arch == CALD_ARCH_RETINANET) {
-        const int K = m->cfg.num_classes, per = m->cfg.detections_per_img;
-        for (int i = 0; i < 3; i++) F.inner[i] = B.get<float>(px[3 + i] * 256);
-        for (int i = 0; i < 5; i++) F.Pf[i] = B.get<float>(px[3 + i] * 256);
-        if (!feat_only) for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) F.ret_t[h][q][i] = B.get<float>(px[3 + i] * 256);
-        // RetinaNet: laterals, P3..P5 and P7 feed conv_h3 / conv_h4 layers only; P6 is also read through a ReLU by p7 (fp32 input path of
-        // conv_h3); the tower tensors go from matrix-pipe layer to matrix-pipe layer.
-        for (int i = 0; i < 3; i++) only(F.inner[i]);
-        only(F.Pf[0]); only(F.Pf[1]); only(F.Pf[2]); both(F.Pf[3], F.Pf16[3], px[6] * 256); only(F.Pf[4]);
-        if (feat_only) return;
-        for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) only(F.ret_t[h][q][i]);
-        for (int i = 0; i < 5; i++) { F.cls_h[i] = B.get<float>(px[3 + i] * m->cls_out.Cout); F.reg_h[i] = B.get<float>(px[3 + i] * 36); }
-        int maxa = 0;
-        for (int v = 0; v < V; v++) { int t = 0; for (int l = 3; l < 8; l++) t += P.seg[l][v].H * P.seg[l][v].W * 9; if (t > maxa) maxa = t; }
-        int cap = 1024; while (cap < maxa) cap <<= 1;
-        F.max_anchors = maxa; F.cand_cap = cap;
-        F.cand_count = B.get<int>((size_t)V * K);
-        F.rcand_key = B.get<unsigned long long>((size_t)V * K * cap);
-        F.rcand_box = B.get<float>((size_t)V * K * cap * 4);
-        F.cand_skip = B.get<unsigned char>((size_t)V * K * cap);
-        F.kept_anchor = B.get<int>((size_t)V * K * per);
-        F.kept_box = B.get<float>((size_t)V * K * per * 4);
-        F.kept_count = B.get<int>((size_t)V * K);
-        return;
-    }
-    for (int i = 0; i < 4; i++) F.inner[i] = B.get<float>(px[2 + i] * 256);
-    for (int i = 0; i < 5; i++) F.Pf[i] = B.get<float>(px[2 + i] * 256);
-    if (!feat_only) for (int i = 0; i < 5; i++) F.rpn_tl[i] = B.get<float>(px[2 + i] * 256);
-    // Faster R-CNN: P2..P5 -> RPN conv (split form) + RoIAlign (fp32): both forms, written by the MFMA-bound 3 x 3 output convs.  P6 is a
-    // strided pixel copy of P5 -- a pixel's 1 KB is copied whole, so the copy of the split twin IS the split form of P6 (only the RPN
-    // conv reads it).  Laterals: split form only.
-    for (int i = 0; i < 4; i++) only(F.inner[i]);
-    for (int i = 0; i < 4; i++) both(F.Pf[i], F.Pf16[i], px[2 + i] * 256);
-    only(F.Pf[4]);
-    if (feat_only) return;
-    for (int i = 0; i < 5; i++) F.rpn_h[i] = B.get<float>(px[2 + i] * 15);
-    const int pre = m->cfg.rpn_pre_nms_top_n;
-    F.cand_key = B.get<unsigned long long>((size_t)V * 5 * pre);
-    F.cand_box = B.get<float>((size_t)V * 5 * pre * 4);
-    F.sorted_box = B.get<float>((size_t)V * 5 * pre * 4);
-    F.sorted_raw = B.get<float>((size_t)V * 5 * pre * 4);
-    F.sorted_count = B.get<int>(V);
-    F.proposals = B.get<float>((size_t)V * CALD_ROI_CAP * 4);
-    F.prop_count = B.get<int>(V);
-    F.roi_order = B.get<int>((size_t)V * 1024);
-    F.roi = B.get<float>((size_t)V * CALD_ROI_CAP * 12544);
-    F.f6 = B.get<float>((size_t)V * CALD_ROI_CAP * 1024);
-    F.f7 = B.get<float>((size_t)V * CALD_ROI_CAP * 1024);
-    only(F.roi); only(F.f6); only(F.f7);           // RoIAlign -> fc6 -> fc7 -> predictor: conv_h3 layers all the way
-    F.pr = B.get<float>((size_t)V * CALD_ROI_CAP * m->pred.Cout);
-    F.prob = B.get<float>((size_t)V * CALD_ROI_CAP * m->cfg.num_classes);
-    F.pmax = B.get<float>((size_t)V * CALD_ROI_CAP);
-    F.keys = B.get<unsigned long long>((size_t)V * m->key_cap);
-    F.cbox = B.get<float>((size_t)V * 2 * m->key_cap * 4);
-    F.key_count = B.get<int>(V);
-    for (int i = 0; i < 2; i++) {
-        F.prune_energy[i] = F.prune_pn[i] = F.prune_look[i] = nullptr; F.prune_p16[i] = nullptr;
-        for (int s2 = 0; s2 < 2; s2++) { F.prune_rows[s2][i] = nullptr; F.prune_map[s2][i] = nullptr; }
-        if (!m->prune) continue;           // RetinaNet never gets here; f16x3 / pruning-off models do not pay for the scratch
-        F.prune_energy[i] = B.get<float>(px[2 + i] * 4); F.prune_pn[i] = B.get<float>(px[2 + i]); F.prune_p16[i] = B.get<unsigned>(px[2 + i] * 256);
-        for (int s2 = 0; s2 < 2; s2++) { F.prune_rows[s2][i] = B.get<float>(px[2 + i] * 15); F.prune_map[s2][i] = B.get<int>(px[2 + i]); }
-        if (m->prune_capture) F.prune_look[i] = B.get<float>(px[2 + i] * 15);
-    }
-    for (int s2 = 0; s2 < 2; s2++) F.prune_nsel[s2] = m->prune ? B.get<int>((size_t)2 * V) : nullptr;
-    F.prune_tau = m->prune ? B.get<unsigned>((size_t)2 * V) : nullptr;
-    F.next_key = B.get<unsigned long long>((size_t)V * 10); F.trunc_key = B.get<unsigned long long>((size_t)V * 2);
-    F.kept_key = B.get<unsigned long long>((size_t)V * m->det_cap()); F.post_maxc = B.get<float>(V);
-}
-
 __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, unsigned long long* acc) {
     unsigned long long s = 0;
     for (int v = threadIdx.x; v < V; v += 64) s += (unsigned long long)counts[v];
@@ -271,46 +288,73 @@ __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, un
     if (threadIdx.x == 0) atomicAdd(acc, s);
 }
 
-// views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled here.  feat (host.h FwdFeatures): the forward stops after
-// the FPN and hands out the pyramid; `det` is then not used, and pruning, cut_out reuse and the audit do not apply.
-int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
-                             FwdFeatures* feat) {
-    cald_ctx* c = m->ctx;
-    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
-    if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
-    if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
-    if (!feat && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
-    HIPCHK(hipSetDevice(c->device));
-    int hp[CALD_MAX_VIEWS][2];
-    int max_pix0 = 0, max_pix2 = 0, max_pix6 = 0;
-    for (int v = 0; v < V; v++) {
-        ViewDesc& d = views[v];
-        if (!d.src || d.H <= 0 || d.W <= 0 || d.nrect < 0 || d.nrect > CALD_MAX_CUT) return fail(CALD_ERR_INVALID, "view %d is malformed", v);
-        int Hp, Wp;
-        transform_size(d.H, d.W, m->cfg.min_size, m->cfg.max_size, &d.Hr, &d.Wr, &Hp, &Wp);
-        d.Ho = d.H; d.Wo = d.W;
-        if (feat && feat->pad_to) {      // the loader batch's common size (torchvision's ImageList): Hr / Wr stay the view's own, the rest is zero
-            const int Hq = feat->pad_to[v][0], Wq = feat->pad_to[v][1];
-            if (Hq % 32 || Wq % 32 || Hq < Hp || Wq < Wp)
-                return fail(CALD_ERR_INVALID, "view %d: pad_to %d x %d must be a multiple of 32 and at least the view's own %d x %d", v, Hq, Wq, Hp, Wp);
-            Hp = Hq; Wp = Wq;
+static const float RPN_MIN_SIZE = 1e-3f;
+// One forward as a run of named stages (run() chains them).  views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled
+// by prepare().  feat (host.h FwdFeatures): the forward stops after the FPN and hands out the pyramid; `det` is then not used, and pruning,
+// cut_out reuse and the audit do not apply.
+struct ForwardRun {
+    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat;
+    // ---- filled by prepare() ----
+    cald_ctx* c = nullptr; hipStream_t st = nullptr; const BatchPlan* dp = nullptr;
+    bool retina = false, prune = false;
+    int hp[CALD_MAX_VIEWS][2], max_pix0 = 0, max_pix2 = 0, max_pix6 = 0;
+    BodyBufs Fb; PyramidBufs Fp; RetinaBufs Fr; RpnBufs Fn; PruneBufs Fq; BoxBufs Fx; AuditBufs Fa;
+    // the scratch of the stages this forward will run, in their order
+    void layout(Bump& B) {
+        const BatchPlan& P = m->plan; long long px[8];
+        for (int l = 0; l < 8; l++) px[l] = level_pix(P, l, V);
+        m->split.clear();
+        static const bool split_on = !(getenv("CALD_H3_S16") && atoi(getenv("CALD_H3_S16")) == 0);
+        SplitReg S{m, B, m->cfg.precision == CALD_PRECISION_F16X3 && split_on};
+        Fb.layout(B, S, px);
+        Fp.layout(B, S, px, retina);
+        if (feat) return;
+        if (retina) {
+            int maxa = 0;
+            for (int v = 0; v < V; v++) { int t = 0; for (int l = 3; l < 8; l++) t += P.seg[l][v].H * P.seg[l][v].W * 9; if (t > maxa) maxa = t; }
+            Fr.layout(B, S, px, V, m->cls_out.Cout, m->cfg.num_classes, m->cfg.detections_per_img, maxa);
+            return;
         }
-        hp[v][0] = Hp; hp[v][1] = Wp;
-        if (Hp * Wp > max_pix0) max_pix0 = Hp * Wp;
+        Fn.layout(B, px, V, m->cfg.rpn_pre_nms_top_n);
+        if (m->prune) Fq.layout(B, px, V, m->prune_capture);
+        Fx.layout(B, S, V, m->pred.Cout, m->cfg.num_classes, m->key_cap);
+        Fa.layout(B, V, m->det_cap());
     }
-    const bool retina = m->cfg.arch == CALD_ARCH_RETINANET;
-    if (audit_out && (retina || m->cfg.rpn_pre_nms_top_n > 1024 || m->det_cap() > 512))
-        return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit covers Faster R-CNN with rpn_pre_nms_top_n <= 1024 and <= 512 detections per image");
-    build_plan(m->plan, V, views, hp, retina);
-    m->last_V = V; m->last_views.assign(views, views + V);
-    for (int v = 0; v < V; v++) {
-        int p2 = m->plan.seg[2][v].H * m->plan.seg[2][v].W; if (p2 > max_pix2) max_pix2 = p2;
-        int p6 = m->plan.seg[6][v].H * m->plan.seg[6][v].W; if (p6 > max_pix6) max_pix6 = p6;
-    }
-    FwdBufs F;
-    { Bump dry(nullptr, true); fwd_layout(m, dry, F, V, feat != nullptr); int rc = arena_reserve(c, dry.off); if (rc) return rc; }
-    { Bump real(c->arena, false); fwd_layout(m, real, F, V, feat != nullptr); }
-    {
+    // argument checks, the level plan, the arena, the staging-ring copy of plan and views
+    int prepare() {
+        c = m->ctx;
+        if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
+        if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
+        if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
+        if (!feat && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
+        HIPCHK(hipSetDevice(c->device));
+        for (int v = 0; v < V; v++) {
+            ViewDesc& d = views[v];
+            if (!d.src || d.H <= 0 || d.W <= 0 || d.nrect < 0 || d.nrect > CALD_MAX_CUT) return fail(CALD_ERR_INVALID, "view %d is malformed", v);
+            int Hp, Wp;
+            transform_size(d.H, d.W, m->cfg.min_size, m->cfg.max_size, &d.Hr, &d.Wr, &Hp, &Wp);
+            d.Ho = d.H; d.Wo = d.W;
+            if (feat && feat->pad_to) {      // the loader batch's common size (torchvision's ImageList): Hr / Wr stay the view's own, the rest is zero
+                const int Hq = feat->pad_to[v][0], Wq = feat->pad_to[v][1];
+                if (Hq % 32 || Wq % 32 || Hq < Hp || Wq < Wp)
+                    return fail(CALD_ERR_INVALID, "view %d: pad_to %d x %d must be a multiple of 32 and at least the view's own %d x %d", v, Hq, Wq, Hp, Wp);
+                Hp = Hq; Wp = Wq;
+            }
+            hp[v][0] = Hp; hp[v][1] = Wp;
+            if (Hp * Wp > max_pix0) max_pix0 = Hp * Wp;
+        }
+        retina = m->cfg.arch == CALD_ARCH_RETINANET;
+        prune = m->prune && prune_ok;
+        if (audit_out && (retina || m->cfg.rpn_pre_nms_top_n > 1024 || m->det_cap() > 512))
+            return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit covers Faster R-CNN with rpn_pre_nms_top_n <= 1024 and <= 512 detections per image");
+        build_plan(m->plan, V, views, hp, retina);
+        m->last_V = V; m->last_views.assign(views, views + V);
+        for (int v = 0; v < V; v++) {
+            int p2 = m->plan.seg[2][v].H * m->plan.seg[2][v].W; if (p2 > max_pix2) max_pix2 = p2;
+            int p6 = m->plan.seg[6][v].H * m->plan.seg[6][v].W; if (p6 > max_pix6) max_pix6 = p6;
+        }
+        { Bump dry(nullptr, true); layout(dry); int rc = arena_reserve(c, dry.off); if (rc) return rc; }
+        { Bump real(c->arena, false); layout(real); }
         const int si = c->stage_i; c->stage_i = (si + 1) % cald_ctx::NSTAGE;
         HIPCHK(hipEventSynchronize(c->stage_ev[si]));
         memcpy(c->h_stage[si], &m->plan, sizeof(BatchPlan));
@@ -318,154 +362,137 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
         HIPCHK(hipMemcpyAsync(c->d_plan, c->h_stage[si], sizeof(BatchPlan), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipMemcpyAsync(c->d_views, c->h_stage[si] + sizeof(BatchPlan), sizeof(ViewDesc) * V, hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipEventRecord(c->stage_ev[si], c->stream));
+        dp = c->d_plan; st = c->stream;
+        m->dbg.clear();
+        return 0;
     }
-    const BatchPlan* dp = c->d_plan;
-    hipStream_t st = c->stream;
-    int rc;
-    m->dbg.clear();
-
-    // ---- transform + ResNet body (rows A14, A15) ----
-    launch_preprocess(c->d_views, dp->seg[0], F.in0, V, max_pix0, st);
-    m->dbg["input"] = {F.in0, 0, 4, 0};
-    if ((rc = conv_on(m, m->conv1, F.in0, F.c1, 0, 1, V, true))) return rc;
-    m->dbg["conv1"] = {F.c1, 1, 64, 0};
-    launch_maxpool(F.c1, F.p1, dp->seg[1], dp->seg[2], 64, V, max_pix2, st, m->split.count(F.p1) != 0);
-    m->dbg["pool1"] = {F.p1, 2, 64, 0};
-    const float* cur = F.p1; int lvl = 2, layer = 0, xi = 0;
-    for (size_t b = 0; b < m->blocks.size(); b++) {
-        const Bottleneck& B = m->blocks[b];
-        const int lout = lvl + (B.c2.stride == 2 ? 1 : 0);
-        const bool kept = ru && (int)b < ru->nblk;          // cut_out reuse: this block's output is the retained tensor
-        float* dst = kept ? ru->out[b] : (B.layer_end ? F.Cf[layer] : F.X[xi]);
-        const float* idn = cur;
-        if (kept && ru->mode == 2 && ru->gather[layer]) {
-            // the dirty pixels only: T1 on what conv2's windows read, the rest on the dirty set of the output, written over the retained tensor
-            if (B.has_down) { if ((rc = gconv_on(m, B.down, cur, F.D, lvl, lout, V, false, nullptr, *ru, (int)b, 0))) return rc; idn = F.D; }
-            if ((rc = gconv_on(m, B.c1, cur, F.T1, lvl, lvl, V, true, nullptr, *ru, (int)b, 1))) return rc;
-            if ((rc = gconv_on(m, B.c2, F.T1, F.T2, lvl, lout, V, true, nullptr, *ru, (int)b, 0))) return rc;
-            if ((rc = gconv_on(m, B.c3, F.T2, dst, lout, lout, V, true, idn, *ru, (int)b, 0))) return rc;
-        } else {
-            if (B.has_down) { if ((rc = conv_on(m, B.down, cur, F.D, lvl, lout, V, false))) return rc; idn = F.D; }
-            if ((rc = conv_on(m, B.c1, cur, F.T1, lvl, lvl, V, true))) return rc;
-            if ((rc = conv_pair_on(m, B.c2, B.c3, F.T1, F.T2, dst, lvl, lout, V, idn))) return rc;
-        }
-        if (B.layer_end) F.Cf[layer] = dst;
-        cur = dst; lvl = lout;
-        if (B.layer_end) layer++; else xi ^= 1;
+    int dense_block(const Bottleneck& B, const float* cur, float* dst, int lvl, int lout) {
+        int rc; const float* idn = cur;
+        if (B.has_down) { if ((rc = conv_on(m, B.down, cur, Fb.D, lvl, lout, V, false))) return rc; idn = Fb.D; }
+        if ((rc = conv_on(m, B.c1, cur, Fb.T1, lvl, lvl, V, true))) return rc;
+        return conv_pair_on(m, B.c2, B.c3, Fb.T1, Fb.T2, dst, lvl, lout, V, idn);
     }
-    const char* cn[4] = {"C2", "C3", "C4", "C5"};
-    const int cch[4] = {256, 512, 1024, 2048};
-    for (int i = 0; i < 4; i++) m->dbg[cn[i]] = {F.Cf[i], 2 + i, cch[i], 0};
-    if (retina) {
-        // ---- FPN on C3..C5 + LastLevelP6P7 (retinanet_cal.py:618-619) ----
-        if ((rc = conv_on(m, m->fpn_inner[2], F.Cf[3], F.inner[2], 5, 5, V, false))) return rc;
-        for (int i = 1; i >= 0; i--)
-            if ((rc = conv_on(m, m->fpn_inner[i], F.Cf[1 + i], F.inner[i], 3 + i, 3 + i, V, false, nullptr, F.inner[i + 1], 4 + i))) return rc;
-        {
-            ConvSpec sp[3];
-            for (int i = 0; i < 3; i++) sp[i] = {&m->fpn_layer[i], F.inner[i], F.Pf[i], 3 + i, false};
-            if ((rc = conv_group_on(m, sp, 3, V))) return rc;
+    // cut_out reuse, the dirty pixels only: T1 on what conv2's windows read, the rest on the dirty set of the output, written over the retained tensor
+    int gathered_block(const Bottleneck& B, int b, const float* cur, float* dst, int lvl, int lout) {
+        int rc; const float* idn = cur;
+        if (B.has_down) { if ((rc = gconv_on(m, B.down, cur, Fb.D, lvl, lout, V, false, nullptr, *ru, b, 0))) return rc; idn = Fb.D; }
+        if ((rc = gconv_on(m, B.c1, cur, Fb.T1, lvl, lvl, V, true, nullptr, *ru, b, 1))) return rc;
+        if ((rc = gconv_on(m, B.c2, Fb.T1, Fb.T2, lvl, lout, V, true, nullptr, *ru, b, 0))) return rc;
+        return gconv_on(m, B.c3, Fb.T2, dst, lout, lout, V, true, idn, *ru, b, 0);
+    }
+    // transform + ResNet body (rows A14, A15)
+    int body() {
+        int rc;
+        launch_preprocess(c->d_views, dp->seg[0], Fb.in0, V, max_pix0, st);
+        m->dbg["input"] = {Fb.in0, 0, 4, 0};
+        if ((rc = conv_on(m, m->conv1, Fb.in0, Fb.c1, 0, 1, V, true))) return rc;
+        m->dbg["conv1"] = {Fb.c1, 1, 64, 0};
+        launch_maxpool(Fb.c1, Fb.p1, dp->seg[1], dp->seg[2], 64, V, max_pix2, st, m->split.count(Fb.p1) != 0);
+        m->dbg["pool1"] = {Fb.p1, 2, 64, 0};
+        const float* cur = Fb.p1; int lvl = 2, layer = 0, xi = 0;
+        for (size_t b = 0; b < m->blocks.size(); b++) {
+            const Bottleneck& B = m->blocks[b];
+            const int lout = lvl + (B.c2.stride == 2 ? 1 : 0);
+            const bool kept = ru && (int)b < ru->nblk;          // cut_out reuse: this block's output is the retained tensor
+            float* dst = kept ? ru->out[b] : (B.layer_end ? Fb.Cf[layer] : Fb.X[xi]);
+            if ((rc = kept && ru->mode == 2 && ru->gather[layer] ? gathered_block(B, (int)b, cur, dst, lvl, lout) : dense_block(B, cur, dst, lvl, lout))) return rc;
+            if (B.layer_end) Fb.Cf[layer] = dst;
+            cur = dst; lvl = lout;
+            if (B.layer_end) layer++; else xi ^= 1;
         }
-        if ((rc = conv_on(m, m->p6, F.Pf[2], F.Pf[3], 5, 6, V, false))) return rc;
-        const char* pn[5] = {"P3", "P4", "P5", "P6", "P7"};
-        if (feat) {                  // P3..P6, and P7 where the caller pools it
-            const int np = feat->p7 ? 5 : 4;
-            if (feat->p7 && (rc = conv_on(m, m->p7, F.Pf[3], F.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true))) return rc;
-            for (int i = 0; i < np; i++) {
-                m->dbg[pn[i]] = {F.Pf[i], 3 + i, 256, 0};
-                auto sp = m->split.find(F.Pf[i]);
-                feat->P[i] = F.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = 3 + i;
-            }
-            HIPCHK(hipGetLastError());
-            return 0;
+        const char* cn[4] = {"C2", "C3", "C4", "C5"};
+        for (int i = 0; i < 4; i++) m->dbg[cn[i]] = {Fb.Cf[i], 2 + i, CCH[i], 0};
+        return 0;
+    }
+    void name_pyramid(int first, int n) { for (int i = 0; i < n; i++) m->dbg["P" + std::to_string(first + i)] = {Fp.Pf[i], first + i, 256, 0}; }
+    // FPN (row A16) on C2..C5, or on C3..C5 + LastLevelP6P7 (retinanet_cal.py:618-619; a features-only forward runs p7 only where the caller pools it)
+    int fpn() {
+        const int first = retina ? 3 : 2, nl = retina ? 3 : 4, c0 = 4 - nl;      // RetinaNet: Cf[1..3] = C3..C5 -> P3..P5; Faster R-CNN: Cf[0..3] = C2..C5 -> P2..P5
+        int rc; ConvSpec sp[4];
+        if ((rc = conv_on(m, m->fpn_inner[nl - 1], Fb.Cf[3], Fp.inner[nl - 1], 5, 5, V, false))) return rc;
+        for (int i = nl - 2; i >= 0; i--)
+            if ((rc = conv_on(m, m->fpn_inner[i], Fb.Cf[c0 + i], Fp.inner[i], first + i, first + i, V, false, nullptr, Fp.inner[i + 1], first + 1 + i))) return rc;
+        for (int i = 0; i < nl; i++) sp[i] = {&m->fpn_layer[i], Fp.inner[i], Fp.Pf[i], first + i, false};
+        if (prune)                // (Faster R-CNN only) the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
+            for (int i = 0; i < 2; i++) { sp[i].out16 = Fq.p16[i]; sp[i].energy4 = Fq.energy[i]; }
+        if ((rc = conv_group_on(m, sp, nl, V))) return rc;
+        if (!retina) return 0;
+        if ((rc = conv_on(m, m->p6, Fp.Pf[2], Fp.Pf[3], 5, 6, V, false))) return rc;
+        if (feat && !feat->p7) return 0;
+        return conv_on(m, m->p7, Fp.Pf[3], Fp.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true);
+    }
+    // the features-only forward's result: `n` pyramid tensors from plan level `first` (neither LastLevelMaxPool nor a head runs)
+    void hand_out(int first, int n) {
+        name_pyramid(first, n);
+        for (int i = 0; i < n; i++) {
+            auto sp = m->split.find(Fp.Pf[i]);
+            feat->P[i] = Fp.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = first + i;
         }
-        if ((rc = conv_on(m, m->p7, F.Pf[3], F.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true))) return rc;
-        const char* cnm[5] = {"cls0", "cls1", "cls2", "cls3", "cls4"};
-        const char* rnm[5] = {"reg0", "reg1", "reg2", "reg3", "reg4"};
-        for (int i = 0; i < 5; i++) m->dbg[pn[i]] = {F.Pf[i], 3 + i, 256, 0};
-        // ---- heads (retinanet_cal.py:36-241): 4 x (3x3 conv + ReLU) + 3x3 output conv, per level ----
+    }
+    // heads (retinanet_cal.py:36-241): 4 x (3x3 conv + ReLU) + 3x3 output conv, per level; then the tail
+    int retina_head_and_tail() {
+        int rc;
         // both towers x five levels share one launch per tower depth (10 independent problems, weights shared across levels)
         for (int t = 0; t < 4; t++) {
             ConvSpec sp[10];
             for (int hsel = 0; hsel < 2; hsel++)
                 for (int i = 0; i < 5; i++)
-                    sp[hsel * 5 + i] = {&(hsel == 0 ? m->cls_tower : m->reg_tower)[t], t == 0 ? F.Pf[i] : F.ret_t[hsel][(t - 1) & 1][i],
-                                        F.ret_t[hsel][t & 1][i], 3 + i, true};
+                    sp[hsel * 5 + i] = {&(hsel == 0 ? m->cls_tower : m->reg_tower)[t], t == 0 ? Fp.Pf[i] : Fr.ret_t[hsel][(t - 1) & 1][i],
+                                        Fr.ret_t[hsel][t & 1][i], 3 + i, true};
             if ((rc = conv_group_on(m, sp, 10, V))) return rc;
         }
         for (int hsel = 0; hsel < 2; hsel++) {
             ConvSpec sp[5];
-            for (int i = 0; i < 5; i++) sp[i] = {hsel == 0 ? &m->cls_out : &m->reg_out, F.ret_t[hsel][1][i], hsel == 0 ? F.cls_h[i] : F.reg_h[i], 3 + i, false};
+            for (int i = 0; i < 5; i++) sp[i] = {hsel == 0 ? &m->cls_out : &m->reg_out, Fr.ret_t[hsel][1][i], hsel == 0 ? Fr.cls_h[i] : Fr.reg_h[i], 3 + i, false};
             if ((rc = conv_group_on(m, sp, 5, V))) return rc;
         }
         for (int i = 0; i < 5; i++) {
-            m->dbg[cnm[i]] = {F.cls_h[i], 3 + i, m->cls_out.Cout, 0};
-            m->dbg[rnm[i]] = {F.reg_h[i], 3 + i, 36, 0};
+            m->dbg["cls" + std::to_string(i)] = {Fr.cls_h[i], 3 + i, m->cls_out.Cout, 0};
+            m->dbg["reg" + std::to_string(i)] = {Fr.reg_h[i], 3 + i, 36, 0};
         }
-        RetinaArgs ra;
-        for (int i = 0; i < 5; i++) { ra.cls[i] = F.cls_h[i]; ra.reg[i] = F.reg_h[i]; ra.seg[i] = dp->seg[3 + i]; }
-        ra.seg0 = dp->seg[0]; ra.views = c->d_views; ra.base_anchors = m->d_anchors;
-        ra.cls_ld = m->cls_out.Cout; ra.reg_ld = 36; ra.A = 9; ra.K = m->cfg.num_classes; ra.V = V;
-        ra.score_thr = m->cfg.box_score_thresh; ra.nms_thr = m->cfg.box_nms_thresh; ra.min_box = 1e-2f;
-        ra.per_class = m->cfg.detections_per_img; ra.cand_cap = F.cand_cap;
-        ra.cand_count = F.cand_count; ra.cand_key = F.rcand_key; ra.cand_box = F.rcand_box; ra.cand_skip = F.cand_skip;
-        ra.kept_anchor = F.kept_anchor; ra.kept_box = F.kept_box; ra.kept_count = F.kept_count; ra.det = det;
-        launch_retina_postprocess(ra, F.max_anchors, st);
-        HIPCHK(hipGetLastError());
+        launch_retina_postprocess(retina_args(Fr.tail, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
+                                              m->cfg.box_nms_thresh, m->cfg.detections_per_img, det), Fr.tail.max_anchors, st);
         return 0;
     }
-    // ---- FPN (row A16) ----
-    const bool prune = m->prune && prune_ok;
-    if ((rc = conv_on(m, m->fpn_inner[3], F.Cf[3], F.inner[3], 5, 5, V, false))) return rc;
-    for (int i = 2; i >= 0; i--)
-        if ((rc = conv_on(m, m->fpn_inner[i], F.Cf[i], F.inner[i], 2 + i, 2 + i, V, false, nullptr, F.inner[i + 1], 3 + i))) return rc;
-    {
-        ConvSpec sp[4];
-        for (int i = 0; i < 4; i++) sp[i] = {&m->fpn_layer[i], F.inner[i], F.Pf[i], 2 + i, false};
-        if (prune)                // the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
-            for (int i = 0; i < 2; i++) { sp[i].out16 = F.prune_p16[i]; sp[i].energy4 = F.prune_energy[i]; }
-        if ((rc = conv_group_on(m, sp, 4, V))) return rc;
+    // LastLevelMaxPool: max_pool2d(P5, 1, 2) = every other pixel of every other row; in F16X3 the copy runs on P5's split twin
+    void p6_subsample() {
+        auto tw = m->split.find(Fp.Pf[3]);
+        const bool p6_split = m->split.count(Fp.Pf[4]) != 0 && tw != m->split.end();
+        launch_subsample2(p6_split ? reinterpret_cast<const float*>(tw->second.s16) : Fp.Pf[3], Fp.Pf[4], dp->seg[5], dp->seg[6], 256, V, max_pix6, st);
+        name_pyramid(2, 5);
     }
-    if (feat) {                      // P2..P5: neither LastLevelMaxPool nor the RPN runs
-        const char* fn[4] = {"P2", "P3", "P4", "P5"};
-        for (int i = 0; i < 4; i++) {
-            m->dbg[fn[i]] = {F.Pf[i], 2 + i, 256, 0};
-            auto sp = m->split.find(F.Pf[i]);
-            feat->P[i] = F.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = 2 + i;
-        }
-        HIPCHK(hipGetLastError());
+    void name_rpn(int first) { for (int i = first; i < 5; i++) m->dbg["rpn" + std::to_string(i)] = {Fn.rpn_h[i], 2 + i, 15, 0}; }
+    // RPN (row A17): the shared-weight head over the five levels, one launch for the 3x3 conv, one for the fused 1x1 heads
+    int rpn_dense() {
+        int rc; ConvSpec sp[5];
+        for (int i = 0; i < 5; i++) sp[i] = {&m->rpn_conv, Fp.Pf[i], Fn.rpn_tl[i], 2 + i, true};
+        if ((rc = conv_group_on(m, sp, 5, V))) return rc;
+        for (int i = 0; i < 5; i++) sp[i] = {&m->rpn_head, Fn.rpn_tl[i], Fn.rpn_h[i], 2 + i, false};
+        if ((rc = conv_group_on(m, sp, 5, V))) return rc;
+        name_rpn(0);
         return 0;
     }
-    {   // LastLevelMaxPool: max_pool2d(P5, 1, 2) = every other pixel of every other row; in F16X3 the copy runs on P5's split twin
-        auto tw = m->split.find(F.Pf[3]);
-        const bool p6_split = m->split.count(F.Pf[4]) != 0 && tw != m->split.end();
-        launch_subsample2(p6_split ? reinterpret_cast<const float*>(tw->second.s16) : F.Pf[3], F.Pf[4], dp->seg[5], dp->seg[6], 256, V, max_pix6, st);
-    }
-    const char* pn[5] = {"P2", "P3", "P4", "P5", "P6"};
-    for (int i = 0; i < 5; i++) m->dbg[pn[i]] = {F.Pf[i], 2 + i, 256, 0};
-    // ---- RPN (row A17) ----
-    const char* rn[5] = {"rpn0", "rpn1", "rpn2", "rpn3", "rpn4"};
-    if (prune) {
-        // certified pruning (rpn_prune.hip): P2 / P3 first on the fp16 matrix pipe, then exactly at the pixels that can hold one of the
-        // level's pre_nms_top_n anchors; P4..P6 dense as ever.  Same bits at every anchor the top-k can select.
-        ConvSpec sp[5];
+    // certified pruning (rpn_prune.hip): P2 / P3 first on the fp16 matrix pipe, then exactly at the pixels that can hold one of the
+    // level's pre_nms_top_n anchors; P4..P6 dense as ever.  Same bits at every anchor the top-k can select.
+    int rpn_pruned() {
+        int rc; ConvSpec sp[5];
         RpnPruneArgs pr;
         for (int i = 0; i < 2; i++) {
-            pr.seg[i] = dp->seg[2 + i]; pr.energy[i] = F.prune_energy[i]; pr.pnorm[i] = F.prune_pn[i]; pr.head[i] = F.rpn_h[i]; pr.head_out[i] = F.rpn_h[i];
-            for (int s2 = 0; s2 < 2; s2++) { pr.head_rows[s2][i] = F.prune_rows[s2][i]; pr.row_map[s2][i] = F.prune_map[s2][i]; }
+            pr.seg[i] = dp->seg[2 + i]; pr.energy[i] = Fq.energy[i]; pr.pnorm[i] = Fq.pn[i]; pr.head[i] = Fn.rpn_h[i]; pr.head_out[i] = Fn.rpn_h[i];
+            for (int s2 = 0; s2 < 2; s2++) { pr.head_rows[s2][i] = Fq.rows[s2][i]; pr.row_map[s2][i] = Fq.map[s2][i]; }
         }
         int log_slot[2];
         for (int s2 = 0; s2 < 2; s2++) {
             log_slot[s2] = (c->prof && c->prune_log_n < CALD_PRUNE_LOG) ? c->prune_log_n++ : -1;
-            pr.nsel[s2] = F.prune_nsel[s2]; pr.log[s2] = log_slot[s2] >= 0 ? c->d_prune_log + (size_t)log_slot[s2] * 4 : nullptr;
+            pr.nsel[s2] = Fq.nsel[s2]; pr.log[s2] = log_slot[s2] >= 0 ? c->d_prune_log + (size_t)log_slot[s2] * 4 : nullptr;
         }
-        pr.tau_key = F.prune_tau; pr.stat = c->prof ? c->d_prune_stat : nullptr; pr.check = c->d_prune_check;
+        pr.tau_key = Fq.tau; pr.stat = c->prof ? c->d_prune_stat : nullptr; pr.check = c->d_prune_check;
         for (int q = 0; q < 3; q++) { pr.c1[q] = m->prune_c1[q]; pr.c0[q] = m->prune_c0[q]; }
         pr.head_ld = 15; pr.pre_n = m->cfg.rpn_pre_nms_top_n; pr.V = V;
         c->prof_tag_now = 1;
-        for (int i = 0; i < 2; i++) { sp[i] = {&m->rpn_conv16, F.Pf[i], F.rpn_tl[i], 2 + i, true}; sp[i].in16 = F.prune_p16[i]; }
+        for (int i = 0; i < 2; i++) { sp[i] = {&m->rpn_conv16, Fp.Pf[i], Fn.rpn_tl[i], 2 + i, true}; sp[i].in16 = Fq.p16[i]; }
         rc = conv_group_on(m, sp, 2, V);
-        for (int i = 0; i < 2; i++) sp[i] = {&m->rpn_head, F.rpn_tl[i], F.rpn_h[i], 2 + i, false};
+        for (int i = 0; i < 2; i++) sp[i] = {&m->rpn_head, Fn.rpn_tl[i], Fn.rpn_h[i], 2 + i, false};
         if (!rc) rc = conv_group_on(m, sp, 2, V);
         c->prof_tag_now = 0;
         if (rc) return rc;
@@ -474,23 +501,23 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
         const double cap_head[2] = {2.0 * (double)level_pix(m->plan, 2, V) * 256.0 * 15.0, 2.0 * (double)level_pix(m->plan, 3, V) * 256.0 * 15.0};
         if (m->prune_capture)
             for (int i = 0; i < 2; i++) {
-                HIPCHK(hipMemcpyAsync(F.prune_look[i], F.rpn_h[i], (size_t)level_pix(m->plan, 2 + i, V) * 15 * sizeof(float), hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipMemcpyAsync(Fq.look[i], Fn.rpn_h[i], (size_t)level_pix(m->plan, 2 + i, V) * 15 * sizeof(float), hipMemcpyDeviceToDevice, st));
                 const char* ln[2] = {"rpn_look0", "rpn_look1"}; const char* bn[2] = {"rpn_pnorm0", "rpn_pnorm1"};
-                m->dbg[ln[i]] = {F.prune_look[i], 2 + i, 15, 0}; m->dbg[bn[i]] = {F.prune_pn[i], 2 + i, 1, 0};
+                m->dbg[ln[i]] = {Fq.look[i], 2 + i, 15, 0}; m->dbg[bn[i]] = {Fq.pn[i], 2 + i, 1, 0};
             }
         // stage 0 recomputes P2 / P3 rows only; stage 1's launches also carry the dense levels P4..P6
         for (int s2 = 0; s2 < 2; s2++) {
             const int np = s2 == 1 ? 5 : 2;
             launch_rpn_prune_select(pr, max_pix2, s2, st);
-            for (int i = 0; i < np; i++) sp[i] = {&m->rpn_conv, F.Pf[i], F.rpn_tl[i], 2 + i, true};
-            for (int i = 0; i < 2; i++) { sp[i].dyn = F.prune_nsel[s2] + i * V; sp[i].row_map = F.prune_map[s2][i]; }      // gathered rows, compact output
+            for (int i = 0; i < np; i++) sp[i] = {&m->rpn_conv, Fp.Pf[i], Fn.rpn_tl[i], 2 + i, true};
+            for (int i = 0; i < 2; i++) { sp[i].dyn = Fq.nsel[s2] + i * V; sp[i].row_map = Fq.map[s2][i]; }      // gathered rows, compact output
             if ((rc = conv_group_on(m, sp, np, V))) return rc;
             if (c->prof) {
                 for (int i = 0; i < 2; i++) c->prof_prune_flops_cap[i] += cap_conv[i];
                 if (log_slot[s2] >= 0) c->prof_gather[c->prof_launches.size() - 1] = {log_slot[s2], {cap_conv[0], cap_conv[1]}};
             }
-            for (int i = 0; i < np; i++) sp[i] = {&m->rpn_head, F.rpn_tl[i], i < 2 ? F.prune_rows[s2][i] : F.rpn_h[i], 2 + i, false};
-            for (int i = 0; i < 2; i++) sp[i].dyn = F.prune_nsel[s2] + i * V;
+            for (int i = 0; i < np; i++) sp[i] = {&m->rpn_head, Fn.rpn_tl[i], i < 2 ? Fq.rows[s2][i] : Fn.rpn_h[i], 2 + i, false};
+            for (int i = 0; i < 2; i++) sp[i].dyn = Fq.nsel[s2] + i * V;
             if ((rc = conv_group_on(m, sp, np, V))) return rc;
             if (c->prof) {
                 for (int i = 0; i < 2; i++) c->prof_prune_flops_cap[i] += cap_head[i];
@@ -498,68 +525,81 @@ int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuf
             }
         }
         launch_rpn_prune_scatter(pr, st);
-        for (int i = m->prune_capture ? 0 : 2; i < 5; i++) m->dbg[rn[i]] = {F.rpn_h[i], 2 + i, 15, 0};      // (P2 / P3 head maps are exact only where selected, -FLT_MAX elsewhere: a debug view in capture mode only)
-    } else {   // the shared-weight RPN head over the five levels: one launch for the 3x3 conv, one for the fused 1x1 heads
-        ConvSpec sp[5];
-        for (int i = 0; i < 5; i++) sp[i] = {&m->rpn_conv, F.Pf[i], F.rpn_tl[i], 2 + i, true};
-        if ((rc = conv_group_on(m, sp, 5, V))) return rc;
-        for (int i = 0; i < 5; i++) sp[i] = {&m->rpn_head, F.rpn_tl[i], F.rpn_h[i], 2 + i, false};
-        if ((rc = conv_group_on(m, sp, 5, V))) return rc;
-        for (int i = 0; i < 5; i++) m->dbg[rn[i]] = {F.rpn_h[i], 2 + i, 15, 0};
+        name_rpn(m->prune_capture ? 0 : 2);      // (P2 / P3 head maps are exact only where selected, -FLT_MAX elsewhere: a debug view in capture mode only)
+        return 0;
     }
-    RpnArgs ra;
-    for (int i = 0; i < 5; i++) { ra.head[i] = F.rpn_h[i]; ra.seg[i] = dp->seg[2 + i]; }
-    ra.seg0 = dp->seg[0]; ra.views = c->d_views; ra.base_anchors = m->d_anchors;
-    ra.head_ld = 15; ra.A = 3; ra.V = V; ra.pre_n = m->cfg.rpn_pre_nms_top_n; ra.post_n = m->cfg.rpn_post_nms_top_n;
-    ra.nms_thr = m->cfg.rpn_nms_thresh; ra.min_size = 1e-3f;
-    ra.cand_key = F.cand_key; ra.cand_box = F.cand_box; ra.sorted_box = F.sorted_box; ra.sorted_raw = F.sorted_raw;
-    ra.sorted_count = F.sorted_count; ra.proposals = F.proposals; ra.prop_stride = CALD_ROI_CAP; ra.prop_count = F.prop_count;
-    ra.next_key = audit_out ? F.next_key : nullptr; ra.trunc_key = audit_out ? F.trunc_key : nullptr;
-    launch_rpn(ra, st);
-    m->dbg["proposals"] = {F.proposals, 7, 4, 1};
-    // ---- box head (rows A18, A19, A20) ----
-    RoiArgs ro;
-    for (int i = 0; i < 4; i++) { ro.feat[i] = F.Pf[i]; ro.seg[i] = dp->seg[2 + i]; }
-    ro.C = 256; ro.V = V; ro.proposals = F.proposals; ro.prop_count = F.prop_count; ro.out = F.roi; ro.order = F.roi_order;
-    ro.out16 = m->split.count(F.roi) ? 1 : 0;
-    launch_roi_align(ro, st);
-    m->dbg["roi"] = {F.roi, 7, 12544, 1};
-    const double fl_before_roi = c->prof_flops;
-    // The RoI buffers are dense [V][1000][C]; as per-view problems every view pads its 1 000 rows to eight 128-row tiles (2.4 % idle
-    // rows in fc6).  Rows of a GEMM are independent, so the three layers run as ONE problem of V * 1000 rows (level 8: 500 tiles for
-    // 64 views, a tile may straddle two views; segments of 32 views keep byte offsets inside 31 bits).  Rows beyond a view's proposal count hold stale finite-or-not data and are never
-    // read downstream (post-processing walks r < count); the profile counts FLOPs on the measured rows as before.
-    const int Vr = (V + ROI_DENSE_VIEWS - 1) / ROI_DENSE_VIEWS;
-    if ((rc = conv_on(m, m->fc6, F.roi, F.f6, 8, 8, Vr, true))) return rc;
-    if ((rc = conv_on(m, m->fc7, F.f6, F.f7, 8, 8, Vr, true))) return rc;
-    if ((rc = conv_on(m, m->pred, F.f7, F.pr, 8, 8, Vr, false))) return rc;
-    if (c->prof) {
-        hipLaunchKernelGGL(accumulate_rows_kernel, dim3(1), dim3(64), 0, st, F.prop_count, V, c->d_roi_rows);
-        c->prof_roi_rows_cap += (double)V * CALD_ROI_CAP; c->prof_roi_flops_cap += c->prof_flops - fl_before_roi; c->prof_roi_views += V;
+    void proposals() {
+        RpnArgs ra;
+        for (int i = 0; i < 5; i++) { ra.head[i] = Fn.rpn_h[i]; ra.seg[i] = dp->seg[2 + i]; }
+        ra.seg0 = dp->seg[0]; ra.views = c->d_views; ra.base_anchors = m->d_anchors;
+        ra.head_ld = 15; ra.A = 3; ra.V = V; ra.pre_n = m->cfg.rpn_pre_nms_top_n; ra.post_n = m->cfg.rpn_post_nms_top_n;
+        ra.nms_thr = m->cfg.rpn_nms_thresh; ra.min_size = RPN_MIN_SIZE;
+        ra.cand_key = Fn.cand_key; ra.cand_box = Fn.cand_box; ra.sorted_box = Fn.sorted_box; ra.sorted_raw = Fn.sorted_raw;
+        ra.sorted_count = Fn.sorted_count; ra.proposals = Fn.prop.proposals; ra.prop_stride = CALD_ROI_CAP; ra.prop_count = Fn.prop.prop_count;
+        ra.next_key = audit_out ? Fa.next_key : nullptr; ra.trunc_key = audit_out ? Fa.trunc_key : nullptr;
+        launch_rpn(ra, st);
+        m->dbg["proposals"] = {Fn.prop.proposals, 7, 4, 1};
     }
-    m->dbg["fc6"] = {F.f6, 7, 1024, 1}; m->dbg["fc7"] = {F.f7, 7, 1024, 1}; m->dbg["pred"] = {F.pr, 7, m->pred.Cout, 1};
-    PostArgs pa;
-    pa.pred = F.pr; pa.pred_ld = m->pred.Cout; pa.C = m->cfg.num_classes; pa.V = V;
-    pa.proposals = F.proposals; pa.prop_count = F.prop_count; pa.views = c->d_views;
-    pa.score_thr = m->cfg.box_score_thresh; pa.nms_thr = m->cfg.box_nms_thresh;
-    pa.prob = F.prob; pa.pmax = F.pmax; pa.keys = F.keys; pa.cbox = F.cbox; pa.key_count = F.key_count; pa.key_cap = m->key_cap;
-    pa.det = det;
-    pa.kept_key = audit_out ? F.kept_key : nullptr; pa.post_maxc = audit_out ? F.post_maxc : nullptr;
-    launch_frcnn_postprocess(pa, st);
-    if (audit_out) {
+    // box head (rows A18, A19, A20)
+    int box_head() {
+        int rc;
+        launch_roi_align(roi_args(Fx.roi, Fp.Pf, dp, 256, V, Fn.prop, m->split.count(Fx.roi.roi) != 0), st);
+        m->dbg["roi"] = {Fx.roi.roi, 7, 12544, 1};
+        const double fl_before_roi = c->prof_flops;
+        // The RoI buffers are dense [V][1000][C]; as per-view problems every view pads its 1 000 rows to eight 128-row tiles (2.4 % idle
+        // rows in fc6).  Rows of a GEMM are independent, so the three layers run as ONE problem of V * 1000 rows (level 8: 500 tiles for
+        // 64 views, a tile may straddle two views; segments of 32 views keep byte offsets inside 31 bits).  Rows beyond a view's proposal count hold stale finite-or-not data and are never
+        // read downstream (post-processing walks r < count); the profile counts FLOPs on the measured rows as before.
+        const int Vr = (V + ROI_DENSE_VIEWS - 1) / ROI_DENSE_VIEWS;
+        if ((rc = conv_on(m, m->fc6, Fx.roi.roi, Fx.f6, 8, 8, Vr, true))) return rc;
+        if ((rc = conv_on(m, m->fc7, Fx.f6, Fx.f7, 8, 8, Vr, true))) return rc;
+        if ((rc = conv_on(m, m->pred, Fx.f7, Fx.pr, 8, 8, Vr, false))) return rc;
+        if (c->prof) {
+            hipLaunchKernelGGL(accumulate_rows_kernel, dim3(1), dim3(64), 0, st, Fn.prop.prop_count, V, c->d_roi_rows);
+            c->prof_roi_rows_cap += (double)V * CALD_ROI_CAP; c->prof_roi_flops_cap += c->prof_flops - fl_before_roi; c->prof_roi_views += V;
+        }
+        m->dbg["fc6"] = {Fx.f6, 7, 1024, 1}; m->dbg["fc7"] = {Fx.f7, 7, 1024, 1}; m->dbg["pred"] = {Fx.pr, 7, m->pred.Cout, 1};
+        return 0;
+    }
+    void postprocess() {
+        PostArgs pa = post_args(Fx.post, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh, m->cfg.box_nms_thresh, det);
+        pa.kept_key = audit_out ? Fa.kept_key : nullptr; pa.post_maxc = audit_out ? Fa.post_maxc : nullptr;
+        launch_frcnn_postprocess(pa, st);
+    }
+    void audit() {
         AuditArgs au;
-        au.cand_key = F.cand_key; au.cand_box = F.cand_box; au.sorted_box = F.sorted_box; au.flags = reinterpret_cast<const unsigned char*>(F.sorted_raw);
-        au.next_key = F.next_key; au.trunc_key = F.trunc_key; au.pre_n = ra.pre_n; au.post_n = ra.post_n; au.rpn_nms_thr = ra.nms_thr; au.min_size = ra.min_size;
-        au.proposals = F.proposals; au.prop_count = F.prop_count;
+        au.cand_key = Fn.cand_key; au.cand_box = Fn.cand_box; au.sorted_box = Fn.sorted_box; au.flags = reinterpret_cast<const unsigned char*>(Fn.sorted_raw);
+        au.next_key = Fa.next_key; au.trunc_key = Fa.trunc_key; au.pre_n = m->cfg.rpn_pre_nms_top_n; au.post_n = m->cfg.rpn_post_nms_top_n;
+        au.rpn_nms_thr = m->cfg.rpn_nms_thresh; au.min_size = RPN_MIN_SIZE;
+        au.proposals = Fn.prop.proposals; au.prop_count = Fn.prop.prop_count;
         for (int i = 0; i < 4; i++) au.seg[i] = dp->seg[2 + i];
-        au.prob = F.prob; au.pred = F.pr; au.pred_ld = m->pred.Cout; au.C = m->cfg.num_classes; au.views = c->d_views;
-        au.keys = F.keys; au.key_count = F.key_count; au.key_cap = m->key_cap; au.kept_key = F.kept_key; au.post_maxc = F.post_maxc;
-        au.det_count = det.count; au.cap = det.cap; au.score_thr = pa.score_thr; au.post_nms_thr = pa.nms_thr;
+        au.prob = Fx.post.prob; au.pred = Fx.pr; au.pred_ld = m->pred.Cout; au.C = m->cfg.num_classes; au.views = c->d_views;
+        au.keys = Fx.post.keys; au.key_count = Fx.post.key_count; au.key_cap = m->key_cap; au.kept_key = Fa.kept_key; au.post_maxc = Fa.post_maxc;
+        au.det_count = det.count; au.cap = det.cap; au.score_thr = m->cfg.box_score_thresh; au.post_nms_thr = m->cfg.box_nms_thresh;
         au.V = V; au.delta = 1e-2f; au.out = audit_out;
         launch_audit(au, st);
     }
-    HIPCHK(hipGetLastError());
-    return 0;
+    int run() {
+        int rc;
+        if ((rc = prepare()) || (rc = body()) || (rc = fpn())) return rc;
+        if (feat) hand_out(retina ? 3 : 2, retina && feat->p7 ? 5 : 4);
+        else if (retina) { name_pyramid(3, 5); if ((rc = retina_head_and_tail())) return rc; }
+        else {
+            p6_subsample();
+            if ((rc = prune ? rpn_pruned() : rpn_dense())) return rc;
+            proposals();
+            if ((rc = box_head())) return rc;
+            postprocess();
+            if (audit_out) audit();
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
+int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
+                             FwdFeatures* feat) {
+    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat}.run();
 }
 
 static int fill_view(ViewDesc& d, const cald_view& v) {

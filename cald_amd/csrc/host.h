@@ -79,9 +79,17 @@ struct ScopedDev {
     hipStream_t st;
     explicit ScopedDev(hipStream_t s) : st(s) {}
     ~ScopedDev() { if (!ptrs.empty()) { hipStreamSynchronize(st); for (void* p : ptrs) hipFree(p); } }
+    void release() { ptrs.clear(); }      // the caller keeps what was allocated so far
     template <typename T> int alloc(T** out, size_t bytes) {
         HIPCHK(hipMalloc((void**)out, bytes ? bytes : 1));
-        ptrs.push_back(*out);
+        ptrs.push_back((void*)*out);
+        return 0;
+    }
+    template <typename T> int upload(T** out, const void* h, size_t bytes) {      // device copy of a host array (null stays null)
+        *out = nullptr;
+        if (!h) return 0;
+        if (int rc = alloc(out, bytes)) return rc;
+        HIPCHK(hipMemcpy((void*)*out, h, bytes, hipMemcpyHostToDevice));
         return 0;
     }
 };
@@ -189,6 +197,24 @@ struct FwdFeatures {
     // split form only (h16.h), and its level in the plan
     const float* P[5] = {}; bool split_only[5] = {}; int plan_level[5] = {};
 };
+// ---- the tail stages that the forward (forward.hip ForwardRun) and the hooks cald_op_roi_align / _frcnn_postprocess / _retina_postprocess (ops.hip) both run:
+// the stage's scratch, laid out from the sizes alone, and the filler of its kernel arguments.  `plan` / `views` are device pointers. ----
+struct ProposalBufs { float* proposals = nullptr; int* prop_count = nullptr; void layout(Bump& B, int V); };   // RPN -> RoIAlign, post-processing: CALD_ROI_CAP rows a view
+struct RoiBufs { float* roi = nullptr; int* order = nullptr; void layout(Bump& B, int V, int C); };
+struct PostBufs {
+    float *prob = nullptr, *pmax = nullptr, *cbox = nullptr; unsigned long long* keys = nullptr; int* key_count = nullptr; int key_cap = 0;
+    void layout(Bump& B, int V, int C, int key_cap);
+};
+struct RetinaTailBufs {
+    int *cand_count = nullptr, *kept_anchor = nullptr, *kept_count = nullptr, cand_cap = 0, max_anchors = 0; unsigned long long* cand_key = nullptr;
+    float *cand_box = nullptr, *kept_box = nullptr; unsigned char* cand_skip = nullptr;
+    void layout(Bump& B, int V, int K, int per_class, int max_anchors);      // max_anchors: the largest anchor count of a view
+};
+RoiArgs roi_args(const RoiBufs& S, const float* const* feat, const BatchPlan* plan, int C, int V, const ProposalBufs& P, bool out16);
+PostArgs post_args(const PostBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views,
+                   float score_thr, float nms_thr, const DetBuffers& det);
+RetinaArgs retina_args(const RetinaTailBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
+                       const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class, const DetBuffers& det);
 inline size_t cut_plan_set_bytes(int V) { return (size_t)(V + 1) * sizeof(LevelSeg) + (size_t)V * sizeof(GatherSet); }
 inline long long level_pix(const BatchPlan& P, int l, int V) { return P.seg[l][V].pix_off; }
 
@@ -212,4 +238,6 @@ int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, 
 // sweep.hip
 void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);
+// detection buffers that live for one API call
+struct ScopedDet { DetBuffers d{}; ~ScopedDet() { free_det(d); } int alloc(int V, int cap, int C) { return alloc_det(d, V, cap, C); } };
 }  // namespace cald_host

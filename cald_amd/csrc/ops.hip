@@ -42,10 +42,9 @@ static int get_pil(cald_ctx* c, int inSize, int outSize, int fid, PilCoef* out) 
     if (it == c->pil.end()) {
         std::vector<int> b, k;
         PilCoef pc; pc.ksize = pil_coeffs(inSize, outSize, fid, b, k);
-        HIPCHK(hipMalloc((void**)&pc.d_bounds, b.size() * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&pc.d_kk, k.size() * sizeof(int)));
-        HIPCHK(hipMemcpy(pc.d_bounds, b.data(), b.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(pc.d_kk, k.data(), k.size() * sizeof(int), hipMemcpyHostToDevice));
+        ScopedDev sd(c->stream); int rc;
+        if ((rc = sd.upload(&pc.d_bounds, b.data(), b.size() * sizeof(int))) || (rc = sd.upload(&pc.d_kk, k.data(), k.size() * sizeof(int)))) return rc;
+        sd.release();           // both tables exist: the context's cache owns them from here on
         it = c->pil.insert(std::make_pair(key, pc)).first;
     }
     *out = it->second;
@@ -70,12 +69,10 @@ int cald_host::pil_resize(cald_ctx* c, const uint8_t* src, int H, int W, uint8_t
 }
 extern "C" int cald_op_pil_resize(cald_ctx* c, const uint8_t* src_dev, int H, int W, uint8_t* dst_dev, int oh, int ow) {
     if (!c || !src_dev || !dst_dev || H <= 0 || W <= 0 || oh <= 0 || ow <= 0) return fail(CALD_ERR_INVALID, "bad arguments");
-    uint8_t* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, (size_t)H * ow * 3));
-    int rc = pil_resize(c, src_dev, H, W, dst_dev, oh, ow, tmp);
-    hipStreamSynchronize(c->stream);
-    hipFree(tmp);
-    return rc;
+    ScopedDev sd(c->stream);
+    uint8_t* tmp; int rc;
+    if ((rc = sd.alloc(&tmp, (size_t)H * ow * 3))) return rc;
+    return pil_resize(c, src_dev, H, W, dst_dev, oh, ow, tmp);
 }
 
 // One NoiseJob of up to CALD_MAX_NOISE_SEG views drawn in order from one generator, one launch of noise_stream_kernel: what the sweep
@@ -100,11 +97,11 @@ extern "C" int cald_op_noise_stream(cald_ctx* c, uint64_t seed, const uint8_t* s
         } else return fail(CALD_ERR_INVALID, "cald_op_noise_stream: segment %d: kind %d is neither GAUSS nor SALT_PEPPER", g, kinds[g]);
     }
     HIPCHK(hipSetDevice(c->device));
-    NoiseJob* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, sizeof(NoiseJob)));
-    hipError_t e = hipMemcpyAsync(d, &nj, sizeof(nj), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) { launch_noise_stream(d, 1, c->stream); e = hipStreamSynchronize(c->stream); }
-    hipFree(d);
+    ScopedDev sd(c->stream);
+    NoiseJob* d; int rc;
+    if ((rc = sd.upload(&d, &nj, sizeof(nj)))) return rc;
+    launch_noise_stream(d, 1, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(CALD_ERR_HIP, "noise stream failed: %s", hipGetErrorString(e));
     return CALD_OK;
 }
@@ -123,31 +120,29 @@ extern "C" int cald_op_augment(cald_ctx* c, int kind, double param, uint64_t see
     if (!src_dev || !dst_dev) return fail(CALD_ERR_INVALID, "null image pointer");
     HIPCHK(hipSetDevice(c->device));
     const size_t nbytes = (size_t)H * W * 3;
+    ScopedDev sd(c->stream); int rc;
     if (kind == CALD_AUG_GAUSS || kind == CALD_AUG_SALT_PEPPER) {
         void* dsts[1] = {dst_dev};
         return cald_op_noise_stream(c, seed, src_dev, H, W, 1, &kind, &param, dsts);
     }
     if (kind == CALD_AUG_COLOR_ADJUST) {
-        uint8_t* tmp = nullptr;
-        HIPCHK(hipMalloc((void**)&tmp, nbytes + 256));
+        uint8_t* tmp;
+        if ((rc = sd.alloc(&tmp, nbytes + 256))) return rc;
         unsigned long long* lsum = reinterpret_cast<unsigned long long*>(tmp + ((nbytes + 7) & ~(size_t)7));
         launch_color_adjust(src_dev, H, W, (float)param, tmp, lsum, reinterpret_cast<uint8_t*>(dst_dev), c->stream);
-        hipError_t e = hipStreamSynchronize(c->stream);
-        hipFree(tmp);
+        const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(CALD_ERR_HIP, "color adjust failed: %s", hipGetErrorString(e));
         return CALD_OK;
     }
     if (kind == CALD_AUG_ROTATE) {
         if (n_boxes < 0 || (n_boxes && (!boxes || !boxes_out))) return fail(CALD_ERR_INVALID, "rotate: null boxes");
         int fx[6], nh, nw; pil_rotate_setup(H, W, param, fx, &nh, &nw);
-        uint8_t* ws = nullptr;
+        uint8_t* ws;
         const size_t a = ((size_t)nh * nw * 3 + 255) & ~(size_t)255;
-        HIPCHK(hipMalloc((void**)&ws, a + (size_t)nh * W * 3));
+        if ((rc = sd.alloc(&ws, a + (size_t)nh * W * 3))) return rc;
         launch_affine_nearest(src_dev, H, W, ws, nh, nw, fx, c->stream);
-        int rc = pil_resize(c, ws, nh, nw, reinterpret_cast<uint8_t*>(dst_dev), H, W, ws + a, 1);
-        hipError_t e = hipStreamSynchronize(c->stream);
-        hipFree(ws);
-        if (rc) return rc;
+        if ((rc = pil_resize(c, ws, nh, nw, reinterpret_cast<uint8_t*>(dst_dev), H, W, ws + a, 1))) return rc;
+        const hipError_t e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(CALD_ERR_HIP, "rotate failed: %s", hipGetErrorString(e));
         float par[12]; rotate_box_params(H, W, param, nw, nh, par);
         rotate_boxes_host(par, boxes, n_boxes, boxes_out);
@@ -159,6 +154,22 @@ extern "C" int cald_op_augment(cald_ctx* c, int kind, double param, uint64_t see
 // =============================================================================================
 // operator-level entry points
 // =============================================================================================
+// device copies, owned by `sd`, of a layer's packings -- those the caller leaves in `pk`: they decide the kernel launch_conv picks -- and of its
+// epilogue vectors (the first n entries of each, padded with zeros to CoutPad; null: no such term), into the weight and epilogue fields of `a`
+static int upload_layer(ScopedDev& sd, const ConvPack& pk, const float* bias, const float* scale, const float* shift, int n, ConvArgs& a) {
+    int rc;
+    const float* src[3] = {bias, scale, shift}; const float** dst[3] = {&a.bias, &a.scale, &a.shift};
+    for (int i = 0; i < 3; i++) {
+        std::vector<float> v(pk.CoutPad, 0.0f);
+        if (src[i]) std::copy(src[i], src[i] + n, v.begin());
+        if ((rc = sd.upload(dst[i], src[i] ? v.data() : nullptr, v.size() * 4))) return rc;
+    }
+    if ((rc = sd.upload(&a.w, pk.w.data(), pk.w.size() * 4)) || (rc = sd.upload(&a.w4, pk.w4.empty() ? nullptr : pk.w4.data(), pk.w4.size() * 4)) ||
+        (rc = sd.upload(&a.w16, pk.w16.empty() ? nullptr : pk.w16.data(), pk.w16.size() * 2)) ||
+        (rc = sd.upload(&a.wstem, pk.wstem.empty() ? nullptr : pk.wstem.data(), pk.wstem.size() * 4))) return rc;
+    a.w16_unscale = pk.w16_unscale; a.CoutPad = pk.CoutPad; a.Kpad = pk.Kpad;
+    return 0;
+}
 static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
                      int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
                      const float* residual, int relu, float* out) {
@@ -168,47 +179,23 @@ static int op_conv2d(cald_ctx* c, int precision, const float* in, int H, int W, 
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
     ConvPack pk;
     pack_conv({weight}, {Cout}, Cin, Cin, KH, KW, stride, pad, precision == CALD_PRECISION_F16X3, &pk);
-    const int CoutPad = pk.CoutPad, Kpad = pk.Kpad;
-    const std::vector<float>& w = pk.w;
-    std::vector<float> b(CoutPad, 0.0f), sc(CoutPad, 0.0f), sh(CoutPad, 0.0f);
-    for (int i = 0; i < Cout; i++) { if (bias) b[i] = bias[i]; if (bn_scale) { sc[i] = bn_scale[i]; sh[i] = bn_shift[i]; } }
+    pk.wstem.clear();       // this entry point never runs conv_stem.hip
     BatchPlan P; memset(&P, 0, sizeof(P));
     P.seg[0][0].H = H; P.seg[0][0].W = W; P.seg[0][1].pix_off = (long long)H * W; P.seg[0][1].tile_start = (H * W + 127) / 128;
     P.seg[1][0].H = Ho; P.seg[1][0].W = Wo; P.seg[1][1].pix_off = (long long)Ho * Wo; P.seg[1][1].tile_start = (Ho * Wo + 127) / 128;
-    float *d_in, *d_out, *d_w, *d_b, *d_sc, *d_sh, *d_res = nullptr; BatchPlan* d_p;
-    HIPCHK(hipMalloc((void**)&d_in, (size_t)H * W * Cin * 4)); HIPCHK(hipMalloc((void**)&d_out, (size_t)Ho * Wo * Cout * 4));
-    HIPCHK(hipMalloc((void**)&d_w, w.size() * 4)); HIPCHK(hipMalloc((void**)&d_b, b.size() * 4));
-    HIPCHK(hipMalloc((void**)&d_sc, sc.size() * 4)); HIPCHK(hipMalloc((void**)&d_sh, sh.size() * 4));
-    HIPCHK(hipMalloc((void**)&d_p, sizeof(BatchPlan)));
-    HIPCHK(hipMemcpy(d_in, in, (size_t)H * W * Cin * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    float* d_w4 = nullptr;
-    if (!pk.w4.empty()) {
-        HIPCHK(hipMalloc((void**)&d_w4, pk.w4.size() * 4));
-        HIPCHK(hipMemcpy(d_w4, pk.w4.data(), pk.w4.size() * 4, hipMemcpyHostToDevice));
-    }
-    uint16_t* d_w16 = nullptr; const float w16_unscale = pk.w16_unscale;
-    if (!pk.w16.empty()) {
-        HIPCHK(hipMalloc((void**)&d_w16, pk.w16.size() * 2));
-        HIPCHK(hipMemcpy(d_w16, pk.w16.data(), pk.w16.size() * 2, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_sc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_sh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
-    if (residual) { HIPCHK(hipMalloc((void**)&d_res, (size_t)Ho * Wo * Cout * 4)); HIPCHK(hipMemcpy(d_res, residual, (size_t)Ho * Wo * Cout * 4, hipMemcpyHostToDevice)); }
+    ScopedDev sd(c->stream);
     ConvArgs a; memset(&a, 0, sizeof(a));
-    a.in = d_in; a.out = d_out; a.w = d_w; a.w4 = d_w4; a.w16 = d_w16; a.w16_unscale = w16_unscale; a.bias = bias ? d_b : nullptr; a.scale = bn_scale ? d_sc : nullptr; a.shift = bn_scale ? d_sh : nullptr;
-    a.residual = d_res; a.up = nullptr; a.seg_in = d_p->seg[0]; a.seg_out = d_p->seg[1]; a.seg_up = d_p->seg[1]; a.dyn_rows = nullptr;
-    a.V = 1; a.Cin = Cin; a.Cout = Cout; a.CoutPad = CoutPad; a.Kpad = Kpad; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-    a.relu = relu; a.total_mtiles = (Ho * Wo + 127) / 128; a.out_ld = Cout; a.in_relu = 0; a.zeros = c->d_zeros;
+    BatchPlan* d_p; int rc;
+    if ((rc = upload_layer(sd, pk, bias, bn_scale, bn_scale ? bn_shift : nullptr, Cout, a)) || (rc = sd.upload(&a.in, in, (size_t)H * W * Cin * 4)) ||
+        (rc = sd.alloc(&a.out, (size_t)Ho * Wo * Cout * 4)) || (rc = sd.upload(&a.residual, residual, (size_t)Ho * Wo * Cout * 4)) ||
+        (rc = sd.upload(&d_p, &P, sizeof(P)))) return rc;
+    a.seg_in = d_p->seg[0]; a.seg_out = d_p->seg[1]; a.seg_up = d_p->seg[1];
+    a.V = 1; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+    a.relu = relu; a.total_mtiles = (Ho * Wo + 127) / 128; a.out_ld = Cout; a.zeros = c->d_zeros;
     const bool launched = launch_conv(a, c->stream) != nullptr;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, d_out, (size_t)Ho * Wo * Cout * 4, hipMemcpyDeviceToHost));
-    if (d_w4) hipFree(d_w4);
-    if (d_w16) hipFree(d_w16);
-    hipFree(d_in); hipFree(d_out); hipFree(d_w); hipFree(d_b); hipFree(d_sc); hipFree(d_sh); hipFree(d_p); if (d_res) hipFree(d_res);
+    HIPCHK(hipMemcpy(out, a.out, (size_t)Ho * Wo * Cout * 4, hipMemcpyDeviceToHost));
     return launched ? 0 : conv_refused(a);
 }
 extern "C" int cald_op_conv2d(cald_ctx* c, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
@@ -232,13 +219,6 @@ extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* p
     struct Back { void* dev; void* host; size_t bytes; };
     std::vector<Back> back;
     int rc;
-    auto up = [&](const void* h, size_t bytes, void** d) -> int {       // device copy of a host array (null stays null)
-        *d = nullptr;
-        if (!h) return 0;
-        if ((rc = sd.alloc(d, bytes))) return rc;
-        HIPCHK(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
     for (int i = 0; i < n; i++) {
         const cald_conv_probe& p = pr[i];
         if (p.V < 1 || p.V > CALD_PROBE_MAX_VIEWS || p.Cin < 4 || p.Cin % 4 || p.Cout < 1 || p.KH < 1 || p.KW < 1 || p.stride < 1 || p.pad < 0 ||
@@ -283,36 +263,24 @@ extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* p
         const int cin_true = p.cin_true > 0 ? p.cin_true : p.Cin;
         if (cin_true > p.Cin) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: cin_true > Cin");
         pack_conv({p.weight}, {p.Cout}, cin_true, p.Cin, p.KH, p.KW, p.stride, p.pad, precision == CALD_PRECISION_F16X3, &pk);
-        std::vector<float> vb(pk.CoutPad, 0.0f), vs(pk.CoutPad, 0.0f), vh(pk.CoutPad, 0.0f);
-        for (int k = 0; k < p.Cout; k++) { if (p.bias) vb[k] = p.bias[k]; if (p.bn_scale) { vs[k] = p.bn_scale[k]; vh[k] = p.bn_shift[k]; } }
+        if (!stem_grid_exact(so, p.V)) pk.wstem.clear();
         ConvArgs& A = a[i]; memset(&A, 0, sizeof(A));
-        void* d;
+        const LevelSeg* d_seg;
         const size_t out_b = (size_t)p.out_ld * 4;
-        if ((rc = up(pk.w.data(), pk.w.size() * 4, &d))) return rc; A.w = (const float*)d;
-        if ((rc = up(pk.w4.empty() ? nullptr : pk.w4.data(), pk.w4.size() * 4, &d))) return rc; A.w4 = (const float*)d;
-        if ((rc = up(pk.w16.empty() ? nullptr : pk.w16.data(), pk.w16.size() * 2, &d))) return rc; A.w16 = d; A.w16_unscale = pk.w16_unscale;
-        if ((rc = up(pk.wstem.empty() || !stem_grid_exact(so, p.V) ? nullptr : pk.wstem.data(), pk.wstem.size() * 4, &d))) return rc; A.wstem = (const float*)d;
-        if ((rc = up(p.bias ? vb.data() : nullptr, vb.size() * 4, &d))) return rc; A.bias = (const float*)d;
-        if ((rc = up(p.bn_scale ? vs.data() : nullptr, vs.size() * 4, &d))) return rc; A.scale = (const float*)d;
-        if ((rc = up(p.bn_scale ? vh.data() : nullptr, vh.size() * 4, &d))) return rc; A.shift = (const float*)d;
-        if ((rc = up(p.in, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in = (const float*)d;
-        if ((rc = up(p.in16, (size_t)pix_in * p.Cin * 4, &d))) return rc; A.in16 = (const unsigned*)d;
-        if ((rc = up(p.residual, (size_t)rows_out * out_b, &d))) return rc; A.residual = (const float*)d;
-        if ((rc = up(p.up, (size_t)pix_up * out_b, &d))) return rc; A.up = (const float*)d;
-        if ((rc = up(p.mask, (size_t)rows_out * out_b, &d))) return rc; A.mask = (const float*)d;
-        if ((rc = up(p.row_map, (size_t)rows_out * 4, &d))) return rc; A.row_map = (const int*)d;
-        if ((rc = up(p.has_dyn ? p.dyn_rows : nullptr, (size_t)p.V * 4, &d))) return rc; A.dyn_rows = (const int*)d;
-        if ((rc = up(p.gather ? gs.data() : nullptr, gs.size() * sizeof(GatherSet), &d))) return rc; A.gather = (const GatherSet*)d;
-        if ((rc = up(seg.data(), seg.size() * sizeof(LevelSeg), &d))) return rc;
-        A.seg_in = (const LevelSeg*)d; A.seg_out = A.seg_in + CALD_PROBE_MAX_VIEWS + 1; A.seg_up = A.seg_in + 2 * (CALD_PROBE_MAX_VIEWS + 1);
-        if ((rc = up(p.out, (size_t)p.out_n * 4, &d))) return rc; A.out = (float*)d;
-        if (p.out) back.push_back({d, p.out, (size_t)p.out_n * 4});
-        if ((rc = up(p.out16, (size_t)p.out16_n * 4, &d))) return rc; A.out16 = (unsigned*)d;
-        if (p.out16) back.push_back({d, p.out16, (size_t)p.out16_n * 4});
-        if ((rc = up(p.energy4, (size_t)p.energy4_n * 4, &d))) return rc; A.energy4 = (float*)d;
-        if (p.energy4) back.push_back({d, p.energy4, (size_t)p.energy4_n * 4});
+        if ((rc = upload_layer(sd, pk, p.bias, p.bn_scale, p.bn_scale ? p.bn_shift : nullptr, p.Cout, A)) ||
+            (rc = sd.upload(&A.in, p.in, (size_t)pix_in * p.Cin * 4)) || (rc = sd.upload(&A.in16, p.in16, (size_t)pix_in * p.Cin * 4)) ||
+            (rc = sd.upload(&A.residual, p.residual, (size_t)rows_out * out_b)) || (rc = sd.upload(&A.up, p.up, (size_t)pix_up * out_b)) ||
+            (rc = sd.upload(&A.mask, p.mask, (size_t)rows_out * out_b)) || (rc = sd.upload(&A.row_map, p.row_map, (size_t)rows_out * 4)) ||
+            (rc = sd.upload(&A.dyn_rows, p.has_dyn ? p.dyn_rows : nullptr, (size_t)p.V * 4)) ||
+            (rc = sd.upload(&A.gather, p.gather ? gs.data() : nullptr, gs.size() * sizeof(GatherSet))) ||
+            (rc = sd.upload(&d_seg, seg.data(), seg.size() * sizeof(LevelSeg))) || (rc = sd.upload(&A.out, p.out, (size_t)p.out_n * 4)) ||
+            (rc = sd.upload(&A.out16, p.out16, (size_t)p.out16_n * 4)) || (rc = sd.upload(&A.energy4, p.energy4, (size_t)p.energy4_n * 4))) return rc;
+        A.seg_in = d_seg; A.seg_out = d_seg + CALD_PROBE_MAX_VIEWS + 1; A.seg_up = d_seg + 2 * (CALD_PROBE_MAX_VIEWS + 1);
+        if (p.out) back.push_back({A.out, p.out, (size_t)p.out_n * 4});
+        if (p.out16) back.push_back({A.out16, p.out16, (size_t)p.out16_n * 4});
+        if (p.energy4) back.push_back({A.energy4, p.energy4, (size_t)p.energy4_n * 4});
         A.ex16 = p.ex16 ? 1 : 0;
-        A.V = p.V; A.Cin = p.Cin; A.Cout = p.Cout; A.CoutPad = pk.CoutPad; A.Kpad = pk.Kpad;
+        A.V = p.V; A.Cin = p.Cin; A.Cout = p.Cout;
         A.KH = p.KH; A.KW = p.KW; A.stride = p.stride; A.pad = p.pad; A.relu = p.relu ? 1 : 0; A.in_relu = p.in_relu ? 1 : 0;
         A.total_mtiles = so[p.V].tile_start; A.out_ld = p.out_ld; A.zeros = c->d_zeros;
     }
@@ -337,18 +305,13 @@ void launch_mfma_f16_probe(const unsigned short* A, const unsigned short* B, con
 extern "C" int cald_op_mfma_f16(cald_ctx* c, const uint16_t* A, const uint16_t* B, const uint32_t* C, uint32_t* D, int64_t n) {
     if (!c || !A || !B || !C || !D || n < 1) return fail(CALD_ERR_INVALID, "cald_op_mfma_f16: null argument or n < 1");
     HIPCHK(hipSetDevice(c->device));
-    struct Bufs {       // freed on every exit path
-        void* p[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Bufs() { for (void* q : p) if (q) hipFree(q); }
-    } d;
-    HIPCHK(hipMalloc(&d.p[0], (size_t)n * 32)); HIPCHK(hipMalloc(&d.p[1], (size_t)n * 32));
-    HIPCHK(hipMalloc(&d.p[2], (size_t)n * 4)); HIPCHK(hipMalloc(&d.p[3], (size_t)n * 4));
-    HIPCHK(hipMemcpyAsync(d.p[0], A, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d.p[1], B, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d.p[2], C, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-    launch_mfma_f16_probe((const unsigned short*)d.p[0], (const unsigned short*)d.p[1], (const unsigned*)d.p[2], (unsigned*)d.p[3], (long long)n, c->stream);
+    ScopedDev sd(c->stream);
+    const unsigned short *dA, *dB; const unsigned* dC; unsigned* dD; int rc;
+    if ((rc = sd.upload(&dA, A, (size_t)n * 32)) || (rc = sd.upload(&dB, B, (size_t)n * 32)) || (rc = sd.upload(&dC, C, (size_t)n * 4)) ||
+        (rc = sd.alloc(&dD, (size_t)n * 4))) return rc;
+    launch_mfma_f16_probe(dA, dB, dC, dD, (long long)n, c->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(D, d.p[3], (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(D, dD, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -374,39 +337,32 @@ extern "C" int cald_op_conv_bench(cald_ctx* c, int V, int H, int W, int Cin, int
     if (Cin % 4) return fail(CALD_ERR_INVALID, "Cin must be a multiple of 4");
     HIPCHK(hipSetDevice(c->device));
     const int KW = KH, Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    const int CoutPad = cout_pad(Cout), K = KH * KW * Cin, Kpad = round_up(K, 16);
-    std::vector<float> w((size_t)Kpad * CoutPad, 0.0f), b(CoutPad, 0.1f), sc(CoutPad, 1.0f), sh(CoutPad, 0.01f);
+    const int K = KH * KW * Cin;
+    ConvPack pk; pk.CoutPad = cout_pad(Cout); pk.Kpad = round_up(K, 16);
+    const int CoutPad = pk.CoutPad, Kpad = pk.Kpad;
+    pk.w.assign((size_t)Kpad * CoutPad, 0.0f);
+    const std::vector<float> b(CoutPad, 0.1f), sc(CoutPad, 1.0f), sh(CoutPad, 0.01f);
     unsigned r = 12345u;
-    for (int k = 0; k < K; k++) for (int n = 0; n < Cout; n++) { r = r * 1664525u + 1013904223u; w[(size_t)k * CoutPad + n] = ((float)(r >> 8) / 8388608.0f - 1.0f) * 0.05f; }
+    for (int k = 0; k < K; k++) for (int n = 0; n < Cout; n++) { r = r * 1664525u + 1013904223u; pk.w[(size_t)k * CoutPad + n] = ((float)(r >> 8) / 8388608.0f - 1.0f) * 0.05f; }
+    if (CoutPad % 64 == 0 && ((Cin % 16 == 0 && KH * KW <= 32) || Cin == 4)) pk.w4 = pack_w4(pk.w, Kpad, CoutPad);
     BatchPlan P; memset(&P, 0, sizeof(P));
     for (int v = 0; v <= V; v++) {
         P.seg[0][v].pix_off = (long long)v * H * W; P.seg[0][v].tile_start = v * ((H * W + 127) / 128); P.seg[0][v].H = H; P.seg[0][v].W = W;
         P.seg[1][v].pix_off = (long long)v * Ho * Wo; P.seg[1][v].tile_start = v * ((Ho * Wo + 127) / 128); P.seg[1][v].H = Ho; P.seg[1][v].W = Wo;
     }
     ScopedDev sd(c->stream);
-    float *d_in, *d_out, *d_w, *d_w4 = nullptr, *d_b, *d_sc, *d_sh, *d_res = nullptr; BatchPlan* d_p;
+    float *d_in, *d_out, *d_res = nullptr; BatchPlan* d_p;
     const size_t n_in = (size_t)V * H * W * Cin, n_out = (size_t)V * Ho * Wo * Cout;
+    ConvArgs a[CALD_MAX_GROUP]; memset(a, 0, sizeof(a));
     int rc;
-    if ((rc = sd.alloc(&d_in, n_in * 4)) || (rc = sd.alloc(&d_out, n_out * 4 * group)) || (rc = sd.alloc(&d_w, w.size() * 4)) || (rc = sd.alloc(&d_b, b.size() * 4)) ||
-        (rc = sd.alloc(&d_sc, sc.size() * 4)) || (rc = sd.alloc(&d_sh, sh.size() * 4)) || (rc = sd.alloc(&d_p, sizeof(BatchPlan)))) return rc;
+    if ((rc = sd.alloc(&d_in, n_in * 4)) || (rc = sd.alloc(&d_out, n_out * 4 * group)) || (rc = upload_layer(sd, pk, b.data(), sc.data(), sh.data(), CoutPad, a[0])) ||
+        (rc = sd.upload(&d_p, &P, sizeof(P)))) return rc;
     if (residual && (rc = sd.alloc(&d_res, n_out * 4))) return rc;
     hipLaunchKernelGGL(fill_random_kernel, dim3(4096), dim3(256), 0, c->stream, d_in, (long long)n_in, 1u);
     if (d_res) hipLaunchKernelGGL(fill_random_kernel, dim3(4096), dim3(256), 0, c->stream, d_res, (long long)n_out, 2u);
-    HIPCHK(hipMemcpy(d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice));
-    if (CoutPad % 64 == 0 && ((Cin % 16 == 0 && KH * KW <= 32) || Cin == 4)) {
-        std::vector<float> w4 = pack_w4(w, Kpad, CoutPad);
-        if ((rc = sd.alloc(&d_w4, w4.size() * 4))) return rc;
-        HIPCHK(hipMemcpy(d_w4, w4.data(), w4.size() * 4, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(d_b, b.data(), b.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_sc, sc.data(), sc.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_sh, sh.data(), sh.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
-    ConvArgs a[CALD_MAX_GROUP];
-    for (int gi = 0; gi < group; gi++) {
-        memset(&a[gi], 0, sizeof(ConvArgs));
-        a[gi].in = d_in; a[gi].out = d_out + (size_t)gi * n_out; a[gi].w = d_w; a[gi].w4 = d_w4; a[gi].bias = d_b; a[gi].scale = d_sc; a[gi].shift = d_sh; a[gi].residual = d_res;
-        a[gi].seg_in = d_p->seg[0]; a[gi].seg_out = d_p->seg[1]; a[gi].seg_up = d_p->seg[1]; a[gi].V = V; a[gi].Cin = Cin; a[gi].Cout = Cout; a[gi].CoutPad = CoutPad; a[gi].Kpad = Kpad;
-        a[gi].KH = KH; a[gi].KW = KW; a[gi].stride = stride; a[gi].pad = pad; a[gi].relu = relu; a[gi].total_mtiles = V * ((Ho * Wo + 127) / 128); a[gi].out_ld = Cout; a[gi].zeros = c->d_zeros;
-    }
+    a[0].in = d_in; a[0].residual = d_res; a[0].seg_in = d_p->seg[0]; a[0].seg_out = d_p->seg[1]; a[0].seg_up = d_p->seg[1]; a[0].V = V; a[0].Cin = Cin; a[0].Cout = Cout;
+    a[0].KH = KH; a[0].KW = KW; a[0].stride = stride; a[0].pad = pad; a[0].relu = relu; a[0].total_mtiles = V * ((Ho * Wo + 127) / 128); a[0].out_ld = Cout; a[0].zeros = c->d_zeros;
+    for (int gi = 0; gi < group; gi++) { a[gi] = a[0]; a[gi].out = d_out + (size_t)gi * n_out; }
     auto launch = [&]() { if (group > 1) launch_conv_group(a, group, c->stream); else launch_conv(a[0], c->stream); };
     launch(); launch();
     HIPCHK(hipGetLastError());
@@ -443,7 +399,9 @@ extern "C" int cald_op_consistency(cald_ctx* c, int N, const float* aug_box, con
     if (N > 50) return fail(CALD_ERR_INVALID, "at most 50 reference boxes (cald_train.py:110-113)");
     HIPCHK(hipSetDevice(c->device));
     const int cap = (N > M ? N : M) > 0 ? (N > M ? N : M) : 1;
-    DetBuffers d; int rc = alloc_det(d, 2, cap, C); if (rc) return rc;
+    ScopedDev sd(c->stream); ScopedDet sdet;
+    int rc = sdet.alloc(2, cap, C); if (rc) return rc;
+    const DetBuffers& d = sdet.d;
     if (N) {
         HIPCHK(hipMemcpy(d.boxes, aug_box, (size_t)N * 16, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(d.scores_cls, ref_scores_cls, (size_t)N * C * 4, hipMemcpyHostToDevice));
@@ -461,8 +419,7 @@ extern "C" int cald_op_consistency(cald_ctx* c, int N, const float* aug_box, con
     for (int i = 0; i < 50; i++) h[4 + i] = i;
     h[54] = N;
     int* dh; float* dpar; float* dcons;
-    HIPCHK(hipMalloc((void**)&dh, sizeof(h))); HIPCHK(hipMalloc((void**)&dpar, 48)); HIPCHK(hipMalloc((void**)&dcons, 4));
-    HIPCHK(hipMemcpy(dh, h, sizeof(h), hipMemcpyHostToDevice));
+    if ((rc = sd.upload(&dh, h, sizeof(h))) || (rc = sd.alloc(&dpar, 48)) || (rc = sd.alloc(&dcons, 4))) return rc;
     HIPCHK(hipMemset(dpar, 0, 48));
     ScoreArgs a; a.det = d; a.ref_view = dh; a.aug_view = dh + 1; a.aug_kind = dh + 2; a.pair_img = dh + 3; a.ref_sel = dh + 4; a.ref_n = dh + 54;
     a.aug_param = dpar; a.P = 1; a.bp = bp; a.cons = dcons;
@@ -470,7 +427,36 @@ extern "C" int cald_op_consistency(cald_ctx* c, int N, const float* aug_box, con
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(consistency_out, dcons, 4, hipMemcpyDeviceToHost));
-    hipFree(dh); hipFree(dpar); hipFree(dcons); free_det(d);
+    return 0;
+}
+
+// one ScopedDev allocation carved by `lay`: a dry Bump for the size, then the real one over it (the forward's arena, in small)
+template <typename F> static int carve(ScopedDev& sd, F lay) {
+    Bump dry(nullptr, true), real(nullptr, false); lay(dry);
+    int rc = sd.alloc(&real.base, dry.off); if (rc) return rc;
+    lay(real);
+    return 0;
+}
+// one view's R proposals as the RPN leaves them: CALD_ROI_CAP rows, zero beyond the count
+static int put_proposals(const ProposalBufs& P, const float* rois, int R) {
+    HIPCHK(hipMemset(P.proposals, 0, (size_t)CALD_ROI_CAP * 16));
+    if (R) HIPCHK(hipMemcpy(P.proposals, rois, (size_t)R * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(P.prop_count, &R, 4, hipMemcpyHostToDevice));
+    return 0;
+}
+// the detections of view 0 to the host: the count, refused outside 0..cap (a kernel is wrong), then the arrays (props_out: Faster R-CNN only)
+static int download_dets(cald_ctx* c, const DetBuffers& det, const char* what, float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out,
+                         float* prob_max_out, float* scores_cls_out, int* n_out) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, det.count, 4, hipMemcpyDeviceToHost));
+    if (n < 0 || n > det.cap) return fail(CALD_ERR_HIP, "%s postprocess returned %d detections (cap %d)", what, n, det.cap);
+    if (!n) { *n_out = 0; return 0; }
+    HIPCHK(hipMemcpy(boxes_out, det.boxes, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(scores_out, det.scores, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(labels_out, det.labels, (size_t)n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(prob_max_out, det.prob_max, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(scores_cls_out, det.scores_cls, (size_t)n * det.C * 4, hipMemcpyDeviceToHost));
+    if (props_out) HIPCHK(hipMemcpy(props_out, det.props, (size_t)n * 16, hipMemcpyDeviceToHost));
+    *n_out = n;       // only once every array has arrived
     return 0;
 }
 
@@ -484,7 +470,6 @@ extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float*
         return fail(CALD_ERR_INVALID, "null argument");
     if (R < 0 || R > CALD_ROI_CAP || C < 2 || C > 256 || det_max < 1 || det_max > 512) return fail(CALD_ERR_INVALID, "bad geometry (R <= %d, 2 <= C <= 256, det_max <= 512)", CALD_ROI_CAP);
     HIPCHK(hipSetDevice(c->device));
-    ScopedDev sd(c->stream);
     const int ld = 5 * C;
     int key_cap = 1024; while (key_cap < R * (C - 1)) key_cap <<= 1;
     std::vector<float> pred((size_t)CALD_ROI_CAP * ld, 0.0f);
@@ -493,40 +478,19 @@ extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float*
         memcpy(&pred[(size_t)r * ld + C], deltas + (size_t)r * 4 * C, (size_t)4 * C * 4);
     }
     ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
-    PostArgs pa; float *d_pred, *d_props, *d_prob, *d_pmax, *d_cbox; unsigned long long* d_keys; int *d_kc, *d_pc; ViewDesc* d_vd;
-    int rc;
-    if ((rc = sd.alloc(&d_pred, pred.size() * 4)) || (rc = sd.alloc(&d_props, (size_t)CALD_ROI_CAP * 16)) || (rc = sd.alloc(&d_prob, (size_t)CALD_ROI_CAP * C * 4)) ||
-        (rc = sd.alloc(&d_pmax, (size_t)CALD_ROI_CAP * 4)) || (rc = sd.alloc(&d_cbox, (size_t)2 * key_cap * 16)) || (rc = sd.alloc(&d_keys, (size_t)key_cap * 8)) ||
-        (rc = sd.alloc(&d_kc, 4)) || (rc = sd.alloc(&d_pc, 4)) || (rc = sd.alloc(&d_vd, sizeof(ViewDesc)))) return rc;
-    DetBuffers det; if ((rc = alloc_det(det, 1, det_max, C))) return rc;
-    HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_props, 0, (size_t)CALD_ROI_CAP * 16));
-    if (R) HIPCHK(hipMemcpy(d_props, proposals, (size_t)R * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_pc, &R, 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
-    pa.pred = d_pred; pa.pred_ld = ld; pa.C = C; pa.V = 1; pa.proposals = d_props; pa.prop_count = d_pc; pa.views = d_vd;
-    pa.score_thr = score_thr; pa.nms_thr = nms_thr; pa.prob = d_prob; pa.pmax = d_pmax; pa.keys = d_keys; pa.cbox = d_cbox; pa.key_count = d_kc;
-    pa.key_cap = key_cap; pa.det = det;
-    launch_frcnn_postprocess(pa, c->stream);
+    ScopedDev sd(c->stream); ScopedDet det;
+    ProposalBufs pb; PostBufs S; float* d_pred; ViewDesc* d_vd; int rc;
+    if ((rc = carve(sd, [&](Bump& B) { d_pred = B.get<float>(pred.size()); d_vd = B.get<ViewDesc>(1); pb.layout(B, 1); S.layout(B, 1, C, key_cap); })) ||
+        (rc = det.alloc(1, det_max, C)) || (rc = put_proposals(pb, proposals, R))) return rc;
+    HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+    launch_frcnn_postprocess(post_args(S, d_pred, ld, C, 1, pb, d_vd, score_thr, nms_thr, det.d), c->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int n = 0;
-    HIPCHK(hipMemcpy(&n, det.count, 4, hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n) {
-        HIPCHK(hipMemcpy(boxes_out, det.boxes, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(scores_out, det.scores, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(labels_out, det.labels, (size_t)n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(props_out, det.props, (size_t)n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(prob_max_out, det.prob_max, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(scores_cls_out, det.scores_cls, (size_t)n * C * 4, hipMemcpyDeviceToHost));
-    }
-    free_det(det);
-    return 0;
+    return download_dets(c, det.d, "frcnn", boxes_out, scores_out, labels_out, props_out, prob_max_out, scores_cls_out, n_out);
 }
 
 // RetinaNet.postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the forward (retina.hip
-// retina_cand_kernel / retina_class_nms_kernel / retina_emit_kernel): host arrays in, host arrays out.  The RetinaArgs are filled as
-// forward.hip fills them (cand_cap = power of two >= anchors, min_box 1e-2, det cap K * per_class).  Parity hook for
-// detection/retinanet_cal.py:402-490.
+// retina_cand_kernel / retina_class_nms_kernel / retina_emit_kernel): host arrays in, host arrays out, through the forward's own
+// RetinaTailBufs::layout and retina_args (host.h); det cap K * per_class.  Parity hook for detection/retinanet_cal.py:402-490.
 extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
                                           const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
                                           float score_thr, float nms_thr, int per_class,
@@ -536,59 +500,34 @@ extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, 
         return fail(CALD_ERR_INVALID, "null argument");
     if (A < 1 || A > 64 || K < 1 || K > 256 || per_class < 1 || per_class > 1024 || Hp < 1 || Wp < 1 || Hr < 1 || Wr < 1 || Ho < 1 || Wo < 1)
         return fail(CALD_ERR_INVALID, "bad geometry (1 <= A <= 64, 1 <= K <= 256, 1 <= per_class <= 1024, positive sizes)");
-    long long anchors = 0;
+    BatchPlan P; memset(&P, 0, sizeof(P));      // level 0: the padded input; levels 3..7: P3..P7
+    P.seg[0][0].H = Hp; P.seg[0][0].W = Wp; P.seg[0][1].pix_off = (long long)Hp * Wp;
+    long long anchors = 0; size_t pix[5];
     for (int l = 0; l < 5; l++) {
         const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
         if (H < 1 || W < 1 || H > Hp || W > Wp || !cls[l] || !reg[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
+        P.seg[3 + l][0].H = H; P.seg[3 + l][0].W = W; P.seg[3 + l][1].pix_off = (long long)H * W; pix[l] = (size_t)H * W;
         anchors += (long long)H * W * A;
     }
     if (anchors > (1 << 20)) return fail(CALD_ERR_INVALID, "at most %d anchors", 1 << 20);
     HIPCHK(hipSetDevice(c->device));
-    ScopedDev sd(c->stream);
-    const int maxa = (int)anchors;
-    int cap = 1024; while (cap < maxa) cap <<= 1;
-    BatchPlan P; memset(&P, 0, sizeof(P));      // level 0: the padded input; levels 3..7: P3..P7
-    P.seg[0][0].H = Hp; P.seg[0][0].W = Wp; P.seg[0][1].pix_off = (long long)Hp * Wp;
     ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
-    RetinaArgs ra; BatchPlan* d_p; ViewDesc* d_vd; float *d_cls[5], *d_reg[5], *d_base;
-    int rc;
+    ScopedDev sd(c->stream); ScopedDet det;
+    RetinaTailBufs S; BatchPlan* d_p; ViewDesc* d_vd; float *d_cls[5], *d_reg[5], *d_base; int rc;
+    if ((rc = carve(sd, [&](Bump& B) {
+            for (int l = 0; l < 5; l++) { d_cls[l] = B.get<float>(pix[l] * A * K); d_reg[l] = B.get<float>(pix[l] * A * 4); }
+            d_p = B.get<BatchPlan>(1); d_vd = B.get<ViewDesc>(1); d_base = B.get<float>((size_t)5 * A * 4);
+            S.layout(B, 1, K, per_class, (int)anchors);
+        })) || (rc = det.alloc(1, K * per_class, K))) return rc;
     for (int l = 0; l < 5; l++) {
-        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
-        P.seg[3 + l][0].H = H; P.seg[3 + l][0].W = W; P.seg[3 + l][1].pix_off = (long long)H * W;
-        if ((rc = sd.alloc(&d_cls[l], (size_t)H * W * A * K * 4)) || (rc = sd.alloc(&d_reg[l], (size_t)H * W * A * 16))) return rc;
-        HIPCHK(hipMemcpy(d_cls[l], cls[l], (size_t)H * W * A * K * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_reg[l], reg[l], (size_t)H * W * A * 16, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_cls[l], cls[l], pix[l] * A * K * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_reg[l], reg[l], pix[l] * A * 16, hipMemcpyHostToDevice));
     }
-    if ((rc = sd.alloc(&d_p, sizeof(BatchPlan))) || (rc = sd.alloc(&d_vd, sizeof(ViewDesc))) || (rc = sd.alloc(&d_base, (size_t)5 * A * 16)) ||
-        (rc = sd.alloc(&ra.cand_count, (size_t)K * 4)) || (rc = sd.alloc(&ra.cand_key, (size_t)K * cap * 8)) || (rc = sd.alloc(&ra.cand_box, (size_t)K * cap * 16)) ||
-        (rc = sd.alloc(&ra.cand_skip, (size_t)K * cap)) || (rc = sd.alloc(&ra.kept_anchor, (size_t)K * per_class * 4)) ||
-        (rc = sd.alloc(&ra.kept_box, (size_t)K * per_class * 16)) || (rc = sd.alloc(&ra.kept_count, (size_t)K * 4))) return rc;
-    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_base, base_anchors, (size_t)5 * A * 16, hipMemcpyHostToDevice));
-    DetBuffers det; if ((rc = alloc_det(det, 1, K * per_class, K))) return rc;
-    for (int l = 0; l < 5; l++) { ra.cls[l] = d_cls[l]; ra.reg[l] = d_reg[l]; ra.seg[l] = d_p->seg[3 + l]; }
-    ra.seg0 = d_p->seg[0]; ra.views = d_vd; ra.base_anchors = d_base;
-    ra.cls_ld = A * K; ra.reg_ld = A * 4; ra.A = A; ra.K = K; ra.V = 1;
-    ra.score_thr = score_thr; ra.nms_thr = nms_thr; ra.min_box = 1e-2f;
-    ra.per_class = per_class; ra.cand_cap = cap; ra.det = det;
-    launch_retina_postprocess(ra, maxa, c->stream);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    int n = 0;
-    if (e == hipSuccess) e = hipMemcpy(&n, det.count, 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && (n < 0 || n > K * per_class)) { free_det(det); return fail(CALD_ERR_HIP, "retina postprocess returned %d detections (cap %d)", n, K * per_class); }
-    if (e == hipSuccess && n) {
-        e = hipMemcpy(boxes_out, det.boxes, (size_t)n * 16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(scores_out, det.scores, (size_t)n * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(labels_out, det.labels, (size_t)n * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(prob_max_out, det.prob_max, (size_t)n * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(scores_cls_out, det.scores_cls, (size_t)n * K * 4, hipMemcpyDeviceToHost);
-    }
-    free_det(det);
-    if (e != hipSuccess) return fail(CALD_ERR_HIP, "retina postprocess failed: %s", hipGetErrorString(e));
-    *n_out = n;
-    return 0;
+    launch_retina_postprocess(retina_args(S, d_cls, d_reg, d_p, d_vd, d_base, A, K, 1, score_thr, nms_thr, per_class, det.d), S.max_anchors, c->stream);
+    HIPCHK(hipGetLastError());
+    return download_dets(c, det.d, "retina", boxes_out, scores_out, labels_out, nullptr, prob_max_out, scores_cls_out, n_out);
 }
 
 // MultiScaleRoIAlign(7, sampling_ratio 2) of ONE view on the inference kernels (roi.hip): feats[l] = host [H_l][W_l][C] for the four
@@ -598,45 +537,38 @@ extern "C" int cald_op_roi_align(cald_ctx* c, const float* const* feats, const i
     if (!c || !feats || !level_hw || !rois || !out) return fail(CALD_ERR_INVALID, "null argument");
     if (R < 1 || R > CALD_ROI_CAP || C < 4 || C % 4) return fail(CALD_ERR_INVALID, "bad geometry (1 <= R <= %d, C a positive multiple of 4)", CALD_ROI_CAP);
     HIPCHK(hipSetDevice(c->device));
-    ScopedDev sd(c->stream);
     BatchPlan P; memset(&P, 0, sizeof(P));
-    RoiArgs ro; float* d_f[4]; BatchPlan* d_p; float *d_rois, *d_out; int *d_pc, *d_order;
-    int rc;
+    size_t pix[4];
     for (int l = 0; l < 4; l++) {
         const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
         if (H < 1 || W < 1 || !feats[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
-        P.seg[2 + l][0].H = H; P.seg[2 + l][0].W = W; P.seg[2 + l][1].pix_off = (long long)H * W;
-        if ((rc = sd.alloc(&d_f[l], (size_t)H * W * C * 4))) return rc;
-        HIPCHK(hipMemcpy(d_f[l], feats[l], (size_t)H * W * C * 4, hipMemcpyHostToDevice));
+        P.seg[2 + l][0].H = H; P.seg[2 + l][0].W = W; P.seg[2 + l][1].pix_off = (long long)H * W; pix[l] = (size_t)H * W;
     }
-    if ((rc = sd.alloc(&d_p, sizeof(BatchPlan))) || (rc = sd.alloc(&d_rois, (size_t)CALD_ROI_CAP * 16)) || (rc = sd.alloc(&d_out, (size_t)CALD_ROI_CAP * 49 * C * 4)) ||
-        (rc = sd.alloc(&d_pc, 4)) || (rc = sd.alloc(&d_order, 1024 * 4))) return rc;
+    ScopedDev sd(c->stream);
+    ProposalBufs pb; RoiBufs S; float* d_f[4]; BatchPlan* d_p; int rc;
+    if ((rc = carve(sd, [&](Bump& B) { for (int l = 0; l < 4; l++) d_f[l] = B.get<float>(pix[l] * C); d_p = B.get<BatchPlan>(1); pb.layout(B, 1); S.layout(B, 1, C); })) ||
+        (rc = put_proposals(pb, rois, R))) return rc;
+    for (int l = 0; l < 4; l++) HIPCHK(hipMemcpy(d_f[l], feats[l], pix[l] * C * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(d_rois, 0, (size_t)CALD_ROI_CAP * 16));
-    HIPCHK(hipMemcpy(d_rois, rois, (size_t)R * 16, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_pc, &R, 4, hipMemcpyHostToDevice));
-    for (int l = 0; l < 4; l++) { ro.feat[l] = d_f[l]; ro.seg[l] = d_p->seg[2 + l]; }
-    ro.C = C; ro.V = 1; ro.proposals = d_rois; ro.prop_count = d_pc; ro.out = d_out; ro.order = d_order; ro.out16 = 0;
-    launch_roi_align(ro, c->stream);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, d_out, (size_t)R * 49 * C * 4, hipMemcpyDeviceToHost));
+    launch_roi_align(roi_args(S, d_f, d_p, C, 1, pb, false), c->stream);
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, S.roi, (size_t)R * 49 * C * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int cald_op_cls_corr(cald_ctx* c, int n, const float* scores, const int64_t* labels, int C, float* out) {
     if (!c || !out || n < 0 || C < 2 || C > 256) return fail(CALD_ERR_INVALID, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
-    DetBuffers d; int rc = alloc_det(d, 1, n > 0 ? n : 1, C); if (rc) return rc;
+    ScopedDev sd(c->stream); ScopedDet sdet;
+    int rc = sdet.alloc(1, n > 0 ? n : 1, C); if (rc) return rc;
+    const DetBuffers& d = sdet.d;
     if (n) { HIPCHK(hipMemcpy(d.scores, scores, (size_t)n * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d.labels, labels, (size_t)n * 8, hipMemcpyHostToDevice)); }
     HIPCHK(hipMemcpy(d.count, &n, 4, hipMemcpyHostToDevice));
     int h[2] = {0, 0}; int* dh; float* dout;
-    HIPCHK(hipMalloc((void**)&dh, 8)); HIPCHK(hipMalloc((void**)&dout, (size_t)(C - 1) * 4));
-    HIPCHK(hipMemcpy(dh, h, 8, hipMemcpyHostToDevice));
+    if ((rc = sd.upload(&dh, h, 8)) || (rc = sd.alloc(&dout, (size_t)(C - 1) * 4))) return rc;
     launch_cls_corr(d, nullptr, nullptr, dh, dh + 1, 1, dout, c->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out, dout, (size_t)(C - 1) * 4, hipMemcpyDeviceToHost));
-    hipFree(dh); hipFree(dout); free_det(d);
     return 0;
 }

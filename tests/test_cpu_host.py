@@ -37,6 +37,16 @@ def test_product_never_touches_the_oracle():
                 assert "cald_oracle" not in txt and "#include \"../../oracle" not in txt, f
 
 
+def test_ops_per_call_memory_has_one_owner():
+    """ops.hip acquires device memory through ScopedDev / ScopedDet (host.h) alone: no hipMalloc at all, and no hipFree outside get_pil,
+    whose tables the context's cache owns."""
+    txt = open(os.path.join(ROOT, "cald_amd", "csrc", "ops.hip")).read()
+    assert "hipMalloc(" not in txt
+    start = txt.index("static int get_pil(")
+    end = txt.index("\n}\n", start)
+    assert "hipFree(" not in txt[:start] + txt[end:]
+
+
 def test_compute_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -39,7 +39,7 @@ def hip():
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
     from cald_amd import _ffi, detector
-    return dict(L=_ffi.lib(), ffi=_ffi, ctx=detector.get_ctx(0), torch=torch)
+    return dict(L=_ffi.lib(), ffi=_ffi, ctx=detector.get_ctx(0), det=detector, torch=torch)
 
 
 def _assert_bytes(got, want, what):
@@ -334,13 +334,13 @@ def test_frcnn_restatement_equals_oracle(orc, det_max):
         assert pairs[:20] == [(0, c) for c in range(1, 11)] + [(24, c) for c in range(1, 11)]            # 20 kept before the first suppression
 
 
-def gpu_frcnn(hip, logits, deltas, props, Hr, Wr, Ho, Wo, det_max):
+def gpu_frcnn(hip, logits, deltas, props, Hr, Wr, Ho, Wo, det_max, score_thr=0.05, nms_thr=0.5):
     ffi, L = hip["ffi"], hip["L"]
     logits, deltas, props = [np.ascontiguousarray(a, F32) for a in (logits, deltas, props)]
     Rn, Cn = logits.shape
     ob = np.empty((det_max, 4), F32); osc = np.empty(det_max, F32); ol = np.empty(det_max, np.int64); op = np.empty((det_max, 4), F32)
     opm = np.empty(det_max, F32); ocl = np.empty((det_max, Cn), F32); n = C.c_int(-1)
-    ffi.check(L.cald_op_frcnn_postprocess(hip["ctx"], Rn, Cn, ffi.ptr(logits), ffi.ptr(deltas), ffi.ptr(props), Hr, Wr, Ho, Wo, 0.05, 0.5, det_max,
+    ffi.check(L.cald_op_frcnn_postprocess(hip["ctx"], Rn, Cn, ffi.ptr(logits), ffi.ptr(deltas), ffi.ptr(props), Hr, Wr, Ho, Wo, score_thr, nms_thr, det_max,
                                           ffi.ptr(ob), ffi.ptr(osc), ffi.ptr(ol, ffi.c_i64), ffi.ptr(op), ffi.ptr(opm), ffi.ptr(ocl), C.byref(n)))
     m = n.value
     assert 0 <= m <= det_max
@@ -595,3 +595,59 @@ def test_cls_corr_kernel_list_lengths(hip, orc, n):
     for s, l in zip(sc.astype(np.float64), lab):
         ref[(l - 1) % (SC_C - 1)] = max(ref[(l - 1) % (SC_C - 1)], s)
     np.testing.assert_array_equal(out, ref.astype(F32))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The hooks above run the forward's own scratch layout and argument filling (host.h: RetinaTailBufs / PostBufs / RoiBufs and
+# retina_args / post_args / roi_args): fed a forward's intermediate tensors, each returns that forward's bytes.
+# ---------------------------------------------------------------------------------------------------------------------------
+from test_gpu_parity import _gpu_roi_align, small_model, small_retina      # noqa: E402,F401  (the 300 / 500 models of the parity tests)
+
+
+def _one_view(hip, model):
+    from cald_amd import synth, train_ops
+    img = synth.make_pool(3, "voc", 0, scale=0.5)[1]
+    got = model.forward_views([(hip["torch"].from_numpy(img).cuda(), False, None)])[0]
+    Hr, Wr, Hp, Wp = train_ops.transform_size(img.shape[0], img.shape[1], model.cfg.min_size, model.cfg.max_size)
+    return img, {k: v.cpu().numpy() for k, v in got.items()}, (Hp, Wp, Hr, Wr)
+
+
+@pytest.mark.gpu
+def test_retina_hook_on_the_forwards_head_maps_returns_the_forwards_detections(hip, orc, small_retina):
+    model, _ = small_retina
+    img, want, sizes = _one_view(hip, model)
+    cls = [model.debug_tensor("cls%d" % l, 0) for l in range(5)]; reg = [model.debug_tensor("reg%d" % l, 0) for l in range(5)]
+    got = gpu_retina(hip, cls, reg, _retina_base(orc), model.num_classes, 9, sizes, img.shape[:2], model.cfg.detections_per_img,
+                     model.cfg.box_score_thresh, model.cfg.box_nms_thresh)
+    assert len(want["labels"]) > 0
+    _assert_bytes(got, want, "retina tail")
+
+
+def _frcnn_view(hip, orc, small_model):
+    model, P = small_model
+    img, want, sizes = _one_view(hip, model)
+    keep = {}
+    orc.frcnn_forward(P, img, 300, 500, keep=keep)
+    n = keep["proposals"].shape[0]
+    assert 0 < n <= 1000
+    return model, img, want, sizes, np.ascontiguousarray(model.debug_tensor("proposals", 0).reshape(-1, 4)[:n])
+
+
+@pytest.mark.gpu
+def test_frcnn_hook_on_the_forwards_predictions_returns_the_forwards_detections(hip, orc, small_model):
+    model, img, want, (Hp, Wp, Hr, Wr), props = _frcnn_view(hip, orc, small_model)
+    Cn = model.num_classes
+    pred = model.debug_tensor("pred", 0).reshape(1000, 5 * Cn)[:len(props)]
+    got = gpu_frcnn(hip, pred[:, :Cn], pred[:, Cn:], props, Hr, Wr, img.shape[0], img.shape[1], model.cfg.detections_per_img,
+                    model.cfg.box_score_thresh, model.cfg.box_nms_thresh)
+    assert set(want) == set(got) and len(want["labels"]) > 0          # all six outputs; the count is their common length
+    assert len(got["labels"]) == len(want["labels"])
+    _assert_bytes(got, want, "frcnn tail")
+
+
+@pytest.mark.gpu
+def test_roi_align_hook_on_the_forwards_pyramid_returns_the_forwards_rows(hip, orc, small_model):
+    model, _, _, _, props = _frcnn_view(hip, orc, small_model)
+    got = _gpu_roi_align(hip, [model.debug_tensor("P%d" % (2 + l), 0) for l in range(4)], props)
+    want = model.debug_tensor("roi", 0).reshape(1000, 49, 256)[:len(props)]
+    assert got.shape == want.shape and got.tobytes() == want.tobytes()
