@@ -90,7 +90,8 @@ class ConvProbe(C.Structure):
                 ("weight", c_f), ("bias", c_f), ("bn_scale", c_f), ("bn_shift", c_f), ("in_", c_f), ("in16", C.POINTER(C.c_uint32)),
                 ("residual", c_f), ("up", c_f), ("ex16", C.c_int), ("mask", c_f), ("row_map", c_i),
                 ("out", c_f), ("out_n", C.c_int64), ("out16", C.POINTER(C.c_uint32)), ("out16_n", C.c_int64),
-                ("energy4", c_f), ("energy4_n", C.c_int64)]
+                ("energy4", c_f), ("energy4_n", C.c_int64),
+                ("head_w", c_f), ("head_b", c_f), ("head_out", c_f), ("head_out_n", C.c_int64), ("head_ld", C.c_int)]
 
 
 class WgradPlan(C.Structure):
@@ -165,6 +166,7 @@ SIGNATURES = {
     "cald_profile_roi_rows": (C.c_int, [C.c_void_p, c_d, c_i64]),
     "cald_profile_cutout": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_i64]),
     "cald_model_set_cutout_reuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
+    "cald_model_set_look_fuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_profile_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     # training step (device pointers as c_void_p)
     "cald_train_packed_floats": (C.c_int, [C.c_int] * 6 + [c_i64]),

@@ -104,6 +104,14 @@ struct ConvArgs {
     // conv_p4.hip only: per view the rows of a gathered-and-scattered launch (GatherSet), else null.  seg_out's tile_start then counts
     // the gathered rows' tiles; pix_off / H / W stay the full tensor's.
     const GatherSet* gather;
+    // conv_h4.hip only, the look-ahead of the certified RPN pruning (rpn_prune.hip): the 1 x 1 head's first three output channels (the
+    // objectness logits) evaluated in the epilogue, where the workgroup holds all 256 hidden channels of its rows -- per row and logit the
+    // k-ascending fp32 fma chain over the hidden channels, then + head_b, the exact 1 x 1 kernel's arithmetic.  head_w: [3][256] fp32,
+    // head_out: [pixel][head_ld], channels 0..2 written.  head_out set = the hidden tensor is not stored (out / out16 are ignored); else null
+    const float* head_w;
+    float head_b[3];
+    float* head_out;
+    int head_ld;
 };
 
 // Several independent conv problems in ONE launch (the five FPN levels under the shared-weight RPN / RetinaNet heads, the
@@ -115,6 +123,7 @@ struct ConvGroup {
     int blk0[CALD_MAX_GROUP + 1];
     ConvArgs p[CALD_MAX_GROUP];
 };
+static_assert(sizeof(ConvGroup) <= 4096, "ConvGroup is passed by value: it must fit the kernel argument segment");
 
 // Position of input element (tap = kh*KW + kw, channel ci) in the k-ordered fma chain (DESIGN.md arithmetic contract).
 //   Cin % 16 == 0:  (channel chunk of 16, kh, kw, channel inside the chunk) -- all taps of a 16-channel chunk are consecutive
@@ -296,3 +305,4 @@ const char* launch_conv_h3(const ConvArgs& a, hipStream_t stream);              
 const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream);
 const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced = false);              // conv_h4.hip
 const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced = false);
+bool conv_h4_group_takes(const ConvArgs* p, int n, bool forced = false);                                  // would launch_conv_h4_group take it?

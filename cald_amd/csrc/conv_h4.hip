@@ -28,7 +28,7 @@ typedef __attribute__((address_space(3))) void lds_void;
 #define H4_STAGE 32768
 #define H4_NSTAGE 4
 
-template <int EPI>
+template <int EPI, bool HEAD = false>
 __device__ __forceinline__ void conv_h4_body(const ConvArgs& a, const int blk) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar branches, SGPR descriptors
@@ -229,6 +229,74 @@ __device__ __forceinline__ void conv_h4_body(const ConvArgs& a, const int blk) {
 #undef H4_ISSUE
 #undef H4_STEP
 
+    // ---------------- look-ahead epilogue (ConvArgs::head_out): the 1 x 1 head's objectness logits, computed where the hidden values are ----------------
+    // The workgroup owns all 256 hidden channels of its rows (CoutPad == 256: one N tile), and the k-loop's 128 KB of LDS are free now.  Two
+    // rounds; in round t every wave finishes the hidden values (h16_epilogue's operation order: * unscale, + bias, ReLU) of rows [64 t, 64 t + 64)
+    // of its 128-row half and all eight transpose them through LDS to [128 rows: 64 of each half][256 channels] fp32 -- exactly the 128 KB, so
+    // conflicts are avoided by a swizzle, not by padding: the 16-byte slot of channels 4 g .. 4 g + 3 is stored at slot g ^ (row & 63), which
+    // makes the ds_write_b32 of a 32-channel run and the ds_read_b128 of 64 consecutive rows both conflict-free.  Then thread (row, logit) of
+    // waves 0-5 walks its row: s = fma(h_c, w_c, s) for c = 0 .. 255 from +0, + bias -- the chain v_mfma_f32_32x32x2_f32 evaluates in the exact
+    // 1 x 1 kernel (conv_mfma.hip), hence its bits.  The logit, and so the weights, are wave-uniform.  The hidden tensor is not stored.
+    if (HEAD) {
+        // (lane geometry recomputed from an opaque copy of the thread index: nothing lane-derived has to stay in a register across the k-loop, which
+        // uses all 256)
+        int tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));
+        const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 2, wn = wave & 3, l31 = tid & 31, kh_lane = (tid >> 5) & 1;
+        const float unscale = a.w16_unscale;
+        const float bs0 = a.bias[wn * 64 + l31], bs1 = a.bias[wn * 64 + 32 + l31];
+        const bool have2 = 2 * mt2 + 1 < a.total_mtiles;         // (workgroup-uniform) false: the absent second half of an odd tile count
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            __syncthreads();                                      // every wave is done reading: the k-loop's fragments / the previous round's rows
+            if (wm == 0 || have2) {
+                // byte address of (staged row, n) = lane part ^ compile-time part: staged row = 64 wm + (4 kh_lane | rc), rc = 32 (i & 1) + 8 (r >> 2) + (r & 3),
+                // slot = n >> 2.  The lane part is made opaque per round so that the 64 addresses are one v_xor each at their store instead of 64 live registers
+                int sbase = (wm << 16) + (kh_lane << 12) + (((wn * 16 + (l31 >> 2)) ^ (4 * kh_lane)) << 4) + (l31 & 3) * 4;
+                asm volatile("" : "+v"(sbase));
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const float bs = j ? bs1 : bs0;
+#pragma unroll
+                    for (int ii = 0; ii < 2; ii++)
+#pragma unroll
+                        for (int r = 0; r < 16; r++) {
+                            float val = acc[2 * t + ii][j][r] * unscale;
+                            val = val + bs;
+                            val = val > 0.0f ? val : 0.0f;
+                            const int rc = ii * 32 + (r & 3) + 8 * (r >> 2);                 // compile-time after unrolling
+                            *reinterpret_cast<float*>(smem + (sbase ^ (((j << 7) ^ (rc << 4)) | (rc << 10)))) = val;
+                        }
+                }
+            }
+            __syncthreads();
+            if (wave < 6) {
+                const int srow = tid & 127, q = wave >> 1;        // staged row; q (wave-uniform): the logit
+                const int mt = 2 * mt2 + (srow >> 6);             // (wave-uniform: a wave's 64 staged rows lie in one half)
+                if (mt < a.total_mtiles) {
+                    const int v = seg_find_view(a.seg_out, a.V, mt);
+                    const LevelSeg so = a.seg_out[v];
+                    const int m = (mt - so.tile_start) * 128 + 64 * t + (srow & 63);
+                    const float4* const hrow = reinterpret_cast<const float4*>(smem + srow * 1024);
+                    // (constant address space: the weights are wave-uniform and written before the launch -- scalar loads, SGPR operands of v_fma_f32)
+                    typedef const __attribute__((address_space(4))) float cfloat;
+                    cfloat* const w = (cfloat*)a.head_w + q * 256;
+                    float s0 = 0.0f;
+#pragma unroll 16
+                    for (int g = 0; g < 64; g++) {
+                        const float4 hv = hrow[(g ^ srow) & 63];
+                        s0 = __builtin_fmaf(hv.x, w[4 * g], s0);
+                        s0 = __builtin_fmaf(hv.y, w[4 * g + 1], s0);
+                        s0 = __builtin_fmaf(hv.z, w[4 * g + 2], s0);
+                        s0 = __builtin_fmaf(hv.w, w[4 * g + 3], s0);
+                    }
+                    if (m < so.H * so.W) a.head_out[(so.pix_off + m) * (long long)a.head_ld + q] = s0 + a.head_b[q];
+                }
+            }
+        }
+        return;
+    }
+
     // ---------------- epilogue (h16.h) ----------------
     const int mt = 2 * mt2 + wm;
     if (mt >= a.total_mtiles) return;
@@ -255,15 +323,28 @@ __global__ __launch_bounds__(512, 2) void conv_h4_group_kernel(const ConvGroup g
     conv_h4_body<0>(a, local);
 }
 
+// the look-ahead of rpn_prune.hip: the group kernel with the 1 x 1 head's three objectness logits in its epilogue (ConvArgs::head_out)
+__global__ __launch_bounds__(512, 2) void conv_h4_look_kernel(const ConvGroup g) {
+    int i = 0;
+    while (i + 1 < g.n && g.blk0[i + 1] <= (int)blockIdx.x) i++;
+    const int local = (int)blockIdx.x - g.blk0[i];
+    const ConvArgs& a = g.p[i];
+    if (local >= (a.total_mtiles + 1) >> 1) return;
+    conv_h4_body<0, true>(a, local);
+}
+
 static bool h4_covers(const ConvArgs& a) {
+    // with the head in the epilogue the workgroup must own every hidden channel of its rows (one N tile) and all rows of the view
+    // (its epilogue is the RPN conv's: + bias, ReLU, no FrozenBN)
+    if (a.head_out && !(a.head_w && a.head_ld >= 3 && a.Cout == 256 && a.CoutPad == 256 && !a.residual && !a.up && !a.dyn_rows && a.bias && !a.scale && a.relu)) return false;
     return a.w16 && a.in16 && !a.in_relu && a.CoutPad % 256 == 0 && a.Cin % 16 == 0 && a.KH * a.KW <= 32 && !a.mask && !(a.residual && a.up) &&
-           !a.gather && !a.row_map && !a.energy4 && (a.out || a.out16);
+           !a.gather && !a.row_map && !a.energy4 && (a.out || a.out16 || a.head_out);
 }
 static int h4_mode() { static const int mode = getenv("CALD_H4") ? atoi(getenv("CALD_H4")) : 1; return mode; }   // 0: off, 1: where it fills the chip, 2: wherever it fits
-static PerDeviceOnce h4_once[4];
+static PerDeviceOnce h4_once[5];
 // the kernel if it took the launch, else nullptr.  forced: wherever it is correct (cald_op_conv_probe), not only where it pays
 const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced) {
-    if (!(forced || h4_mode()) || !h4_covers(a)) return nullptr;
+    if (!(forced || h4_mode()) || !h4_covers(a) || a.head_out) return nullptr;      // (the head epilogue exists in the group kernel only)
     const int wgs = ((a.total_mtiles + 1) >> 1) * (a.CoutPad >> 8);
     // where it pays, measured per layer class on BASELINE configs[4] with CALD_H4=2 against CALD_H4=0 (profiles/r4_h4_everywhere_vs_default.txt):
     // every class with K >= 1024 and at least two rounds of one workgroup per CU gains 4-9 % (3 x 3 layers of >= 256 channels, the
@@ -278,17 +359,33 @@ const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced) {
     allow_big_lds(h4_once[0], conv_h4_kernel<0>); hipLaunchKernelGGL((conv_h4_kernel<0>), grid, block, lds, stream, a);
     return "conv_h4_kernel<0>";
 }
-const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced) {
-    if (!(forced || h4_mode()) || n < 1 || n > CALD_MAX_GROUP) return nullptr;
-    ConvGroup g; g.n = n; int blk = 0;
+// the group's block ranges.  0: conv_h4 does not take the group, 1: it does, 2: it does and there is nothing to launch
+static int h4_group_plan(const ConvArgs* p, int n, bool forced, ConvGroup* g, int* blocks) {
+    if (!(forced || h4_mode()) || n < 1 || n > CALD_MAX_GROUP) return 0;
+    int blk = 0;
+    const bool head = p[0].head_out != nullptr;
     for (int i = 0; i < n; i++) {
-        if (!h4_covers(p[i]) || p[i].residual || p[i].up) return nullptr;
-        g.blk0[i] = blk; g.p[i] = p[i];
+        if (!h4_covers(p[i]) || p[i].residual || p[i].up || (p[i].head_out != nullptr) != head) return 0;
+        if (g) { g->blk0[i] = blk; g->p[i] = p[i]; }
         blk += (((p[i].total_mtiles + 1) >> 1) * (p[i].CoutPad >> 8) + 7) & ~7;
     }
-    g.blk0[n] = blk;
-    if (!forced && h4_mode() == 1 && (blk < 512 || p[0].Kpad < 1024)) return nullptr;
-    if (blk == 0) return "none (no output tiles)";
+    if (g) { g->n = n; g->blk0[n] = blk; }
+    if (!forced && h4_mode() == 1 && (blk < 512 || p[0].Kpad < 1024)) return 0;
+    *blocks = blk;
+    return blk == 0 ? 2 : 1;
+}
+// whether launch_conv_h4_group would take the group (a caller that prepares something only for that case asks first)
+bool conv_h4_group_takes(const ConvArgs* p, int n, bool forced) { int blk; return h4_group_plan(p, n, forced, nullptr, &blk) != 0; }
+const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced) {
+    ConvGroup g; int blk = 0;
+    const int take = h4_group_plan(p, n, forced, &g, &blk);
+    if (!take) return nullptr;
+    if (take == 2) return "none (no output tiles)";
+    if (p[0].head_out) {
+        allow_big_lds(h4_once[4], conv_h4_look_kernel);
+        hipLaunchKernelGGL(conv_h4_look_kernel, dim3((unsigned)blk), dim3(512), (size_t)H4_NSTAGE * H4_STAGE, stream, g);
+        return "conv_h4_look_kernel";
+    }
     allow_big_lds(h4_once[3], conv_h4_group_kernel);
     hipLaunchKernelGGL(conv_h4_group_kernel, dim3((unsigned)blk), dim3(512), (size_t)H4_NSTAGE * H4_STAGE, stream, g);
     return "conv_h4_group_kernel";

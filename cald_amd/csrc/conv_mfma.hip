@@ -292,6 +292,10 @@ const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream) {
 
 int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream, const char** names, ConvForce f) {
     const char* gname = nullptr;
+    // the head epilogue (ConvArgs::head_out) exists in conv_h4's group kernel only, which its callers reach directly or by pinning it: no
+    // other kernel may take such a problem and store a hidden tensor nobody asked for
+    for (int i = 0; i < n; i++)
+        if (probs[i].head_out && f.path != CONV_H4_GROUP) { if (names) for (int j = 0; j < n; j++) names[j] = nullptr; return 0; }
     if (f.path == CONV_P4_GROUP) gname = launch_conv_p4_group(probs, n, stream, f);
     else if (f.path == CONV_H3_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h3_group(probs, n, stream) : nullptr;
     else if (f.path == CONV_H4_GROUP) gname = f.tile == TILE_AUTO ? launch_conv_h4_group(probs, n, stream, true) : nullptr;
@@ -314,6 +318,7 @@ int launch_conv_group(const ConvArgs* probs, int n, hipStream_t stream, const ch
 }
 
 const char* launch_conv(const ConvArgs& a, hipStream_t stream, ConvForce f) {
+    if (a.head_out) return nullptr;                  // (the head epilogue is conv_h4's group kernel's alone)
     switch (f.path) {
     case CONV_AUTO: break;
     case CONV_P4: return launch_conv_p4(a, stream, f);

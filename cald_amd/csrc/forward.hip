@@ -191,6 +191,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
         }
     }
     a.in16 = nullptr; a.out16 = nullptr; a.ex16 = 0; a.energy4 = nullptr; a.trace = nullptr;
+    a.head_w = nullptr; a.head_out = nullptr; a.head_ld = 0; a.head_b[0] = a.head_b[1] = a.head_b[2] = 0.0f;
     if (!m->split.empty()) {
         const float* ex = residual ? residual : up;
         if (ex) {
@@ -472,6 +473,28 @@ struct ForwardRun {
         name_rpn(0);
         return 0;
     }
+    // the look-ahead of P2 / P3 as ONE conv_h4 launch with the 1 x 1 head's objectness logits in its epilogue (ConvArgs::head_out); *fused stays
+    // false, and nothing was launched, where conv_h4 does not take the launch.  Booked with the FLOPs it executes: the 3 x 3 conv + 3 head channels
+    int look_fused_on(const ConvSpec* sp, bool* fused) {
+        ConvArgs a[2]; double flops = 0.0; int tiles = 0;
+        for (int i = 0; i < 2; i++) {
+            const double f = fill_conv_args(m, a[i], *sp[i].L, sp[i].in, nullptr, sp[i].level, sp[i].level, V, sp[i].relu);
+            if (f < 0.0) return (int)f;
+            a[i].in16 = sp[i].in16;
+            a[i].head_w = m->look_head_w; a[i].head_out = Fn.rpn_h[i]; a[i].head_ld = 15;
+            for (int q = 0; q < 3; q++) a[i].head_b[q] = m->look_head_b[q];
+            flops += f + 2.0 * (double)level_pix(m->plan, sp[i].level, V) * 256.0 * 3.0; tiles += a[i].total_mtiles;
+        }
+        if (!m->look_head_w || !conv_h4_group_takes(a, 2, m->look_fuse == 2)) return 0;       // nothing prepared, nothing launched: the two launches follow
+        if (m->prune_capture)       // the debug view "rpn_look0/1" shows zeros in the channels the fused look-ahead does not evaluate
+            for (int i = 0; i < 2; i++) HIPCHK(hipMemsetAsync(Fn.rpn_h[i], 0, (size_t)level_pix(m->plan, 2 + i, V) * 15 * sizeof(float), st));
+        ProfLaunch t; int rc;
+        if ((rc = prof_begin(c, t))) return rc;
+        const char* k = launch_conv_h4_group(a, 2, st, m->look_fuse == 2);
+        *fused = true;
+        if (!k) { prof_end(c, t, 0.0, c->prof_tag_now, "refused"); return conv_refused(a[0]); }
+        return prof_end(c, t, flops, c->prof_tag_now, "mt=%d,Cin=%d,Cout=%d,k=%dx%d,s=%d,group=2,head=3", tiles, a[0].Cin, a[0].Cout, a[0].KH, a[0].KW, a[0].stride);
+    }
     // certified pruning (rpn_prune.hip): P2 / P3 first on the fp16 matrix pipe, then exactly at the pixels that can hold one of the
     // level's pre_nms_top_n anchors; P4..P6 dense as ever.  Same bits at every anchor the top-k can select.
     int rpn_pruned() {
@@ -491,9 +514,15 @@ struct ForwardRun {
         pr.head_ld = 15; pr.pre_n = m->cfg.rpn_pre_nms_top_n; pr.V = V;
         c->prof_tag_now = 1;
         for (int i = 0; i < 2; i++) { sp[i] = {&m->rpn_conv16, Fp.Pf[i], Fn.rpn_tl[i], 2 + i, true}; sp[i].in16 = Fq.p16[i]; }
-        rc = conv_group_on(m, sp, 2, V);
-        for (int i = 0; i < 2; i++) sp[i] = {&m->rpn_head, Fn.rpn_tl[i], Fn.rpn_h[i], 2 + i, false};
-        if (!rc) rc = conv_group_on(m, sp, 2, V);
+        // one launch where conv_h4 takes it (cald_model_set_look_fuse): the objectness logits come out of its epilogue; else the hidden tensor
+        // is written and the exact 1 x 1 head reads it, as on small inputs (conv_h3)
+        bool fused = false;
+        rc = m->look_fuse ? look_fused_on(sp, &fused) : 0;
+        if (!rc && !fused) {
+            rc = conv_group_on(m, sp, 2, V);
+            for (int i = 0; i < 2; i++) sp[i] = {&m->rpn_head, Fn.rpn_tl[i], Fn.rpn_h[i], 2 + i, false};
+            if (!rc) rc = conv_group_on(m, sp, 2, V);
+        }
         c->prof_tag_now = 0;
         if (rc) return rc;
         // FLOPs the gathered launches are booked with when they cover every pixel (each stage's launches are: cald_profile_read / _dump rescale them)
@@ -524,7 +553,7 @@ struct ForwardRun {
                 if (log_slot[s2] >= 0) c->prof_gather[c->prof_launches.size() - 1] = {log_slot[s2], {cap_head[0], cap_head[1]}};
             }
         }
-        launch_rpn_prune_scatter(pr, st);
+        launch_rpn_prune_scatter(pr, max_pix2, st);
         name_rpn(m->prune_capture ? 0 : 2);      // (P2 / P3 head maps are exact only where selected, -FLT_MAX elsewhere: a debug view in capture mode only)
         return 0;
     }

@@ -165,7 +165,7 @@ struct RpnPruneArgs {
     int head_ld, pre_n, V;
 };
 void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipStream_t st);   // stage 0, then -- after stage 0's exact rows exist -- stage 1
-void launch_rpn_prune_scatter(const RpnPruneArgs& a, hipStream_t st);
+void launch_rpn_prune_scatter(const RpnPruneArgs& a, int max_pix, hipStream_t st);
 
 // audit.hip -- decision margins of one Faster R-CNN forward (cascade mode: which images may differ from the exact mode by more than
 // continuous rounding).  Every discrete decision of the forward (top-k cut, NMS IoU test, score threshold, RoI level, sort

@@ -274,6 +274,11 @@ extern "C" int cald_model_finalize(cald_model* m) {
             }
             m->prune_allowed = finite && m->rpn_conv16.w16 != nullptr;
             m->prune = m->prune_allowed;
+            // the look-ahead's objectness head for conv_h4.hip's epilogue (ConvArgs::head_w / head_b): rpn_head's first three output channels
+            // (cls_logits), [3][256] fp32 -- the values the exact 1 x 1 kernel reads from its own packing
+            std::vector<float> hw(wl->data.begin(), wl->data.begin() + 3 * 256);
+            if ((rc = upload(m, hw, &m->look_head_w))) return rc;
+            for (int a = 0; a < 3; a++) m->look_head_b[a] = bl->data[a];
         }
         {   // fc6: torch K order is (c, bin); the RoIAlign kernel writes (bin, c) -> permute the weight's K axis
             const HostTensor* t; if ((rc = get_t(m, "roi_heads.box_head.fc6.weight", &t))) return rc;
@@ -358,6 +363,12 @@ extern "C" int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was) {
     if (!m || mode < -1 || mode > 2) return fail(CALD_ERR_INVALID, "bad argument");
     if (was) *was = m->cr.mode;
     m->cr.mode = mode;
+    return 0;
+}
+extern "C" int cald_model_set_look_fuse(cald_model* m, int mode, int* was) {
+    if (!m || mode < 0 || mode > 2) return fail(CALD_ERR_INVALID, "bad argument");
+    if (was) *was = m->look_fuse;
+    m->look_fuse = mode;
     return 0;
 }
 // Test hooks of the certified pruning: in capture mode cald_forward takes the pruned path as well (it is dense otherwise) and keeps the

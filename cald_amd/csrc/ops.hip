@@ -275,6 +275,14 @@ extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* p
             (rc = sd.upload(&A.gather, p.gather ? gs.data() : nullptr, gs.size() * sizeof(GatherSet))) ||
             (rc = sd.upload(&d_seg, seg.data(), seg.size() * sizeof(LevelSeg))) || (rc = sd.upload(&A.out, p.out, (size_t)p.out_n * 4)) ||
             (rc = sd.upload(&A.out16, p.out16, (size_t)p.out16_n * 4)) || (rc = sd.upload(&A.energy4, p.energy4, (size_t)p.energy4_n * 4))) return rc;
+        if (p.head_out) {        // the look-ahead's head epilogue (conv_h4 grouped only: no other launcher knows the fields)
+            if (path != CONV_H4_GROUP || !p.head_w || !p.head_b || p.head_ld < 3 || p.head_out_n < rows_out * p.head_ld)
+                return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: head fields need path 9, head_w, head_b, head_ld >= 3 and a buffer of the output's rows", i);
+            if ((rc = sd.upload(&A.head_w, p.head_w, (size_t)3 * p.Cout * 4)) || (rc = sd.upload(&A.head_out, p.head_out, (size_t)p.head_out_n * 4))) return rc;
+            for (int q = 0; q < 3; q++) A.head_b[q] = p.head_b[q];
+            A.head_ld = p.head_ld;
+            back.push_back({A.head_out, p.head_out, (size_t)p.head_out_n * 4});
+        }
         A.seg_in = d_seg; A.seg_out = d_seg + CALD_PROBE_MAX_VIEWS + 1; A.seg_up = d_seg + 2 * (CALD_PROBE_MAX_VIEWS + 1);
         if (p.out) back.push_back({A.out, p.out, (size_t)p.out_n * 4});
         if (p.out16) back.push_back({A.out16, p.out16, (size_t)p.out16_n * 4});

@@ -4,8 +4,10 @@
 // largest objectness logit -- 1 000 of 91 200 on P2, 1 000 of 22 800 on P3 at VOC size -- and nothing downstream ever reads another
 // anchor's logit or deltas.  The RPN head (3 x 3 conv 256 -> 256 + ReLU, 1 x 1 -> 15; frcnn_la.py:199-203) is 23 % of a view's FLOPs and
 // P2 + P3 carry 94 % of its pixels.  The exact sweep therefore computes the head in two steps on those two levels:
-//   1. everywhere, cheaply: the 3 x 3 conv on the fp16 matrix pipe (conv_h4.hip, 3 MFMAs per product, ~2.7 x the fp32 rate), the 1 x 1 head on
-//      the exact kernel -> approximate logits L~ with an error bound B(anchor) against the exact mode's own value L (below);
+//   1. everywhere, cheaply: the 3 x 3 conv on the fp16 matrix pipe (conv_h4.hip, 3 MFMAs per product, ~2.7 x the fp32 rate) and, in the same
+//      launch's epilogue, the 1 x 1 head's three objectness logits as the exact kernel's own fp32 fma chain over the hidden channels (the hidden
+//      tensor is never written, the twelve box deltas never computed; on small inputs, where conv_h3 takes the conv, the 1 x 1 head still runs as a
+//      launch of the exact kernel) -> approximate logits L~ with an error bound B(anchor) against the exact mode's own value L (below);
 //   2. only where it can matter, exactly: tau = the k-th largest LOWER bound L~ - B.  At least k anchors have L >= tau, so an anchor with
 //      L~ + B < tau is not among the k largest of L, whatever the rounding did.  The pixels that hold a surviving anchor (~10 % of P2,
 //      ~35 % of P3 on the configs[1] pool) are recomputed by the exact kernels as gathered rows (ConvArgs::row_map) -- per output element the same k-ordered
@@ -189,8 +191,12 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(RpnPruneArgs a) {
 // the exact head rows of the selected pixels back into the dense [pixel][head_ld] map -- and the bound put to the test: every selected anchor
 // has both values, the look-ahead's L~ (still in the map) and the exact L; max |L~ - L| / B over all of them goes to a.check[0]
 // (non-negative floats order like their bit patterns).  A ratio above 1 means the bound does not hold on this data: the sweep then repeats
-// itself with the dense head (sweep.hip sweep_checked).  grid = (blocks, V, 4): z = level + 2 * stage
+// itself with the dense head (sweep.hip sweep_checked).  grid = (blocks, V, 4): z = level + 2 * stage.  The maximum is reduced over the block
+// first and reaches a.check[0] with at most one atomic per block, none when a plain load already shows a value at least as large (the word
+// only grows, so a stale smaller value costs an atomic that was not needed, never one that was): every wavefront with work once sent its own
+// atomicMax to that one word, ~60 000 same-address atomics a launch, which were the kernel's time.
 __global__ __launch_bounds__(256) void prune_scatter_kernel(RpnPruneArgs a) {
+    __shared__ float s_worst[4];
     const int l = blockIdx.z & 1, st = blockIdx.z >> 1, v = blockIdx.y;
     const LevelSeg sg = a.seg[l][v];
     const int ns = a.nsel[st][l * a.V + v], ld = a.head_ld;
@@ -212,8 +218,15 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(RpnPruneArgs a) {
         dst[(long long)p * ld + c] = exact;
     }
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) worst = fmaxf(worst, __shfl_xor(worst, off, 64));      // one atomic per wavefront, not per element
-    if ((threadIdx.x & 63) == 0 && worst > 0.0f && a.check) atomicMax(reinterpret_cast<unsigned*>(a.check), __float_as_uint(worst));
+    for (int off = 32; off >= 1; off >>= 1) worst = fmaxf(worst, __shfl_xor(worst, off, 64));
+    if ((threadIdx.x & 63) == 0) s_worst[threadIdx.x >> 6] = worst;
+    __syncthreads();
+    if (threadIdx.x == 0 && a.check) {
+        worst = fmaxf(fmaxf(s_worst[0], s_worst[1]), fmaxf(s_worst[2], s_worst[3]));
+        unsigned* const ck = reinterpret_cast<unsigned*>(a.check);
+        const unsigned wb = __float_as_uint(worst);                 // (non-negative floats order like their bit patterns)
+        if (worst > 0.0f && *reinterpret_cast<volatile unsigned*>(ck) < wb) atomicMax(ck, wb);
+    }
 }
 }   // namespace
 
@@ -223,6 +236,11 @@ void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipS
     if (stage == 0) { allow_big_lds(once1, prune_select_kernel<1>); hipLaunchKernelGGL(prune_select_kernel<1>, dim3(2, a.V), dim3(1024), lds, st, a); }
     else { allow_big_lds(once2, prune_select_kernel<2>); hipLaunchKernelGGL(prune_select_kernel<2>, dim3(2, a.V), dim3(1024), lds, st, a); }
 }
-void launch_rpn_prune_scatter(const RpnPruneArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(prune_scatter_kernel, dim3(64, a.V, 4), dim3(256), 0, st, a);
+void launch_rpn_prune_scatter(const RpnPruneArgs& a, int max_pix, hipStream_t st) {
+    // a view's selected rows are known on the device only: blocks for four elements a thread if every pixel of the largest view were selected,
+    // 64 at the most, which is what full-size views get (P2 at VOC size: 30 400 pixels x 15 / 16 384 threads = 28 elements a thread if every
+    // pixel were selected, ~2 at the measured 8 %); only small views get a smaller grid
+    const long long want = ((long long)max_pix * a.head_ld + 1023) / 1024;
+    const unsigned bx = (unsigned)(want < 1 ? 1 : want > 64 ? 64 : want);
+    hipLaunchKernelGGL(prune_scatter_kernel, dim3(bx, a.V, 4), dim3(256), 0, st, a);
 }

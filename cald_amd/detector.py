@@ -251,6 +251,13 @@ class HipDetector:
         _ffi.check(_ffi.lib().cald_model_set_rpn_prune(self.handle(), int(bool(on)), C.byref(was)))
         return bool(was.value)
 
+    def set_look_fuse(self, mode):
+        """The pruning's look-ahead (cald_model_set_look_fuse): 0 two launches, 1 the objectness head in conv_h4's epilogue where conv_h4 takes the
+        launch by its own rule (default), 2 wherever conv_h4 can run.  Returns the previous mode."""
+        was = C.c_int(0)
+        _ffi.check(_ffi.lib().cald_model_set_look_fuse(self.handle(), int(mode), C.byref(was)))
+        return was.value
+
     def set_rpn_prune_capture(self, on):
         """Test hook (cald_model_set_rpn_prune_capture): forward_views then takes the pruned RPN path and keeps the look-ahead's maps."""
         _ffi.check(_ffi.lib().cald_model_set_rpn_prune_capture(self.handle(), int(bool(on))))

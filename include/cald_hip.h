@@ -84,7 +84,8 @@ int cald_model_finalize(cald_model* m);
  * the previous state in *was (may be null).  cald_forward runs the dense head (unless capture mode is on, below). */
 int cald_model_set_rpn_prune(cald_model* m, int on, int* was);
 /* test hooks of the pruning: capture mode makes cald_forward take the pruned path too and keep the look-ahead's head maps as debug tensors
- * ("rpn_look0/1": [H][W][15], logits = channels 0..2; "rpn_pnorm0/1": the per-pixel |3 x 3 patch|_2; "rpn0/1": the maps the top-k reads, exact
+ * ("rpn_look0/1": [H][W][15], logits = channels 0..2, channels 3..14 the look-ahead's box deltas under cald_model_set_look_fuse mode 0 and zero
+ * where the fused look-ahead ran, which evaluates the logits only; "rpn_pnorm0/1": the per-pixel |3 x 3 patch|_2; "rpn0/1": the maps the top-k reads, exact
  * at selected pixels and -FLT_MAX elsewhere); cald_model_rpn_prune_bound returns the constants of B_a(p) = c1[a] * pnorm(p) + c0[a], a < 3 */
 int cald_model_set_rpn_prune_capture(cald_model* m, int on);
 int cald_model_rpn_prune_bound(cald_model* m, float* c1, float* c0);
@@ -343,6 +344,11 @@ typedef struct cald_conv_probe {
     float* out; int64_t out_n;             /* words, >= sum Ho Wo * out_ld; null = split-form output only */
     uint32_t* out16; int64_t out16_n;      /* split-form output or null */
     float* energy4; int64_t energy4_n;     /* [pixel][4] partial sums of squares or null */
+    /* conv_h4 grouped (path 9) only, optional: the look-ahead's head epilogue.  head_w [3][Cout] and head_b [3] of a 1 x 1 head on this conv's
+     * output (Cout == 256); head_out [>= sum Ho Wo][head_ld] receives the three logits in channels 0..2 and the conv's own output is not
+     * written (out / out16 may be null).  head_out null = no head */
+    const float* head_w; const float* head_b;
+    float* head_out; int64_t head_out_n; int head_ld;
 } cald_conv_probe;
 int cald_op_conv_probe(cald_ctx* ctx, int precision, cald_conv_probe* probs, int n, int path, int tile, char* kernel, int kernel_cap);
 /* Parity hook of CALD_PRECISION_F16X3's arithmetic primitive: n independent dot products D[i] = C[i] + sum_{k<16} A[i][k] B[i][k], each
@@ -411,6 +417,11 @@ int cald_profile_prune_fallbacks(cald_ctx* ctx, int64_t* n);
 /* cut_out reuse for one model: -1 = the process default (on unless CALD_CUTOUT_REUSE=0), 0 = off, 1 = on, 2 = on with every reused stage
  * run dense over the retained tensors (test hook).  Returns the previous setting in *was. */
 int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was);
+/* the certified pruning's look-ahead for one model: 0 = two launches (the split-fp16 3 x 3 conv writes the hidden tensor, the exact 1 x 1 head
+ * reads it), 1 = one launch wherever conv_h4 takes the look-ahead by its own rule, its epilogue evaluating the three objectness logits with the
+ * exact head's fma chain (default; same bits, the hidden tensor is never written), 2 = one launch wherever conv_h4 can run at all (test hook
+ * for small views).  Returns the previous setting in *was. */
+int cald_model_set_look_fuse(cald_model* m, int mode, int* was);
 /* cut_out reuse of the exact sweeps (CALD_CUTOUT_REUSE=0 disables it): per reused stage (layer1..layer3) the conv output rows the cut_out
  * forwards computed and the rows the dense stages would have (summed over the stage's convs), the batches that reused the reference
  * forward, and the batches whose cut_out views ran dense for want of retention memory.  Accumulated over the context's life. */
