@@ -94,6 +94,18 @@ class ConvProbe(C.Structure):
                 ("head_w", c_f), ("head_b", c_f), ("head_out", c_f), ("head_out_n", C.c_int64), ("head_ld", C.c_int)]
 
 
+PRUNE_PROBE_MAX_VIEWS = 8
+
+
+class RpnPruneProbe(C.Structure):
+    """cald_rpn_prune_probe (include/cald_hip.h): the arguments and results of cald_op_rpn_prune."""
+    _fields_ = [("V", C.c_int), ("guard", C.c_int), ("hw", ((C.c_int * 2) * PRUNE_PROBE_MAX_VIEWS) * 2),
+                ("pre_n", C.c_int), ("head_ld", C.c_int), ("c1", C.c_float * 3), ("c0", C.c_float * 3),
+                ("energy", c_f * 2), ("exact", c_f * 2), ("head", c_f * 2), ("pnorm", c_f * 2),
+                ("tau_key", C.POINTER(C.c_uint32)), ("row_map", (c_i * 2) * 2), ("nsel", c_i * 2),
+                ("check", C.c_float * 2), ("stat", C.c_uint64 * 4)]
+
+
 class WgradPlan(C.Structure):
     """cald_wgrad_plan (include/cald_hip.h): what cald_train_wgrad_plan answers."""
     _fields_ = [("variant", C.c_int), ("reduce", C.c_int), ("MT", C.c_int), ("JT", C.c_int), ("S", C.c_longlong), ("chunk", C.c_longlong),
@@ -114,6 +126,7 @@ SIGNATURES = {
     "cald_model_set_rpn_prune": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_rpn_prune_capture": (C.c_int, [C.c_void_p, C.c_int]),
     "cald_model_rpn_prune_bound": (C.c_int, [C.c_void_p, c_f, c_f]),
+    "cald_model_set_rpn_prune_bound": (C.c_int, [C.c_void_p, c_f, c_f]),
     "cald_profile_prune_fallbacks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "cald_model_destroy": (C.c_int, [C.c_void_p]),
     "cald_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(View), C.POINTER(Dets)]),
@@ -145,6 +158,7 @@ SIGNATURES = {
                                             C.c_int, c_f, c_f, c_i64, c_f, c_f, c_f, c_i]),
     "cald_op_retina_postprocess": (C.c_int, [C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f] + [C.c_int] * 6
                                    + [C.c_float, C.c_float, C.c_int, c_f, c_f, c_i64, c_f, c_f, c_i]),
+    "cald_op_rpn_prune": (C.c_int, [C.c_void_p, C.POINTER(RpnPruneProbe)]),
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),
     "cald_op_conv2d": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),

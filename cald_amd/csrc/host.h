@@ -129,6 +129,7 @@ struct cald_model {
     // the look-ahead's 1 x 1 objectness head in conv_h4.hip's epilogue (cald_model_set_look_fuse): 0 off (two launches), 1 where conv_h4 takes the
     // look-ahead launch by its own rule, 2 wherever conv_h4 is correct (test hook for small views); the head's first three channels [3][256] + bias
     int look_fuse = 1; float* look_head_w = nullptr; float look_head_b[3] = {0, 0, 0};
+    bool prune_bound_voided = false;   // test hook cald_model_set_rpn_prune_bound replaced finalize's constants: the sweeps' ratios are not the certificate's
     bool prune_capture = false;     // test hook: cald_forward takes the pruned path too and keeps the look-ahead's logit map (cald_model_set_rpn_prune_capture)
     ConvLayer p6, p7, cls_tower[4], reg_tower[4], cls_out, reg_out;   // RetinaNet
     int det_cap() const { return cfg.arch == CALD_ARCH_RETINANET ? cfg.num_classes * cfg.detections_per_img : cfg.detections_per_img; }

@@ -386,6 +386,15 @@ extern "C" int cald_model_rpn_prune_bound(cald_model* m, float* c1, float* c0) {
     for (int a = 0; a < 3; a++) { c1[a] = m->prune_c1[a]; c0[a] = m->prune_c0[a]; }
     return 0;
 }
+// test hook: other constants from the next forward on.  Voids the certificate (the header says so): the sweep keeps its tripwires, but its ratio
+// no longer enters cald_profile_prune's worst_bound_ratio.  Any float is taken -- a NaN constant is one of the tripwire's tests.
+extern "C" int cald_model_set_rpn_prune_bound(cald_model* m, const float* c1, const float* c0) {
+    if (!m || !c1 || !c0) return fail(CALD_ERR_INVALID, "null argument");
+    if (!m->rpn_conv16.w16) return fail(CALD_ERR_STATE, "the model has no look-ahead layer (not an exact Faster R-CNN model)");
+    for (int a = 0; a < 3; a++) { m->prune_c1[a] = c1[a]; m->prune_c0[a] = c0[a]; }
+    m->prune_bound_voided = true;
+    return 0;
+}
 extern "C" int cald_model_destroy(cald_model* m) {
     if (!m) return 0;
     hipSetDevice(m->ctx->device);

@@ -538,6 +538,90 @@ extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, 
     return download_dets(c, det.d, "retina", boxes_out, scores_out, labels_out, nullptr, prob_max_out, scores_cls_out, n_out);
 }
 
+// ---------------------------------------------------------------------------------------------
+// test-only probe of the certified pruning (tests/test_gpu_rpn_prune_edges.py): one RpnPruneArgs and what ForwardRun::rpn_pruned runs with
+// it, in its order -- select stage 0, select stage 1, scatter -- with the gathered exact convs between them PLAYED by the host: after each
+// select, nsel / row_map come back, that stage's head_rows are gathered from the caller's dense exact map (compact per view at the view's
+// pixel offset; NaN past nsel, so a row read beyond the count shows in check[0]) and go up again.  A count or a row index outside its view
+// is refused before anything reads through it.  In / out arrays travel whole, guard words included (the header has the layout).
+// ---------------------------------------------------------------------------------------------
+extern "C" int cald_op_rpn_prune(cald_ctx* c, cald_rpn_prune_probe* p) {
+    if (!c || !p) return fail(CALD_ERR_INVALID, "cald_op_rpn_prune: null argument");
+    if (p->V < 1 || p->V > CALD_PRUNE_PROBE_MAX_VIEWS || p->guard < 0 || p->guard > 4096 || p->head_ld < 3 || p->head_ld > 64 || p->pre_n < 1)
+        return fail(CALD_ERR_INVALID, "cald_op_rpn_prune: 1..%d views, guard 0..4096, head_ld 3..64, pre_n >= 1", CALD_PRUNE_PROBE_MAX_VIEWS);
+    const int V = p->V, ld = p->head_ld; const size_t G = (size_t)p->guard;
+    constexpr int SV = CALD_PRUNE_PROBE_MAX_VIEWS + 1;
+    LevelSeg seg[2 * SV]; memset(seg, 0, sizeof(seg));
+    size_t pix[2]; int max_pix = 0;                 // the select kernels' mask holds one bit per pixel of the largest view of EITHER level
+    for (int l = 0; l < 2; l++) {
+        for (int v = 0; v < V; v++) {
+            const int H = p->hw[l][v][0], W = p->hw[l][v][1];
+            if (H < 1 || W < 1 || (long long)H * W > (1 << 19)) return fail(CALD_ERR_INVALID, "cald_op_rpn_prune: level %d view %d: 1 <= H * W <= 2^19", l, v);
+            seg[l * SV + v].H = H; seg[l * SV + v].W = W; seg[l * SV + v + 1].pix_off = seg[l * SV + v].pix_off + (long long)H * W;
+            if (H * W > max_pix) max_pix = H * W;
+        }
+        pix[l] = (size_t)seg[l * SV + V].pix_off;
+        if (!p->energy[l] || !p->exact[l] || !p->head[l] || !p->pnorm[l]) return fail(CALD_ERR_INVALID, "cald_op_rpn_prune: level %d: null array", l);
+    }
+    for (int s = 0; s < 2; s++) if (!p->nsel[s] || !p->row_map[s][0] || !p->row_map[s][1] || !p->tau_key) return fail(CALD_ERR_INVALID, "cald_op_rpn_prune: null output array");
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    RpnPruneArgs pr; memset(&pr, 0, sizeof(pr));
+    const LevelSeg* d_seg; float* d_rows[2][2]; int rc;
+    const size_t nw = (size_t)2 * V + G;
+    if ((rc = sd.upload(&d_seg, seg, sizeof(seg))) || (rc = sd.upload(&pr.tau_key, p->tau_key, nw * 4)) || (rc = sd.upload(&pr.check, p->check, 8)) ||
+        (rc = sd.alloc(&pr.stat, 32))) return rc;
+    HIPCHK(hipMemset(pr.stat, 0, 32));
+    for (int l = 0; l < 2; l++) {
+        pr.seg[l] = d_seg + l * SV;
+        if ((rc = sd.upload(&pr.energy[l], p->energy[l], pix[l] * 16)) || (rc = sd.upload(&pr.pnorm[l], p->pnorm[l], (pix[l] + G) * 4)) ||
+            (rc = sd.upload(&pr.head_out[l], p->head[l], (pix[l] + G) * ld * 4))) return rc;
+        pr.head[l] = pr.head_out[l];
+        for (int s = 0; s < 2; s++) {
+            if ((rc = sd.upload(&pr.row_map[s][l], p->row_map[s][l], (pix[l] + G) * 4)) || (rc = sd.alloc(&d_rows[s][l], pix[l] * ld * 4))) return rc;
+            pr.head_rows[s][l] = d_rows[s][l];
+        }
+    }
+    for (int s = 0; s < 2; s++) if ((rc = sd.upload(&pr.nsel[s], p->nsel[s], nw * 4))) return rc;
+    for (int q = 0; q < 3; q++) { pr.c1[q] = p->c1[q]; pr.c0[q] = p->c0[q]; }
+    pr.head_ld = ld; pr.pre_n = p->pre_n; pr.V = V;
+    auto maps_back = [&](int s) {
+        HIPCHK(hipMemcpy(p->nsel[s], pr.nsel[s], nw * 4, hipMemcpyDeviceToHost));
+        for (int l = 0; l < 2; l++) HIPCHK(hipMemcpy(p->row_map[s][l], pr.row_map[s][l], (pix[l] + G) * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    for (int s = 0; s < 2; s++) {
+        launch_rpn_prune_select(pr, max_pix, s, c->stream);
+        HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = maps_back(s))) return rc;
+        if (s == 0) HIPCHK(hipMemcpy(p->tau_key, pr.tau_key, nw * 4, hipMemcpyDeviceToHost));
+        for (int l = 0; l < 2; l++) {       // the gathered exact conv + head of this stage
+            std::vector<float> rows(pix[l] * ld, NAN);
+            for (int v = 0; v < V; v++) {
+                const LevelSeg& sg = seg[l * SV + v];
+                const int npx = sg.H * sg.W, ns = p->nsel[s][l * V + v];
+                if (ns < 0 || ns > npx) return fail(CALD_ERR_HIP, "cald_op_rpn_prune: stage %d level %d view %d selected %d of %d pixels", s, l, v, ns, npx);
+                for (int r = 0; r < ns; r++) {
+                    const int px = p->row_map[s][l][sg.pix_off + r];
+                    if (px < 0 || px >= npx) return fail(CALD_ERR_HIP, "cald_op_rpn_prune: stage %d level %d view %d row %d maps to pixel %d of %d", s, l, v, r, px, npx);
+                    memcpy(&rows[(size_t)(sg.pix_off + r) * ld], p->exact[l] + (size_t)(sg.pix_off + px) * ld, (size_t)ld * 4);
+                }
+            }
+            HIPCHK(hipMemcpy(d_rows[s][l], rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+        }
+    }
+    launch_rpn_prune_scatter(pr, max_pix, c->stream);
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < 2; s++) if ((rc = maps_back(s))) return rc;          // once more, whole: neither a later select nor the scatter may have touched them
+    for (int l = 0; l < 2; l++) {
+        HIPCHK(hipMemcpy(p->head[l], pr.head_out[l], (pix[l] + G) * ld * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(p->pnorm[l], pr.pnorm[l], (pix[l] + G) * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(p->check, pr.check, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(p->stat, pr.stat, 32, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // MultiScaleRoIAlign(7, sampling_ratio 2) of ONE view on the inference kernels (roi.hip): feats[l] = host [H_l][W_l][C] for the four
 // levels P2..P5 (level_hw = {H0, W0, ..., H3, W3}), rois [R][4] in image coordinates, out [R][49][C] (host).  C == 256 runs the
 // row-walk kernel, other C (multiple of 4) the gather kernel.  Parity hook for detection/frcnn_la.py:205-209.

@@ -595,7 +595,7 @@ static int sweep_checked(cald_model* m, int n_images, const uint8_t* const* imag
     float chk[2] = {0.0f, 0.0f};
     HIPCHK(hipMemcpy(chk, c->d_prune_check, 8, hipMemcpyDeviceToHost));
     const bool range = chk[1] != 0.0f;
-    if (chk[0] == chk[0] && !range) c->prune_worst = chk[0] > c->prune_worst ? chk[0] : c->prune_worst;
+    if (chk[0] == chk[0] && !range && !m->prune_bound_voided) c->prune_worst = chk[0] > c->prune_worst ? chk[0] : c->prune_worst;
     if (!(chk[0] <= 1.0f) || range) {
         c->prune_fallbacks++;
         SweepRun dense{m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, true};

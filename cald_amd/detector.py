@@ -269,6 +269,13 @@ class HipDetector:
         _ffi.check(_ffi.lib().cald_model_rpn_prune_bound(self.handle(), _ffi.ptr(c1), _ffi.ptr(c0)))
         return c1, c0
 
+    def set_rpn_prune_bound(self, c1, c0):
+        """Test hook (cald_model_set_rpn_prune_bound): other constants from the next forward on.  Voids the pruning's certificate."""
+        import numpy as np
+        c1 = np.ascontiguousarray(c1, np.float32); c0 = np.ascontiguousarray(c0, np.float32)
+        assert c1.shape == (3,) and c0.shape == (3,)
+        _ffi.check(_ffi.lib().cald_model_set_rpn_prune_bound(self.handle(), _ffi.ptr(c1), _ffi.ptr(c0)))
+
     def debug_tensor(self, name, view=0):
         shape = (C.c_int64 * 3)()
         cap = 1 << 26

@@ -89,6 +89,11 @@ int cald_model_set_rpn_prune(cald_model* m, int on, int* was);
  * at selected pixels and -FLT_MAX elsewhere); cald_model_rpn_prune_bound returns the constants of B_a(p) = c1[a] * pnorm(p) + c0[a], a < 3 */
 int cald_model_set_rpn_prune_capture(cald_model* m, int on);
 int cald_model_rpn_prune_bound(cald_model* m, float* c1, float* c0);
+/* test hook, the setter twin: replaces the bound's constants from the next forward on.  This VOIDS THE CERTIFICATE -- the constants of
+ * cald_model_finalize are the theorem's, any others are not -- and exists so that a test can make the sweep's ratio tripwire fire (a bound
+ * scaled far below the look-ahead's error, a NaN constant).  Sweeps of a model whose bound was set this way still check and fall back, but
+ * their ratio is not entered into cald_profile_prune's worst_bound_ratio, which speaks about the certified bound only. */
+int cald_model_set_rpn_prune_bound(cald_model* m, const float* c1, const float* c0);
 int cald_model_destroy(cald_model* m);
 
 /* One detector input: task_model([tensor]) in cald_train.py:107 / :186.  The view is described by
@@ -297,6 +302,30 @@ int cald_op_retina_postprocess(cald_ctx* ctx, const float* const* cls, const flo
                                float score_thr, float nms_thr, int per_class,
                                float* boxes_out, float* scores_out, int64_t* labels_out, float* prob_max_out,
                                float* scores_cls_out, int* n_out);
+/* The certified pruning's three kernels outside any model (rpn_prune.hip: select stage 0, select stage 1, scatter, in the forward's order;
+ * tests/test_gpu_rpn_prune_edges.py).  The hook plays the gathered exact convs itself: after each select it reads nsel / row_map back and
+ * gathers that stage's exact head rows from `exact` by row_map -- compact per view at the view's pixel offset, as the gathered launch
+ * writes them; rows past nsel hold NaN.  All arrays are host memory.  Per level l < 2 and view v < V the geometry is hw[l][v] = {H, W}
+ * (ragged views; level 1 need not be smaller than level 0); pix_l = sum of H * W.  Every per-pixel array holds pix_l + guard pixels and
+ * tau_key / nsel[s] hold 2 * V + guard words: in / out arrays are copied to the device whole and back whole, so sentinels the caller put
+ * into unused slots and guard words show any stray store. */
+#define CALD_PRUNE_PROBE_MAX_VIEWS 8
+typedef struct {
+    int V, guard;
+    int hw[2][CALD_PRUNE_PROBE_MAX_VIEWS][2];
+    int pre_n, head_ld;                 /* head_ld >= 3: logits are channels 0..2 */
+    float c1[3], c0[3];                 /* B_a(p) = c1[a] * pnorm(p) + c0[a] */
+    const float* energy[2];             /* in  [pix_l][4] (no guard) */
+    const float* exact[2];              /* in  [pix_l][head_ld]: the dense exact head map (no guard) */
+    float* head[2];                     /* in: the look-ahead's map, out: the final map; [pix_l + guard][head_ld] */
+    float* pnorm[2];                    /* in / out [pix_l + guard] */
+    uint32_t* tau_key;                  /* in / out [2 * V + guard], read back after stage 0 */
+    int* row_map[2][2];                 /* in / out [stage][level] [pix_l + guard] */
+    int* nsel[2];                       /* in / out [stage] [2 * V + guard] */
+    float check[2];                     /* in: the initial check words, out: the final ones */
+    uint64_t stat[4];                   /* out: selected / total pixels of level 0, of level 1 (from zero) */
+} cald_rpn_prune_probe;
+int cald_op_rpn_prune(cald_ctx* ctx, cald_rpn_prune_probe* p);
 /* MultiScaleRoIAlign(output 7, sampling_ratio 2, aligned=False; detection/frcnn_la.py:205-209) of one view on the forward's own
  * kernels: feats[l] = [H_l][W_l][C] (host) for P2..P5, level_hw = {H0, W0, ..., H3, W3}, rois [R][4]; out [R][49][C] (host) */
 int cald_op_roi_align(cald_ctx* ctx, const float* const* feats, const int* level_hw, int C, int R, const float* rois, float* out);
