@@ -80,7 +80,7 @@ struct ConvArgs {
     int out_ld;            // output row stride in floats (== Cout normally)
     const float* zeros;    // >= 16 bytes of zeros, 16-byte aligned (source of out-of-image taps)
     int in_relu;           // apply ReLU to the input while gathering (LastLevelP6P7: p7(relu(p6)))
-    // training backward only (train.hip; honoured by conv_p4.hip): after everything else, out = mask > 0 ? out : 0 -- the ReLU backward
+    // training backward only (train_conv.hip; honoured by conv_p4.hip): after everything else, out = mask > 0 ? out : 0 -- the ReLU backward
     // of the layer whose saved post-ReLU output `mask` (same geometry and row stride as out) this data gradient flows into; else null
     const float* mask;
     // conv_stem.hip: the 7 x 7 / 2 stem's weights packed [20 quads of k-pairs][2 h][64 n][4] over the 154-slot chain (7 filter rows x

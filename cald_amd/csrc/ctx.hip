@@ -1,4 +1,4 @@
-// ctx.hip -- error state, the context (stream, arena, scratch), the cald_internal_* accessors of train.hip / jpeg.hip / comm.hip, the event
+// ctx.hip -- error state, the context (stream, arena, scratch), the cald_internal_* accessors of train_*.hip (train_host.h) / jpeg.hip / comm.hip, the event
 // profile (cald_profile_*) and the one conv launch every layer goes through (run_conv).
 #include "host.h"
 
@@ -13,7 +13,7 @@ int cald_internal_fail(int code, const char* fmt, ...) {
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
     return code;
 }
-void cald_internal_train_release(cald_ctx* c);   // train.hip: per-context geometry cache
+void cald_internal_train_release(cald_ctx* c);   // train_geom.hip: per-context geometry cache and staging ring
 
 extern "C" const char* cald_last_error(void) { return g_err; }
 extern "C" int cald_version(void) { return 100; }

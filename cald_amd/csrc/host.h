@@ -1,6 +1,6 @@
 // host.h -- what the host files of the C ABI (ctx.hip, ops.hip, model.hip, forward.hip, sweep.hip, lossnet.hip) share: the context and the model
 // behind the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those six
-// files alone: train.hip, jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
+// files alone: the train_*.hip files (train_host.h), jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
 #pragma once
 #include "../../include/cald_hip.h"
 #include "common.h"
@@ -65,7 +65,7 @@ struct cald_ctx {
     std::map<size_t, GatherNote> prof_gather;     // launch index -> which log slot, and the FLOPs its P2 / P3 problems would cost on every pixel
     unsigned long long* d_roi_rows = nullptr; double prof_roi_rows_cap = 0.0, prof_roi_flops_cap = 0.0; long long prof_roi_views = 0;
     std::map<PilKey, PilCoef> pil;
-    char* train_scratch = nullptr; size_t train_scratch_cap = 0;   // train.hip: split-K partial tiles of the weight gradients
+    char* train_scratch = nullptr; size_t train_scratch_cap = 0;   // cald_internal_scratch: the training operators' scratch (train_wgrad.hip: split-K partial tiles of the weight gradients)
     // cut_out reuse (cald_profile_cutout): per reused stage the conv output rows the cut_out forwards computed and what the dense forwards
     // would have; batches whose cut_out views reused the reference forward, batches that could not (the retention did not fit)
     double cut_rows[3] = {0.0, 0.0, 0.0}, cut_dense[3] = {0.0, 0.0, 0.0};

@@ -83,7 +83,7 @@ struct RoiArgs {
 };
 void launch_roi_align(const RoiArgs& a, hipStream_t st);
 
-// MultiScaleRoIAlign pieces shared by the inference kernel (roi.hip) and the training kernels (train.hip)
+// MultiScaleRoIAlign pieces shared by the inference kernel (roi.hip) and the training kernels (train_roi.hip)
 __device__ inline int roi_level(const float4 b) {
     const float area = (b.z - b.x) * (b.w - b.y);
     const float s = sqrtf(area);

@@ -9,15 +9,7 @@
 // Backward: every sum over the batch runs b ascending from +0 in one thread (product, then add: -ffp-contract=off), the gradient of the
 // pooled vector is one d-ordered fmaf chain from +0; no atomics, two runs are bit-identical.  All kernels are launch-bound (B = 4 images,
 // 0.5 MB of weights): one workgroup per output row, coalesced over the 256 channels where a tensor is that wide.
-#include "common.h"
-#include "../../include/cald_hip.h"
-
-int cald_internal_fail(int code, const char* fmt, ...);
-hipStream_t cald_internal_stream(cald_ctx* c);
-int cald_internal_device(cald_ctx* c);
-
-#define TFAIL(code, ...) return cald_internal_fail(code, __VA_ARGS__)
-#define THIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return cald_internal_fail(CALD_ERR_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+#include "train_host.h"
 
 #define LL_C 256              // channels of every pyramid level
 #define LPL_MAX_B 2048        // LossPredLoss: one workgroup, the pair terms meet in LDS

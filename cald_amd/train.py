@@ -7,7 +7,7 @@ What the reference does per iteration (cald_train.py:40-74 ``train_one_epoch``; 
 
 with ``task_model`` = detection/frcnn_la.py ``FRCNN_Feature`` in train mode -- i.e. torchvision 0.8.2's GeneralizedRCNN training
 forward (transform -> ResNet-FPN -> RPN losses -> sampled RoI-head losses) under torch autograd on cuDNN/cuBLAS.  Here the same
-graph is strung from the ``cald_train_*`` device operators (cald_amd/csrc/train.hip): the forward runs on the inference MFMA
+graph is strung from the ``cald_train_*`` device operators (cald_amd/csrc/train_*.hip): the forward runs on the inference MFMA
 kernels with weights packed on the device every step, the backward is hand-written (data gradients on the same kernels with the
 flipped filter, weight gradients on the split-K MFMA kernel, RoIAlign / FPN / ReLU / FrozenBatchNorm backward kernels), and
 ``SGD`` is one fused kernel per tensor.  torch supplies device memory, the stream, the Parameter / Optimizer / autograd-Function

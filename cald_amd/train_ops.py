@@ -1,4 +1,4 @@
-"""Thin wrappers of the cald_train_* device operators (include/cald_hip.h, cald_amd/csrc/train.hip) on torch CUDA tensors.
+"""Thin wrappers of the cald_train_* device operators (include/cald_hip.h, cald_amd/csrc/train_*.hip) on torch CUDA tensors.
 
 torch supplies device memory and the stream only; every arithmetic step is a libcaldhip kernel.  Activations are NHWC
 float32 [N, H, W, C].  No fallback: without the library or an MI355X every call raises.

@@ -1,5 +1,5 @@
-"""Helper of tests/test_gpu_train_variants.py::test_environment_switch_paths_in_child_processes: train.hip reads its environment
-switches once per process, so each setting runs the fixed subset of cases in a process of its own.  argv: out_prefix repo_root"""
+"""Helper of tests/test_gpu_train_variants.py::test_environment_switch_paths_in_child_processes: train_wgrad.hip and train_roi.hip read their
+environment switches once per process, so each setting runs the fixed subset of cases in a process of its own.  argv: out_prefix repo_root"""
 import os
 import sys
 sys.path.insert(0, sys.argv[2])

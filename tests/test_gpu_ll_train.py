@@ -1,5 +1,5 @@
 """GPU tests of the learning-loss TRAINING step (cald_amd/ll_train.py, lossnet_train.hip, cald_train_gap, the segmented loss kernels and
-the broadcast join of train.hip): operators against the executed reference (tests/golden/lossnet_train.npz, frcnn_losses.npz) and the
+the broadcast join of train_loss.hip / train_elementwise.hip): operators against the executed reference (tests/golden/lossnet_train.npz, frcnn_losses.npz) and the
 sweep's operators bit for bit, and the epoch loop on the reference run's recorded inputs.  Tolerance: test_gpu_train.py's operator-level
 1e-5 of the reference's largest entry.  The tests that build a FasterRCNNTrainer (whole steps, round trip, unchanged behaviour) are in
 tests/test_gpu_train_ll_step.py, which -- like every other file that builds a trainer -- sorts behind test_gpu_parity.py (see its docstring)."""

@@ -1,4 +1,4 @@
-"""Every variant of the training kernels (cald_amd/csrc/train.hip) run directly: the weight-gradient plan pinned by a host query and
+"""Every variant of the training kernels (cald_amd/csrc/train_*.hip) run directly: the weight-gradient plan pinned by a host query and
 driven through every kernel / split / reduction edge with EXACT-INTEGER operands, RoIAlign forward and backward at the production
 channel count with every merge pattern named, the code behind the environment switches in child processes, and the small backward
 kernels at the sizes where a vector grid has a tail block.
@@ -441,7 +441,7 @@ def roi_sample_np(start, bin_, p, i, size):
 
 
 def roi_setup_np(box, dims):
-    """train.hip:roi_setup: level, the 14 row samples and the 14 column samples of one box, and whether rw / rh were raised to 1."""
+    """train_roi.hip:roi_setup: level, the 14 row samples and the 14 column samples of one box, and whether rw / rh were raised to 1."""
     box = [F32(v) for v in box]
     l = roi_level_np(box)
     scale = F32(1.0) / F32(4 << l)
