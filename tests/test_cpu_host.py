@@ -535,6 +535,36 @@ def test_sampler_draws_are_uniform_subsets():
     assert abs(counts / 4000 - 0.1).max() < 0.02          # each element is drawn with probability k / n = 0.1
 
 
+def test_anchor_slots_equal_a_walk_over_the_flat_head_buffer():
+    """cald_amd.train_core.anchor_slots (which float of a flat head buffer a loss kernel reads for an anchor) against a brute-force
+    walk level -> image -> pixel -> anchor over a tiny pyramid with a running offset, for the RPN head's layout (3 anchors per
+    pixel, rows of 16 floats) and RetinaNet's regression head's (9, 36): every offset and every anchor-in-pixel number equal, for
+    indices in unsorted order that include each level's first and last anchor."""
+    from cald_amd.train_core import anchor_slots
+    level_hw, N = [(2, 3), (1, 2), (1, 1)], 2
+    level_pix = [h * w for h, w in level_hw]
+    for per_pix, ld in ((3, 16), (9, 36)):
+        want, off, first = {}, 0, 0                 # (image, anchor number within the image's pyramid) -> (row offset, a)
+        edges = []
+        for h, w in level_hw:
+            for img in range(N):
+                for pix in range(h * w):
+                    for a in range(per_pix):
+                        want[(img, first + pix * per_pix + a)] = (off, a)
+                    off += ld
+            edges += [first, first + h * w * per_pix - 1]
+            first += h * w * per_pix
+        assert first == sum(level_pix) * per_pix and off == N * sum(level_pix) * ld
+        rs = np.random.RandomState(per_pix)
+        idx = rs.permutation(first)                 # every anchor, unsorted
+        assert not np.array_equal(idx, np.sort(idx)) and set(edges) <= set(idx.tolist())
+        for sel in (idx, np.array(edges[::-1]), np.zeros(0, np.int64)):
+            for img in range(N):
+                row, a = anchor_slots(img, sel, level_pix, per_pix, ld, N)
+                assert len(row) == len(a) == len(sel)
+                assert [(int(r), int(k)) for r, k in zip(row, a)] == [want[(img, int(i))] for i in sel], (per_pix, ld, img)
+
+
 def test_training_transform_flip_matches_reference_golden(golden):
     """cald_amd.voc_utils.RandomHorizontalFlip (the training transform of get_transform(train=True)) == the imported
     detection/transforms.py class on ten draws of Python's `random` (seed 11): same flips, same mirrored boxes."""

@@ -527,7 +527,7 @@ def test_pack_plan_writes_the_per_layer_packs_bit_for_bit(T):
     # and the model: a step with the plan equals a step with per-layer packs
     res = []
     for use_plan in (True, False):
-        train._PACK_PLAN = use_plan
+        train.FasterRCNNTrainer._PACK_PLAN = use_plan
         try:
             net = train.FasterRCNNTrainer(sd, 21, min_size=160, max_size=256, generator=torch.Generator().manual_seed(5))
             out = []
@@ -538,7 +538,7 @@ def test_pack_plan_writes_the_per_layer_packs_bit_for_bit(T):
             res.append(out)
             assert (net._pack_plan is not None) == use_plan
         finally:
-            train._PACK_PLAN = True
+            del train.FasterRCNNTrainer._PACK_PLAN             # back to _TrainerBase's, read from CALD_TRAIN_PACK_PLAN
     for a, b in zip(*res):
         assert a[0] == b[0]
         for k in a[1]:
