@@ -222,6 +222,9 @@ SIGNATURES = {
     "cald_train_smooth_l1_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, c_f, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "cald_train_bce_logits_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cald_train_focal_loss_seg": (C.c_int, [C.c_void_p, C.c_int, c_i, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            c_f, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "cald_train_seg_mean": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "cald_train_add_bcast": (C.c_int, [C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]),
     "cald_train_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_i, C.c_int, C.c_int, C.c_void_p]),
     "cald_train_maxpool": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

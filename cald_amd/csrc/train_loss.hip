@@ -219,3 +219,99 @@ extern "C" int cald_train_focal_loss(cald_ctx* c, int N, const int* level_pix, i
     THIP(hipGetLastError());
     return 0;
 }
+
+// The same loss per IMAGE (retina_ll.py:100-132): loss[n] = (sum of image n's raw terms) / denom[n], one IEEE division, as the
+// reference's sigmoid_focal_loss(..., 'sum') / max(1, num_foreground); grad = g * (gs[n] / denom[n]).  The grid is (blocks per
+// image, N): no workgroup covers anchors of two images, block (b, n) sums anchors [256 b, 256 b + 256) of image n and the finishing
+// kernel (one workgroup per image) adds image n's partials with the thread-strided sum + block_sum_256 -- so image n's loss and gradient
+// bits are those of the same image submitted alone.  Ignored anchors write nothing (the caller zeroed grad); pad columns are not touched.
+struct FocalSegArgs { FocalArgs f; float denom[TRAIN_MAX_SEG]; const float* seg_gscale; };
+__global__ __launch_bounds__(256) void focal_loss_seg_kernel(const FocalSegArgs s, float* partial) {
+    __shared__ float red[256];
+    const FocalArgs& a = s.f;
+    const int n = blockIdx.y;
+    const long long an = (long long)blockIdx.x * 256 + threadIdx.x;
+    float local = 0.0f;
+    if (an < a.A_tot) {
+        const int m = a.matched[(long long)n * a.A_tot + an];
+        if (m != -2) {
+            int l = 0;
+            while (l < 4 && an >= a.lvl_anchor0[l + 1]) l++;
+            const long long rel = an - a.lvl_anchor0[l];
+            const long long pix = rel / a.A; const int aa = (int)(rel - pix * a.A);
+            const long long base = a.lvl_off[l] + ((long long)n * a.lvl_pix[l] + pix) * a.ld + (long long)aa * a.K;
+            const int cls = m >= 0 ? (int)a.gt_labels[a.gt_off[n] + m] : -1;
+            const float w = (s.seg_gscale ? s.seg_gscale[n] : 1.0f) / s.denom[n];
+            for (int k = 0; k < a.K; k++) {
+                const float x = a.logits[base + k];
+                const float lse = det_logf(1.0f + det_expf(-fabsf(x)));          // log(1 + exp(-|x|))
+                const float logp = -((x < 0.0f ? -x : 0.0f) + lse);               // log sigmoid(x)
+                const float log1mp = -((x > 0.0f ? x : 0.0f) + lse);              // log (1 - sigmoid(x))
+                const float p = det_sigmoidf(x), q = 1.0f - p;
+                float loss, g;
+                if (k == cls) { loss = -a.alpha * q * q * logp; g = a.alpha * q * q * (2.0f * p * logp - q); }
+                else { loss = -(1.0f - a.alpha) * p * p * log1mp; g = (1.0f - a.alpha) * p * p * (p - 2.0f * q * log1mp); }
+                local += loss;
+                if (a.grad) a.grad[base + k] = g * w;
+            }
+        }
+    }
+    const float tot = block_sum_256(local, red);
+    if (threadIdx.x == 0) partial[(long long)n * gridDim.x + blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(256) void focal_seg_finish_kernel(const FocalSegArgs s, const float* partial, int per_img, float* loss) {
+    __shared__ float red[256];
+    const int n = blockIdx.x;
+    float local = 0.0f;
+    for (int i = threadIdx.x; i < per_img; i += 256) local += partial[(long long)n * per_img + i];
+    const float tot = block_sum_256(local, red);
+    if (threadIdx.x == 0) loss[n] = tot / s.denom[n];
+}
+// _sum(losses) / len(targets) of retina_ll.py:132 and :220 in float32: (((l_0 + l_1) + ...) + l_{N-1}) / (float)N, image order
+__global__ void seg_mean_kernel(const float* loss, int N, float* mean_out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float s = loss[0];
+        for (int i = 1; i < N; i++) s += loss[i];
+        *mean_out = s / (float)N;
+    }
+}
+extern "C" int cald_train_seg_mean(cald_ctx* c, int N, const float* losses, float* mean_out) {
+    if (!c || !losses || !mean_out || N < 1) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipLaunchKernelGGL(seg_mean_kernel, dim3(1), dim3(64), 0, cald_internal_stream(c), losses, N, mean_out);
+    THIP(hipGetLastError());
+    return 0;
+}
+extern "C" int cald_train_focal_loss_seg(cald_ctx* c, int N, const int* level_pix, int A, int K, int ld, const float* logits, const int* matched,
+                                         const int64_t* gt_labels, const int* gt_off, const float* denom, float alpha, const float* gscale,
+                                         float* loss_out, float* mean_out, float* grad) {
+    if (!c || !level_pix || !logits || !matched || !gt_labels || !gt_off || !denom || !loss_out) TFAIL(CALD_ERR_INVALID, "null argument");
+    if (N < 1 || N > TRAIN_MAX_SEG) TFAIL(CALD_ERR_INVALID, "%d images outside [1, %d]", N, TRAIN_MAX_SEG);
+    if (A < 1 || K < 1 || ld < A * K) TFAIL(CALD_ERR_INVALID, "bad geometry");
+    FocalSegArgs s; memset(&s, 0, sizeof(s));
+    FocalArgs& a = s.f;
+    for (int n = 0; n < N; n++) {
+        if (!(denom[n] > 0.0f)) TFAIL(CALD_ERR_INVALID, "denominator of image %d is not positive", n);
+        s.denom[n] = denom[n];
+    }
+    s.seg_gscale = gscale;
+    a.logits = logits; a.grad = grad; a.matched = matched; a.gt_labels = (const long long*)gt_labels; a.gt_off = gt_off;
+    long long an = 0, off = 0;
+    for (int l = 0; l < 5; l++) {
+        if (level_pix[l] < 0) TFAIL(CALD_ERR_INVALID, "negative level size");
+        a.lvl_anchor0[l] = an; a.lvl_off[l] = off; a.lvl_pix[l] = level_pix[l];
+        an += (long long)level_pix[l] * A; off += (long long)N * level_pix[l] * ld;
+    }
+    if (an < 1 || (an + 255) / 256 > 0x7fffffffLL) TFAIL(CALD_ERR_INVALID, "bad geometry");
+    a.lvl_anchor0[5] = an; a.A_tot = an; a.N = N; a.A = A; a.K = K; a.ld = ld; a.alpha = alpha; a.gscale = 1.0f;
+    const int per_img = (int)((an + 255) / 256);
+    THIP(hipSetDevice(cald_internal_device(c)));
+    hipStream_t st = cald_internal_stream(c);
+    void* scratch = nullptr;
+    if (int rc = cald_internal_scratch(c, (size_t)N * per_img * 4 + 64, &scratch)) return rc;
+    hipLaunchKernelGGL(focal_loss_seg_kernel, dim3(per_img, N), dim3(256), 0, st, s, (float*)scratch);
+    hipLaunchKernelGGL(focal_seg_finish_kernel, dim3(N), dim3(256), 0, st, s, (const float*)scratch, per_img, loss_out);
+    if (mean_out) hipLaunchKernelGGL(seg_mean_kernel, dim3(1), dim3(64), 0, st, (const float*)loss_out, N, mean_out);
+    THIP(hipGetLastError());
+    return 0;
+}

@@ -1,6 +1,6 @@
 """Training the loss-prediction module (LL4AL's LossNet) beside the detector: ll_train.py:55-142 on the MI355X.
 
-    features, task_loss_dict = task_model(images, targets)       # train.TrainableDetector over FasterRCNNTrainer(loss_mode="ll")
+    features, task_loss_dict = task_model(images, targets)       # train.TrainableDetector over FasterRCNNTrainer(loss_mode="ll") or RetinaNetLLTrainer
     ll_pred = ll_model(features)                                   # LossNet below: cald_lossnet_train_fwd
     ll_loss = ll_weight * LossPredLoss(ll_pred, sum of the per-image task losses, margin)      # cald_loss_pred_loss
     (task_losses + ll_loss).backward()                             # cald_lossnet_train_bwd, then the detector's hand-written backward
@@ -175,10 +175,11 @@ def LossPredLoss(input, target, margin=1.0, reduction='mean'):
 
 def train_one_epoch(task_model, task_optimizer, ll_model, ll_optimizer, data_loader, device, cycle, epoch, print_freq,
                     task_epochs=0, ll_weight=1.0, margin=1.0):
-    """ll_train.py:55-142 for Faster R-CNN with the reference's positional signature; ``task_epochs`` / ``ll_weight`` stand for
-    ``args.task_epochs`` / ``args.ll_weight`` and ``margin`` for ll4al.config.MARGIN.  ``task_model(images, targets)`` returns
-    ``(features, {name: [N] losses})`` (train.TrainableDetector over a ``loss_mode="ll"`` trainer).  Warm-up of both optimizers in epoch 0,
-    the finite-loss stop, both zero_grad / step pairs.  Returns one dict per iteration: task_loss, ll_loss, task_lr, ll_lr (the reference
+    """ll_train.py:55-142 with the reference's positional signature; ``task_epochs`` / ``ll_weight`` stand for ``args.task_epochs`` /
+    ``args.ll_weight`` and ``margin`` for ll4al.config.MARGIN.  ``task_model(images, targets)`` returns ``(features, {name: [N] losses})``
+    (train.TrainableDetector over FasterRCNNTrainer(loss_mode="ll")) or ``(feature list, {name: (mean, [N scalars])})`` (over a
+    RetinaNetLLTrainer); the loss dict's keys choose the reference's 'faster' or 'retina' branch, not an ``args.model`` string.  Warm-up
+    of both optimizers in epoch 0, the finite-loss stop, both zero_grad / step pairs.  Returns one dict per iteration: task_loss, ll_loss, task_lr, ll_lr (the reference
     returns its MetricLogger).  Single process (no reduce_dict)."""
     from .engine import warmup_lr_scheduler
     task_model.train()
@@ -195,17 +196,27 @@ def train_one_epoch(task_model, task_optimizer, ll_model, ll_optimizer, data_loa
         images = list(image.to(device) for image in images)
         targets = [{k: v.to(device) for k, v in t.items()} for t in targets]
         features, task_loss_dict = task_model(images, targets)
-        _task_losses = sum(loss for loss in task_loss_dict.values())
         task_loss_dict = dict(task_loss_dict)
-        for k in ('loss_objectness', 'loss_rpn_box_reg', 'loss_classifier', 'loss_box_reg'):
-            task_loss_dict[k] = torch.mean(task_loss_dict[k])
-        task_losses = sum(loss for loss in task_loss_dict.values())
-        task_loss_value = float(task_losses.detach())
-        if epoch >= task_epochs:
+        if 'classification' in task_loss_dict:
+            # the 'retina' branch (ll_train.py:97-120): every loss is (mean, [per image]), the features a list indexed by int
+            _task_losses = sum(torch.stack(loss[1]) for loss in task_loss_dict.values())
+            for k in ('classification', 'bbox_regression'):
+                task_loss_dict[k] = task_loss_dict[k][0]
+            task_losses = sum(loss for loss in task_loss_dict.values())
+            task_loss_value = float(task_losses.detach())
             # After task_epochs epochs, stop the gradient from the loss prediction module propagated to the target model.
-            features = {k: v for k, v in features.items()}
-            for k in ('0', '1', '2', '3'):
-                features[k] = features[k].detach()
+            features = {str(k): (features[k].detach() if epoch >= task_epochs else features[k]) for k in range(4)}
+        else:
+            _task_losses = sum(loss for loss in task_loss_dict.values())
+            for k in ('loss_objectness', 'loss_rpn_box_reg', 'loss_classifier', 'loss_box_reg'):
+                task_loss_dict[k] = torch.mean(task_loss_dict[k])
+            task_losses = sum(loss for loss in task_loss_dict.values())
+            task_loss_value = float(task_losses.detach())
+            if epoch >= task_epochs:
+                # After task_epochs epochs, stop the gradient from the loss prediction module propagated to the target model.
+                features = {k: v for k, v in features.items()}
+                for k in ('0', '1', '2', '3'):
+                    features[k] = features[k].detach()
         ll_pred = ll_model(features)
         ll_pred = ll_pred.view(ll_pred.size(0))
         ll_loss = ll_weight * LossPredLoss(ll_pred, _task_losses, margin=margin)

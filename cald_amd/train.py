@@ -30,7 +30,8 @@ image, RPN before the RoI heads -- exactly the calls torchvision's BalancedPosit
 generator reproduces torchvision's own samples (``tests/test_gpu_train.py::test_randperm_sampler_*``).
 
 The code by concern: ``train_core`` (layers, parameter storage, the body, what both detectors share), ``train_frcnn`` and
-``train_retina`` (one detector's step each, as named stages over a step record), and here the autograd bridge and the optimizer.
+``train_retina`` (one detector's step each, as named stages over a step record), ``train_retina_ll`` (the RetinaNet with per-image
+losses that trains LossNet beside it), and here the autograd bridge and the optimizer.
 """
 import torch
 
@@ -38,6 +39,7 @@ from . import train_ops as ops
 from .train_core import choose_k                    # noqa: F401  (every public name still resolves here)
 from .train_frcnn import FasterRCNNTrainer          # noqa: F401
 from .train_retina import RetinaNetTrainer          # noqa: F401
+from .train_retina_ll import RetinaNetLLTrainer     # noqa: F401
 
 
 def _backward_into_grads(net, gscale, **kw):
@@ -86,9 +88,10 @@ class _LossFn(torch.autograd.Function):
 
 
 class _LossFnLL(torch.autograd.Function):
-    """_LossFn for a ``loss_mode="ll"`` trainer: four [N] loss vectors and the pooled pyramid vectors [N, 4, 256] leave the forward; the
-    backward takes one gradient per loss and image and -- unless the features were detached (ll_train.py:90-95) -- LossNet's gradient
-    of the pooled vectors."""
+    """_LossFn for a ``loss_mode="ll"`` trainer: one [N] loss vector per name in LOSS_NAMES and the pooled pyramid vectors [N, 4, 256]
+    leave the forward -- between them, for RetinaNetLLTrainer, each loss's mean over the batch (retina_ll.py:132, :220); the backward
+    takes one gradient per loss and image (a mean's upstream gradient is folded in as g_mean / N on the device) and -- unless the
+    features were detached (ll_train.py:90-95, :107-113) -- LossNet's gradient of the pooled vectors."""
 
     @staticmethod
     def forward(ctx, anchor, net, images, targets):
@@ -96,7 +99,8 @@ class _LossFnLL(torch.autograd.Function):
         ctx.set_materialize_grads(False)                   # detached features reach backward() as None, not as a tensor of zeros
         d, pooled = net.forward(images, targets)
         net.forward_serial = ctx.serial = getattr(net, "forward_serial", 0) + 1
-        return tuple(d[k] for k in net.LOSS_NAMES) + (pooled,)
+        means = tuple(net.last["means"][k].reshape(()) for k in net.LOSS_NAMES) if getattr(net, "LL_MEANS", False) else ()
+        return tuple(d[k] for k in net.LOSS_NAMES) + means + (pooled,)
 
     @staticmethod
     def backward(ctx, *gs):
@@ -104,22 +108,28 @@ class _LossFnLL(torch.autograd.Function):
         if net.forward_serial != ctx.serial:
             raise RuntimeError("backward() of a training forward after a later forward of the same model: its saved activations "
                                "were replaced; call backward() before the next model(images, targets)")
-        N = net.last["N"]
+        N, n = net.last["N"], len(net.LOSS_NAMES)
         zero = None
         rows = []
-        for g in gs[:4]:
+        for i, g in enumerate(gs[:n]):
             if g is None:
                 zero = torch.zeros(N, dtype=torch.float32, device=net.dev) if zero is None else zero
                 g = zero
-            rows.append(g.reshape(N).to(torch.float32))
-        _backward_into_grads(net, torch.stack(rows), g_pooled=gs[4])
+            g = g.reshape(N).to(torch.float32)
+            g_mean = gs[n + i] if len(gs) > n + 1 else None
+            if g_mean is not None:                         # mean = sum_n loss_n / N: its upstream gradient reaches every image as g_mean / N
+                g = g + g_mean.to(torch.float32) / N
+            rows.append(g)
+        _backward_into_grads(net, torch.stack(rows), g_pooled=gs[-1])
         return None, None, None, None
 
 
 class TrainableDetector(object):
     """``task_model`` in train mode: ``model(images, targets) -> {loss name: scalar tensor}`` whose sum can be ``.backward()``-ed.
     Over a ``loss_mode="ll"`` trainer: ``-> (features, {loss name: [N] tensor})`` as detection/frcnn_ll.py returns them, ``features``
-    = {'0'..'3'}: [N, 256] views of the pooled pyramid vectors (one autograd tensor), ready for ll_train.LossNet."""
+    = {'0'..'3'}: [N, 256] views of the pooled pyramid vectors (one autograd tensor), ready for ll_train.LossNet.  Over a
+    RetinaNetLLTrainer: ``-> (features, {loss name: (mean, [N scalars])})`` as detection/retina_ll.py returns them, ``features`` a LIST of the
+    four views, indexed by int as ll_train.py:110-119 does."""
 
     def __init__(self, net):
         self.net = net
@@ -132,8 +142,11 @@ class TrainableDetector(object):
     def __call__(self, images, targets):
         if getattr(self.net, "loss_mode", None) == "ll":
             out = _LossFnLL.apply(self._anchor, self.net, images, targets)
-            pooled = out[4]
-            return {str(k): pooled[:, k, :] for k in range(4)}, dict(zip(self.net.LOSS_NAMES, out[:4]))
+            names, pooled = self.net.LOSS_NAMES, out[-1]
+            n = len(names)
+            if getattr(self.net, "LL_MEANS", False):        # retina_ll.py:554: features as a list, every loss as (mean, [per image])
+                return [pooled[:, k, :] for k in range(4)], {k: (out[n + i], list(out[i].unbind(0))) for i, k in enumerate(names)}
+            return {str(k): pooled[:, k, :] for k in range(4)}, dict(zip(names, out[:n]))
         out = _LossFn.apply(self._anchor, self.net, images, targets)
         return dict(zip(self.net.LOSS_NAMES, out))
 

@@ -364,13 +364,37 @@ def softmax_ce_seg(logits, labels, Ccls, counts, grad=None, gscale=None):
     return loss
 
 
-def smooth_l1_seg(pred, idx, target, beta, counts, denoms, grad=None, gscale=None):
-    """smooth_l1 per image: image i owns the next counts[i] gathered 4-vectors and divides its sum by denoms[i].  Returns the losses [N]."""
+def smooth_l1_seg(pred, idx, target, beta, counts, denoms, grad=None, gscale=None, mean_out=None):
+    """smooth_l1 per image: image i owns the next counts[i] gathered 4-vectors and divides its sum by denoms[i].  Returns the losses [N].
+    mean_out (optional, 1 float32): receives seg_mean of the losses."""
     N = len(counts)
     loss = torch.empty(N, dtype=torch.float32, device=pred.device)
     den = (C.c_float * N)(*[float(d) for d in denoms])
     _ffi.check(_ffi.lib().cald_train_smooth_l1_seg(_wctx(pred), N, _int_array(_seg_off(counts)), _p(pred), _p(idx), _p(target), beta, den,
                                                    _p(gscale), _p(loss), _p(grad)))
+    if mean_out is not None:
+        seg_mean(loss, out=mean_out)
+    return loss
+
+
+def seg_mean(losses, out=None):
+    """(((l_0 + l_1) + ...) + l_{N-1}) / N in float32, image order: ``_sum(losses) / len(targets)`` of retina_ll.py:132.  Returns [1]."""
+    _chk(losses, "losses")
+    out = out if out is not None else torch.empty(1, dtype=torch.float32, device=losses.device)
+    _ffi.check(_ffi.lib().cald_train_seg_mean(_wctx(losses), losses.numel(), _p(losses), _p(out)))
+    return out
+
+
+def focal_loss_seg(logits_flat, level_pix, N, A, K, ld, matched, gt_labels, gt_off, denoms, grad=None, gscale=None, alpha=0.25, mean_out=None):
+    """focal_loss per image: loss[n] = (sum of image n's terms) / denoms[n] (host floats > 0); image n's gradient is scaled by gscale[n]
+    / denoms[n] (gscale: None or a float32 device tensor [N]).  mean_out (optional, 1 float32) receives seg_mean of the losses.
+    Returns the losses [N]; nothing is launched or written when N exceeds the 64 images the call takes."""
+    if len(denoms) != N or (gscale is not None and (gscale.numel() != N or gscale.dtype != torch.float32 or not gscale.is_contiguous())):
+        raise ValueError("focal_loss_seg takes one denominator and one float32 gradient scale per image")
+    loss = torch.empty(N, dtype=torch.float32, device=logits_flat.device)
+    den = (C.c_float * N)(*[float(d) for d in denoms])
+    _ffi.check(_ffi.lib().cald_train_focal_loss_seg(_wctx(logits_flat), N, _int_array(level_pix), A, K, ld, _p(logits_flat), _p(matched),
+                                                    _p(gt_labels), _p(gt_off), den, alpha, _p(gscale), _p(loss), _p(mean_out), _p(grad)))
     return loss
 
 

@@ -11,7 +11,7 @@ class _RetinaStep(object):
     """What the stages of one RetinaNetTrainer.forward hand to each other.  KEPT: the fields that become ``self.last`` (what backward(),
     the tests and the tools read of the last forward) -- all but the prepared input, which only _targets and _fpn read."""
     KEPT = ("N", "level_hw", "level_pix", "cls_sizes", "reg_sizes", "matched", "matched_host", "gt_labels", "gt_off", "box_idx", "box_w", "img_w",
-            "reg_tgt",                                      # set by _targets
+            "reg_tgt", "nfg",                               # set by _targets
             "feats", "inner", "P", "p6_relu",               # by _fpn
             "acts", "cls_flat", "reg_flat")                 # by _heads
     __slots__ = KEPT + ("u8", "rem", "Hp", "Wp", "img_sizes")
@@ -28,9 +28,11 @@ class RetinaNetTrainer(_TrainerBase):
 
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
                  fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None):
+        if loss_mode not in (None, "ll"):
+            raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
         if loss_mode is not None:
-            raise NotImplementedError("loss_mode=%r: training LossNet beside a RetinaNet (ll_train.py:97-120, retina_ll.py's per-image "
-                                      "losses) is outside the scope of the learning-loss training step, which covers Faster R-CNN" % (loss_mode,))
+            raise NotImplementedError("loss_mode=%r: the RetinaNet that trains LossNet beside it (ll_train.py:97-120, retina_ll.py's per-image "
+                                      "losses) is a model of its own, as in the reference: build a RetinaNetLLTrainer" % (loss_mode,))
         self.loss_mode = None
         self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator)
         self.cfg = dict(fg=fg_iou_thresh, bg=bg_iou_thresh)
@@ -94,6 +96,7 @@ class RetinaNetTrainer(_TrainerBase):
             s.box_idx, anc_sel, gt_sel = packed[:nb], packed[nb:2 * nb], packed[2 * nb:]
             fl = torch.from_numpy(np.concatenate([np.concatenate(wts), np.array([1.0 / (max(1, n) * N) for n in nfg], np.float32)])).to(self.dev)
             s.box_w, s.img_w = fl[:nb], fl[nb:]
+            s.nfg = nfg                                     # host: the per-image losses' segments and normalisers (RetinaNetLLTrainer)
             s.reg_tgt = ops.box_encode(gts_all[gt_sel], anchors[anc_sel], (1.0, 1.0, 1.0, 1.0))
             s.gt_labels = torch.cat(gt_labels).to(self.dev)
             s.gt_off = torch.from_numpy(gt_off.astype(np.int32)).to(self.dev)
@@ -156,15 +159,19 @@ class RetinaNetTrainer(_TrainerBase):
         self._join_side()
         return self.grads
 
-    def _heads_backward(self, gscale):
+    def _loss_grads(self, L, gscale, gcls, greg):
+        """The two losses' gradients into the zeroed head-output gradient buffers."""
+        ops.focal_loss(L["cls_flat"], L["level_pix"], L["N"], 9, self.K, self.cls_ld, L["matched"], L["gt_labels"], L["gt_off"], L["img_w"], grad=gcls, gscale=gscale[0])
+        ops.smooth_l1(L["reg_flat"], L["box_idx"], L["reg_tgt"], 0.0, 1.0, weights=L["box_w"], grad=greg, gscale=gscale[1])
+
+    def _heads_backward(self, gscale, g_pooled=None):
         """Both losses' gradients, then the output convs and the towers backwards: weight gradients level by level (shared weights
         accumulate; they run on the side stream), data gradients of one layer of BOTH towers on all five levels in one grouped launch.
-        Returns the gradients wrt P3..P7."""
+        Returns the gradients wrt P3..P7; g_pooled ([N, 4, 256], RetinaNetLLTrainer) joins those of P3..P6 in the same pass."""
         L = self.last
         N, level_hw, acts = L["N"], L["level_hw"], L["acts"]
         gcls = torch.zeros_like(L["cls_flat"]); greg = torch.zeros_like(L["reg_flat"])
-        ops.focal_loss(L["cls_flat"], L["level_pix"], N, 9, self.K, self.cls_ld, L["matched"], L["gt_labels"], L["gt_off"], L["img_w"], grad=gcls, gscale=gscale[0])
-        ops.smooth_l1(L["reg_flat"], L["box_idx"], L["reg_tgt"], 0.0, 1.0, weights=L["box_w"], grad=greg, gscale=gscale[1])
+        self._loss_grads(L, gscale, gcls, greg)
         g_cls = level_views(gcls, L["cls_sizes"], level_hw, N, self.cls_ld)
         g_reg = level_views(greg, L["reg_sizes"], level_hw, N, 36)
         for l in range(5):
@@ -184,7 +191,9 @@ class RetinaNetTrainer(_TrainerBase):
             masks = ([acts["cls"][l][j] for l in range(5)] + [acts["reg"][l][j] for l in range(5)]) if j > 0 else None
             gs = ops.conv_group(g_cls + g_reg, [self.cls_tower[j]._packed_grad()] * 5 + [self.reg_tower[j]._packed_grad()] * 5, pad=1, masks=masks)
             g_cls, g_reg = gs[:5], gs[5:]
-        return [ops.add(g_cls[l], g_reg[l]) for l in range(5)]
+        if g_pooled is None:
+            return [ops.add(g_cls[l], g_reg[l]) for l in range(5)]
+        return [ops.add_bcast(g_cls[l], g_reg[l], g_pooled[:, l, :]) for l in range(4)] + [ops.add(g_cls[4], g_reg[4])]
 
     def _fpn_backward(self, gP):
         """P7 and P6 backwards into P5's gradient, the FPN output convs and the top-down pass backwards, then the body."""

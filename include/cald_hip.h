@@ -610,6 +610,16 @@ int cald_train_smooth_l1_seg(cald_ctx* ctx, int N, const int* seg_off, const flo
                              const float* denom, const float* gscale, float* loss_out, float* grad);
 int cald_train_bce_logits_seg(cald_ctx* ctx, int N, const int* seg_off, const float* logits, const int64_t* idx, const float* labels,
                               const float* gscale, float* loss_out, float* grad);
+/* cald_train_focal_loss per IMAGE (retina_ll.py:100-132), same logit layout and target rule: loss_out[n] = (sum of image n's raw terms)
+ * / denom[n] with one IEEE division (denom: HOST, N floats > 0, normally max(1, #foreground)); grad = d term * (gscale[n] / denom[n])
+ * (gscale: DEVICE, N floats; null = 1).  An ignored anchor's gradient words are not written (the caller zeroes grad); the pad columns
+ * A * K .. ld - 1 are neither read nor written.  N <= 64.  No workgroup covers two images and no atomics are used: the results repeat bit
+ * for bit, and image n's loss and gradient are those of the same image submitted alone.  mean_out (1 float, may be null) =
+ * (((l_0 + l_1) + ...) + l_{N-1}) / (float)N; cald_train_seg_mean is that sum alone, for any per-image loss vector. */
+int cald_train_focal_loss_seg(cald_ctx* ctx, int N, const int* level_pix, int A, int K, int ld, const float* logits, const int* matched,
+                              const int64_t* gt_labels, const int* gt_off, const float* denom, float alpha, const float* gscale,
+                              float* loss_out, float* mean_out, float* grad);
+int cald_train_seg_mean(cald_ctx* ctx, int N, const float* losses, float* mean_out);
 /* dst[n][p][c] = (a[n][p][c] + b[n][p][c]) + g[n * g_stride + c] / (float)HW: the join of two gradient maps [N][HW][C] (C a multiple of 4)
  * with the gradient of a global average pooling of the same map (IEEE division), in one pass */
 int cald_train_add_bcast(cald_ctx* ctx, int N, long long HW, int C, float* dst, const float* a, const float* b, const float* g,

@@ -2,15 +2,17 @@
 + SGD at the reference's training configuration (batch 4, VOC-sized images at min_size 600 / max_size 1000, 2 000 proposals, 512 RoIs
 per image) for
 
-    plain      FasterRCNNTrainer as cald_train.py uses it: four scalar losses
-    detached   loss_mode="ll", features detached (the reference's default, task_epochs = 0): per-image losses, cald_train_gap, LossNet forward /
+    plain      FasterRCNNTrainer as cald_train.py uses it: four scalar losses (--model retinanet: RetinaNetTrainer, two)
+    detached   loss_mode="ll" (--model retinanet: RetinaNetLLTrainer), features detached (the reference's default, task_epochs = 0): per-image losses, cald_train_gap, LossNet forward /
                backward, LossPredLoss, a second fused SGD launch
     live       loss_mode="ll", LossNet's gradient enters the pyramid through the broadcast join (task_epochs > epoch)
 
 alternated ``--rounds`` times in ONE process (so that clock and thermal drift hit the three alike); each block is timed with HIP events
 between two synchronisations.  Writes the per-block times, their means and spreads and the differences to ``--out``.
 
-    python tools/bench_ll_train.py [--steps 10] [--warmup 3] [--rounds 3] [--out profiles/ll_train_bench.json]
+    python tools/bench_ll_train.py [--model faster_rcnn|retinanet] [--steps 10] [--warmup 3] [--rounds 3] [--out profiles/ll_train_bench.json]
+
+--model retinanet writes profiles/ll_train_bench_retinanet.json unless --out says otherwise.
 """
 import argparse
 import json
@@ -46,11 +48,15 @@ def batches_of(batch):
 
 
 class Mode(object):
-    def __init__(self, name, batch):
-        self.name = name
-        sd = synth.pseudo_trained_frcnn(21, 50, seed=0)
-        self.net = train.FasterRCNNTrainer(sd, 21, min_size=600, max_size=1000, generator=torch.Generator().manual_seed(0),
-                                           loss_mode=None if name == "plain" else "ll")
+    def __init__(self, name, batch, model="faster_rcnn"):
+        self.name, self.retina = name, model == "retinanet"
+        if self.retina:
+            sd = synth.pseudo_trained_retinanet(21, 50, seed=0)
+            self.net = (train.RetinaNetTrainer if name == "plain" else train.RetinaNetLLTrainer)(sd, 21, min_size=600, max_size=1000)
+        else:
+            sd = synth.pseudo_trained_frcnn(21, 50, seed=0)
+            self.net = train.FasterRCNNTrainer(sd, 21, min_size=600, max_size=1000, generator=torch.Generator().manual_seed(0),
+                                               loss_mode=None if name == "plain" else "ll")
         self.model = train.TrainableDetector(self.net)
         self.opt = train.SGD(self.model.parameters(), lr=1e-5, momentum=0.9, weight_decay=1e-4, net=self.net)
         if name != "plain":
@@ -64,8 +70,13 @@ class Mode(object):
             self.opt.zero_grad(); losses.backward(); self.opt.step()
             return
         features, d = self.model(ims, tgs)                  # the loop body of ll_train.train_one_epoch without its host read of the loss
-        target = sum(d.values())
-        task = sum(torch.mean(v) for v in d.values())
+        if self.retina:                                     # ll_train.py:98-119
+            target = sum(torch.stack(v[1]) for v in d.values())
+            task = sum(v[0] for v in d.values())
+            features = {str(k): features[k] for k in range(4)}
+        else:
+            target = sum(d.values())
+            task = sum(torch.mean(v) for v in d.values())
         if self.name == "detached":
             features = {k: v.detach() for k, v in features.items()}
         pred = self.ll(features)
@@ -76,10 +87,13 @@ class Mode(object):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4); ap.add_argument("--steps", type=int, default=10); ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--out", default=os.path.join("profiles", "ll_train_bench.json"))
+    ap.add_argument("--rounds", type=int, default=3); ap.add_argument("--out", default=None)
+    ap.add_argument("--model", choices=("faster_rcnn", "retinanet"), default="faster_rcnn")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "ll_train_bench.json" if a.model == "faster_rcnn" else "ll_train_bench_retinanet.json")
     batches = batches_of(a.batch)
-    modes = [Mode(n, a.batch) for n in ("plain", "detached", "live")]
+    modes = [Mode(n, a.batch, a.model) for n in ("plain", "detached", "live")]
     # Every trainer opens two streams of its own beside the main one.  With those, the second trainer built here measured ~4 ms per step
     # slower than the other two whatever its mode's work (consistent with a process's four hardware queues: its streams come to share a
     # queue with the main stream, and its backward loses its overlap) -- a cost of holding three trainers in one process, not of the mode.
@@ -99,7 +113,7 @@ def main():
             e1.record(); torch.cuda.synchronize()
             blocks[m.name].append(e0.elapsed_time(e1) / a.steps)
     mean = {k: float(np.mean(v)) for k, v in blocks.items()}
-    res = {"metric": "training step, ms per step (forward + backward + SGD), batch %d at 600/1000" % a.batch, "unit": "ms",
+    res = {"metric": "training step, ms per step (forward + backward + SGD), batch %d at 600/1000" % a.batch, "unit": "ms", "model": a.model,
            "steps_per_block": a.steps, "warmup_steps": a.warmup, "rounds": a.rounds, "timer": "HIP events between two synchronisations",
            "blocks_ms": {k: [round(x, 3) for x in v] for k, v in blocks.items()},
            "mean_ms": {k: round(v, 3) for k, v in mean.items()},
