@@ -66,6 +66,14 @@ class LLCfg(C.Structure):
     _fields_ = [("batch_views", C.c_int), ("levels", C.c_int * 4)]
 
 
+class VaalCfg(C.Structure):
+    """cald_vaal_cfg of include/cald_hip.h."""
+    _fields_ = [("bn_mode", C.c_int), ("batch_images", C.c_int)]
+
+
+VAAL_BN_BATCH, VAAL_BN_RUNNING = 0, 1
+
+
 class LossNetTensors(C.Structure):
     """cald_lossnet_tensors of include/cald_hip.h: LossNet's parameters (or gradients) as device pointers in state_dict() layout."""
     _fields_ = [("fc_w", C.c_void_p * 4), ("fc_b", C.c_void_p * 4), ("lin_w", C.c_void_p), ("lin_b", C.c_void_p)]
@@ -139,6 +147,15 @@ SIGNATURES = {
     "cald_lossnet_finalize": (C.c_int, [C.c_void_p]),
     "cald_lossnet_destroy": (C.c_int, [C.c_void_p]),
     "cald_sweep_ll": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i, C.POINTER(LLCfg), c_d, c_f]),
+    "cald_vaal_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "cald_vaal_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, c_f, c_i64, C.c_int]),
+    "cald_vaal_finalize": (C.c_int, [C.c_void_p]),
+    "cald_vaal_destroy": (C.c_int, [C.c_void_p]),
+    "cald_sweep_vaal": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.POINTER(VaalCfg), c_f, c_f]),
+    "cald_op_vaal_resize": (C.c_int, [C.c_void_p, c_u8, C.c_int, C.c_int, c_f]),
+    "cald_op_vaal_bn_relu": (C.c_int, [C.c_void_p, c_f, C.c_longlong, C.c_int, C.c_int, C.c_int, c_f, c_f, c_f]),
+    "cald_op_vaal_fc_mu": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
+    "cald_op_vaal_head": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
     "cald_train_gap": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, C.c_void_p]),
     "cald_lossnet_train_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossNetTensors), C.c_void_p, C.c_void_p, C.c_void_p]),
     "cald_lossnet_train_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(LossNetTensors), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

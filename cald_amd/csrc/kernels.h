@@ -220,3 +220,14 @@ void launch_retina_postprocess(const RetinaArgs& a, int max_anchors, hipStream_t
 // baseline sweeps
 void launch_lt_uncertainty(const DetBuffers& det, int V, float* out, hipStream_t st);
 void launch_max_iou(const ScoreArgs& a, float* out /*[P][50]*/, hipStream_t st);
+
+// vaal.hip -- the VAAL sweep's own kernels (the file's header states every summation order); the convolutions go through launch_conv
+struct VaalImage { const uint8_t* src; int H, W; };   // device uint8 HWC pool image
+void launch_vaal_resize(const VaalImage* imgs, int n, float* out /*[n][256][256][4], channel 3 = 0*/, hipStream_t st);
+int vaal_bn_chunks(int HW);                           // 256-pixel chunks of a map: `partial` holds [n][chunks][C] floats
+// batch-statistics BatchNorm2d + ReLU in place over x [n][HW][C] (C % 4 == 0), per (image, channel); mean / istd: [n][C] scratch
+void launch_vaal_bn_relu(float* x, int n, int HW, int C, const float* gamma, const float* beta, float* partial, float* mean, float* istd, hipStream_t st);
+// act [n][65536] (k' = pixel * 1024 + channel), wt [65536][256], partial [n][256][256] scratch -> mu [n][256]
+void launch_vaal_fc_mu(const float* act, const float* wt, const float* bias, int n, float* partial, float* mu, hipStream_t st);
+void launch_vaal_head(const float* mu, const float* w1t, const float* b1, const float* w2t, const float* b2, const float* w3, float b3, int n, float* out,
+                      hipStream_t st);

@@ -242,7 +242,38 @@ int cald_lossnet_train_bwd(cald_ctx* ctx, int B, int D, const cald_lossnet_tenso
 int cald_loss_pred_loss(cald_ctx* ctx, int B, const float* input, const float* target, float margin, int per_pair, const float* g_up_dev,
                         float* loss_out, float* terms_out, float* grad_out);
 
+/* ---- the VAAL sweep (vaal/vaal_helper.py:186-222 AdversarySampler.sample): nearest resize of the uint8 pool image to 256 x 256, the VAE's
+ * five 4 x 4 / 2 / 1 convolutions each followed by BatchNorm2d and ReLU, fc_mu 65 536 -> 256, and the discriminator 256 -> 512 -> 512 -> 1
+ * with a sigmoid (vaal.hip).  Every image's result depends on that image alone. ---- */
+typedef struct cald_vaal cald_vaal;
+int cald_vaal_create(cald_ctx* ctx, cald_vaal** out);
+/* state_dict() keys of VAE and Discriminator: "encoder.{0,3,6,9,12}.{weight,bias}", "encoder.{1,4,7,10,13}.{weight,bias,running_mean,
+ * running_var}", "fc_mu.{weight,bias}", "net.{0,2,4}.{weight,bias}".  Any other key (the decoder, fc_logvar, num_batches_tracked) is
+ * accepted and ignored. */
+int cald_vaal_load_tensor(cald_vaal* v, const char* key, const float* data, const int64_t* shape, int ndim);
+/* CALD_ERR_MISSING_WEIGHT for a missing tensor, CALD_ERR_INVALID for a mis-shaped one */
+int cald_vaal_finalize(cald_vaal* v);
+int cald_vaal_destroy(cald_vaal* v);
+#define CALD_VAAL_BN_BATCH 0     /* the module in train(): every BatchNorm normalises with the statistics of its one image */
+#define CALD_VAAL_BN_RUNNING 1   /* the module in eval(): running statistics, folded into the convolution's scale / shift */
+typedef struct cald_vaal_cfg {
+    int bn_mode;           /* CALD_VAAL_BN_* */
+    int batch_images;      /* images per launch sequence (0 = default 64; capped at 128); results do not depend on it */
+} cald_vaal_cfg;
+/* images_dev[i]: uint8 HWC image of H[i] x W[i] in device memory.  cfg NULL: batch statistics, 64 images per launch sequence.
+ * preds_out [n]: the discriminator's output; mu_out: NULL or [n][256]. */
+int cald_sweep_vaal(cald_ctx* ctx, cald_vaal* v, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
+                    const cald_vaal_cfg* cfg, float* preds_out, float* mu_out);
+
 /* ---- operator-level entry points (used by the parity tests; same kernels as the paths above) ---- */
+/* pieces of the VAAL sweep; host pointers.  resize: uint8 [H][W][3] -> float32 [256][256][3].  bn_relu: x holds x_floats >= n HW C floats of
+ * which [n][HW][C] are the maps (the rest is uploaded too and must not be read); out [n][HW][C].  fc_mu: act [n][64][1024] (pixel-major,
+ * NHWC) -> mu [n][256].  head: mu [n][256] -> preds [n]. */
+int cald_op_vaal_resize(cald_ctx* ctx, const uint8_t* image, int H, int W, float* out);
+int cald_op_vaal_bn_relu(cald_ctx* ctx, const float* x, long long x_floats, int n, int HW, int C, const float* gamma, const float* beta,
+                         float* out);
+int cald_op_vaal_fc_mu(cald_vaal* v, int n, const float* act, float* mu_out);
+int cald_op_vaal_head(cald_vaal* v, int n, const float* mu, float* preds_out);
 /* the learning-loss sweep's pooling of one [H][W][C] tensor (C == 256) in its fixed order (lossnet.hip), and LossNet on n x [4][256] pooled
  * vectors; host pointers */
 int cald_op_gap(cald_ctx* ctx, const float* x, int H, int W, int C, float* mean_out);
