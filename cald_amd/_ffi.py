@@ -16,6 +16,7 @@ c_i = C.POINTER(C.c_int)
 c_i64 = C.POINTER(C.c_int64)
 c_d = C.POINTER(C.c_double)
 c_u8 = C.POINTER(C.c_uint8)
+c_i8 = C.POINTER(C.c_int8)
 
 
 class ModelCfg(C.Structure):
@@ -141,6 +142,7 @@ SIGNATURES = {
     "cald_sweep": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d]),
     "cald_sweep_audit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d, c_f]),
     "cald_sweep_ltc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, c_d]),
+    "cald_sweep_ssm": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, C.c_int64, c_i, c_i, c_f, c_f, c_i8, c_i64]),
     "cald_sweep_lsc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.c_uint64, C.c_int, c_d]),
     "cald_lossnet_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cald_lossnet_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, c_f, c_i64, C.c_int]),
@@ -173,6 +175,10 @@ SIGNATURES = {
     "cald_op_noise_stream": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i, c_d, C.POINTER(C.c_void_p)]),
     "cald_op_frcnn_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             C.c_int, c_f, c_f, c_i64, c_f, c_f, c_f, c_i]),
+    "cald_op_frcnn_postprocess_min": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                C.c_int, C.c_float, c_f, c_f, c_i64, c_f, c_f, c_f, c_i]),
+    "cald_op_ssm_postprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f, c_f, c_f, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                          c_i, c_i, c_f, c_f, c_i8]),
     "cald_op_retina_postprocess": (C.c_int, [C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f] + [C.c_int] * 6
                                    + [C.c_float, C.c_float, C.c_int, c_f, c_f, c_i64, c_f, c_f, c_i]),
     "cald_op_rpn_prune": (C.c_int, [C.c_void_p, C.POINTER(RpnPruneProbe)]),
@@ -198,6 +204,7 @@ SIGNATURES = {
     "cald_profile_cutout": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_i64]),
     "cald_model_set_cutout_reuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_look_fuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
+    "cald_model_set_box_min_size": (C.c_int, [C.c_void_p, C.c_float, c_f]),
     "cald_profile_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     # training step (device pointers as c_void_p)
     "cald_train_packed_floats": (C.c_int, [C.c_int] * 6 + [c_i64]),

@@ -115,6 +115,14 @@ void cald_host::PostBufs::layout(Bump& B, int V, int C, int cap) {
     key_cap = cap;
     prob = B.get<float>((size_t)V * CALD_ROI_CAP * C); pmax = B.get<float>((size_t)V * CALD_ROI_CAP);
     keys = B.get<unsigned long long>((size_t)V * key_cap); cbox = B.get<float>((size_t)V * 2 * key_cap * 4); key_count = B.get<int>(V);
+    skip = B.get<unsigned char>((size_t)V * key_cap);
+}
+void cald_host::SsmBufs::layout(Bump& B, int V, int C, int cap) {
+    const size_t K = (size_t)(C - 1), rows = (size_t)V * K * cap;
+    prob = B.get<float>((size_t)V * CALD_ROI_CAP * C); vmax = B.get<unsigned>(V);
+    kept_prop = B.get<int>(rows); kept_box = B.get<float>(rows * 4); cls_count = B.get<int>((size_t)V * K); row_off = B.get<int>((size_t)V * K);
+    al = B.get<int>(V); count = B.get<int>(V); total = B.get<int>(1);
+    boxes = B.get<float>(rows * 4); scores = B.get<float>(rows * K); labels = B.get<signed char>(rows * K);
 }
 struct BoxBufs {
     RoiBufs roi; float *f6, *f7, *pr; PostBufs post;
@@ -146,7 +154,16 @@ PostArgs cald_host::post_args(const PostBufs& S, const float* pred, int pred_ld,
     PostArgs pa{};
     pa.pred = pred; pa.pred_ld = pred_ld; pa.C = C; pa.V = V; pa.proposals = P.proposals; pa.prop_count = P.prop_count; pa.views = views; pa.score_thr = score_thr; pa.nms_thr = nms_thr;
     pa.prob = S.prob; pa.pmax = S.pmax; pa.keys = S.keys; pa.cbox = S.cbox; pa.key_count = S.key_count; pa.key_cap = S.key_cap; pa.det = det;
+    pa.skip = S.skip;
     return pa;
+}
+SsmArgs cald_host::ssm_args(const SsmBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views, float score_thr, int cap) {
+    SsmArgs sa{};
+    sa.pred = pred; sa.pred_ld = pred_ld; sa.C = C; sa.V = V; sa.proposals = P.proposals; sa.prop_count = P.prop_count; sa.views = views;
+    sa.score_thr = score_thr; sa.nms_thr = SSM_NMS_THR; sa.conf_thr = SSM_CONF_THR; sa.cap = cap;
+    sa.prob = S.prob; sa.vmax = S.vmax; sa.kept_prop = S.kept_prop; sa.kept_box = S.kept_box; sa.cls_count = S.cls_count; sa.row_off = S.row_off;
+    sa.al = S.al; sa.count = S.count; sa.total = S.total; sa.boxes = S.boxes; sa.scores = S.scores; sa.labels = S.labels;
+    return sa;
 }
 RetinaArgs cald_host::retina_args(const RetinaTailBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
                                   const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class, const DetBuffers& det) {
@@ -294,7 +311,7 @@ static const float RPN_MIN_SIZE = 1e-3f;
 // by prepare().  feat (host.h FwdFeatures): the forward stops after the FPN and hands out the pyramid; `det` is then not used, and pruning,
 // cut_out reuse and the audit do not apply.
 struct ForwardRun {
-    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat;
+    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat; FwdSsm* ssm;
     // ---- filled by prepare() ----
     cald_ctx* c = nullptr; hipStream_t st = nullptr; const BatchPlan* dp = nullptr;
     bool retina = false, prune = false;
@@ -320,6 +337,7 @@ struct ForwardRun {
         if (m->prune) Fq.layout(B, px, V, m->prune_capture);
         Fx.layout(B, S, V, m->pred.Cout, m->cfg.num_classes, m->key_cap);
         Fa.layout(B, V, m->det_cap());
+        if (ssm) ssm->out.layout(B, V, m->cfg.num_classes, m->cfg.detections_per_img);
     }
     // argument checks, the level plan, the arena, the staging-ring copy of plan and views
     int prepare() {
@@ -327,7 +345,8 @@ struct ForwardRun {
         if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
         if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
         if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
-        if (!feat && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
+        if (ssm && (feat || audit_out || ru || m->cfg.arch != CALD_ARCH_FRCNN)) return fail(CALD_ERR_INVALID, "the SSM forward is a plain Faster R-CNN forward");
+        if (!feat && !ssm && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
         HIPCHK(hipSetDevice(c->device));
         for (int v = 0; v < V; v++) {
             ViewDesc& d = views[v];
@@ -346,6 +365,7 @@ struct ForwardRun {
         }
         retina = m->cfg.arch == CALD_ARCH_RETINANET;
         prune = m->prune && prune_ok;
+        if (audit_out && m->box_min_size > 0.0f) return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit does not cover small-box removal (box_min_size > 0)");
         if (audit_out && (retina || m->cfg.rpn_pre_nms_top_n > 1024 || m->det_cap() > 512))
             return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit covers Faster R-CNN with rpn_pre_nms_top_n <= 1024 and <= 512 detections per image");
         build_plan(m->plan, V, views, hp, retina);
@@ -593,7 +613,13 @@ struct ForwardRun {
     void postprocess() {
         PostArgs pa = post_args(Fx.post, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh, m->cfg.box_nms_thresh, det);
         pa.kept_key = audit_out ? Fa.kept_key : nullptr; pa.post_maxc = audit_out ? Fa.post_maxc : nullptr;
+        pa.min_box = m->box_min_size;
         launch_frcnn_postprocess(pa, st);
+    }
+    // the SSM tail (ssm.hip) on the same predictor rows and proposals
+    void ssm_postprocess() {
+        launch_ssm_postprocess(ssm_args(ssm->out, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh,
+                                        m->cfg.detections_per_img), st);
     }
     void audit() {
         AuditArgs au;
@@ -618,7 +644,7 @@ struct ForwardRun {
             if ((rc = prune ? rpn_pruned() : rpn_dense())) return rc;
             proposals();
             if ((rc = box_head())) return rc;
-            postprocess();
+            if (ssm) ssm_postprocess(); else postprocess();
             if (audit_out) audit();
         }
         HIPCHK(hipGetLastError());
@@ -627,8 +653,8 @@ struct ForwardRun {
 };
 
 int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
-                             FwdFeatures* feat) {
-    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat}.run();
+                             FwdFeatures* feat, FwdSsm* ssm) {
+    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat, ssm}.run();
 }
 
 static int fill_view(ViewDesc& d, const cald_view& v) {

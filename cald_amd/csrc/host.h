@@ -154,6 +154,7 @@ struct cald_model {
         char* dev = nullptr; char* pin = nullptr; uint8_t* d_aug = nullptr;
         hipEvent_t ev_ref[2] = {nullptr, nullptr}, ev_score[2] = {nullptr, nullptr};
     } ss;
+    float box_min_size = 0.0f;   // cald_model_set_box_min_size: stock remove_small_boxes in the ordinary tail (0 = off, frcnn_la.py)
     int key_cap = 32768;   // FRCNN candidate (proposal, class) list capacity per view, sized from box_score_thresh at create
     // cut_out reuse (sweep.hip SweepRun): the reference forward's block outputs of the first three stages, one slot per batch parity (batch k + 1's
     // reference forward runs before batch k's cut_out forward), and the gather plans of the cut_out forwards (pinned by parity + device)
@@ -207,8 +208,20 @@ struct ProposalBufs { float* proposals = nullptr; int* prop_count = nullptr; voi
 struct RoiBufs { float* roi = nullptr; int* order = nullptr; void layout(Bump& B, int V, int C); };
 struct PostBufs {
     float *prob = nullptr, *pmax = nullptr, *cbox = nullptr; unsigned long long* keys = nullptr; int* key_count = nullptr; int key_cap = 0;
+    unsigned char* skip = nullptr;      // remove_small_boxes marks (PostArgs::skip)
     void layout(Bump& B, int V, int C, int key_cap);
 };
+// the SSM tail (ssm.hip): scratch and results of V views; the results hold (C - 1) * cap rows a view, the most a view can give
+struct SsmBufs {
+    float *prob = nullptr, *kept_box = nullptr, *boxes = nullptr, *scores = nullptr; unsigned* vmax = nullptr; signed char* labels = nullptr;
+    int *kept_prop = nullptr, *cls_count = nullptr, *row_off = nullptr, *al = nullptr, *count = nullptr, *total = nullptr;
+    void layout(Bump& B, int V, int C, int cap);
+};
+// ---- the SSM forward (cald_sweep_ssm): Faster R-CNN up to the box predictor, then ssm_postprocess() in place of postprocess().  `det` is
+// not used.  Filled by forward_model: the tail's buffers in the arena (valid until the context's next forward) ----
+struct FwdSsm { SsmBufs out; };
+#define SSM_NMS_THR 0.3f     // frcnn_ssm.py:88
+#define SSM_CONF_THR 0.5f    // frcnn_ssm.py:60 CONF_THRESH
 struct RetinaTailBufs {
     int *cand_count = nullptr, *kept_anchor = nullptr, *kept_count = nullptr, cand_cap = 0, max_anchors = 0; unsigned long long* cand_key = nullptr;
     float *cand_box = nullptr, *kept_box = nullptr; unsigned char* cand_skip = nullptr;
@@ -217,6 +230,7 @@ struct RetinaTailBufs {
 RoiArgs roi_args(const RoiBufs& S, const float* const* feat, const BatchPlan* plan, int C, int V, const ProposalBufs& P, bool out16);
 PostArgs post_args(const PostBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views,
                    float score_thr, float nms_thr, const DetBuffers& det);
+SsmArgs ssm_args(const SsmBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views, float score_thr, int cap);
 RetinaArgs retina_args(const RetinaTailBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
                        const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class, const DetBuffers& det);
 inline size_t cut_plan_set_bytes(int V) { return (size_t)(V + 1) * sizeof(LevelSeg) + (size_t)V * sizeof(GatherSet); }
@@ -238,7 +252,7 @@ void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& cout
 void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], bool retina);
 bool stem_grid_exact(const LevelSeg* seg, int V);
 int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
-                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr);
+                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr, FwdSsm* ssm = nullptr);
 // sweep.hip
 void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);

@@ -124,8 +124,39 @@ struct PostArgs {
     // decision-margin audit (audit.hip), both null in a plain forward:
     unsigned long long* kept_key = nullptr;   // [V][det.cap]: candidate key of every detection kept, in output order
     float* post_maxc = nullptr;               // [V]: largest clipped coordinate over the view's candidates (the class offset's scale)
+    // stock remove_small_boxes (cald_model_set_box_min_size), off at 0: candidates whose clipped width or height is < min_box take no part
+    // in NMS and are left out of the class offset's maximum
+    float min_box = 0.0f;
+    unsigned char* skip = nullptr;            // [V][key_cap] scratch, written and read only when min_box > 0
 };
 void launch_frcnn_postprocess(const PostArgs& a, hipStream_t st);
+
+// ssm.hip -- the SSM tail (detection/frcnn_ssm.py:44-102 ssm_postprocess_detections + transform.postprocess): per view the flag `al`, and per
+// foreground class an NMS of its own over ALL proposals, the first `cap` survivors, the score cut; rows compacted in (view, class, kept) order
+struct SsmArgs {
+    const float* pred;        // [V][ROI_CAP][pred_ld]: logits C, then deltas 4C
+    int pred_ld, C, V;
+    const float* proposals;   // [V][ROI_CAP][4]
+    const int* prop_count;    // [V]
+    const ViewDesc* views;
+    float score_thr, nms_thr, conf_thr;   // 0.05 (box_score_thresh), 0.3, 0.5
+    int cap;                  // detections_per_img: kept boxes per class
+    // scratch
+    float* prob;              // [V][ROI_CAP][C] softmax
+    unsigned* vmax;           // [V] orderable key of the view's largest foreground probability (0 = no proposals)
+    int* kept_prop;           // [V][C-1][cap] proposal index of every row of the class
+    float* kept_box;          // [V][C-1][cap][4] its box, scaled to the original image
+    int* cls_count;           // [V][C-1] rows of the class
+    int* row_off;             // [V][C-1] first output row of the class (exclusive prefix sum over the batch)
+    // results: the rows of all V views consecutively
+    int* al;                  // [V]
+    int* count;               // [V] rows of the view
+    int* total;               // [1] rows of the batch
+    float* boxes;             // [rows][4]
+    float* scores;            // [rows][C-1]
+    signed char* labels;      // [rows][C-1] +1 / -1
+};
+void launch_ssm_postprocess(const SsmArgs& a, hipStream_t st);
 
 // score.hip
 struct ScoreArgs {

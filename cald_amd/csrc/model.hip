@@ -371,6 +371,13 @@ extern "C" int cald_model_set_look_fuse(cald_model* m, int mode, int* was) {
     m->look_fuse = mode;
     return 0;
 }
+extern "C" int cald_model_set_box_min_size(cald_model* m, float min_size, float* was) {
+    if (!m || !(min_size >= 0.0f)) return fail(CALD_ERR_INVALID, "bad argument");
+    if (m->cfg.arch != CALD_ARCH_FRCNN) return fail(CALD_ERR_INVALID, "box_min_size belongs to the Faster R-CNN tail (RetinaNet's always removes small boxes)");
+    if (was) *was = m->box_min_size;
+    m->box_min_size = min_size;
+    return 0;
+}
 // Test hooks of the certified pruning: in capture mode cald_forward takes the pruned path as well (it is dense otherwise) and keeps the
 // look-ahead's head map (debug tensors "rpn_look0/1", the per-pixel |patch|_2 "rpn_pnorm0/1", the scattered maps "rpn0/1"); the bound is
 // B_a(p) = c1[a] * rpn_pnorm(p) + c0[a].

@@ -474,6 +474,15 @@ extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float*
                                          int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max,
                                          float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
                                          float* scores_cls_out, int* n_out) {
+    return cald_op_frcnn_postprocess_min(c, R, C, logits, deltas, proposals, Hr, Wr, Ho, Wo, score_thr, nms_thr, det_max, 0.0f, boxes_out, scores_out,
+                                         labels_out, props_out, prob_max_out, scores_cls_out, n_out);
+}
+// the same with the stock tail's remove_small_boxes (cald_model_set_box_min_size; 0 = off)
+extern "C" int cald_op_frcnn_postprocess_min(cald_ctx* c, int R, int C, const float* logits, const float* deltas, const float* proposals,
+                                             int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max, float box_min_size,
+                                             float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
+                                             float* scores_cls_out, int* n_out) {
+    if (!(box_min_size >= 0.0f)) return fail(CALD_ERR_INVALID, "box_min_size must be >= 0");
     if (!c || !logits || !deltas || !proposals || !boxes_out || !scores_out || !labels_out || !props_out || !prob_max_out || !scores_cls_out || !n_out)
         return fail(CALD_ERR_INVALID, "null argument");
     if (R < 0 || R > CALD_ROI_CAP || C < 2 || C > 256 || det_max < 1 || det_max > 512) return fail(CALD_ERR_INVALID, "bad geometry (R <= %d, 2 <= C <= 256, det_max <= 512)", CALD_ROI_CAP);
@@ -491,9 +500,52 @@ extern "C" int cald_op_frcnn_postprocess(cald_ctx* c, int R, int C, const float*
     if ((rc = carve(sd, [&](Bump& B) { d_pred = B.get<float>(pred.size()); d_vd = B.get<ViewDesc>(1); pb.layout(B, 1); S.layout(B, 1, C, key_cap); })) ||
         (rc = det.alloc(1, det_max, C)) || (rc = put_proposals(pb, proposals, R))) return rc;
     HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
-    launch_frcnn_postprocess(post_args(S, d_pred, ld, C, 1, pb, d_vd, score_thr, nms_thr, det.d), c->stream);
+    PostArgs pa = post_args(S, d_pred, ld, C, 1, pb, d_vd, score_thr, nms_thr, det.d);
+    pa.min_box = box_min_size;
+    launch_frcnn_postprocess(pa, c->stream);
     HIPCHK(hipGetLastError());
     return download_dets(c, det.d, "frcnn", boxes_out, scores_out, labels_out, props_out, prob_max_out, scores_cls_out, n_out);
+}
+
+// one view's predictor rows as the forward's box head leaves them: CALD_ROI_CAP rows of [C logits | 4 C deltas], zero beyond R
+static std::vector<float> pack_pred(int R, int C, const float* logits, const float* deltas) {
+    const int ld = 5 * C;
+    std::vector<float> pred((size_t)CALD_ROI_CAP * ld, 0.0f);
+    for (int r = 0; r < R; r++) {
+        memcpy(&pred[(size_t)r * ld], logits + (size_t)r * C, (size_t)C * 4);
+        memcpy(&pred[(size_t)r * ld + C], deltas + (size_t)r * 4 * C, (size_t)4 * C * 4);
+    }
+    return pred;
+}
+// RoIHeads.ssm_postprocess_detections + transform.postprocess of ONE view on the kernels of the SSM forward (ssm.hip), through the forward's
+// own SsmBufs::layout and ssm_args: host arrays in, host arrays out.  Parity hook for detection/frcnn_ssm.py:44-102, :367, :400.
+extern "C" int cald_op_ssm_postprocess(cald_ctx* c, int R, int C, const float* logits, const float* deltas, const float* proposals,
+                                       int Hr, int Wr, int Ho, int Wo, float score_thr, int det_max,
+                                       int* al_out, int* n_out, float* boxes_out, float* scores_out, int8_t* labels_out) {
+    if (!c || !logits || !deltas || !proposals || !al_out || !n_out || !boxes_out || !scores_out || !labels_out) return fail(CALD_ERR_INVALID, "null argument");
+    if (R < 0 || R > CALD_ROI_CAP || C < 2 || C > 256 || det_max < 1 || det_max > 512 || Hr < 1 || Wr < 1 || Ho < 1 || Wo < 1)
+        return fail(CALD_ERR_INVALID, "bad geometry (R <= %d, 2 <= C <= 256, det_max <= 512, positive sizes)", CALD_ROI_CAP);
+    HIPCHK(hipSetDevice(c->device));
+    const std::vector<float> pred = pack_pred(R, C, logits, deltas);
+    ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
+    ScopedDev sd(c->stream);
+    ProposalBufs pb; SsmBufs S; float* d_pred; ViewDesc* d_vd; int rc;
+    if ((rc = carve(sd, [&](Bump& B) { d_pred = B.get<float>(pred.size()); d_vd = B.get<ViewDesc>(1); pb.layout(B, 1); S.layout(B, 1, C, det_max); })) ||
+        (rc = put_proposals(pb, proposals, R))) return rc;
+    HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+    launch_ssm_postprocess(ssm_args(S, d_pred, 5 * C, C, 1, pb, d_vd, score_thr, det_max), c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int al = 0, n = 0, total = 0;
+    HIPCHK(hipMemcpy(&al, S.al, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&n, S.count, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&total, S.total, 4, hipMemcpyDeviceToHost));
+    if (n < 0 || n > (C - 1) * det_max || total != n || (al && n)) return fail(CALD_ERR_HIP, "ssm postprocess returned %d rows (al %d, total %d, cap %d)", n, al, total, (C - 1) * det_max);
+    if (n) {
+        HIPCHK(hipMemcpy(boxes_out, S.boxes, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(scores_out, S.scores, (size_t)n * (C - 1) * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(labels_out, S.labels, (size_t)n * (C - 1), hipMemcpyDeviceToHost));
+    }
+    *al_out = al; *n_out = n;
+    return 0;
 }
 
 // RetinaNet.postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the forward (retina.hip

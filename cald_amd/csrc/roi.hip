@@ -293,6 +293,7 @@ __global__ __launch_bounds__(1024) void post_nms_kernel(PostArgs a) {
     float4* cbox = reinterpret_cast<float4*>(a.cbox) + (long long)v * 2 * a.key_cap;
     const float4* props = reinterpret_cast<const float4*>(a.proposals) + (long long)v * CALD_ROI_CAP;
     float mx = -INFINITY;
+    unsigned char* skip = a.min_box > 0.0f ? a.skip + (long long)v * a.key_cap : nullptr;
     for (int i = tid; i < n; i += 1024) {
         const int pos = (int)(0xFFFFFFFFu - (unsigned)(keys[i] & 0xFFFFFFFFull));
         const int r = pos / (C - 1), c = pos - r * (C - 1) + 1;
@@ -306,6 +307,11 @@ __global__ __launch_bounds__(1024) void post_nms_kernel(PostArgs a) {
         b.x = det_clamp(o[0], 0.0f, Wr); b.z = det_clamp(o[2], 0.0f, Wr);
         b.y = det_clamp(o[1], 0.0f, Hr); b.w = det_clamp(o[3], 0.0f, Hr);
         cbox[i] = b;
+        if (skip) {      // stock remove_small_boxes: keep = (ws >= min_size) & (hs >= min_size), before batched_nms takes its maximum
+            const bool small = !((b.z - b.x) >= a.min_box) || !((b.w - b.y) >= a.min_box);
+            skip[i] = small ? 1 : 0;
+            if (small) continue;
+        }
         mx = fmaxf(mx, fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
     }
     red[tid] = mx;
@@ -322,7 +328,7 @@ __global__ __launch_bounds__(1024) void post_nms_kernel(PostArgs a) {
         obox[i] = make_float4(b.x + off, b.y + off, b.z + off, b.w + off);
     }
     __syncthreads();
-    block_nms_sorted(obox, n, a.nms_thr, cap, kept_box, kept_area, dead_or, keep_idx, &s_nk);
+    block_nms_sorted(obox, n, a.nms_thr, cap, kept_box, kept_area, dead_or, keep_idx, &s_nk, skip);
     const int nk = s_nk;
     const float rh = (float)((double)vd.Ho / (double)vd.Hr), rw = (float)((double)vd.Wo / (double)vd.Wr);
     for (int i = tid; i < nk; i += 1024) {

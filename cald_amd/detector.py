@@ -60,10 +60,13 @@ def _u8_over_255(device):
 class HipDetector:
     def __init__(self, num_classes, depth=50, min_size=800, max_size=1333, box_score_thresh=0.05, box_nms_thresh=0.5,
                  box_detections_per_img=100, rpn_pre_nms_top_n_test=1000, rpn_post_nms_top_n_test=1000,
-                 rpn_nms_thresh=0.7, arch=0, precision="fp32", **unused):
+                 rpn_nms_thresh=0.7, arch=0, precision="fp32", box_min_size=0.0, **unused):
         """precision: "fp32" (exact, bit-identical to the oracle; default) or "f16x3" (split-fp16 MFMA path, 2x faster, fp32-grade
-        but not bit-identical to fp32 and not reproducible on a CPU) -- include/cald_hip.h, DESIGN.md section 6."""
+        but not bit-identical to fp32 and not reproducible on a CPU) -- include/cald_hip.h, DESIGN.md section 6.
+        box_min_size: torchvision's stock remove_small_boxes in the Faster R-CNN tail (cald_model_set_box_min_size); 0 = off, the tail of
+        detection/frcnn_la.py."""
         self.arch = arch
+        self.box_min_size = float(box_min_size)
         self.cfg = _ffi.ModelCfg(self.arch, depth, num_classes, int(min_size), int(max_size), box_score_thresh,
                                  box_nms_thresh, box_detections_per_img, rpn_pre_nms_top_n_test, rpn_post_nms_top_n_test,
                                  rpn_nms_thresh, _ffi.PRECISION[precision])
@@ -177,6 +180,8 @@ class HipDetector:
                 shape = (C.c_int64 * a.ndim)(*a.shape)
                 _ffi.check(L.cald_model_load_tensor(h, k.encode(), _ffi.ptr(a), shape, a.ndim))
             _ffi.check(L.cald_model_finalize(h))
+            if self.box_min_size > 0.0:
+                _ffi.check(L.cald_model_set_box_min_size(h, self.box_min_size, None))
             self._handle = h
         return self._handle
 

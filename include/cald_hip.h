@@ -187,6 +187,14 @@ int cald_sweep_audit(cald_model* m, int n_images, const uint8_t* const* images_d
 /* lt_c_train.py:105-121 get_uncertainty(task_model, unlabeled_loader) -> one float per image */
 int cald_sweep_ltc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                    int batch_images, double* uncertainty_out);
+/* ssm/ssm_helper.py:9-33 get_uncertainty on a Faster R-CNN model: one forward per image with the SSM tail (cald_op_ssm_postprocess) in
+ * place of the ordinary one, batch_images images a forward (0 = 64; results do not depend on it).  al_out / count_out [n_images]; the rows
+ * of all images consecutively in image order: boxes_out [rows][4], scores_out [rows][C - 1], labels_out [rows][C - 1].  *rows_needed_out
+ * receives the total; if it exceeds rows_cap the call returns CALD_ERR_INVALID ("... needs N rows"), al_out / count_out are complete and
+ * the row arrays hold nothing to rely on.  A RetinaNet model or a null argument: CALD_ERR_INVALID. */
+int cald_sweep_ssm(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
+                   int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out, int8_t* labels_out,
+                   int64_t* rows_needed_out);
 /* ls_c_train.py:108-155 get_uncertainty(task_model, unlabeled_loader) -> one float per image (six GaussianNoise views) */
 int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                    const int64_t* pool_pos, uint64_t base_seed, int batch_images, double* stability_out);
@@ -323,6 +331,21 @@ int cald_op_frcnn_postprocess(cald_ctx* ctx, int R, int C, const float* logits, 
                               int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max,
                               float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
                               float* scores_cls_out, int* n_out);
+/* The same with torchvision's stock remove_small_boxes between the score threshold and NMS (cald_model_set_box_min_size): candidates whose
+ * clipped width or height is < box_min_size are dropped and do not count towards batched_nms's maximum coordinate.  0 = the call above. */
+int cald_op_frcnn_postprocess_min(cald_ctx* ctx, int R, int C, const float* logits, const float* deltas, const float* proposals,
+                                  int Hr, int Wr, int Ho, int Wo, float score_thr, float nms_thr, int det_max, float box_min_size,
+                                  float* boxes_out, float* scores_out, int64_t* labels_out, float* props_out, float* prob_max_out,
+                                  float* scores_cls_out, int* n_out);
+/* RoIHeads.ssm_postprocess_detections + GeneralizedRCNNTransform.postprocess of one view (detection/frcnn_ssm.py:44-102, :367, :400) on the
+ * SSM forward's own kernels (ssm.hip); inputs as above.  *al_out = 1 when the largest foreground probability is < 0.5 (or R == 0, where the
+ * reference raises): no rows then.  Else per foreground class NMS at IoU 0.3 over all R proposals, the first det_max survivors, of those the
+ * ones scoring > score_thr: *n_out <= (C - 1) * det_max rows in (class, kept) order -- boxes_out [n][4] on the original image, scores_out
+ * [n][C - 1] the proposal's foreground probabilities, labels_out [n][C - 1] = +1 where the probability is > 0.5, else -1.  The output
+ * arrays hold (C - 1) * det_max rows.  R <= 1000, det_max <= 512. */
+int cald_op_ssm_postprocess(cald_ctx* ctx, int R, int C, const float* logits, const float* deltas, const float* proposals,
+                            int Hr, int Wr, int Ho, int Wo, float score_thr, int det_max,
+                            int* al_out, int* n_out, float* boxes_out, float* scores_out, int8_t* labels_out);
 /* RetinaNet.postprocess_detections + the stock GeneralizedRCNNTransform.postprocess of one view (detection/retinanet_cal.py:402-490) on
  * the forward's own kernels: cls[l] = [H_l][W_l][A*K] logits (channel a*K + k), reg[l] = [H_l][W_l][A*4] deltas for the five levels
  * P3..P7 (host), level_hw = {H0, W0, ..., H4, W4}, base_anchors [5][A][4], padded size Hp x Wp (anchor strides Hp / H_l, Wp / W_l),
@@ -482,6 +505,11 @@ int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was);
  * exact head's fma chain (default; same bits, the hidden tensor is never written), 2 = one launch wherever conv_h4 can run at all (test hook
  * for small views).  Returns the previous setting in *was. */
 int cald_model_set_look_fuse(cald_model* m, int mode, int* was);
+/* torchvision's stock remove_small_boxes in the Faster R-CNN tail: with min_size > 0, candidates above the score threshold whose clipped
+ * width or height is < min_size are dropped before NMS (and before batched_nms takes its maximum coordinate).  Default 0: the tail of
+ * detection/frcnn_la.py, which has no such step.  The decision-margin audit does not cover it (cald_sweep_audit: CALD_ERR_UNSUPPORTED).
+ * Returns the previous value in *was (may be null). */
+int cald_model_set_box_min_size(cald_model* m, float min_size, float* was);
 /* cut_out reuse of the exact sweeps (CALD_CUTOUT_REUSE=0 disables it): per reused stage (layer1..layer3) the conv output rows the cut_out
  * forwards computed and the rows the dense stages would have (summed over the stage's convs), the batches that reused the reference
  * forward, and the batches whose cut_out views ran dense for want of retention memory.  Accumulated over the context's life. */
