@@ -100,7 +100,8 @@ class ConvProbe(C.Structure):
                 ("residual", c_f), ("up", c_f), ("ex16", C.c_int), ("mask", c_f), ("row_map", c_i),
                 ("out", c_f), ("out_n", C.c_int64), ("out16", C.POINTER(C.c_uint32)), ("out16_n", C.c_int64),
                 ("energy4", c_f), ("energy4_n", C.c_int64),
-                ("head_w", c_f), ("head_b", c_f), ("head_out", c_f), ("head_out_n", C.c_int64), ("head_ld", C.c_int)]
+                ("head_w", c_f), ("head_b", c_f), ("head_out", c_f), ("head_out_n", C.c_int64), ("head_ld", C.c_int),
+                ("row_packing", C.c_int)]      # 0 auto (the product's choice), 1 per-view row tiles, 2 packed row tiles
 
 
 PRUNE_PROBE_MAX_VIEWS = 8
@@ -190,6 +191,7 @@ SIGNATURES = {
     "cald_op_conv2d_f16x3": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),
     "cald_op_conv_bench": (C.c_int, [C.c_void_p] + [C.c_int] * 12 + [c_d, c_d]),
+    "cald_op_row_pack_lookup": (C.c_int, [C.c_int, c_i, c_i, C.c_int, C.c_int, C.c_int64, c_i64, c_i, c_i64, c_i64]),
     "cald_op_transform_size": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_i, c_i, c_i, c_i]),
     "cald_debug_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, c_f, C.c_int64, c_i64]),
     "cald_jpeg_info": (C.c_int, [C.c_void_p, C.c_size_t, c_i, c_i, c_i]),
@@ -204,6 +206,7 @@ SIGNATURES = {
     "cald_profile_cutout": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_i64]),
     "cald_model_set_cutout_reuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_look_fuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
+    "cald_model_set_row_packing": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_box_min_size": (C.c_int, [C.c_void_p, C.c_float, c_f]),
     "cald_profile_dump": (C.c_int, [C.c_void_p, C.c_char_p]),
     # training step (device pointers as c_void_p)

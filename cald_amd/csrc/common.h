@@ -31,7 +31,41 @@ __device__ __forceinline__ int seg_find_view(const LevelSeg* __restrict__ seg, c
     }
     return lo;
 }
+// Packed row tiles (ConvArgs::packed_rows): the view a row of the level's flat row space belongs to -- the largest v in [0, V) with
+// seg[v].pix_off <= row (pix_off is the running sum of the views' H * W).  Empty views share their successor's pix_off, so the rule
+// skips them; row < the level's row count, so the view found holds the row.  The same bisection, on the other prefix sum (host-callable:
+// cald_op_row_pack_lookup runs it on the CPU for tests/test_row_packing_lookup.py).
+__host__ __device__ __forceinline__ int seg_find_row(const LevelSeg* __restrict__ seg, const int V, const long long row) {
+    int lo = 0, hi = V - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (seg[mid].pix_off <= row) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 #endif
+
+// Packed row tiles, host side (seg arrays: host copies, V + 1 entries each, entry V the sentinel): the output level's row count if a conv
+// launch over these levels may tile the level's flat row space instead of each view (conv_p4.hip), else 0.  A tile that straddles views
+// addresses all of them from its FIRST view's base through 32-bit byte offsets below the out-of-range offset 0x7FFF0000 and inside the
+// 0x7FFE0000 bytes of a buffer descriptor: the input (and the coarser level of `up`, su, or null) from the first view's start to the last
+// touched view's end, the output from the first view's start to the tile's end.  Refused (per-view tiles stay) where that does not hold.
+static inline int conv_pack_rows(const LevelSeg* si, const LevelSeg* so, const LevelSeg* su, int V, int Cin, int out_ld) {
+    const long long total = so[V].pix_off, LIM = 0x7FFE0000LL - (1 << 16);      // (slack: the k-loop's scalar channel offset, < 4 Cin bytes)
+    if (V < 1 || total < 1 || total > 0x7FFFFFFFLL - 128) return 0;
+    int vf = 0;
+    for (int v = 0; v < V; v++) {
+        const long long b = so[v].pix_off, e = so[v + 1].pix_off;
+        if (e == b) continue;
+        if ((e - b + 128) * out_ld * 4 > LIM) return 0;           // a tile that begins in this view ends at most 128 rows past it
+        if (b % 128 == 0) continue;                               // no tile reaches into this view from an earlier one
+        const long long t0 = b / 128 * 128;
+        while (so[vf + 1].pix_off <= t0) vf++;                    // the view of that tile's first row (t0 < b: vf < v)
+        if ((si[v + 1].pix_off - si[vf].pix_off) * Cin * 4 > LIM) return 0;
+        if (su && (su[v + 1].pix_off - su[vf].pix_off) * out_ld * 4 > LIM) return 0;
+    }
+    return (int)total;
+}
 
 // One batch plan = geometry of every level for every view (+ sentinel entry V for tile_start).
 struct BatchPlan {
@@ -112,6 +146,12 @@ struct ConvArgs {
     float head_b[3];
     float* head_out;
     int head_ld;
+    // Packed row tiles (conv_p4.hip; a hint every other kernel family ignores): 0 = every view is tiled on its own (total_mtiles = the sum of
+    // the views' tiles, seg_out's tile_start); else the output level's row count (conv_pack_rows) -- the launcher then tiles the level's flat
+    // row space (seg_out's pix_off): M tile mt covers rows [128 mt, 128 mt + 128) of the level, across view ends, total_mtiles = ceil(rows /
+    // 128), so only the level's last tile is partly empty.  Per problem: the problems of a ConvGroup may differ.  Never with dyn_rows,
+    // row_map, gather, mask or the 4-channel input (their launchers keep per-view tiles).
+    int packed_rows;
 };
 
 // Several independent conv problems in ONE launch (the five FPN levels under the shared-weight RPN / RetinaNet heads, the

@@ -18,7 +18,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ---- fused epilogue (shared by the plain kernels and by the bottleneck-fused kernel's second GEMM) ----
 template <int EPI, bool MASK, int TM, int TN, bool GATHER = false>
 __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&acc)[TM][TN], float* smem, const int v, const LevelSeg& so,
-                                            const int m0, const int Mv, const int n0) {
+                                            const int m0, const int Mv, const int n0, const bool straddle = false) {
     constexpr int BM = 128, WN = 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
@@ -34,9 +34,11 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
     const float* __restrict__ ex_v = nullptr;
     int upH = 1, upW = 1;
     float uph_s = 0.f, upw_s = 0.f;
+    long long up_off = 0;
     if (EPI == 1) ex_v = a.residual + so.pix_off * (long long)out_ld;
     if (EPI == 2) {
         const LevelSeg su = a.seg_up[v];
+        up_off = su.pix_off;
         ex_v = a.up + su.pix_off * (long long)out_ld;
         upH = su.H; upW = su.W;
         uph_s = (float)upH / (float)Ho; upw_s = (float)upW / (float)Wo;
@@ -48,6 +50,9 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
     // The descriptors of everything addressed by output row END at the view's last valid row: a row past it loads zeros and its store is
     // dropped by the hardware, so a view's last, partial tile runs the same branch-free code as a full one (no per-element row tests, no
     // 64-bit addresses).  A lane of a padded output channel uses an offset beyond any descriptor.
+    // packed row tiles (ConvArgs::packed_rows): Mv counts the rows from view v's start to the tile's end, or to the level's end in its last
+    // tile -- output, residual, out16 and energy rows of a level are contiguous across views, so a tile that straddles views stores through
+    // the same descriptor at the same offsets; only the top-down term needs the row's own view (below)
     // gathered rows (ConvArgs::gather): row m goes to its own pixel of the full tensor -- the descriptors span the whole view, and a row
     // past the view's count gets the out-of-range offset instead
     const unsigned long long vb64 = (unsigned long long)(GATHER ? Ho * Wo : Mv) * (unsigned)row_b;
@@ -66,6 +71,22 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
             int m = m0 + tid;
             if (GATHER) {
                 s_src[tid] = m < Mv ? gather_pixel(a.gather[v], m, Wo) * row_b : 0x7FFF0000;
+            } else if (EPI == 2 && straddle) {
+                // packed rows, a tile across view ends: the row's own view, its grids of this level and of the coarser one (the same
+                // source-pixel arithmetic on them), addressed from view v's start of `up`
+                int src = 0;
+                if (m < Mv) {
+                    const long long r = so.pix_off + m;
+                    int vr = v;
+                    while (vr + 1 < a.V && a.seg_out[vr + 1].pix_off <= r) vr++;
+                    const LevelSeg sor = a.seg_out[vr], sur = a.seg_up[vr];
+                    const int ml = (int)(r - sor.pix_off), oy = ml / sor.W, ox = ml - oy * sor.W;
+                    const float hs = (float)sur.H / (float)sor.H, ws = (float)sur.W / (float)sor.W;
+                    int sy = (int)floorf((float)oy * hs); sy = sy > sur.H - 1 ? sur.H - 1 : sy;
+                    int sx = (int)floorf((float)ox * ws); sx = sx > sur.W - 1 ? sur.W - 1 : sx;
+                    src = ((int)(sur.pix_off - up_off) + sy * sur.W + sx) * out_ld * 4;
+                }
+                s_src[tid] = src;
             } else {
                 m = m < Mlast ? m : Mlast;
                 const int oy = m / Wo, ox = m - oy * Wo;
@@ -278,14 +299,28 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
         else { const int r = b - MT8 * NT; mt = MT8 + r / NT; nt = r % NT; }
     }
     const int n0 = nt * BN;
-    const int v = seg_find_view(a.seg_out, a.V, mt);
+    // Packed row tiles (ConvArgs::packed_rows): tile mt is rows [128 mt, 128 mt + 128) of the level's flat row space; v = the view of its
+    // first row, m0 that row inside the view (no longer a multiple of 128: nothing below needs one), Mv the rows from the view's start to
+    // the tile's (or the level's) end.  A tile that ends inside view v -- all but one per view -- is an ordinary tile from here on.  One
+    // that goes past the view's end STRADDLES: each A row then finds its own view below, and addresses it from view v's base.
+    constexpr bool CAN_PACK = !C4 && !MASK && !FUSE && !GATHER;
+    const bool packed = CAN_PACK && a.packed_rows != 0;
+    const int v = packed ? seg_find_row(a.seg_out, a.V, (long long)mt * BM) : seg_find_view(a.seg_out, a.V, mt);
     const LevelSeg so = a.seg_out[v];
     const LevelSeg si = a.seg_in[v];
     const int Ho = so.H, Wo = so.W, Hi = si.H, Wi = si.W;
     int Mv = Ho * Wo;
     if (a.dyn_rows) { const int d = a.dyn_rows[v]; Mv = d < Mv ? d : Mv; }
     if (GATHER) Mv = a.gather[v].cum[a.gather[v].nr];
-    const int m0 = (mt - so.tile_start) * BM;
+    int m0 = (mt - so.tile_start) * BM;
+    bool straddle = false;
+    if (CAN_PACK && packed) {
+        const int row0 = mt * BM, left = a.packed_rows - row0;
+        m0 = row0 - (int)so.pix_off;
+        const int end = m0 + (left < BM ? left : BM);
+        straddle = end > Mv;
+        Mv = end;
+    }
     if (m0 >= Mv) return;
     const float* __restrict__ in_v = a.in + si.pix_off * (long long)a.Cin;
     const int Cin = a.Cin, KW = a.KW, KH = a.KH, CoutPad = a.CoutPad;
@@ -295,27 +330,46 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
     const int g = tid & 3, arow = tid >> 2;
     unsigned rowmask[2];
     int rowvoff[2], riy0[2], rix0[2];
+    int tapw[2] = {0, 0};           // straddling tile: the row's own input width (its tap offsets are per row), else 0
 #pragma unroll
     for (int p = 0; p < 2; p++) {
         const int m = m0 + arow + 64 * p;
+        // straddling tile: the row's own view vr (a linear walk from v: a tile of a small level may touch many views, empty ones are
+        // passed over by the pix_off rule), its row ml inside that view, that view's geometry of both levels, and the view's distance
+        // from view v in the input tensor
+        int ml = m, Wo_r = Wo, Hi_r = Hi, Wi_r = Wi, dpix = 0;
+        if (CAN_PACK && straddle && m < Mv) {
+            const long long r = so.pix_off + m;
+            int vr = v;
+            while (vr + 1 < a.V && a.seg_out[vr + 1].pix_off <= r) vr++;
+            const LevelSeg sor = a.seg_out[vr], sir = a.seg_in[vr];
+            ml = (int)(r - sor.pix_off); Wo_r = sor.W; Hi_r = sir.H; Wi_r = sir.W; dpix = (int)(sir.pix_off - si.pix_off);
+        }
         // gathered rows (ConvArgs::row_map): row m is the output pixel row_map[m] of the view's grid; everything below addresses the INPUT
         // from (oy, ox), the epilogue stores at row m
-        const int mp = GATHER ? (m < Mv ? gather_pixel(a.gather[v], m, Wo) : 0) : (a.row_map && m < Mv) ? a.row_map[so.pix_off + m] : m;
-        const int oy = mp / Wo, ox = mp - oy * Wo;
+        const int mp = GATHER ? (m < Mv ? gather_pixel(a.gather[v], m, Wo) : 0) : (a.row_map && m < Mv) ? a.row_map[so.pix_off + m] : ml;
+        const int oy = mp / Wo_r, ox = mp - oy * Wo_r;
         const int iy0 = oy * a.stride - a.pad, ix0 = ox * a.stride - a.pad;
         unsigned msk = 0;
         if (!C4 && m < Mv)
             for (int t = 0; t < KH * KW; t++) {
                 const int th = t / KW, tw = t - th * KW;
                 const int iy = iy0 + th, ix = ix0 + tw;
-                if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) msk |= 1u << t;
+                if (iy >= 0 && iy < Hi_r && ix >= 0 && ix < Wi_r) msk |= 1u << t;
             }
         rowmask[p] = msk;
         rowvoff[p] = (((oy * a.stride) * Wi + ox * a.stride) * Cin + (C4 ? 0 : 4 * g)) * 4;
+        // straddling tile: the byte offset of the row's tap (0, 0) from view v's UNSHIFTED base (it may lie before the base for a row
+        // of view v itself: only in-image taps, whose offsets are not, are ever loaded); the taps' own offsets join it per row below
+        if (CAN_PACK && straddle) { rowvoff[p] = ((dpix + iy0 * Wi_r + ix0) * Cin + 4 * g) * 4; tapw[p] = Wi_r; }
         riy0[p] = m < Mv ? iy0 : -0x40000000; rix0[p] = ix0;
     }
+    // straddling tile: the k-loop's wave-uniform tap offset (soffA) is zero -- widths differ from row to row -- and the descriptor starts
+    // at view v's first pixel; it spans the later views the tile touches (conv_pack_rows), and an out-of-image tap still takes the
+    // out-of-range offset, never a pixel of the neighbouring view
+    const int Wi_s = straddle ? 0 : Wi, Cin_s = straddle ? 0 : Cin, cin_v4 = straddle ? Cin * 4 : 0;
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(in_v - (long long)a.pad * (Wi + 1) * Cin), 0, 0x7FFE0000, 0x00020000);
+        (void*)(in_v - (straddle ? 0ll : (long long)a.pad * (Wi + 1) * Cin)), 0, 0x7FFE0000, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(a.w4 + (long long)n0 * 8), 0, 0x7FFE0000, 0x00020000);
     int u_kh = 0, u_kw = 0, u_ci = 0, u_kt = 0;
     // A LDS write offsets (floats): k = 4g + t -> kq = g >> 1, j = 2 (g & 1) + (t >> 1), h = t & 1
@@ -350,9 +404,10 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             v1 = ok1 ? rowvoff[1] + toff : 0x7FFF0000;                                                     \
         } else {                                                                                           \
             const unsigned u_bit = 1u << (u_kh * KW + u_kw);                                               \
-            soffA = ((u_kh * Wi + u_kw) * Cin + u_ci) * 4;                                                 \
-            v0 = (rowmask[0] & u_bit) ? rowvoff[0] : 0x7FFF0000;                                           \
-            v1 = (rowmask[1] & u_bit) ? rowvoff[1] : 0x7FFF0000;                                           \
+            soffA = ((u_kh * Wi_s + u_kw) * Cin_s + u_ci) * 4;                                             \
+            /* straddling tile (cin_v4 != 0): the tap's offset at the row's own input width */              \
+            v0 = (rowmask[0] & u_bit) ? rowvoff[0] + (CAN_PACK ? (u_kh * tapw[0] + u_kw) * cin_v4 : 0) : 0x7FFF0000; \
+            v1 = (rowmask[1] & u_bit) ? rowvoff[1] + (CAN_PACK ? (u_kh * tapw[1] + u_kw) * cin_v4 : 0) : 0x7FFF0000; \
         }                                                                                                  \
         ra0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, v0, soffA, 0));         \
         ra1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, v1, soffA, 0));         \
@@ -405,6 +460,13 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
         for (int p = 0; p < 2; p++)
 #pragma unroll
             for (int t = 0; t < (TAPS > 0 ? TAPS : 1); t++) voffA[p][t] = ((rowmask[p] >> t) & 1u) ? rowvoff[p] : 0x7FFF0000;
+        if (CAN_PACK && TAPS == 9 && straddle) {       // straddling tile: each tap's offset at the row's own input width (soffA carries none)
+#pragma unroll
+            for (int p = 0; p < 2; p++)
+#pragma unroll
+                for (int t = 0; t < 9; t++)
+                    if ((rowmask[p] >> t) & 1u) voffA[p][t < TAPS ? t : 0] = rowvoff[p] + ((t / 3) * tapw[p] + t % 3) * cin_v4;
+        }
     }
     if (TAPS == 0) {
         P4_LOAD();
@@ -414,7 +476,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
 #define U_LOAD0(T)                                                                                         \
     {                                                                                                      \
         const int soffB = u_kt * 2 * CoutPad * 8 * 4;                                                      \
-        const int soffA = (TAPS == 9 ? ((((T) / 3) * Wi + ((T) % 3)) * Cin + ci_ld) : ci_ld) * 4;          \
+        const int soffA = (TAPS == 9 ? ((((T) / 3) * Wi_s + ((T) % 3)) * Cin_s + ci_ld) : ci_ld) * 4;      \
         ra0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[0][T], soffA, 0)); \
         ra1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[1][T], soffA, 0)); \
         rb0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, bvoff0, soffB, 0));     \
@@ -498,7 +560,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
 #define U_LOAD(T)                                                                                          \
     {                                                                                                      \
         const int soffB = u_kt * 2 * CoutPad * 8 * 4;                                                      \
-        const int soffA = (TAPS == 9 ? ((((T) / 3) * Wi + ((T) % 3)) * Cin + ci_ld) : ci_ld) * 4;          \
+        const int soffA = (TAPS == 9 ? ((((T) / 3) * Wi_s + ((T) % 3)) * Cin_s + ci_ld) : ci_ld) * 4;      \
         ra0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[0][T], soffA, 0)); \
         ra1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[1][T], soffA, 0)); \
         rb0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, bvoff0, soffB, 0));     \
@@ -684,7 +746,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             }
         }
     } else {
-        p4_epilogue<EPI, MASK, TM, TN, GATHER>(a, acc, smem, v, so, m0, Mv, n0);
+        p4_epilogue<EPI, MASK, TM, TN, GATHER>(a, acc, smem, v, so, m0, Mv, n0, CAN_PACK && straddle);
     }
     if (trace && tid == 0) {
         trace[3] = __builtin_amdgcn_s_memtime();
@@ -731,6 +793,15 @@ static inline bool p4_tile_ok(const ConvArgs& a, const bool wide, const ConvForc
     return !(a.energy4 && !wide);                               // the energy is written by the 128 x 128 tile only
 }
 
+// Packed row tiles: the problem as this family launches it -- with the level's packed tile count where the caller offered the row count
+// (ConvArgs::packed_rows) and the kernels pack the launch, else with the hint cleared and the per-view tiles it came with.  Grid sizes and
+// the tail-quantisation rule below see the count that is launched.
+static inline ConvArgs p4_tiled(ConvArgs a) {
+    if (a.packed_rows > 0 && a.Cin != 4 && !a.dyn_rows && !a.row_map && !a.gather && !a.mask) a.total_mtiles = (a.packed_rows + 127) / 128;
+    else a.packed_rows = 0;
+    return a;
+}
+
 #define P4_NAME(K, EPIV, C4V, TNV, TAPSV) K "<" #EPIV "," #C4V "," #TNV "," #TAPSV ">"
 template <int EPI, bool C4, int TN, int TAPS>
 static const char* p4_go(const dim3 grid, hipStream_t stream, const ConvArgs& a, const char* name) {
@@ -749,7 +820,7 @@ const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, C
     const bool wide = f.tile == TILE_NARROW ? false : p[0].CoutPad % 128 == 0;
     ConvGroup g; g.n = n; int blk = 0;
     for (int i = 0; i < n; i++) {
-        const ConvArgs& a = p[i];
+        const ConvArgs a = p4_tiled(p[i]);
         if (p4_refuses(a) || !p4_tile_ok(a, wide, f) || (a.CoutPad % 128 == 0) != (p[0].CoutPad % 128 == 0)) return nullptr;
         if (a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return nullptr;
         if ((a.mask != nullptr) != (p[0].mask != nullptr)) return nullptr;
@@ -785,7 +856,8 @@ const char* launch_conv_p4_fused(const ConvArgs& c2, const ConvArgs& c3, hipStre
 }
 
 // the kernel if this variant handled the launch, else nullptr
-const char* launch_conv_p4(const ConvArgs& a, hipStream_t stream, ConvForce f) {
+const char* launch_conv_p4(const ConvArgs& a_in, hipStream_t stream, ConvForce f) {
+    const ConvArgs a = p4_tiled(a_in);
     if (p4_refuses(a)) return nullptr;
     bool wide = a.CoutPad % 128 == 0;
     if (wide) {

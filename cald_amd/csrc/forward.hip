@@ -196,7 +196,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
     a.dyn_rows = dyn; a.row_map = nullptr; a.gather = nullptr; a.V = V;
     a.Cin = L.Cin; a.Cout = L.Cout; a.CoutPad = L.CoutPad; a.Kpad = L.Kpad;
     a.KH = L.KH; a.KW = L.KW; a.stride = L.stride; a.pad = L.pad; a.relu = relu ? 1 : 0;
-    a.total_mtiles = level_tiles(m->plan, lout, V);
+    a.total_mtiles = level_tiles(m->plan, lout, V); a.packed_rows = 0;
     a.out_ld = L.Cout; a.in_relu = in_relu ? 1 : 0; a.zeros = m->ctx->d_zeros;
     a.mask = nullptr;
     // the kernels address a view's tensor through a buffer resource / 32-bit byte offsets: a view (or a dense RoI-row segment) must stay
@@ -233,12 +233,24 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
     a.wstem = L.wstem && stem_grid_exact(m->plan.seg[lout], V) ? L.wstem : nullptr;
     return 2.0 * (double)level_pix(m->plan, lout, V) * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue);
 }
+// Packed row tiles ("packed row tiles"): a dense launch -- host-planned rows, every pixel of the level -- offers conv_p4
+// the level's row count; the tile count a launch is booked and classed with stays the per-view one.  Not offered: launches whose row
+// counts live on the device (dyn_rows / row_map), the gathered launches of the cut_out reuse, the fused layer-1 pair.
+bool cald_host::conv_pack_default() {
+    static const bool on = !(getenv("CALD_CONV_PACK") && atoi(getenv("CALD_CONV_PACK")) == 0);
+    return on;
+}
+static void offer_packing(cald_model* m, ConvArgs& a, int lin, int lout, int lup, int V) {
+    if (!(m->row_packing < 0 ? conv_pack_default() : m->row_packing != 0) || a.dyn_rows || a.row_map || a.gather || a.mask) return;
+    a.packed_rows = conv_pack_rows(m->plan.seg[lin], m->plan.seg[lout], a.up ? m->plan.seg[lup] : nullptr, V, a.Cin, a.out_ld);
+}
 static int conv_on(cald_model* m, const ConvLayer& L, const float* in, float* out, int lin, int lout, int V, bool relu,
                    const float* residual = nullptr, const float* up = nullptr, int lup = 0, const int* dyn = nullptr,
                    bool in_relu = false) {
     ConvArgs a;
     const double flops = fill_conv_args(m, a, L, in, out, lin, lout, V, relu, residual, up, lup, dyn, in_relu);
     if (flops < 0.0) return (int)flops;            // fill_conv_args failed: the (negative) status code
+    offer_packing(m, a, lin, lout, lup, V);
     return run_conv(m->ctx, a, flops);
 }
 // Bottleneck conv2 (3 x 3) + conv3 (1 x 1 expand, + residual) of one block: ONE launch when conv_p4.hip's fused kernel covers the
@@ -272,6 +284,7 @@ static int conv_group_on(cald_model* m, const ConvSpec* sp, int n, int V) {
         if (sp[i].in16) a[i].in16 = sp[i].in16;       // the input also exists in split form (rpn_prune.hip's look-ahead)
         if (sp[i].out16) a[i].out16 = sp[i].out16;
         a[i].energy4 = sp[i].energy4;
+        offer_packing(m, a[i], sp[i].level, sp[i].level, 0, V);
         flops += f; tiles += a[i].total_mtiles;
     }
     cald_ctx* c = m->ctx;

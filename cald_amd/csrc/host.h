@@ -129,6 +129,7 @@ struct cald_model {
     // the look-ahead's 1 x 1 objectness head in conv_h4.hip's epilogue (cald_model_set_look_fuse): 0 off (two launches), 1 where conv_h4 takes the
     // look-ahead launch by its own rule, 2 wherever conv_h4 is correct (test hook for small views); the head's first three channels [3][256] + bias
     int look_fuse = 1; float* look_head_w = nullptr; float look_head_b[3] = {0, 0, 0};
+    int row_packing = -1;           // cald_model_set_row_packing: -1 the process default (conv_pack_default), 0 per-view row tiles, 1 packed row tiles
     bool prune_bound_voided = false;   // test hook cald_model_set_rpn_prune_bound replaced finalize's constants: the sweeps' ratios are not the certificate's
     bool prune_capture = false;     // test hook: cald_forward takes the pruned path too and keeps the look-ahead's logit map (cald_model_set_rpn_prune_capture)
     ConvLayer p6, p7, cls_tower[4], reg_tower[4], cls_out, reg_out;   // RetinaNet
@@ -251,6 +252,7 @@ void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& cout
 // forward.hip
 void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], bool retina);
 bool stem_grid_exact(const LevelSeg* seg, int V);
+bool conv_pack_default();       // packed row tiles (ConvArgs::packed_rows) in the dense conv_p4 launches: on unless CALD_CONV_PACK=0
 int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
                   const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr, FwdSsm* ssm = nullptr);
 // sweep.hip

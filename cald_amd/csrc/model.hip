@@ -365,6 +365,12 @@ extern "C" int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was) {
     m->cr.mode = mode;
     return 0;
 }
+extern "C" int cald_model_set_row_packing(cald_model* m, int mode, int* was) {
+    if (!m || mode < -1 || mode > 1) return fail(CALD_ERR_INVALID, "bad argument");
+    if (was) *was = m->row_packing;
+    m->row_packing = mode;
+    return 0;
+}
 extern "C" int cald_model_set_look_fuse(cald_model* m, int mode, int* was) {
     if (!m || mode < 0 || mode > 2) return fail(CALD_ERR_INVALID, "bad argument");
     if (was) *was = m->look_fuse;

@@ -291,6 +291,12 @@ extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* p
         A.V = p.V; A.Cin = p.Cin; A.Cout = p.Cout;
         A.KH = p.KH; A.KW = p.KW; A.stride = p.stride; A.pad = p.pad; A.relu = p.relu ? 1 : 0; A.in_relu = p.in_relu ? 1 : 0;
         A.total_mtiles = so[p.V].tile_start; A.out_ld = p.out_ld; A.zeros = c->d_zeros;
+        // row tiles (cald_conv_probe::row_packing): auto offers conv_p4 the packed row count under a forward's own rule
+        if (p.row_packing < CALD_PROBE_PACK_AUTO || p.row_packing > CALD_PROBE_PACK_ON) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d: bad row_packing", i);
+        const bool packable = !p.has_dyn && !p.row_map && !p.gather && !p.mask && p.Cin != 4 && path != CONV_P4_FUSED;
+        if (packable && (p.row_packing == CALD_PROBE_PACK_ON || (p.row_packing == CALD_PROBE_PACK_AUTO && conv_pack_default())))
+            A.packed_rows = conv_pack_rows(si, so, p.up ? su : nullptr, p.V, p.Cin, p.out_ld);
+        if (p.row_packing == CALD_PROBE_PACK_ON && !A.packed_rows) return fail(CALD_ERR_INVALID, "cald_op_conv_probe: problem %d cannot run on packed row tiles", i);
     }
     if (path == CONV_P4_FUSED) a[1].in = a[0].out;       // conv3 reads conv2's output (which the fused kernel keeps on chip)
     const ConvForce f{path, tile};
@@ -307,6 +313,27 @@ extern "C" int cald_op_conv_probe(cald_ctx* c, int precision, cald_conv_probe* p
     }
     for (const Back& b : back) HIPCHK(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
     snprintf(kernel, (size_t)kernel_cap, "%s", all.c_str());
+    return 0;
+}
+// host-only: the packed row tiles' lookup (common.h seg_find_row) and admission rule (conv_pack_rows) on a plan the caller describes
+extern "C" int cald_op_row_pack_lookup(int V, const int* in_hw, const int* out_hw, int Cin, int out_ld, int64_t n, const int64_t* rows,
+                                       int* view_out, int64_t* local_out, int64_t* packed_rows_out) {
+    if (V < 1 || V > CALD_MAX_VIEWS || !in_hw || !out_hw || n < 0 || (n && (!rows || !view_out || !local_out)))
+        return fail(CALD_ERR_INVALID, "cald_op_row_pack_lookup: bad arguments");
+    std::vector<LevelSeg> si(V + 1), so(V + 1);
+    memset(si.data(), 0, si.size() * sizeof(LevelSeg)); memset(so.data(), 0, so.size() * sizeof(LevelSeg));
+    for (int v = 0; v < V; v++) {
+        if (in_hw[2 * v] < 0 || in_hw[2 * v + 1] < 0 || out_hw[2 * v] < 0 || out_hw[2 * v + 1] < 0) return fail(CALD_ERR_INVALID, "cald_op_row_pack_lookup: negative size");
+        si[v].H = in_hw[2 * v]; si[v].W = in_hw[2 * v + 1]; so[v].H = out_hw[2 * v]; so[v].W = out_hw[2 * v + 1];
+        si[v + 1].pix_off = si[v].pix_off + (long long)si[v].H * si[v].W;
+        so[v + 1].pix_off = so[v].pix_off + (long long)so[v].H * so[v].W;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        if (rows[i] < 0 || rows[i] >= so[V].pix_off) return fail(CALD_ERR_INVALID, "cald_op_row_pack_lookup: row %lld outside the level", (long long)rows[i]);
+        const int v = seg_find_row(so.data(), V, rows[i]);
+        view_out[i] = v; local_out[i] = rows[i] - so[v].pix_off;
+    }
+    if (packed_rows_out) *packed_rows_out = conv_pack_rows(si.data(), so.data(), nullptr, V, Cin, out_ld);
     return 0;
 }
 void launch_mfma_f16_probe(const unsigned short* A, const unsigned short* B, const unsigned* C, unsigned* D, long long n, hipStream_t stream);   // conv_h3.hip

@@ -432,8 +432,21 @@ typedef struct cald_conv_probe {
      * written (out / out16 may be null).  head_out null = no head */
     const float* head_w; const float* head_b;
     float* head_out; int64_t head_out_n; int head_ld;
+    /* conv_p4's row tiles: 0 auto = the product's choice (packed wherever a forward would pack this launch, unless CALD_CONV_PACK=0),
+     * 1 = per-view tiles, 2 = packed tiles (CALD_ERR_INVALID for a problem that cannot be packed: dyn_rows, row_map, gather, mask,
+     * Cin == 4, the fused pair).  Kernel families other than conv_p4 tile per view whatever this says. */
+    int row_packing;
 } cald_conv_probe;
+#define CALD_PROBE_PACK_AUTO 0
+#define CALD_PROBE_PACK_OFF 1
+#define CALD_PROBE_PACK_ON 2
 int cald_op_conv_probe(cald_ctx* ctx, int precision, cald_conv_probe* probs, int n, int path, int tile, char* kernel, int kernel_cap);
+/* Host-only test hook of the packed row tiles (tests/test_row_packing_lookup.py; needs no GPU): on a level of V views with the given input
+ * and output sizes ([V][2] H, W; 0 x 0 = empty), for each of n rows of the output level's flat row space the view that holds it and the row
+ * inside that view, by the kernels' own bisection (largest v with pix_off[v] <= row); *packed_rows_out = the row count a launch with Cin
+ * input channels and row stride out_ld may be packed with, or 0 where a straddling tile would leave the 32-bit offset range. */
+int cald_op_row_pack_lookup(int V, const int* in_hw, const int* out_hw, int Cin, int out_ld, int64_t n, const int64_t* rows,
+                            int* view_out, int64_t* local_out, int64_t* packed_rows_out);
 /* Parity hook of CALD_PRECISION_F16X3's arithmetic primitive: n independent dot products D[i] = C[i] + sum_{k<16} A[i][k] B[i][k], each
  * evaluated by the hardware as ONE output element of v_mfma_f32_32x32x16_f16 (the instruction conv_h3.hip / conv_h4.hip are built on;
  * there is no reference function -- the reference has no fp16 path).  A, B: fp16 bit patterns [n][16], C / D: fp32
@@ -505,6 +518,10 @@ int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was);
  * exact head's fma chain (default; same bits, the hidden tensor is never written), 2 = one launch wherever conv_h4 can run at all (test hook
  * for small views).  Returns the previous setting in *was. */
 int cald_model_set_look_fuse(cald_model* m, int mode, int* was);
+/* packed row tiles of the dense conv_p4 launches of one model's forwards: -1 = the process default (on unless
+ * CALD_CONV_PACK=0), 0 = every view is tiled on its own (each view ends with a partly empty 128-row tile), 1 = the tiles cover the level's
+ * flat row space across view ends.  Same bits either way.  Returns the previous setting in *was. */
+int cald_model_set_row_packing(cald_model* m, int mode, int* was);
 /* torchvision's stock remove_small_boxes in the Faster R-CNN tail: with min_size > 0, candidates above the score threshold whose clipped
  * width or height is < min_size are dropped before NMS (and before batched_nms takes its maximum coordinate).  Default 0: the tail of
  * detection/frcnn_la.py, which has no such step.  The decision-margin audit does not cover it (cald_sweep_audit: CALD_ERR_UNSUPPORTED).
