@@ -123,6 +123,11 @@ class WgradPlan(C.Structure):
                 ("kernel", C.c_char * 48), ("reduce_kernel", C.c_char * 32)]
 
 
+# cald_ssm_pick_fn of include/cald_hip.h.  The entry points that take one declare it c_void_p, so that a Python callback
+# (C.cast(PICK_FN(f), C.c_void_p)) and a C function of the library (C.cast(lib().cald_ssm_pick_mt19937, C.c_void_p)) both pass.
+PICK_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, c_i, c_i, c_i)
+SSM_RETINA_TAKE = 500    # CALD_SSM_RETINA_TAKE
+
 # name -> (restype, argtypes): must list every symbol of include/cald_hip.h
 SIGNATURES = {
     "cald_last_error": (C.c_char_p, []),
@@ -144,6 +149,9 @@ SIGNATURES = {
     "cald_sweep_audit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d, c_f]),
     "cald_sweep_ltc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, c_d]),
     "cald_sweep_ssm": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, C.c_int64, c_i, c_i, c_f, c_f, c_i8, c_i64]),
+    "cald_ssm_pick_mt19937": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i, c_i, c_i]),
+    "cald_sweep_ssm_retina": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, c_i, c_i, c_f, c_f,
+                                        c_i8, c_i64]),
     "cald_sweep_lsc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.c_uint64, C.c_int, c_d]),
     "cald_lossnet_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "cald_lossnet_load_tensor": (C.c_int, [C.c_void_p, C.c_char_p, c_f, c_i64, C.c_int]),
@@ -182,6 +190,8 @@ SIGNATURES = {
                                           c_i, c_i, c_f, c_f, c_i8]),
     "cald_op_retina_postprocess": (C.c_int, [C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f] + [C.c_int] * 6
                                    + [C.c_float, C.c_float, C.c_int, c_f, c_f, c_i64, c_f, c_f, c_i]),
+    "cald_op_retina_ssm_postprocess": (C.c_int, [C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f] + [C.c_int] * 6
+                                       + [C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_f, c_f, c_i8]),
     "cald_op_rpn_prune": (C.c_int, [C.c_void_p, C.POINTER(RpnPruneProbe)]),
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),
     "cald_op_conv2d": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -78,12 +78,21 @@ void cald_host::RetinaTailBufs::layout(Bump& B, int V, int K, int per_class, int
     cand_box = B.get<float>((size_t)V * K * cand_cap * 4); cand_skip = B.get<unsigned char>((size_t)V * K * cand_cap);
     kept_anchor = B.get<int>((size_t)V * K * per_class); kept_box = B.get<float>((size_t)V * K * per_class * 4); kept_count = B.get<int>((size_t)V * K);
 }
+void cald_host::RetinaSsmBufs::layout(Bump& B, int V, int K, int per_class, int maxa) {
+    cand_cap = maxa > 0 ? maxa : 1; nblk = (cand_cap + 255) / 256;
+    const size_t VK = (size_t)V * K, rows = VK * per_class;
+    cand_count = B.get<int>(VK); blk_off = B.get<int>(VK * nblk); list = B.get<int>(VK * cand_cap); vmax = B.get<unsigned>(V); al = B.get<int>(V);
+    picks = B.get<int>(VK * CALD_SSM_RETINA_TAKE); n_picks = B.get<int>(VK);
+    kept_anchor = B.get<int>(rows); kept_box = B.get<float>(rows * 4); kept_count = B.get<int>(VK);
+    row_off = B.get<int>(VK); count = B.get<int>(V); total = B.get<int>(1);
+    boxes = B.get<float>(rows * 4); scores = B.get<float>(rows); labels = B.get<signed char>(rows * (K - 1));
+}
 struct RetinaBufs {
     float *ret_t[2][2][5], *cls_h[5], *reg_h[5]; RetinaTailBufs tail;   // ret_t[tower][ping-pong][level]: from matrix-pipe layer to matrix-pipe layer
-    void layout(Bump& B, SplitReg& S, const long long* px, int V, int cls_ld, int K, int per_class, int max_anchors) {
+    void layout(Bump& B, SplitReg& S, const long long* px, int V, int cls_ld, int K, int per_class, int max_anchors, RetinaSsmBufs* ssm_tail) {
         for (int h = 0; h < 2; h++) for (int q = 0; q < 2; q++) for (int i = 0; i < 5; i++) { ret_t[h][q][i] = B.get<float>(px[3 + i] * 256); S.only(ret_t[h][q][i]); }
         for (int i = 0; i < 5; i++) { cls_h[i] = B.get<float>(px[3 + i] * cls_ld); reg_h[i] = B.get<float>(px[3 + i] * 36); }
-        tail.layout(B, V, K, per_class, max_anchors);
+        if (ssm_tail) ssm_tail->layout(B, V, K, per_class, max_anchors); else tail.layout(B, V, K, per_class, max_anchors);
     }
 };
 void cald_host::ProposalBufs::layout(Bump& B, int V) { proposals = B.get<float>((size_t)V * CALD_ROI_CAP * 4); prop_count = B.get<int>(V); }
@@ -175,6 +184,42 @@ RetinaArgs cald_host::retina_args(const RetinaTailBufs& S, const float* const* c
     ra.cand_count = S.cand_count; ra.cand_key = S.cand_key; ra.cand_box = S.cand_box; ra.cand_skip = S.cand_skip;
     ra.kept_anchor = S.kept_anchor; ra.kept_box = S.kept_box; ra.kept_count = S.kept_count; ra.det = det;
     return ra;
+}
+
+RetinaSsmArgs cald_host::retina_ssm_args(const RetinaSsmBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
+                                         const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class) {
+    RetinaTailBufs T; T.cand_cap = S.cand_cap; T.cand_count = S.cand_count; T.kept_anchor = S.kept_anchor; T.kept_box = S.kept_box; T.kept_count = S.kept_count;
+    RetinaSsmArgs sa{};
+    sa.r = retina_args(T, cls, reg, plan, views, base_anchors, A, K, V, score_thr, nms_thr, per_class, DetBuffers{});
+    sa.conf_thr = SSM_CONF_THR; sa.nblk = S.nblk; sa.blk_off = S.blk_off; sa.list = S.list; sa.vmax = S.vmax; sa.al = S.al; sa.picks = S.picks; sa.n_picks = S.n_picks;
+    sa.row_off = S.row_off; sa.count = S.count; sa.total = S.total; sa.boxes = S.boxes; sa.scores = S.scores; sa.labels = S.labels;
+    return sa;
+}
+int cald_host::retina_ssm_pick_stop(cald_ctx* c, const RetinaSsmBufs& S, int V, int K, cald_ssm_pick_fn pick, void* user, int image0, int* h_counts) {
+    const int T = CALD_SSM_RETINA_TAKE;
+    std::vector<int> al((size_t)V), counts((size_t)V * K), picks((size_t)V * K * T, 0), np((size_t)V * K, 0);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(al.data(), S.al, (size_t)V * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts.data(), S.cand_count, (size_t)V * K * 4, hipMemcpyDeviceToHost));
+    for (int v = 0; v < V; v++) {
+        const int* cn = &counts[(size_t)v * K]; int* pk = &picks[(size_t)v * K * T]; int* n = &np[(size_t)v * K];
+        for (int k = 0; k < K; k++)
+            if (cn[k] < 0 || cn[k] > S.cand_cap) return fail(CALD_ERR_HIP, "retina ssm: image %d class %d has %d candidates (at most %d anchors)", image0 + v, k, cn[k], S.cand_cap);
+        if (al[(size_t)v]) continue;
+        const int rc = pick(user, image0 + v, K, cn, pk, n);
+        if (rc) return fail(CALD_ERR_INVALID, "retina ssm: the pick callback returned %d for image %d", rc, image0 + v);
+        for (int k = 0; k < K; k++) {
+            if (n[k] < 0 || n[k] > cn[k] || n[k] > T)
+                return fail(CALD_ERR_INVALID, "retina ssm: image %d class %d: %d picks of %d candidates (at most %d)", image0 + v, k, n[k], cn[k], T);
+            for (int j = 0; j < n[k]; j++)
+                if (pk[(size_t)k * T + j] < 0 || pk[(size_t)k * T + j] >= cn[k])
+                    return fail(CALD_ERR_INVALID, "retina ssm: image %d class %d: pick %d is %d, outside 0..%d", image0 + v, k, j, pk[(size_t)k * T + j], cn[k] - 1);
+        }
+    }
+    HIPCHK(hipMemcpy(S.picks, picks.data(), picks.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(S.n_picks, np.data(), np.size() * 4, hipMemcpyHostToDevice));
+    if (h_counts) memcpy(h_counts, counts.data(), counts.size() * 4);
+    return 0;
 }
 
 // conv_stem.hip wants every view's output to be an exact grid of 8 x 16 pixel blocks (padded sizes are multiples of 32); seg: host copy,
@@ -324,7 +369,7 @@ static const float RPN_MIN_SIZE = 1e-3f;
 // by prepare().  feat (host.h FwdFeatures): the forward stops after the FPN and hands out the pyramid; `det` is then not used, and pruning,
 // cut_out reuse and the audit do not apply.
 struct ForwardRun {
-    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat; FwdSsm* ssm;
+    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat; FwdSsm* ssm; FwdRetinaSsm* rssm;
     // ---- filled by prepare() ----
     cald_ctx* c = nullptr; hipStream_t st = nullptr; const BatchPlan* dp = nullptr;
     bool retina = false, prune = false;
@@ -343,7 +388,7 @@ struct ForwardRun {
         if (retina) {
             int maxa = 0;
             for (int v = 0; v < V; v++) { int t = 0; for (int l = 3; l < 8; l++) t += P.seg[l][v].H * P.seg[l][v].W * 9; if (t > maxa) maxa = t; }
-            Fr.layout(B, S, px, V, m->cls_out.Cout, m->cfg.num_classes, m->cfg.detections_per_img, maxa);
+            Fr.layout(B, S, px, V, m->cls_out.Cout, m->cfg.num_classes, m->cfg.detections_per_img, maxa, rssm ? &rssm->out : nullptr);
             return;
         }
         Fn.layout(B, px, V, m->cfg.rpn_pre_nms_top_n);
@@ -359,7 +404,9 @@ struct ForwardRun {
         if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
         if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
         if (ssm && (feat || audit_out || ru || m->cfg.arch != CALD_ARCH_FRCNN)) return fail(CALD_ERR_INVALID, "the SSM forward is a plain Faster R-CNN forward");
-        if (!feat && !ssm && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
+        if (rssm && (feat || audit_out || ru || ssm || !rssm->pick || m->cfg.arch != CALD_ARCH_RETINANET || m->cfg.num_classes < 2))
+            return fail(CALD_ERR_INVALID, "the RetinaNet SSM forward is a plain RetinaNet forward with a pick callback and at least two classes");
+        if (!feat && !ssm && !rssm && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
         HIPCHK(hipSetDevice(c->device));
         for (int v = 0; v < V; v++) {
             ViewDesc& d = views[v];
@@ -484,8 +531,19 @@ struct ForwardRun {
             m->dbg["cls" + std::to_string(i)] = {Fr.cls_h[i], 3 + i, m->cls_out.Cout, 0};
             m->dbg["reg" + std::to_string(i)] = {Fr.reg_h[i], 3 + i, 36, 0};
         }
+        if (rssm) return retina_ssm_tail();
         launch_retina_postprocess(retina_args(Fr.tail, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
                                               m->cfg.box_nms_thresh, m->cfg.detections_per_img, det), Fr.tail.max_anchors, st);
+        return 0;
+    }
+    // the SSM tail (retina_ssm.hip) on the same head tensors: phase A, the host stop for the picks, phase B
+    int retina_ssm_tail() {
+        const RetinaSsmArgs sa = retina_ssm_args(rssm->out, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
+                                                 m->cfg.box_nms_thresh, m->cfg.detections_per_img);
+        launch_retina_ssm_phase_a(sa, st);
+        HIPCHK(hipGetLastError());
+        if (int rc = retina_ssm_pick_stop(c, rssm->out, V, m->cfg.num_classes, rssm->pick, rssm->user, rssm->image0, nullptr)) return rc;
+        launch_retina_ssm_phase_b(sa, st);
         return 0;
     }
     // LastLevelMaxPool: max_pool2d(P5, 1, 2) = every other pixel of every other row; in F16X3 the copy runs on P5's split twin
@@ -666,8 +724,8 @@ struct ForwardRun {
 };
 
 int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
-                             FwdFeatures* feat, FwdSsm* ssm) {
-    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat, ssm}.run();
+                             FwdFeatures* feat, FwdSsm* ssm, FwdRetinaSsm* rssm) {
+    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat, ssm, rssm}.run();
 }
 
 static int fill_view(ViewDesc& d, const cald_view& v) {

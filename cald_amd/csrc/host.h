@@ -228,6 +228,22 @@ struct RetinaTailBufs {
     float *cand_box = nullptr, *kept_box = nullptr; unsigned char* cand_skip = nullptr;
     void layout(Bump& B, int V, int K, int per_class, int max_anchors);      // max_anchors: the largest anchor count of a view
 };
+// the SSM tail of RetinaNet (retina_ssm.hip): scratch and results of V views; the results hold K * per_class rows a view
+struct RetinaSsmBufs {
+    int *cand_count = nullptr, *blk_off = nullptr, *list = nullptr, *al = nullptr, *picks = nullptr, *n_picks = nullptr, *kept_anchor = nullptr, *kept_count = nullptr,
+        *row_off = nullptr, *count = nullptr, *total = nullptr, cand_cap = 0, nblk = 0;
+    unsigned* vmax = nullptr; float *kept_box = nullptr, *boxes = nullptr, *scores = nullptr; signed char* labels = nullptr;
+    void layout(Bump& B, int V, int K, int per_class, int max_anchors);      // max_anchors: the largest anchor count of a view
+};
+// ---- the SSM forward of RetinaNet (cald_sweep_ssm_retina): the heads, then phase A, the host stop (`pick` once per image with al == 0;
+// image = image0 + view) and phase B in place of the stock tail.  `det` is not used.  Filled by forward_model: the tail's buffers in the
+// arena (valid until the context's next forward) ----
+struct FwdRetinaSsm { cald_ssm_pick_fn pick = nullptr; void* user = nullptr; int image0 = 0; RetinaSsmBufs out; };
+RetinaSsmArgs retina_ssm_args(const RetinaSsmBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
+                              const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class);
+// the host stop between the two phases: waits for phase A, reads al and the counts, asks `pick` for every view with al == 0 (in view order),
+// checks every answer and uploads the picks.  h_counts (optional) receives the counts [V][K]
+int retina_ssm_pick_stop(cald_ctx* c, const RetinaSsmBufs& S, int V, int K, cald_ssm_pick_fn pick, void* user, int image0, int* h_counts);
 RoiArgs roi_args(const RoiBufs& S, const float* const* feat, const BatchPlan* plan, int C, int V, const ProposalBufs& P, bool out16);
 PostArgs post_args(const PostBufs& S, const float* pred, int pred_ld, int C, int V, const ProposalBufs& P, const ViewDesc* views,
                    float score_thr, float nms_thr, const DetBuffers& det);
@@ -254,7 +270,7 @@ void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], 
 bool stem_grid_exact(const LevelSeg* seg, int V);
 bool conv_pack_default();       // packed row tiles (ConvArgs::packed_rows) in the dense conv_p4 launches: on unless CALD_CONV_PACK=0
 int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
-                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr, FwdSsm* ssm = nullptr);
+                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr, FwdSsm* ssm = nullptr, FwdRetinaSsm* rssm = nullptr);
 // sweep.hip
 void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);

@@ -247,6 +247,68 @@ struct RetinaArgs {
     DetBuffers det;               // cap >= K * per_class
 };
 void launch_retina_postprocess(const RetinaArgs& a, int max_anchors, hipStream_t st);
+// anchor index -> pyramid level and the index inside it; the decoded, clipped box of an anchor (weights 1, 1, 1, 1): shared by the stock
+// tail (retina.hip) and the SSM tail (retina_ssm.hip)
+__device__ inline int retina_level_of(const RetinaArgs& a, int v, int i, int* local) {
+    int l = 0;
+    int base = 0;
+#pragma unroll
+    for (int t = 0; t < 5; t++) {
+        const int n = a.seg[t][v].H * a.seg[t][v].W * a.A;
+        if (i >= base + n && t < 4) { base += n; l = t + 1; }
+        else break;
+    }
+    *local = i - base;
+    return l;
+}
+__device__ inline float4 retina_decode(const RetinaArgs& a, int v, int i, float Wr, float Hr) {
+    int li;
+    const int l = retina_level_of(a, v, i, &li);
+    const LevelSeg sg = a.seg[l][v];
+    const LevelSeg s0 = a.seg0[v];
+    const int pix = li / a.A, an = li - pix * a.A;
+    const int y = pix / sg.W, x = pix - y * sg.W;
+    const int sth = s0.H / sg.H, stw = s0.W / sg.W;
+    const float* ba = a.base_anchors + (l * a.A + an) * 4;
+    const float anchor[4] = {(float)(x * stw) + ba[0], (float)(y * sth) + ba[1], (float)(x * stw) + ba[2], (float)(y * sth) + ba[3]};
+    const float* rp = a.reg[l] + (sg.pix_off + pix) * (long long)a.reg_ld + an * 4;
+    const float d[4] = {rp[0], rp[1], rp[2], rp[3]};
+    float o[4];
+    det_box_decode(anchor, d, 1.0f, 1.0f, 1.0f, 1.0f, o);
+    float4 b;
+    b.x = det_clamp(o[0], 0.0f, Wr); b.z = det_clamp(o[2], 0.0f, Wr);
+    b.y = det_clamp(o[1], 0.0f, Hr); b.w = det_clamp(o[3], 0.0f, Hr);
+    return b;
+}
+
+// retina_ssm.hip -- the SSM tail of RetinaNet (detection/retina_ssm.py:487-584 ssm_postprocess_detections + transform.postprocess) in two
+// device phases around one host stop.  Phase A: per (view, class) the anchors scoring above score_thr, counted and listed in ascending
+// anchor order, and the view's flag `al`.  The host then draws, per class, up to CALD_SSM_RETINA_TAKE positions into that list (the
+// reference's random.shuffle).  Phase B: per (class, view) the picked candidates decoded, small boxes skipped, NMS, the first per_class
+// survivors; rows compacted in (view, class, kept) order.
+struct RetinaSsmArgs {
+    RetinaArgs r;                 // the heads, geometry, thresholds and per_class; cand_count = the per-class counts [V][K], cand_cap = the list's
+                                  // stride (>= anchors of a view), kept_anchor / kept_box / kept_count as in the stock tail; the rest unused
+    float conf_thr;               // 0.5 (CONF_THRESH, and judge_y's cut)
+    int nblk;                     // 256-anchor blocks of the largest view: grid.x of the count and write kernels
+    // phase A
+    int* blk_off;                 // [V][K][nblk] candidates of the block, then (scan) those of the blocks before it
+    int* list;                    // [V][K][cand_cap] anchor indices, ascending
+    unsigned* vmax;               // [V] orderable key of the view's largest score over all K classes
+    int* al;                      // [V]
+    // the host stop's answer
+    const int* picks;             // [V][K][CALD_SSM_RETINA_TAKE] positions into the class's list, in shuffled order
+    const int* n_picks;           // [V][K] <= min(count, CALD_SSM_RETINA_TAKE); 0 for a view with al = 1
+    // phase B results: the rows of all V views consecutively
+    int* row_off;                 // [V][K]
+    int* count;                   // [V] rows of the view
+    int* total;                   // [1] rows of the batch
+    float* boxes;                 // [rows][4] on the original image
+    float* scores;                // [rows] the score of the row's class
+    signed char* labels;          // [rows][K-1] +1 / -1 over classes 1..K-1
+};
+void launch_retina_ssm_phase_a(const RetinaSsmArgs& a, hipStream_t st);
+void launch_retina_ssm_phase_b(const RetinaSsmArgs& a, hipStream_t st);
 
 // baseline sweeps
 void launch_lt_uncertainty(const DetBuffers& det, int V, float* out, hipStream_t st);

@@ -575,6 +575,41 @@ extern "C" int cald_op_ssm_postprocess(cald_ctx* c, int R, int C, const float* l
     return 0;
 }
 
+// One view's RetinaNet heads for the two tail hooks below: the argument checks, the one-view plan (level 0: the padded input; levels 3..7:
+// P3..P7), and the device copies of heads, plan, view and base anchors
+struct RetinaHookIn {
+    BatchPlan P; ViewDesc vd; size_t pix[5]; long long anchors = 0;
+    BatchPlan* d_p = nullptr; ViewDesc* d_vd = nullptr; float *d_cls[5] = {}, *d_reg[5] = {}, *d_base = nullptr;
+    int check(const float* const* cls, const float* const* reg, const int* level_hw, int A, int K, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo, int per_class) {
+        if (A < 1 || A > 64 || K < 1 || K > 256 || per_class < 1 || per_class > 1024 || Hp < 1 || Wp < 1 || Hr < 1 || Wr < 1 || Ho < 1 || Wo < 1)
+            return fail(CALD_ERR_INVALID, "bad geometry (1 <= A <= 64, 1 <= K <= 256, 1 <= per_class <= 1024, positive sizes)");
+        memset(&P, 0, sizeof(P));
+        P.seg[0][0].H = Hp; P.seg[0][0].W = Wp; P.seg[0][1].pix_off = (long long)Hp * Wp;
+        for (int l = 0; l < 5; l++) {
+            const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
+            if (H < 1 || W < 1 || H > Hp || W > Wp || !cls[l] || !reg[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
+            P.seg[3 + l][0].H = H; P.seg[3 + l][0].W = W; P.seg[3 + l][1].pix_off = (long long)H * W; pix[l] = (size_t)H * W;
+            anchors += (long long)H * W * A;
+        }
+        if (anchors > (1 << 20)) return fail(CALD_ERR_INVALID, "at most %d anchors", 1 << 20);
+        memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
+        return 0;
+    }
+    void layout(Bump& B, int A, int K) {
+        for (int l = 0; l < 5; l++) { d_cls[l] = B.get<float>(pix[l] * A * K); d_reg[l] = B.get<float>(pix[l] * A * 4); }
+        d_p = B.get<BatchPlan>(1); d_vd = B.get<ViewDesc>(1); d_base = B.get<float>((size_t)5 * A * 4);
+    }
+    int upload(const float* const* cls, const float* const* reg, const float* base_anchors, int A, int K) {
+        for (int l = 0; l < 5; l++) {
+            HIPCHK(hipMemcpy(d_cls[l], cls[l], pix[l] * A * K * 4, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(d_reg[l], reg[l], pix[l] * A * 16, hipMemcpyHostToDevice));
+        }
+        HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_base, base_anchors, (size_t)5 * A * 16, hipMemcpyHostToDevice));
+        return 0;
+    }
+};
+
 // RetinaNet.postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the forward (retina.hip
 // retina_cand_kernel / retina_class_nms_kernel / retina_emit_kernel): host arrays in, host arrays out, through the forward's own
 // RetinaTailBufs::layout and retina_args (host.h); det cap K * per_class.  Parity hook for detection/retinanet_cal.py:402-490.
@@ -585,36 +620,51 @@ extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, 
                                           float* scores_cls_out, int* n_out) {
     if (!c || !cls || !reg || !level_hw || !base_anchors || !boxes_out || !scores_out || !labels_out || !prob_max_out || !scores_cls_out || !n_out)
         return fail(CALD_ERR_INVALID, "null argument");
-    if (A < 1 || A > 64 || K < 1 || K > 256 || per_class < 1 || per_class > 1024 || Hp < 1 || Wp < 1 || Hr < 1 || Wr < 1 || Ho < 1 || Wo < 1)
-        return fail(CALD_ERR_INVALID, "bad geometry (1 <= A <= 64, 1 <= K <= 256, 1 <= per_class <= 1024, positive sizes)");
-    BatchPlan P; memset(&P, 0, sizeof(P));      // level 0: the padded input; levels 3..7: P3..P7
-    P.seg[0][0].H = Hp; P.seg[0][0].W = Wp; P.seg[0][1].pix_off = (long long)Hp * Wp;
-    long long anchors = 0; size_t pix[5];
-    for (int l = 0; l < 5; l++) {
-        const int H = level_hw[2 * l], W = level_hw[2 * l + 1];
-        if (H < 1 || W < 1 || H > Hp || W > Wp || !cls[l] || !reg[l]) return fail(CALD_ERR_INVALID, "level %d is malformed", l);
-        P.seg[3 + l][0].H = H; P.seg[3 + l][0].W = W; P.seg[3 + l][1].pix_off = (long long)H * W; pix[l] = (size_t)H * W;
-        anchors += (long long)H * W * A;
-    }
-    if (anchors > (1 << 20)) return fail(CALD_ERR_INVALID, "at most %d anchors", 1 << 20);
+    RetinaHookIn in; int rc;
+    if ((rc = in.check(cls, reg, level_hw, A, K, Hp, Wp, Hr, Wr, Ho, Wo, per_class))) return rc;
     HIPCHK(hipSetDevice(c->device));
-    ViewDesc vd; memset(&vd, 0, sizeof(vd)); vd.Hr = Hr; vd.Wr = Wr; vd.Ho = Ho; vd.Wo = Wo;
     ScopedDev sd(c->stream); ScopedDet det;
-    RetinaTailBufs S; BatchPlan* d_p; ViewDesc* d_vd; float *d_cls[5], *d_reg[5], *d_base; int rc;
-    if ((rc = carve(sd, [&](Bump& B) {
-            for (int l = 0; l < 5; l++) { d_cls[l] = B.get<float>(pix[l] * A * K); d_reg[l] = B.get<float>(pix[l] * A * 4); }
-            d_p = B.get<BatchPlan>(1); d_vd = B.get<ViewDesc>(1); d_base = B.get<float>((size_t)5 * A * 4);
-            S.layout(B, 1, K, per_class, (int)anchors);
-        })) || (rc = det.alloc(1, K * per_class, K))) return rc;
-    for (int l = 0; l < 5; l++) {
-        HIPCHK(hipMemcpy(d_cls[l], cls[l], pix[l] * A * K * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_reg[l], reg[l], pix[l] * A * 16, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_base, base_anchors, (size_t)5 * A * 16, hipMemcpyHostToDevice));
-    launch_retina_postprocess(retina_args(S, d_cls, d_reg, d_p, d_vd, d_base, A, K, 1, score_thr, nms_thr, per_class, det.d), S.max_anchors, c->stream);
+    RetinaTailBufs S;
+    if ((rc = carve(sd, [&](Bump& B) { in.layout(B, A, K); S.layout(B, 1, K, per_class, (int)in.anchors); })) || (rc = det.alloc(1, K * per_class, K)) ||
+        (rc = in.upload(cls, reg, base_anchors, A, K))) return rc;
+    launch_retina_postprocess(retina_args(S, in.d_cls, in.d_reg, in.d_p, in.d_vd, in.d_base, A, K, 1, score_thr, nms_thr, per_class, det.d), S.max_anchors, c->stream);
     HIPCHK(hipGetLastError());
     return download_dets(c, det.d, "retina", boxes_out, scores_out, labels_out, nullptr, prob_max_out, scores_cls_out, n_out);
+}
+
+// RetinaNet.ssm_postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the SSM forward (retina_ssm.hip), through
+// the forward's own RetinaSsmBufs::layout, retina_ssm_args and host stop.  Parity hook for detection/retina_ssm.py:487-584.
+extern "C" int cald_op_retina_ssm_postprocess(cald_ctx* c, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                                              const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                                              float score_thr, float nms_thr, int per_class, cald_ssm_pick_fn pick, void* user,
+                                              int* al_out, int* n_out, int* counts_out, float* boxes_out, float* scores_out, int8_t* labels_out) {
+    if (!c || !cls || !reg || !level_hw || !base_anchors || !pick || !al_out || !n_out || !counts_out || !boxes_out || !scores_out || !labels_out)
+        return fail(CALD_ERR_INVALID, "null argument");
+    if (K < 2) return fail(CALD_ERR_INVALID, "the RetinaNet SSM tail needs K >= 2 (labels have K - 1 columns)");
+    RetinaHookIn in; int rc;
+    if ((rc = in.check(cls, reg, level_hw, A, K, Hp, Wp, Hr, Wr, Ho, Wo, per_class))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    RetinaSsmBufs S;
+    if ((rc = carve(sd, [&](Bump& B) { in.layout(B, A, K); S.layout(B, 1, K, per_class, (int)in.anchors); })) || (rc = in.upload(cls, reg, base_anchors, A, K))) return rc;
+    const RetinaSsmArgs sa = retina_ssm_args(S, in.d_cls, in.d_reg, in.d_p, in.d_vd, in.d_base, A, K, 1, score_thr, nms_thr, per_class);
+    launch_retina_ssm_phase_a(sa, c->stream);
+    HIPCHK(hipGetLastError());
+    if ((rc = retina_ssm_pick_stop(c, S, 1, K, pick, user, 0, counts_out))) return rc;
+    launch_retina_ssm_phase_b(sa, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int al = 0, n = 0, total = 0;
+    HIPCHK(hipMemcpy(&al, S.al, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&n, S.count, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&total, S.total, 4, hipMemcpyDeviceToHost));
+    if (n < 0 || n > K * per_class || total != n || (al && n)) return fail(CALD_ERR_HIP, "retina ssm postprocess returned %d rows (al %d, total %d, cap %d)", n, al, total, K * per_class);
+    if (n) {
+        HIPCHK(hipMemcpy(boxes_out, S.boxes, (size_t)n * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(scores_out, S.scores, (size_t)n * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(labels_out, S.labels, (size_t)n * (K - 1), hipMemcpyDeviceToHost));
+    }
+    if (al) memset(counts_out, 0, (size_t)K * 4);
+    *al_out = al; *n_out = n;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

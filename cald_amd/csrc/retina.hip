@@ -8,19 +8,6 @@
 #include "kernels.h"
 #include "sortnms.h"
 
-__device__ inline int retina_level_of(const RetinaArgs& a, int v, int i, int* local) {
-    int l = 0;
-    int base = 0;
-#pragma unroll
-    for (int t = 0; t < 5; t++) {
-        const int n = a.seg[t][v].H * a.seg[t][v].W * a.A;
-        if (i >= base + n && t < 4) { base += n; l = t + 1; }
-        else break;
-    }
-    *local = i - base;
-    return l;
-}
-
 // Kernel 1: one thread per anchor: K sigmoids, candidate keys per (view, class).
 __global__ __launch_bounds__(256) void retina_cand_kernel(RetinaArgs a) {
     const int v = blockIdx.y;
@@ -42,26 +29,6 @@ __global__ __launch_bounds__(256) void retina_cand_kernel(RetinaArgs a) {
                 ((unsigned long long)det_orderable(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
         }
     }
-}
-
-__device__ inline float4 retina_decode(const RetinaArgs& a, int v, int i, float Wr, float Hr) {
-    int li;
-    const int l = retina_level_of(a, v, i, &li);
-    const LevelSeg sg = a.seg[l][v];
-    const LevelSeg s0 = a.seg0[v];
-    const int pix = li / a.A, an = li - pix * a.A;
-    const int y = pix / sg.W, x = pix - y * sg.W;
-    const int sth = s0.H / sg.H, stw = s0.W / sg.W;
-    const float* ba = a.base_anchors + (l * a.A + an) * 4;
-    const float anchor[4] = {(float)(x * stw) + ba[0], (float)(y * sth) + ba[1], (float)(x * stw) + ba[2], (float)(y * sth) + ba[3]};
-    const float* rp = a.reg[l] + (sg.pix_off + pix) * (long long)a.reg_ld + an * 4;
-    const float d[4] = {rp[0], rp[1], rp[2], rp[3]};
-    float o[4];
-    det_box_decode(anchor, d, 1.0f, 1.0f, 1.0f, 1.0f, o);
-    float4 b;
-    b.x = det_clamp(o[0], 0.0f, Wr); b.z = det_clamp(o[2], 0.0f, Wr);
-    b.y = det_clamp(o[1], 0.0f, Hr); b.w = det_clamp(o[3], 0.0f, Hr);
-    return b;
 }
 
 // Kernel 2: per (class, view): sort candidates, decode, small-box filter, NMS, keep <= per_class.

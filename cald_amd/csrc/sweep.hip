@@ -690,6 +690,54 @@ extern "C" int cald_sweep_ssm(cald_model* m, int n_images, const uint8_t* const*
     return 0;
 }
 
+// ssm/ssm_helper.py:9-33 get_uncertainty on RetinaNet: cald_sweep_ssm's loop with the tail of retina_ssm.hip, whose host stop (the picks of
+// the batch's images, in order) sits inside forward_model, between the tail's two phases
+extern "C" int cald_sweep_ssm_retina(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
+                                     cald_ssm_pick_fn pick, void* user, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out,
+                                     float* scores_out, int8_t* labels_out, int64_t* rows_needed_out) {
+    if (!m || !images_dev || !H || !W || !pick || !al_out || !count_out || !boxes_out || !scores_out || !labels_out || !rows_needed_out)
+        return fail(CALD_ERR_INVALID, "null argument");
+    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+    if (m->cfg.arch != CALD_ARCH_RETINANET) return fail(CALD_ERR_INVALID, "cald_sweep_ssm_retina covers RetinaNet only (Faster R-CNN: cald_sweep_ssm)");
+    if (m->cfg.num_classes < 2) return fail(CALD_ERR_INVALID, "the RetinaNet SSM tail needs at least two classes (labels have K - 1 columns)");
+    if (n_images < 0 || rows_cap < 0) return fail(CALD_ERR_INVALID, "n_images and rows_cap must be >= 0");
+    cald_ctx* c = m->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    int B = batch_images > 0 ? batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    const size_t K = (size_t)m->cfg.num_classes;
+    const int64_t view_rows = (int64_t)K * m->cfg.detections_per_img;
+    const DetBuffers none{};
+    int64_t rows = 0;
+    for (int i0 = 0; i0 < n_images; i0 += B) {
+        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
+        FwdRetinaSsm fs; fs.pick = pick; fs.user = user; fs.image0 = i0;
+        int rc;
+        if ((rc = forward_model(m, nb, views.data(), none, nullptr, false, nullptr, nullptr, nullptr, &fs))) return rc;
+        int total = 0;
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(al_out + i0, fs.out.al, (size_t)nb * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(count_out + i0, fs.out.count, (size_t)nb * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&total, fs.out.total, 4, hipMemcpyDeviceToHost));
+        int64_t sum = 0;
+        for (int i = 0; i < nb; i++) {
+            const int n = count_out[i0 + i];
+            if (n < 0 || n > view_rows || (al_out[i0 + i] && n)) return fail(CALD_ERR_HIP, "ssm postprocess returned %d rows for image %d (cap %lld)", n, i0 + i, (long long)view_rows);
+            sum += n;
+        }
+        if (sum != total) return fail(CALD_ERR_HIP, "ssm postprocess: the batch's rows (%d) are not the sum of its images' (%lld)", total, (long long)sum);
+        if (total && rows + total <= rows_cap) {
+            HIPCHK(hipMemcpy(boxes_out + rows * 4, fs.out.boxes, (size_t)total * 16, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(scores_out + rows, fs.out.scores, (size_t)total * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(labels_out + rows * (K - 1), fs.out.labels, (size_t)total * (K - 1), hipMemcpyDeviceToHost));
+        }
+        rows += total;
+    }
+    *rows_needed_out = rows;
+    if (rows > rows_cap) return fail(CALD_ERR_INVALID, "cald_sweep_ssm_retina: rows_cap %lld is too small, the sweep needs %lld rows", (long long)rows_cap, (long long)rows);
+    return 0;
+}
+
 // ls_c_train.py:108-155 get_uncertainty: reference view + GaussianNoise(image, 8 i), i = 1..6 (six consecutive torch.randn
 // draws on the per-image re-seeded generator), top-30 reference boxes by prob_max, IoU stability weighted by prob_max, minus
 // U = max(1 - prob_max).

@@ -310,7 +310,8 @@ def retinanet_resnet50_fpn_cal(pretrained=False, progress=True, num_classes=91, 
 
 def from_torch_module(task_model):
     """Builds the HIP detector that mirrors a reference torch model (detection/frcnn_la.py FRCNN_Feature or
-    detection/retinanet_cal.py RetinaNet): constructor arguments are read off the module's attributes
+    detection/retinanet_cal.py RetinaNet, or detection/retina_ssm.py's -- it has an ``ssm`` attribute and 50 detections per class where the
+    module does not say): constructor arguments are read off the module's attributes
     (transform.min_size / max_size, roi_heads.*, rpn.*), the weights off ``state_dict()`` -- so
     ``get_uncertainty(task_model, ...)`` accepts the model cald_train.py already has (cald_train.py:436)."""
     sd = task_model.state_dict()
@@ -324,7 +325,7 @@ def from_torch_module(task_model):
         m = HipDetector(ncls, depth=depth, min_size=min_size, max_size=max_size, arch=1,
                         box_score_thresh=float(getattr(task_model, "score_thresh", 0.05)),
                         box_nms_thresh=float(getattr(task_model, "nms_thresh", 0.5)),
-                        box_detections_per_img=int(getattr(task_model, "detections_per_img", 300)))
+                        box_detections_per_img=int(getattr(task_model, "detections_per_img", 50 if hasattr(task_model, "ssm") else 300)))
     else:
         ncls = int(sd["roi_heads.box_predictor.cls_score.weight"].shape[0])
         rh, rpn = getattr(task_model, "roi_heads", None), getattr(task_model, "rpn", None)

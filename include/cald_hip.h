@@ -191,10 +191,37 @@ int cald_sweep_ltc(cald_model* m, int n_images, const uint8_t* const* images_dev
  * place of the ordinary one, batch_images images a forward (0 = 64; results do not depend on it).  al_out / count_out [n_images]; the rows
  * of all images consecutively in image order: boxes_out [rows][4], scores_out [rows][C - 1], labels_out [rows][C - 1].  *rows_needed_out
  * receives the total; if it exceeds rows_cap the call returns CALD_ERR_INVALID ("... needs N rows"), al_out / count_out are complete and
- * the row arrays hold nothing to rely on.  A RetinaNet model or a null argument: CALD_ERR_INVALID. */
+ * the row arrays hold nothing to rely on.  A RetinaNet model (cald_sweep_ssm_retina is its sweep) or a null argument: CALD_ERR_INVALID. */
 int cald_sweep_ssm(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
                    int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out, int8_t* labels_out,
                    int64_t* rows_needed_out);
+/* ---- SSM on RetinaNet (detection/retina_ssm.py:487-584).  The reference sub-samples every class's candidates (the anchors scoring above
+ * box_score_thresh, in anchor order: level P3..P7, pixel row-major, anchor) with random.shuffle on Python's global generator and keeps the
+ * first 500.  The tail therefore stops once on the host: after the device has counted and listed the candidates, the library asks the
+ * caller's cald_ssm_pick_fn which of them to keep, then finishes on the device. ----
+ * pick(user, image, K, counts, picks, n_picks): counts[k] = candidates of class k; the callee writes n_picks[k] <= min(counts[k],
+ * CALD_SSM_RETINA_TAKE) and picks[k * CALD_SSM_RETINA_TAKE + j] = the position (0 .. counts[k] - 1) of the j-th kept candidate, in the order
+ * the reference's list would have (an earlier pick wins an exact score tie), and returns 0.  Called once per image with al == 0, in image
+ * order, for every class (counts of 0 and 1 included); never for an image with al == 1.  A pick outside its range, an n_picks outside
+ * its range or a non-zero return ends the call with CALD_ERR_INVALID naming the image and the class; no pick is read by the device before
+ * it has been checked. */
+#define CALD_SSM_RETINA_TAKE 500
+typedef int (*cald_ssm_pick_fn)(void* user, int image, int K, const int* counts /*[K]*/,
+                                int* picks /*[K][CALD_SSM_RETINA_TAKE]*/, int* n_picks /*[K]*/);
+/* A cald_ssm_pick_fn that IS the reference's draw: per class `keep = list(range(n)); random.shuffle(keep); keep[:500]` of CPython (3.x:
+ * for i in reversed(range(1, n)): j = _randbelow(i + 1); swap -- _randbelow(m) draws genrand_uint32() >> (32 - m.bit_length()) until it is
+ * below m) on the MT19937 state `user` points at: uint32_t[625], the 624 words and then the index, as random.getstate()[1] lists them.
+ * The state is advanced in place.  Host only.  Non-zero for a null argument, an index outside 0..624 or a negative count. */
+int cald_ssm_pick_mt19937(void* user, int image, int K, const int* counts, int* picks, int* n_picks);
+/* ssm/ssm_helper.py:9-33 get_uncertainty on a RetinaNet model (num_classes = K >= 2): cald_sweep_ssm's batch loop, checks and error texts
+ * with the RetinaNet SSM tail (cald_op_retina_ssm_postprocess); `pick` is called between the two device phases of each batch, for the
+ * batch's images in order (image = its index in this call).  Every image gets its own rows (the reference's accumulation across the
+ * images of a batch is not reproduced).  Rows per image <= K * detections_per_img: boxes_out [rows][4], scores_out [rows] (the score of
+ * the row's class), labels_out [rows][K - 1] (+1 / -1 over classes 1..K-1).  Results do not depend on batch_images.  A Faster R-CNN
+ * model or a null argument (user may be null): CALD_ERR_INVALID. */
+int cald_sweep_ssm_retina(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
+                          cald_ssm_pick_fn pick, void* user, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out,
+                          float* scores_out, int8_t* labels_out, int64_t* rows_needed_out);
 /* ls_c_train.py:108-155 get_uncertainty(task_model, unlabeled_loader) -> one float per image (six GaussianNoise views) */
 int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                    const int64_t* pool_pos, uint64_t base_seed, int batch_images, double* stability_out);
@@ -356,6 +383,17 @@ int cald_op_retina_postprocess(cald_ctx* ctx, const float* const* cls, const flo
                                float score_thr, float nms_thr, int per_class,
                                float* boxes_out, float* scores_out, int64_t* labels_out, float* prob_max_out,
                                float* scores_cls_out, int* n_out);
+/* RetinaNet.ssm_postprocess_detections + the stock transform.postprocess of one view (detection/retina_ssm.py:487-584) on the SSM forward's
+ * own kernels (retina_ssm.hip); inputs as for cald_op_retina_postprocess, K >= 2.  *al_out = 1 when the largest score over all K classes
+ * is < 0.5: no rows, counts_out zero, `pick` not called.  Else counts_out[k] = anchors with score[k] > score_thr, `pick` is called once
+ * (image 0), and per class the picked candidates are decoded, clipped, those with a side < 1e-2 dropped, NMS at nms_thr, the first
+ * per_class survivors: *n_out rows in (class, score desc) order -- boxes_out [n][4] on the original image, scores_out [n], labels_out
+ * [n][K - 1] = +1 where the anchor's score of class 1..K-1 is > 0.5, else -1.  The output arrays hold K * per_class rows.
+ * per_class <= 1024, at most 2^20 anchors. */
+int cald_op_retina_ssm_postprocess(cald_ctx* ctx, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                                   const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                                   float score_thr, float nms_thr, int per_class, cald_ssm_pick_fn pick, void* user,
+                                   int* al_out, int* n_out, int* counts_out, float* boxes_out, float* scores_out, int8_t* labels_out);
 /* The certified pruning's three kernels outside any model (rpn_prune.hip: select stage 0, select stage 1, scatter, in the forward's order;
  * tests/test_gpu_rpn_prune_edges.py).  The hook plays the gathered exact convs itself: after each select it reads nsel / row_map back and
  * gathers that stage's exact head rows from `exact` by row_map -- compact per view at the view's pixel offset, as the gathered launch
