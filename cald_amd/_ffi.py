@@ -145,6 +145,7 @@ SIGNATURES = {
     "cald_profile_prune_fallbacks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "cald_model_destroy": (C.c_int, [C.c_void_p]),
     "cald_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(View), C.POINTER(Dets)]),
+    "cald_debug_cutout_forward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(View), C.POINTER(Dets), C.c_int]),
     "cald_sweep": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d]),
     "cald_sweep_audit": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, c_i64, C.POINTER(SweepCfg), c_d, c_d, c_f]),
     "cald_sweep_ltc": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), c_i, c_i, C.c_int, c_d]),
@@ -215,6 +216,9 @@ SIGNATURES = {
     "cald_profile_roi_rows": (C.c_int, [C.c_void_p, c_d, c_i64]),
     "cald_profile_cutout": (C.c_int, [C.c_void_p, c_d, c_d, c_i64, c_i64]),
     "cald_model_set_cutout_reuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
+    "cald_profile_cutout_stages": (C.c_int, [C.c_void_p, c_d, c_d, c_d, c_d, c_i64]),
+    "cald_model_set_cutout_retention_cap": (C.c_int, [C.c_void_p, C.c_int64, c_i64]),
+    "cald_op_cutout_fpn_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i, C.c_int, c_i, c_i]),
     "cald_model_set_look_fuse": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_row_packing": (C.c_int, [C.c_void_p, C.c_int, c_i]),
     "cald_model_set_box_min_size": (C.c_int, [C.c_void_p, C.c_float, c_f]),

@@ -16,7 +16,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- fused epilogue (shared by the plain kernels and by the bottleneck-fused kernel's second GEMM) ----
-template <int EPI, bool MASK, int TM, int TN, bool GATHER = false>
+template <int EPI, bool MASK, int TM, int TN, bool GATHER = false, bool GEXTRA = false>
 __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&acc)[TM][TN], float* smem, const int v, const LevelSeg& so,
                                             const int m0, const int Mv, const int n0, const bool straddle = false) {
     constexpr int BM = 128, WN = 2;
@@ -109,8 +109,11 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
     };
     // The FPN output convs of P2 / P3 under the certified RPN pruning also leave (i) the split-fp16 copy of their output (h16.h) for the
     // look-ahead conv and (ii) per pixel the sum of squares over this wave's 64 channels for the bound, so the pruning needs no second pass
-    // over the tensor.  Compiled into the plain (EPI 0, no mask) kernels only; wave-uniform branches elsewhere.
-    constexpr bool EXTRA = EPI == 0 && !MASK && !GATHER;
+    // over the tensor.  Compiled into the plain (EPI 0, no mask) kernels only; wave-uniform branches elsewhere.  Gathered rows carry them
+    // in one instantiation of their own (GEXTRA: the FPN output convs of the cut_out reuse), stored -- like the row -- at the row's own pixel,
+    // with the arithmetic, and so the bits, of the dense launch.
+    static_assert(!GEXTRA || (GATHER && EPI == 0 && !MASK), "the pruning's extras on gathered rows: EPI 0 only");
+    constexpr bool EXTRA = EPI == 0 && !MASK && (!GATHER || GEXTRA);
     const bool want16 = EXTRA && a.out16 != nullptr, wantE = EXTRA && TN == 2 && a.energy4 != nullptr;      // energy4 has four slots: 2 n-tiles of 128 x 2 wave columns (Cout = 256)
     unsigned char* const out16_v = want16 ? reinterpret_cast<unsigned char*>(a.out16) + so.pix_off * (long long)out_ld * 4 : nullptr;
     const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(want16 ? (void*)out16_v : (void*)out_v), 0, valid_b, 0x00020000);
@@ -214,6 +217,15 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
                 gather_offs(i, n, nok, go);
 #pragma unroll
                 for (int r = 0; r < 16; r++) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, val[r]), rsO, go[r], 0, 0);
+                if (GEXTRA && want16) {      // the split copy at the same pixel: the lane's pair word instead of its channel (a row past the count stays out of range)
+                    const int dn = h16_pair_off(nc) - n * 4;
+#pragma unroll
+                    for (int r = 0; r < 16; r++) {
+                        const unsigned w = h16_split(val[r]);
+                        const unsigned pw = h16_pair_word(w, h16_partner(w), odd);
+                        __builtin_amdgcn_raw_buffer_store_b32(pw, rsS, nok ? go[r] + dn : 0x7FFF0000, 0, 0);
+                    }
+                }
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; r++)
@@ -224,7 +236,7 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
 #pragma unroll
                     for (int r = 0; r < 16; r++) sq[i][r] = sq[i][r] + (nok ? val[r] * val[r] : 0.0f);
                 }
-                if (want16) {       // lanes l and l ^ 1 hold neighbouring channels: the even lane stores {hi, hi}, the odd one {lo, lo} (h16.h)
+                if (want16 && !GATHER) {       // lanes l and l ^ 1 hold neighbouring channels: the even lane stores {hi, hi}, the odd one {lo, lo} (h16.h)
                     const int poff = h16_pair_off(nc);
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
@@ -240,6 +252,8 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
         if (wantE) {
             // sum over the wave's 32 column lanes, in lane order (a fixed order: the energy, and with it the pruning's selection, is the same
             // from run to run): each lane parks its 32 row partials in LDS (free after the k-loop), then lane L adds up row L of the wave's 64
+            // (gathered rows: the row's pixel offset leaves the table the partials are about to overwrite)
+            const int pix_b = GATHER ? s_src[wm * TM * 32 + lane] : 0;
             __syncthreads();
             float* const red = smem + wave * (64 * 33);
 #pragma unroll
@@ -251,7 +265,7 @@ __device__ __forceinline__ void p4_epilogue(const ConvArgs& a, const f32x16 (&ac
 #pragma unroll
             for (int q = 0; q < 32; q++) e = e + red[lane * 33 + q];
             const int m = m0 + wm * TM * 32 + lane;
-            if (m < Mv) a.energy4[(so.pix_off + m) * 4 + (n0 / (64 * TN)) * 2 + wn] = e;
+            if (m < Mv) a.energy4[(so.pix_off + (GATHER ? pix_b / row_b : m)) * 4 + (n0 / (64 * TN)) * 2 + wn] = e;
         }
     }
 }
@@ -269,6 +283,8 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
     constexpr bool MASK = (EPIX & 4) != 0;      // training backward only: the ReLU-backward mask step is compiled in
     constexpr bool FUSE = (EPIX & 8) != 0;      // bottleneck conv2 (3 x 3, 64 -> 64) + conv3 (1 x 1, 64 -> 256, + residual) in one workgroup
     constexpr bool GATHER = (EPIX & 16) != 0;   // gathered rows, each stored at its own pixel (ConvArgs::gather)
+    constexpr bool GEXTRA = (EPIX & 32) != 0;   // gathered rows that also leave the pruning's split copy and energy (out16 / energy4) at that pixel
+    static_assert(!GEXTRA || GATHER, "the extras bit rides on the gathered-rows bit");
     static_assert(!(GATHER && (FUSE || MASK || C4)), "gathered rows: plain EPI 0 / 1 kernels only");
     constexpr int BM = 128, BN = 64 * TN, BK = 16, TM = 2, WN = 2;
     constexpr int TILE_A = 2 * BM * 8, TILE_F = TILE_A + 2 * BN * 8;      // floats: 2048 + 2048 (TN = 2)
@@ -746,7 +762,7 @@ __device__ __forceinline__ void conv_p4_body(const ConvArgs& a, const int blk, c
             }
         }
     } else {
-        p4_epilogue<EPI, MASK, TM, TN, GATHER>(a, acc, smem, v, so, m0, Mv, n0, CAN_PACK && straddle);
+        p4_epilogue<EPI, MASK, TM, TN, GATHER, GEXTRA>(a, acc, smem, v, so, m0, Mv, n0, CAN_PACK && straddle);
     }
     if (trace && tid == 0) {
         trace[3] = __builtin_amdgcn_s_memtime();
@@ -782,7 +798,7 @@ static inline int p4_grid_mtiles(const ConvArgs& a) { return a.KH * a.KW > 1 ? 8
 static inline bool p4_refuses(const ConvArgs& a) {
     if (!a.w4 || !a.out || a.in16 || a.ex16 || a.CoutPad % 64 != 0 || (a.residual && a.up)) return true;
     const bool extra = a.out16 || a.energy4;                    // compiled into the EPI 0, no-mask, no-gather epilogue only
-    if (extra && (a.residual || a.up || a.mask || a.gather)) return true;
+    if (extra && (a.residual || a.up || a.mask)) return true;     // (with gathered rows: the grouped launch's wide 3 x 3 kernel only, below)
     if (a.energy4 && a.CoutPad != 256) return true;              // four slots of 64 channels: 2 n-tiles of 128 x 2 wave columns
     if (a.row_map && (a.residual || a.up || a.mask || a.gather)) return true;   // the epilogue stores (and reads) at the compact row
     return false;
@@ -822,8 +838,10 @@ const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, C
     for (int i = 0; i < n; i++) {
         const ConvArgs a = p4_tiled(p[i]);
         if (p4_refuses(a) || !p4_tile_ok(a, wide, f) || (a.CoutPad % 128 == 0) != (p[0].CoutPad % 128 == 0)) return nullptr;
-        if (a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up || a.gather) return nullptr;
-        if ((a.mask != nullptr) != (p[0].mask != nullptr)) return nullptr;
+        if (a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return nullptr;
+        if ((a.mask != nullptr) != (p[0].mask != nullptr) || (a.gather != nullptr) != (p[0].gather != nullptr)) return nullptr;
+        // gathered rows (every problem of the group, or none): the FPN output convs of the cut_out reuse -- wide 3 x 3 tiles, host-planned rows
+        if (a.gather && (!wide || p4_taps(a) != 9 || a.mask || a.in_relu || a.dyn_rows || a.row_map)) return nullptr;
         if (a.mask && (a.out16 || a.energy4)) return nullptr;
         g.blk0[i] = blk; blk += p4_grid_mtiles(a) * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a;
     }
@@ -834,7 +852,8 @@ const char* launch_conv_p4_group(const ConvArgs* p, int n, hipStream_t stream, C
 #define P4_GROUP(EV, TNV, TAPSV) p4_group_go<EV, TNV, TAPSV>(grid, stream, g, P4_NAME("conv_p4_group_kernel", EV, false, TNV, TAPSV))
 #define P4_GROUP_T(EV) (wide ? (taps == 9 ? P4_GROUP(EV, 2, 9) : taps == 1 ? P4_GROUP(EV, 2, 1) : P4_GROUP(EV, 2, 0)) \
                              : (taps == 9 ? P4_GROUP(EV, 1, 9) : taps == 1 ? P4_GROUP(EV, 1, 1) : P4_GROUP(EV, 1, 0)))
-    const char* name = p[0].mask ? P4_GROUP_T(4) : P4_GROUP_T(0);
+    if (blk == 0) return "none (no gathered rows)";
+    const char* name = p[0].gather ? P4_GROUP(48, 2, 9) : p[0].mask ? P4_GROUP_T(4) : P4_GROUP_T(0);
 #undef P4_GROUP_T
 #undef P4_GROUP
     return name;
@@ -875,6 +894,7 @@ const char* launch_conv_p4(const ConvArgs& a_in, hipStream_t stream, ConvForce f
 #define P4_ONE(EPIV, C4V, TNV, TAPSV) p4_go<EPIV, C4V, TNV, TAPSV>(grid, stream, a, P4_NAME("conv_p4_kernel", EPIV, C4V, TNV, TAPSV))
     if (a.gather) {      // gathered rows: the unrolled 1 x 1 / 3 x 3 kernels, BN (+ residual) epilogue
         const int taps = p4_taps(a);
+        if (a.out16 || a.energy4) return nullptr;
         if (a.Cin == 4 || a.up || a.mask || a.in_relu || a.dyn_rows || a.row_map || (taps != 1 && taps != 9)) return nullptr;
         if (a.total_mtiles == 0) return "none (no gathered rows)";
 #define P4_G(EPIV, TNV) (taps == 9 ? P4_ONE(EPIV, false, TNV, 9) : P4_ONE(EPIV, false, TNV, 1))

@@ -182,6 +182,18 @@ extern "C" int cald_profile_cutout(cald_ctx* c, double* rows3, double* dense_row
     return 0;
 }
 
+extern "C" int cald_profile_cutout_stages(cald_ctx* c, double* rows6, double* dense_rows6, double* tiles6, double* dense_tiles6, int64_t* kept3) {
+    if (!c) return fail(CALD_ERR_INVALID, "ctx is null");
+    for (int i = 0; i < 6; i++) {
+        if (rows6) rows6[i] = c->cut_st_rows[i];
+        if (dense_rows6) dense_rows6[i] = c->cut_st_dense[i];
+        if (tiles6) tiles6[i] = c->cut_st_tiles[i];
+        if (dense_tiles6) dense_tiles6[i] = c->cut_st_dense_tiles[i];
+    }
+    if (kept3) for (int i = 0; i < 3; i++) kept3[i] = c->cut_kept[i];
+    return 0;
+}
+
 extern "C" int cald_profile_dump(cald_ctx* c, const char* path) {
     if (!c || !path) return fail(CALD_ERR_INVALID, "null argument");
     HIPCHK(hipStreamSynchronize(c->stream));

@@ -357,6 +357,30 @@ static int gconv_on(cald_model* m, const ConvLayer& L, const float* in, float* o
     return run_conv(m->ctx, a, 2.0 * ru.rows[b][kind] * (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue));
 }
 
+// the FPN output convs of the cut_out forward on their output dirty sets (gather sets 2 nblk + i of the plan), as ONE grouped launch: every
+// problem carries its own GatherSet -- and P2 / P3 the pruning's extras, patched at the same pixels.  No launch where no view has a rectangle.
+static int gconv_group_on(cald_model* m, const ConvSpec* sp, int n, int V, const FwdReuse& ru) {
+    ConvArgs a[CALD_MAX_GROUP];
+    double flops = 0.0; int tiles = 0;
+    for (int i = 0; i < n; i++) {
+        const double f = fill_conv_args(m, a[i], *sp[i].L, sp[i].in, sp[i].out, sp[i].level, sp[i].level, V, sp[i].relu);
+        if (f < 0.0) return (int)f;
+        const char* base = ru.d_gp + (size_t)(2 * ru.nblk + i) * cut_plan_set_bytes(V);
+        a[i].seg_out = reinterpret_cast<const LevelSeg*>(base);
+        a[i].gather = reinterpret_cast<const GatherSet*>(base + (size_t)(V + 1) * sizeof(LevelSeg));
+        a[i].total_mtiles = ru.fpn_tiles[i];
+        a[i].out16 = sp[i].out16; a[i].energy4 = sp[i].energy4;
+        flops += 2.0 * ru.fpn_rows[i] * (double)sp[i].L->Cout * (double)(sp[i].L->KH * sp[i].L->KW * sp[i].L->CinTrue); tiles += ru.fpn_tiles[i];
+    }
+    if (!tiles) return 0;
+    cald_ctx* c = m->ctx;
+    ProfLaunch t; int rc;
+    if ((rc = prof_begin(c, t))) return rc;
+    const char* k = launch_conv_p4_group(a, n, c->stream);
+    if ((rc = prof_end(c, t, flops, c->prof_tag_now, "mt=%d,Cin=%d,Cout=%d,k=%dx%d,s=%d,group=%d,gathered-rows", tiles, a[0].Cin, a[0].Cout, a[0].KH, a[0].KW, a[0].stride, n))) return rc;
+    return k ? 0 : conv_refused(a[0]);
+}
+
 __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, unsigned long long* acc) {
     unsigned long long s = 0;
     for (int v = threadIdx.x; v < V; v += 64) s += (unsigned long long)counts[v];
@@ -490,13 +514,21 @@ struct ForwardRun {
     int fpn() {
         const int first = retina ? 3 : 2, nl = retina ? 3 : 4, c0 = 4 - nl;      // RetinaNet: Cf[1..3] = C3..C5 -> P3..P5; Faster R-CNN: Cf[0..3] = C2..C5 -> P2..P5
         int rc; ConvSpec sp[4];
+        // cut_out reuse: P2..P5 (and the pruning's extras of P2 / P3) are the retained tensors -- the reference forward writes them, the cut_out
+        // forward patches them below; the RPN, the look-ahead, RoIAlign, p6_subsample and the debug views read them through Fp / Fq
+        const bool kept = ru && ru->fpn && !retina;
+        if (kept) {
+            for (int i = 0; i < 4; i++) Fp.Pf[i] = ru->pf[i];
+            if (prune) for (int i = 0; i < 2; i++) { Fq.p16[i] = ru->p16[i]; Fq.energy[i] = ru->energy[i]; }
+        }
         if ((rc = conv_on(m, m->fpn_inner[nl - 1], Fb.Cf[3], Fp.inner[nl - 1], 5, 5, V, false))) return rc;
         for (int i = nl - 2; i >= 0; i--)
             if ((rc = conv_on(m, m->fpn_inner[i], Fb.Cf[c0 + i], Fp.inner[i], first + i, first + i, V, false, nullptr, Fp.inner[i + 1], first + 1 + i))) return rc;
+        for (int i = 0; i < nl; i++) m->dbg["inner" + std::to_string(first + i)] = {Fp.inner[i], first + i, 256, 0};
         for (int i = 0; i < nl; i++) sp[i] = {&m->fpn_layer[i], Fp.inner[i], Fp.Pf[i], first + i, false};
         if (prune)                // (Faster R-CNN only) the pruning's per-pixel energy and the look-ahead's split-fp16 operand come out of these convs' epilogues (conv_p4.hip)
             for (int i = 0; i < 2; i++) { sp[i].out16 = Fq.p16[i]; sp[i].energy4 = Fq.energy[i]; }
-        if ((rc = conv_group_on(m, sp, nl, V))) return rc;
+        if ((rc = kept && ru->mode == 2 && ru->gather_fpn ? gconv_group_on(m, sp, nl, V, *ru) : conv_group_on(m, sp, nl, V))) return rc;
         if (!retina) return 0;
         if ((rc = conv_on(m, m->p6, Fp.Pf[2], Fp.Pf[3], 5, 6, V, false))) return rc;
         if (feat && !feat->p7) return 0;

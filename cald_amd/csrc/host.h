@@ -70,6 +70,10 @@ struct cald_ctx {
     // would have; batches whose cut_out views reused the reference forward, batches that could not (the retention did not fit)
     double cut_rows[3] = {0.0, 0.0, 0.0}, cut_dense[3] = {0.0, 0.0, 0.0};
     long long cut_batches = 0, cut_fallbacks = 0;
+    // the same per stage of the cut_out forward (cald_profile_cutout_stages; CUT_STAGE_*: layer1..layer4, FPN laterals, FPN output convs): rows
+    // computed, rows of the dense stage, 128-row tiles issued and the dense stage's; batches by retention (CUT_KEPT_*)
+    double cut_st_rows[6] = {}, cut_st_dense[6] = {}, cut_st_tiles[6] = {}, cut_st_dense_tiles[6] = {};
+    long long cut_kept[3] = {0, 0, 0};
 };
 
 namespace cald_host {
@@ -162,6 +166,8 @@ struct cald_model {
     struct CutReuse {
         int mode = -1;              // cald_model_set_cutout_reuse: -1 the process default (CALD_CUTOUT_REUSE), 0 off, 1 on, 2 on with every stage dense
         char* slot[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0};
+        bool ext_refused = false;   // the extended slot (+ the FPN outputs) could not be allocated once: later batches keep the three stages only
+        size_t ext_cap = 0;         // test hook cald_model_set_cutout_retention_cap: an extended slot above this many bytes counts as refused (0: no cap)
         char* h_gp[2] = {nullptr, nullptr}; char* d_gp = nullptr;
     } cr;
 };
@@ -180,7 +186,12 @@ struct ConvSpec { const ConvLayer* L; const float* in; float* out; int level; bo
 // ---- cut_out reuse: the cut_out views of a sweep batch run as a forward of their own, in the reference forward's image order (same plan),
 // and their first three stages recompute only the pixels the filled rectangles reach (host_logic.h cut_geometry), patching the reference
 // forward's retained block outputs in place ----
-#define CUT_MAX_BLOCKS 32          // blocks of the first three stages (ResNet-101: 3 + 4 + 23)
+#define CUT_MAX_BLOCKS 36          // blocks of the backbone (ResNet-101: 3 + 4 + 23 + 3); the first three stages are retained and gathered
+#define CUT_STAGE_LATERAL 4
+#define CUT_STAGE_OUTPUT 5
+#define CUT_KEPT_FPN 0             // cut_kept[]: batches that retained the three stages and the FPN outputs, the three stages only, nothing
+#define CUT_KEPT_STAGES 1
+#define CUT_KEPT_NONE 2
 struct FwdReuse {
     int mode = 0;                  // 1: reference forward, the block outputs of the first nblk blocks go to out[]; 2: the cut_out forward
     int nblk = 0;
@@ -192,6 +203,13 @@ struct FwdReuse {
     const char* d_gp = nullptr;
     int tiles[CUT_MAX_BLOCKS][2] = {};
     double rows[CUT_MAX_BLOCKS][2] = {};
+    // the FPN output convs (Faster R-CNN, P2..P5): retained as well -- mode 1 writes them (and, under the certified pruning, P2 / P3's split
+    // copy and energy) to pf[] / p16[] / energy[], mode 2 patches them on the output dirty sets: gather sets 2 nblk + i of the plan, as ONE
+    // grouped gathered launch (gather_fpn), or runs the dense group over them
+    bool fpn = false, gather_fpn = false;
+    float* pf[4] = {}; unsigned* p16[2] = {}; float* energy[2] = {};
+    int fpn_tiles[4] = {};
+    double fpn_rows[4] = {};
 };
 // ---- features-only forward (the learning-loss sweep, lossnet.hip): the forward stops after the FPN -- Faster R-CNN after the grouped output
 // convs (P2..P5), RetinaNet after P6 (P3..P6; P7 too when p7 is set) ----

@@ -333,6 +333,35 @@ static inline void cut_geometry(int H, int W, int Hr, int Wr, int Hp, int Wp, in
         s = out[b]; l = lo;
     }
 }
+// The FPN of Faster R-CNN on the cut_out view (forward.hip fpn): c[0..3] = the dirty sets of C2..C5 (the `out` sets of the stages' last
+// blocks), levels 2..5 of the plan.  Lateral l is a 1 x 1 conv of C_l plus the 2 x nearest upsample of lateral l + 1, so
+//   inner P5 dirty = C5 dirty;   inner P_l dirty = dirty(C_l) U upsample(inner P_{l + 1} dirty);   output P_l = the 3 x 3 pad-1 map of inner P_l.
+// Padded sizes are multiples of 32: every level is exactly twice the one above, and the upsample of [x0, x1] is [2 x0, 2 x1 + 1].  Each
+// cutout rectangle is carried on its own, as everywhere here: its rectangle of dirty(C_l) lies inside the upsample of its rectangle one
+// level up (a stride-2 3 x 3 map and its 2 x upsample cover the span they came from, later blocks only widen it), so the union per
+// rectangle is the hull of the two.  A set pair that does not line up rectangle by rectangle (none does) takes the whole level.
+static inline CutRect cut_hull(const CutRect& a, const CutRect& b) {
+    return {a.x0 < b.x0 ? a.x0 : b.x0, a.y0 < b.y0 ? a.y0 : b.y0, a.x1 > b.x1 ? a.x1 : b.x1, a.y1 > b.y1 ? a.y1 : b.y1};
+}
+static inline void cut_fpn_geometry(int Hp, int Wp, const CutSet* c, CutSet* inner, CutSet* outp) {
+    inner[3] = c[3];
+    for (int i = 2; i >= 0; i--) {
+        const int Hl = Hp >> (2 + i), Wl = Wp >> (2 + i);
+        const CutSet& up = inner[i + 1];
+        CutSet s; s.n = 0;
+        if (up.n == c[i].n) {
+            for (int q = 0; q < up.n; q++) {
+                CutRect u = {2 * up.r[q].x0, 2 * up.r[q].y0, 2 * up.r[q].x1 + 1, 2 * up.r[q].y1 + 1};
+                if (u.x1 > Wl - 1) u.x1 = Wl - 1; if (u.y1 > Hl - 1) u.y1 = Hl - 1;
+                s.r[s.n++] = cut_hull(u, c[i].r[q]);
+            }
+        } else if (up.n || c[i].n) {
+            s.n = 1; s.r[0] = {0, 0, Wl - 1, Hl - 1};
+        }
+        inner[i] = s;
+    }
+    for (int i = 0; i < 4; i++) outp[i] = cut_map(inner[i], 3, 1, 1, Hp >> (2 + i), Wp >> (2 + i));
+}
 // a set as disjoint rectangles, row bands top to bottom (a band's runs merged, a run that continues one of the band above extends it);
 // -1 if more than cap
 static inline int cut_disjoint(const CutSet& s, CutRect* o, int cap) {

@@ -365,6 +365,12 @@ extern "C" int cald_model_set_cutout_reuse(cald_model* m, int mode, int* was) {
     m->cr.mode = mode;
     return 0;
 }
+extern "C" int cald_model_set_cutout_retention_cap(cald_model* m, int64_t bytes, int64_t* was) {
+    if (!m || bytes < 0) return fail(CALD_ERR_INVALID, "bad argument");
+    if (was) *was = (int64_t)m->cr.ext_cap;
+    m->cr.ext_cap = (size_t)bytes;
+    return 0;
+}
 extern "C" int cald_model_set_row_packing(cald_model* m, int mode, int* was) {
     if (!m || mode < -1 || mode > 1) return fail(CALD_ERR_INVALID, "bad argument");
     if (was) *was = m->row_packing;

@@ -36,6 +36,31 @@ extern "C" int cald_op_cutout_geometry(int H, int W, int min_size, int max_size,
         }
     return 0;
 }
+// The FPN sets of the cut_out reuse (host_logic.h cut_fpn_geometry) over a whole backbone: `strides` are conv2's strides of all nblk blocks;
+// a stage ends before the next stride-2 block and with the last block, and there must be four of them (C2..C5).  out: eight sets in
+// cald_op_cutout_geometry's form ([n, then x0 y0 x1 y1 per rectangle], 1 + 4 CUT_SET_MAX ints each): inner P2..P5, then output P2..P5.
+extern "C" int cald_op_cutout_fpn_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out) {
+    if (H < 1 || W < 1 || nrect < 0 || nrect > CALD_MAX_CUT || (nrect && !rects) || nblk < 4 || nblk > 64 || !strides || !out)
+        return fail(CALD_ERR_INVALID, "bad argument");
+    int ends[4], ne = 0;
+    for (int b = 0; b < nblk; b++)
+        if (b == nblk - 1 || strides[b + 1] == 2) { if (ne == 4) return fail(CALD_ERR_INVALID, "more than four stages"); ends[ne++] = b; }
+    if (ne != 4) return fail(CALD_ERR_INVALID, "the strides describe %d stages, not four", ne);
+    int Hr, Wr, Hp, Wp;
+    transform_size(H, W, min_size, max_size, &Hr, &Wr, &Hp, &Wp);
+    std::vector<CutSet> o(nblk), t(nblk);
+    CutSet pool1, cs[4], sets[8];
+    cut_geometry(H, W, Hr, Wr, Hp, Wp, nrect, rects, nblk, strides, &pool1, o.data(), t.data());
+    for (int i = 0; i < 4; i++) cs[i] = o[ends[i]];
+    cut_fpn_geometry(Hp, Wp, cs, sets, sets + 4);
+    for (int e = 0; e < 8; e++) {
+        int* q = out + (size_t)e * (1 + 4 * CUT_SET_MAX);
+        memset(q, 0, sizeof(int) * (1 + 4 * CUT_SET_MAX));
+        q[0] = sets[e].n;
+        for (int i = 0; i < sets[e].n; i++) { q[1 + 4 * i] = sets[e].r[i].x0; q[2 + 4 * i] = sets[e].r[i].y0; q[3 + 4 * i] = sets[e].r[i].x1; q[4 + 4 * i] = sets[e].r[i].y1; }
+    }
+    return 0;
+}
 static int get_pil(cald_ctx* c, int inSize, int outSize, int fid, PilCoef* out) {
     PilKey key{inSize, outSize, fid};
     auto it = c->pil.find(key);

@@ -78,6 +78,12 @@ static bool cut_reuse_env() {
     return on;
 }
 #define CUT_GATHER_MAX_COST 0.7    // a stage runs gathered while its tiles cost at most this fraction of the dense stage
+// The FPN output convs are one more gated stage under the same rule.  A value of its own is not needed: on the bench pool the grouped
+// gathered launch runs at 141.5 TF/s on the rows it computes against the dense group's 144.9 (profiles/cutout_fpn_launches_new.csv), 0.98 of
+// it, so it pays up to about 0.97 of the dense tiles, and every cut_out forward of that pool is far below either value (tile fraction
+// 0.64).  (The parent's table could not price it: its gathered 3 x 3 256 -> 256 launches, layer3's, are 280 - 540 tiles, under one round of
+// the 768 workgroup slots, so their TF/s shows the round's quantisation and not the gathered rows' cost.)
+#define CUT_FPN_MAX_COST CUT_GATHER_MAX_COST
 
 namespace {
 // The `ints` block of a scoring stage, the same words on the host and on the device: per pair ref_view | aug_view | aug_kind | pair_img
@@ -115,6 +121,7 @@ struct SweepBatch {
     std::vector<char> view_inert;     // cut_out reuse: a stand-in view of an image without detections (its results are not used)
     std::vector<float> cut_margin;
     bool kept = false;                // the reference forward retained its first three stages (retention slot k & 1)
+    bool kept_fpn = false;            // ... and the FPN output convs' results (the extended slot)
     // what build_aug_views hands to enqueue_aug_forwards and enqueue_scoring
     std::vector<int> ref_sel, pair_kind, view_isref;
     std::vector<float> pair_par;
@@ -137,6 +144,10 @@ struct SweepRun {
     SweepBatch bt[2];
     // blocks of the first three stages (cut_out reuse), and the plan scratch of the reuse
     int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
+    // the whole backbone for the geometry (ngeo >= nblk blocks, geo_stride = conv2's strides; the first nblk are blk_stride) and the blocks
+    // whose outputs are C2..C5; fpn_ok: Faster R-CNN with four stages -- the FPN output convs can be retained and patched
+    int ngeo = 0, geo_stride[CUT_MAX_BLOCKS], c_blk[4] = {0, 0, 0, 0};
+    bool fpn_ok = false;
     std::vector<BatchPlan> rplan;
 
     static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -209,17 +220,32 @@ struct SweepRun {
         if (m->prune && prune_ok) HIPCHK(hipMemsetAsync(c->d_prune_check, 0, 8, c->stream));
         // ---- cut_out reuse (exact fp32, conv_p4.hip's gathered rows): the reference forward keeps the block outputs of the first three stages,
         // and the batch's first cut_out augmentation recomputes only its dirty pixels over them ----
-        retina = m->cfg.arch == CALD_ARCH_RETINANET;
         for (int a = 0; a < A && cut_a < 0; a++) if (cfg->augs[a].kind == CALD_AUG_CUTOUT) cut_a = a;
+        init_blocks();
+        reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
+        rplan.resize(reuse ? 1 : 0);
+        return 0;
+    }
+    // the blocks the cut_out reuse retains and gathers (the first three stages), and the whole backbone for its geometry
+    void init_blocks() {
+        retina = m->cfg.arch == CALD_ARCH_RETINANET;
         for (int b = 0, layer = 0, l = 2; b < (int)m->blocks.size() && layer < 3 && nblk < CUT_MAX_BLOCKS; b++) {
             const Bottleneck& Bk = m->blocks[b];
             blk_stride[nblk] = Bk.c2.stride; blk_lin[nblk] = l; l += Bk.c2.stride == 2 ? 1 : 0; blk_lout[nblk] = l; blk_stage[nblk] = layer;
             nblk++;
             if (Bk.layer_end) layer++;
         }
-        reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
-        rplan.resize(reuse ? 1 : 0);
-        return 0;
+        {
+            int layer = 0; bool fits = true;
+            for (size_t b = 0; b < m->blocks.size(); b++) {
+                if (ngeo == CUT_MAX_BLOCKS || layer > 3) { fits = false; break; }
+                geo_stride[ngeo] = m->blocks[b].c2.stride;
+                if (m->blocks[b].layer_end) c_blk[layer++] = ngeo;
+                ngeo++;
+            }
+            fpn_ok = fits && layer == 4 && !retina && ngeo >= nblk;
+            if (!fpn_ok) { ngeo = nblk; for (int b = 0; b < nblk; b++) geo_stride[b] = blk_stride[b]; }
+        }
     }
 
     void plan_of(int nv, const ViewDesc* vs, BatchPlan& P) const {
@@ -236,6 +262,20 @@ struct SweepRun {
         }
         return off;
     }
+    // the extended slot: the same, then P2..P5 of the FPN output convs and, where this run prunes, the split copy and the energy of P2 / P3
+    // (forward.hip PruneBufs) -- a slot laid out this way serves the three-stage retention unchanged
+    size_t retain_layout_fpn(const BatchPlan& P, int nv, char* base, FwdReuse* ru) const {
+        size_t off = retain_layout(P, nv, base, ru ? ru->out : nullptr);
+        auto take = [&](size_t bytes) { char* p = base + off; off += al(bytes); return p; };
+        for (int i = 0; i < 4; i++) { char* p = take((size_t)level_pix(P, 2 + i, nv) * 256 * 4); if (ru) ru->pf[i] = reinterpret_cast<float*>(p); }
+        if (m->prune && prune_ok)
+            for (int i = 0; i < 2; i++) {
+                char* p = take((size_t)level_pix(P, 2 + i, nv) * 256 * 4); char* e = take((size_t)level_pix(P, 2 + i, nv) * 4 * 4);
+                if (ru) { ru->p16[i] = reinterpret_cast<unsigned*>(p); ru->energy[i] = reinterpret_cast<float*>(e); }
+            }
+        if (ru) ru->fpn = true;
+        return off;
+    }
 
     // reference views of batch k -> detections into set k & 1, counts + boxes to the pinned host set, event
     int enqueue_ref(int k) {
@@ -243,27 +283,45 @@ struct SweepRun {
         b.i0 = k * B; b.nb = (n_images - b.i0 < B) ? n_images - b.i0 : B; b.live = true; b.P = 0; b.VV = b.nb;
         std::vector<ViewDesc> views = ref_views(images_dev, H, W, b.i0, b.nb);
         const DetBuffers& D = *DS[k & 1];
-        FwdReuse ru; b.kept = false;
-        if (reuse) {
-            plan_of(b.nb, views.data(), rplan[0]);
-            const size_t need = retain_layout(rplan[0], b.nb, nullptr, nullptr);
-            cald_model::CutReuse& R = m->cr;
-            const int q = k & 1;
-            if (need > R.cap[q]) {         // grown on demand; the slot's last reader (batch k - 2's cut_out forward) is in the stream ahead
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (R.slot[q]) hipFree(R.slot[q]);
-                R.slot[q] = nullptr; R.cap[q] = 0;
-                if (hipMalloc((void**)&R.slot[q], need + (need >> 3)) != hipSuccess) { (void)hipGetLastError(); R.slot[q] = nullptr; }
-                else R.cap[q] = need + (need >> 3);
-            }
-            if (R.slot[q]) { ru.mode = 1; ru.nblk = nblk; retain_layout(rplan[0], b.nb, R.slot[q], ru.out); b.kept = true; }
-            else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
-        }
+        FwdReuse ru;
+        if (int r = retain(k, views.data(), ru)) return r;
         int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, prune_ok, b.kept ? &ru : nullptr);
         if (r) return r;
         if (hipMemcpyAsync(b.h_count, D.count, (size_t)b.nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(b.h_boxes, D.boxes, (size_t)b.nb * cap * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipEventRecord(m->ss.ev_ref[k & 1], c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "D2H of reference detections failed");
+        return 0;
+    }
+    // the retention slot of batch k's reference forward (bt[k & 1].nb views), grown on demand, and `ru` over it; sets the batch's kept / kept_fpn
+    int retain(int k, const ViewDesc* views, FwdReuse& ru) {
+        SweepBatch& b = bt[k & 1];
+        b.kept = b.kept_fpn = false;
+        if (reuse) {
+            plan_of(b.nb, views, rplan[0]);
+            cald_model::CutReuse& R = m->cr;
+            const int q = k & 1;
+            // graded: the extended slot (+ the FPN outputs); where that is refused -- by the allocator, once and for the model's life, or by the
+            // test hook's cap -- the three stages only; where that fails too, nothing (the batch's cut_out views run dense)
+            const size_t need3 = retain_layout(rplan[0], b.nb, nullptr, nullptr), needx = fpn_ok ? retain_layout_fpn(rplan[0], b.nb, nullptr, nullptr) : 0;
+            bool ext = fpn_ok && !R.ext_refused && !(R.ext_cap && needx > R.ext_cap);
+            for (int attempt = 0; attempt < 2; attempt++) {
+                const size_t need = ext ? needx : need3;
+                if (need <= R.cap[q]) break;
+                // grown on demand; the slot's last reader (batch k - 2's cut_out forward) is in the stream ahead
+                HIPCHK(hipStreamSynchronize(c->stream));
+                if (R.slot[q]) hipFree(R.slot[q]);
+                R.slot[q] = nullptr; R.cap[q] = 0;
+                if (hipMalloc((void**)&R.slot[q], need + (need >> 3)) == hipSuccess) { R.cap[q] = need + (need >> 3); break; }
+                (void)hipGetLastError(); R.slot[q] = nullptr;
+                if (!ext) break;
+                ext = false; R.ext_refused = true;
+            }
+            if (R.slot[q]) {
+                ru.mode = 1; ru.nblk = nblk; b.kept = true; b.kept_fpn = ext;
+                if (ext) retain_layout_fpn(rplan[0], b.nb, R.slot[q], &ru); else retain_layout(rplan[0], b.nb, R.slot[q], ru.out);
+            } else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
+            c->cut_kept[!b.kept ? CUT_KEPT_NONE : b.kept_fpn ? CUT_KEPT_FPN : CUT_KEPT_STAGES]++;
+        }
         return 0;
     }
 
@@ -381,43 +439,55 @@ struct SweepRun {
     // gather plan of batch k's cut_out forward (V views in the reference forward's order) into the pinned set k & 1, one H2D, and `ru`
     int cut_plan(int k, int V, const ViewDesc* vs, FwdReuse& ru) {
         cald_model::CutReuse& R = m->cr;
-        const size_t per = cut_plan_set_bytes(V), total = per * 2 * (size_t)nblk;
+        const bool fpn = bt[k & 1].kept_fpn;
+        const size_t per = cut_plan_set_bytes(V), total = per * (2 * (size_t)nblk + (fpn ? 4 : 0));
         if (!R.d_gp) {
-            const size_t cap = cut_plan_set_bytes(CALD_MAX_VIEWS) * 2 * CUT_MAX_BLOCKS;
+            const size_t cap = cut_plan_set_bytes(CALD_MAX_VIEWS) * (2 * CUT_MAX_BLOCKS + 4);
             HIPCHK(hipMalloc((void**)&R.d_gp, cap));
             HIPCHK(hipHostMalloc((void**)&R.h_gp[0], cap)); HIPCHK(hipHostMalloc((void**)&R.h_gp[1], cap));
         }
         plan_of(V, vs, rplan[0]);
         const BatchPlan& P = rplan[0];
         char* const h = R.h_gp[k & 1];
-        std::vector<CutSet> g_out((size_t)V * nblk), g_t1((size_t)V * nblk);
+        std::vector<CutSet> g_out((size_t)V * ngeo), g_t1((size_t)V * ngeo), g_fpn((size_t)V * 4);
         for (int v = 0; v < V; v++) {
             int Hr, Wr, Hp, Wp; CutSet pool1;
             transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &Hp, &Wp);
-            cut_geometry(vs[v].H, vs[v].W, Hr, Wr, Hp, Wp, vs[v].nrect, vs[v].rects, nblk, blk_stride, &pool1, &g_out[(size_t)v * nblk], &g_t1[(size_t)v * nblk]);
+            cut_geometry(vs[v].H, vs[v].W, Hr, Wr, Hp, Wp, vs[v].nrect, vs[v].rects, ngeo, geo_stride, &pool1, &g_out[(size_t)v * ngeo], &g_t1[(size_t)v * ngeo]);
+            if (fpn) {
+                CutSet cs[4], inner[4];
+                for (int i = 0; i < 4; i++) cs[i] = g_out[(size_t)v * ngeo + c_blk[i]];
+                cut_fpn_geometry(Hp, Wp, cs, inner, &g_fpn[(size_t)v * 4]);
+            }
         }
+        // one gather set of the plan: per view the level's geometry with tile_start counting the set's tiles, then the set as disjoint rectangles
+        auto put_set = [&](size_t index, int lvl, const CutSet* sets, size_t stride_v, int* tiles_out, double* rows_out) {
+            LevelSeg* sg = reinterpret_cast<LevelSeg*>(h + index * per);
+            GatherSet* gs = reinterpret_cast<GatherSet*>(reinterpret_cast<char*>(sg) + (size_t)(V + 1) * sizeof(LevelSeg));
+            int tiles = 0; double rows = 0.0;
+            for (int v = 0; v < V; v++) {
+                LevelSeg L = P.seg[lvl][v]; L.tile_start = tiles; sg[v] = L;
+                CutRect rr[CALD_GATHER_RECTS];
+                int n = cut_disjoint(sets[(size_t)v * stride_v], rr, CALD_GATHER_RECTS);
+                if (n < 0) { n = 1; rr[0] = {0, 0, L.W - 1, L.H - 1}; }       // too fragmented: the whole view
+                GatherSet& G = gs[v]; memset(&G, 0, sizeof(G));
+                G.nr = n;
+                for (int q = 0; q < n; q++) {
+                    G.x0[q] = rr[q].x0; G.y0[q] = rr[q].y0; G.w[q] = rr[q].x1 - rr[q].x0 + 1;
+                    G.cum[q + 1] = G.cum[q] + G.w[q] * (rr[q].y1 - rr[q].y0 + 1);
+                }
+                tiles += (G.cum[n] + 127) / 128; rows += (double)G.cum[n];
+            }
+            sg[V] = P.seg[lvl][V]; sg[V].tile_start = tiles;
+            *tiles_out = tiles; *rows_out = rows;
+        };
         auto kf = [](const ConvLayer& L) { return (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue); };
-        double cost_g[3] = {0, 0, 0}, cost_d[3] = {0, 0, 0}, rows_g[3] = {0, 0, 0}, rows_d[3] = {0, 0, 0};
+        double cost_g[3] = {0, 0, 0}, cost_d[3] = {0, 0, 0}, rows_g[3] = {0, 0, 0}, rows_d[3] = {0, 0, 0}, tiles_g[3] = {0, 0, 0}, tiles_d[3] = {0, 0, 0};
         for (int b = 0; b < nblk; b++)
             for (int kind = 0; kind < 2; kind++) {
                 const int lvl = kind ? blk_lin[b] : blk_lout[b];
-                LevelSeg* sg = reinterpret_cast<LevelSeg*>(h + (size_t)(2 * b + kind) * per);
-                GatherSet* gs = reinterpret_cast<GatherSet*>(reinterpret_cast<char*>(sg) + (size_t)(V + 1) * sizeof(LevelSeg));
-                int tiles = 0; double rows = 0.0;
-                for (int v = 0; v < V; v++) {
-                    LevelSeg L = P.seg[lvl][v]; L.tile_start = tiles; sg[v] = L;
-                    CutRect rr[CALD_GATHER_RECTS];
-                    int n = cut_disjoint(kind ? g_t1[(size_t)v * nblk + b] : g_out[(size_t)v * nblk + b], rr, CALD_GATHER_RECTS);
-                    if (n < 0) { n = 1; rr[0] = {0, 0, L.W - 1, L.H - 1}; }       // too fragmented: the whole view
-                    GatherSet& G = gs[v]; memset(&G, 0, sizeof(G));
-                    G.nr = n;
-                    for (int q = 0; q < n; q++) {
-                        G.x0[q] = rr[q].x0; G.y0[q] = rr[q].y0; G.w[q] = rr[q].x1 - rr[q].x0 + 1;
-                        G.cum[q + 1] = G.cum[q] + G.w[q] * (rr[q].y1 - rr[q].y0 + 1);
-                    }
-                    tiles += (G.cum[n] + 127) / 128; rows += (double)G.cum[n];
-                }
-                sg[V] = P.seg[lvl][V]; sg[V].tile_start = tiles;
+                int tiles; double rows;
+                put_set((size_t)(2 * b + kind), lvl, (kind ? g_t1.data() : g_out.data()) + b, (size_t)ngeo, &tiles, &rows);
                 ru.tiles[b][kind] = tiles; ru.rows[b][kind] = rows;
                 const Bottleneck& Bk = m->blocks[b];
                 const double w = kind ? kf(Bk.c1) : kf(Bk.c2) + kf(Bk.c3) + (Bk.has_down ? kf(Bk.down) : 0.0);
@@ -425,16 +495,49 @@ struct SweepRun {
                 const int st = blk_stage[b];
                 cost_g[st] += 128.0 * tiles * w; cost_d[st] += dense * w;
                 rows_g[st] += rows * nconv; rows_d[st] += dense * nconv;
+                tiles_g[st] += tiles * nconv; tiles_d[st] += (double)P.seg[lvl][V].tile_start * nconv;
             }
         // a stage runs gathered while its tiles cost at most CUT_GATHER_MAX_COST of the dense stage (the rest pays the halo, the per-view
         // tile tails and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
         for (int st = 0; st < 3; st++) {
             ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= CUT_GATHER_MAX_COST * cost_d[st];
             c->cut_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_dense[st] += rows_d[st];
+            c->cut_st_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_st_dense[st] += rows_d[st];
+            c->cut_st_tiles[st] += ru.gather[st] ? tiles_g[st] : tiles_d[st]; c->cut_st_dense_tiles[st] += tiles_d[st];
+        }
+        // layer4 and the laterals run dense (their rows are booked as such); the FPN output convs are one more gated stage, all four levels
+        // in one grouped gathered launch -- every level has the same weight per row, so its cost is its tiles
+        {
+            double r4 = 0.0, t4 = 0.0, rl = 0.0, tl = 0.0;
+            int lvl = 2;
+            for (size_t b = 0; b < m->blocks.size(); b++) {
+                const Bottleneck& Bk = m->blocks[b];
+                const int lo = lvl + (Bk.c2.stride == 2 ? 1 : 0);
+                if ((int)b >= nblk) {
+                    const double n_in = 1.0, n_out = Bk.has_down ? 3.0 : 2.0;
+                    r4 += n_in * (double)level_pix(P, lvl, V) + n_out * (double)level_pix(P, lo, V);
+                    t4 += n_in * (double)P.seg[lvl][V].tile_start + n_out * (double)P.seg[lo][V].tile_start;
+                }
+                lvl = lo;
+            }
+            if (!retina) for (int i = 0; i < 4; i++) { rl += (double)level_pix(P, 2 + i, V); tl += (double)P.seg[2 + i][V].tile_start; }
+            c->cut_st_rows[3] += r4; c->cut_st_dense[3] += r4; c->cut_st_tiles[3] += t4; c->cut_st_dense_tiles[3] += t4;
+            c->cut_st_rows[CUT_STAGE_LATERAL] += rl; c->cut_st_dense[CUT_STAGE_LATERAL] += rl;
+            c->cut_st_tiles[CUT_STAGE_LATERAL] += tl; c->cut_st_dense_tiles[CUT_STAGE_LATERAL] += tl;
+            double fg = 0.0, fd = 0.0, frg = 0.0, frd = 0.0;
+            if (fpn)
+                for (int i = 0; i < 4; i++) {
+                    put_set(2 * (size_t)nblk + i, 2 + i, g_fpn.data() + i, 4, &ru.fpn_tiles[i], &ru.fpn_rows[i]);
+                    fg += ru.fpn_tiles[i]; frg += ru.fpn_rows[i];
+                }
+            if (!retina) for (int i = 0; i < 4; i++) { fd += (double)P.seg[2 + i][V].tile_start; frd += (double)level_pix(P, 2 + i, V); }
+            ru.gather_fpn = fpn && m->cr.mode != 2 && 128.0 * fg <= CUT_FPN_MAX_COST * frd;
+            c->cut_st_rows[CUT_STAGE_OUTPUT] += ru.gather_fpn ? frg : frd; c->cut_st_dense[CUT_STAGE_OUTPUT] += frd;
+            c->cut_st_tiles[CUT_STAGE_OUTPUT] += ru.gather_fpn ? fg : fd; c->cut_st_dense_tiles[CUT_STAGE_OUTPUT] += fd;
         }
         if (hipMemcpyAsync(R.d_gp, h, total, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of the cut_out gather plan failed");
         ru.mode = 2; ru.nblk = nblk; ru.d_gp = R.d_gp;
-        retain_layout(P, V, m->cr.slot[k & 1], ru.out);
+        if (fpn) retain_layout_fpn(P, V, m->cr.slot[k & 1], &ru); else retain_layout(P, V, m->cr.slot[k & 1], ru.out);
         c->cut_batches++;
         return 0;
     }
@@ -582,6 +685,44 @@ struct SweepRun {
     }
 };
 }  // namespace
+
+// Test hook: the cut_out forward of a sweep batch on its own.  The views without their rectangles run as the reference forward (retaining
+// what the model's reuse mode retains), then the views as given run as the cut_out forward over it -- mode 0: a plain dense forward -- and
+// leave their detections in `out` and their tensors to cald_debug_tensor.  prune != 0: both forwards take the certified pruning's path.
+extern "C" int cald_debug_cutout_forward(cald_model* m, int n_views, const cald_view* views, const cald_dets* out, int prune) {
+    if (!m || !views || !out || n_views < 1 || n_views > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "bad argument");
+    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
+    std::vector<ViewDesc> cut(n_views), ref(n_views);
+    for (int i = 0; i < n_views; i++) {
+        const cald_view& v = views[i];
+        if (v.nrect < 0 || v.nrect > CALD_MAX_CUT || v.flip || v.noise_dev) return fail(CALD_ERR_INVALID, "view %d is no cut_out view", i);
+        cut[i] = plain_view(v.image_dev, v.H, v.W); ref[i] = cut[i];
+        cut[i].nrect = v.nrect;
+        for (int q = 0; q < 4 * v.nrect; q++) cut[i].rects[q] = v.rects[q];
+    }
+    DetBuffers det;
+    det.boxes = out->boxes_dev; det.scores = out->scores_dev; det.labels = (long long*)out->labels_dev; det.props = out->props_dev;
+    det.prob_max = out->prob_max_dev; det.scores_cls = out->scores_cls_dev; det.count = out->count_dev;
+    det.cap = out->cap; det.C = m->cfg.num_classes;
+    if (!det.boxes || !det.scores || !det.labels || !det.props || !det.prob_max || !det.scores_cls || !det.count)
+        return fail(CALD_ERR_INVALID, "output buffers must all be provided");
+    SweepRun R{m, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
+    R.c = m->ctx;
+    HIPCHK(hipSetDevice(R.c->device));
+    R.prune_ok = prune != 0;
+    R.init_blocks();
+    R.reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && m->cfg.precision == CALD_PRECISION_FP32 && R.nblk < CUT_MAX_BLOCKS;
+    R.rplan.resize(1);
+    R.bt[0].nb = n_views;
+    if (m->prune && R.prune_ok) HIPCHK(hipMemsetAsync(R.c->d_prune_check, 0, 8, R.c->stream));
+    FwdReuse ru, ru2;
+    int rc = R.retain(0, ref.data(), ru);
+    if (!rc) rc = forward_model(m, n_views, ref.data(), det, nullptr, R.prune_ok, R.bt[0].kept ? &ru : nullptr);
+    if (!rc && R.bt[0].kept) rc = R.cut_plan(0, n_views, cut.data(), ru2);
+    if (!rc) rc = forward_model(m, n_views, cut.data(), det, nullptr, R.prune_ok, R.bt[0].kept ? &ru2 : nullptr);
+    if (!rc) HIPCHK(hipStreamSynchronize(R.c->stream));
+    return rc;
+}
 
 static int sweep_checked(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                          const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out) {

@@ -186,7 +186,7 @@ class HipDetector:
         return self._handle
 
     # ---- inference ----
-    def forward_views(self, views):
+    def forward_views(self, views, _entry=None):
         """views: list of (uint8 HWC cuda tensor, flip, rects[, noise]) -- noise: optional float32 CHW cuda tensor added to
         image/255 (cald_view.noise_dev).  Returns list of result dicts (device tensors)."""
         L = _ffi.lib()
@@ -214,7 +214,7 @@ class HipDetector:
                     arr[i].rects[j] = int(r)
         d = _ffi.Dets(out["boxes"].data_ptr(), out["scores"].data_ptr(), out["labels"].data_ptr(), out["props"].data_ptr(),
                       out["prob_max"].data_ptr(), out["scores_cls"].data_ptr(), out["count"].data_ptr(), cap)
-        _ffi.check(L.cald_forward(h, n, arr, C.byref(d)))
+        _ffi.check(L.cald_forward(h, n, arr, C.byref(d)) if _entry is None else _entry(L, h, n, arr, C.byref(d)))
         counts = out["count"].cpu().tolist()
         res = []
         for i, k in enumerate(counts):
@@ -249,6 +249,11 @@ class HipDetector:
             noise = rem.contiguous() if bool((rem != 0).any()) else None
             views.append((g.permute(1, 2, 0).contiguous(), False, None, noise))
         return self.forward_views(views)
+
+    def debug_cutout_forward(self, views, prune=False):
+        """Test hook (cald_debug_cutout_forward): the views without their rectangles as a sweep batch's reference forward, then the views as
+        its cut_out forward under the model's cut_out reuse mode.  Returns the cut_out forward's results; its tensors are debug_tensor()'s."""
+        return self.forward_views(views, _entry=lambda L, h, n, arr, d: L.cald_debug_cutout_forward(h, n, arr, d, int(bool(prune))))
 
     def set_rpn_prune(self, on):
         """Certified RPN pruning of the exact sweeps (include/cald_hip.h cald_model_set_rpn_prune): returns the previous state."""

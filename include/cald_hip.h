@@ -329,6 +329,10 @@ int cald_op_cutout_rects(uint64_t seed, int H, int W, int N, const float* boxes,
  * inclusive}: set 0 of entry 0 = the pooled stem output; entry 1 + b = block b's output (set 0) and the pixels its conv1 computes (set 1).
  * A pixel outside a dirty set has the reference view's bits. */
 int cald_op_cutout_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out);
+/* The same through the FPN of Faster R-CNN (host only): strides of ALL nblk blocks of the backbone (a stage ends before the next stride-2
+ * block; there must be four).  out: 8 sets of 17 ints in the form above: the dirty sets of the laterals (inner P2..P5: C_l's dirty set
+ * joined with the 2 x upsample of the lateral above), then of the 3 x 3 output convs (P2..P5: one ring around the lateral's set). */
+int cald_op_cutout_fpn_geometry(int H, int W, int min_size, int max_size, int nrect, const int* rects, int nblk, const int* strides, int* out);
 /* one augmented view outside the sweep (helper API of cald/cald_helper.py; same kernels as inside cald_sweep).  A fresh
  * generator is seeded with `seed` (torch's CPU generator for GAUSS / SALT_PEPPER, Python's `random` for COLOR_SWAP).
  *   CALD_AUG_GAUSS        GaussianNoise :72-75    dst_dev = float [3][H][W], the additive term randn * param / 255
@@ -569,6 +573,17 @@ int cald_model_set_box_min_size(cald_model* m, float min_size, float* was);
  * forwards computed and the rows the dense stages would have (summed over the stage's convs), the batches that reused the reference
  * forward, and the batches whose cut_out views ran dense for want of retention memory.  Accumulated over the context's life. */
 int cald_profile_cutout(cald_ctx* ctx, double* rows3, double* dense_rows3, int64_t* batches, int64_t* fallbacks);
+/* the same per stage of the cut_out forward -- layer1, layer2, layer3, layer4, the FPN laterals, the FPN output convs (layer4 and the
+ * laterals run dense) -- with the 128-row tiles issued and the dense stage's; kept3: the batches whose reference forward retained the
+ * three stages and the FPN outputs, the three stages only (the extended slot was refused), nothing (the cut_out views ran dense). */
+int cald_profile_cutout_stages(cald_ctx* ctx, double* rows6, double* dense_rows6, double* tiles6, double* dense_tiles6, int64_t* kept3);
+/* test hook: an extended retention slot (three stages + FPN outputs) above `bytes` counts as refused, so the sweep falls back to the
+ * three-stage retention (0 = no cap, the default).  Returns the previous value in *was (may be null). */
+int cald_model_set_cutout_retention_cap(cald_model* m, int64_t bytes, int64_t* was);
+/* test hook: a sweep batch's cut_out forward on its own.  The views without their rectangles run as the reference forward (retaining what
+ * the model's cut_out reuse mode retains), then the views as given (no flip, no noise) as the cut_out forward over it; with the reuse off,
+ * a plain dense forward.  prune != 0: both take the certified pruning's path.  `out` and cald_debug_tensor show the cut_out forward. */
+int cald_debug_cutout_forward(cald_model* m, int n_views, const cald_view* views, const cald_dets* out, int prune);
 /* mean proposals per view (R of SURVEY 8d) over the Faster R-CNN forwards profiled since cald_profile_enable */
 int cald_profile_roi_rows(cald_ctx* ctx, double* mean_rows_per_view, int64_t* views);
 /* per-launch CSV (shape, algorithmic GFLOP, ms, TFLOP/s) of the launches recorded since cald_profile_enable */

@@ -20,6 +20,7 @@ def record(path):
         "selected_sha1": d["config"]["selected_sha1"],
         "pixels_recomputed_exactly": r["rpn_prune"]["pixels_recomputed_exactly"],
         "worst_observed_error_over_bound": r["rpn_prune"]["worst_observed_error_over_bound"],
+        "roi_rows_per_view_measured": r["roi_rows_per_view_measured"],
     }
 
 
@@ -32,7 +33,8 @@ def main(d, what):
     tv = [r["value"] for k, r in runs.items() if k.startswith("this")]
     pm, tm, spread = sum(pv) / len(pv), sum(tv) / len(tv), max(pv) - min(pv)
     ident = {k: len({json.dumps(r[k], sort_keys=True) for r in runs.values()}) == 1
-             for k in ("selected_sha1", "pixels_recomputed_exactly", "worst_observed_error_over_bound", "launches", "algorithmic_gflop_per_launch")}
+             for k in ("selected_sha1", "pixels_recomputed_exactly", "worst_observed_error_over_bound", "roi_rows_per_view_measured", "launches",
+                       "algorithmic_gflop_per_launch")}
     out = {
         "what": what, "runs": runs, "parent_mean": pm, "this_mean": tm, "parent_spread_max_minus_min": spread,
         "this_minus_parent": tm - pm, "this_over_parent": tm / pm,
