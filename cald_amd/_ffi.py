@@ -42,6 +42,7 @@ class Dets(C.Structure):
 
 MAX_AUGS = 32
 N_MARGINS = 16          # CALD_N_MARGINS
+EVAL_MAX_DT, EVAL_MAX_GT = 128, 256     # CALD_EVAL_MAX_DT / CALD_EVAL_MAX_GT: per-segment caps of cald_op_coco_match / cald_op_voc_match
 MARGIN_NAMES = ['rpn_topk', 'rpn_iou', 'rpn_order', 'rpn_trunc', 'rpn_small', 'roi_level', 'roi_edge', 'post_thr', 'post_iou', 'post_order',
                 'post_cap', 'ref_subsample', 'argmax', 'zero_row', 'cutout', 'reserved']
 # Rounding noise of precision="f16x3" against the exact mode on each margin's scale, calibrated on 1 536 configs[1] images
@@ -177,6 +178,9 @@ SIGNATURES = {
     "cald_op_lossnet": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
     "cald_op_consistency": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f, c_f, C.c_int, c_f, c_f, c_f, C.c_int, C.c_float, c_f]),
     "cald_op_cls_corr": (C.c_int, [C.c_void_p, C.c_int, c_f, c_i64, C.c_int, c_f]),
+    "cald_op_coco_match": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_d, c_d, c_d, c_d, c_u8, c_u8, C.c_int, c_d, C.c_int, c_d,
+                                     C.POINTER(C.c_int32), c_u8, c_u8]),
+    "cald_op_voc_match": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_d, c_u8, c_d, c_i64, C.c_int, c_d, C.c_int64, c_d, c_i64, c_u8, c_u8]),
     "cald_op_pil_resize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "cald_op_cutout_rects": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, c_f, C.c_int, c_i, c_i]),
     "cald_op_cutout_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i, C.c_int, c_i, c_i]),

@@ -1,5 +1,5 @@
-// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, model.hip, forward.hip, sweep.hip, lossnet.hip) share: the context and the model
-// behind the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those six
+// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, eval.hip, model.hip, forward.hip, sweep.hip, lossnet.hip) share: the context and the model
+// behind the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those seven
 // files alone: the train_*.hip files (train_host.h), jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
 #pragma once
 #include "../../include/cald_hip.h"

@@ -115,11 +115,13 @@ def write_voc_results_file(all_boxes, image_index, path, classes, root='/tmp'):
     return out_dir
 
 
-def voc_evaluate(model, data_loader, year, feature=False, path='results', root='/tmp', batch_views=64):
+def voc_evaluate(model, data_loader, year, feature=False, path='results', root='/tmp', batch_views=64, matching="host"):
     """detection/engine.py:86-158: forward over the test loader (batched on the GPU), gather over ranks, results files,
-    AP table.  Returns what ``cald_amd.voc_eval.do_python_eval`` returns on the main process, None elsewhere."""
+    AP table.  Returns what ``cald_amd.voc_eval.do_python_eval`` returns on the main process, None elsewhere.
+    ``matching="device"`` matches detections to ground truth with the HIP kernel of eval.hip (same numbers)."""
     import torch.distributed as dist
-    from .voc_eval import do_python_eval
+    from .voc_eval import do_python_eval, check_matching
+    check_matching(matching)
     if feature:
         raise NotImplementedError("feature=True (models returning (features, outputs)) belongs to the LL4AL baselines")
     classes = data_loader.dataset._transforms.transforms[0].CLASSES
@@ -132,7 +134,7 @@ def voc_evaluate(model, data_loader, year, feature=False, path='results', root='
         all_boxes = [sum((p[0][c] for p in parts), []) for c in range(len(classes))]
         image_index = sum((p[1] for p in parts), [])
     write_voc_results_file(all_boxes, image_index, path, classes, root=root)
-    return do_python_eval(data_loader, year, path, root=root)
+    return do_python_eval(data_loader, year, path, root=root, matching=matching)
 
 
 def coco_predictions(model, data_loader, batch_views=64):
@@ -175,15 +177,19 @@ def coco_results(predictions):
     return out
 
 
-def coco_evaluate(model, data_loader, classwise=True, feature=False, batch_views=64):
+def coco_evaluate(model, data_loader, classwise=True, feature=False, batch_views=64, matching="host"):
     """detection/engine.py:178-256: forward over the test loader (batched on the GPU), CocoEvaluator update / accumulate / summarize
-    (cald_amd.coco_eval: bbox AP without pycocotools, parity unpinned), optional per-category AP table.  Returns the evaluator."""
-    from .coco_eval import CocoEvaluator, CocoGT
+    (cald_amd.coco_eval: bbox AP without pycocotools, parity unpinned), optional per-category AP table.  Returns the evaluator.
+    ``matching="device"`` evaluates through FlatCOCOeval and the HIP matching kernel of eval.hip (same numbers; single process only)."""
+    from .coco_eval import CocoEvaluator, CocoGT, check_matching, refuse_multi_rank_device_matching
+    check_matching(matching)
+    if matching == "device":
+        refuse_multi_rank_device_matching()                   # before the forward
     if feature:
         raise NotImplementedError("feature=True (models returning (features, outputs)) belongs to the LL4AL baselines")
     model.eval()
     coco = CocoGT.from_dataset(data_loader.dataset)
-    evaluator = CocoEvaluator(coco, ["bbox"])
+    evaluator = CocoEvaluator(coco, ["bbox"], matching=matching)
     evaluator.update(coco_predictions(model, data_loader, batch_views))
     evaluator.synchronize_between_processes()
     evaluator.accumulate()

@@ -142,10 +142,54 @@ def voc_eval(classname, detpath, imagesetfile, annopath='', ovthresh=0.5, use_07
     return _curve(tp, fp, npos, use_07_metric)
 
 
-def voc_eval_thresholds(classname, detfile, annotations, thresholds=IOU_THRESHOLDS, use_07_metric=False):
-    """[(rec, prec, ap)] of one class at every threshold: one read of the file, one overlap pass, one marking per threshold."""
+MATCHING = ("host", "device")
+
+
+def check_matching(matching):
+    if matching not in MATCHING:
+        raise ValueError("matching must be one of %s, not %r" % (MATCHING, matching))
+
+
+def match_device(image_ids, BB, table, thresholds):
+    """best_overlaps + mark_detections at every threshold in one cald_op_voc_match call (eval.hip): (ovmax [nd], jmax [nd], tp [T, nd],
+    fp [T, nd]), equal to the host functions' results.  The detections are grouped by image (a stable sort, so each image keeps the
+    class's confidence order); an image above the kernel's per-segment caps sends the whole class down the host route."""
+    from . import _ffi, detector
+    ctx = detector.get_ctx()                                  # raises without a GPU: there is no silent host route
+    thrs = np.ascontiguousarray([float(t) for t in thresholds], np.float64)
+    nd, T = len(image_ids), len(thrs)
+    names = sorted(set(image_ids))
+    where = {n: i for i, n in enumerate(names)}
+    seg = np.array([where[n] for n in image_ids], np.int64)
+    order = np.argsort(seg, kind="stable").astype(np.int64)
+    dt_off = np.r_[0, np.cumsum(np.bincount(seg, minlength=len(names)))].astype(np.int64)
+    gts = [table[n] for n in names]
+    gt_off = np.r_[0, np.cumsum([len(g[1]) for g in gts])].astype(np.int64)
+    if nd and (np.diff(dt_off).max() > _ffi.EVAL_MAX_DT or np.diff(gt_off).max() > _ffi.EVAL_MAX_GT or T > 64):
+        ovmax, jmax = best_overlaps(image_ids, BB, table)
+        marks = [mark_detections(image_ids, ovmax, jmax, table, t) for t in thresholds]
+        return ovmax, jmax, np.array([m[0] for m in marks]).reshape(T, nd), np.array([m[1] for m in marks]).reshape(T, nd)
+    gt_box = np.ascontiguousarray(np.concatenate([g[0].reshape(-1, 4) for g in gts]) if gts else np.zeros((0, 4)), np.float64)
+    gt_diff = np.ascontiguousarray(np.concatenate([g[1] for g in gts]) if gts else np.zeros(0), np.uint8)
+    dt_box = np.ascontiguousarray(np.asarray(BB, np.float64).reshape(-1, 4)[order])
+    ovmax, jmax = np.full(nd, -np.inf), np.zeros(nd, dtype=np.int64)
+    tp, fp = np.zeros((T, nd), np.uint8), np.zeros((T, nd), np.uint8)
+    _ffi.check(_ffi.lib().cald_op_voc_match(ctx, len(names), _ffi.ptr(dt_off, _ffi.c_i64), _ffi.ptr(gt_off, _ffi.c_i64), _ffi.ptr(gt_box, _ffi.c_d),
+                                            _ffi.ptr(gt_diff, _ffi.c_u8), _ffi.ptr(dt_box, _ffi.c_d), _ffi.ptr(order, _ffi.c_i64), T,
+                                            _ffi.ptr(thrs, _ffi.c_d), nd, _ffi.ptr(ovmax, _ffi.c_d), _ffi.ptr(jmax, _ffi.c_i64),
+                                            _ffi.ptr(tp, _ffi.c_u8), _ffi.ptr(fp, _ffi.c_u8)))
+    return ovmax, jmax, tp.astype(np.float64), fp.astype(np.float64)
+
+
+def voc_eval_thresholds(classname, detfile, annotations, thresholds=IOU_THRESHOLDS, use_07_metric=False, matching="host"):
+    """[(rec, prec, ap)] of one class at every threshold: one read of the file, one overlap pass, one marking per threshold.
+    ``matching="device"`` does the overlap pass and the markings in one HIP call (match_device); the numbers are the same."""
+    check_matching(matching)
     table, npos = annotations.of_class(classname)
     image_ids, BB = read_detections(detfile)
+    if matching == "device":
+        _, _, tp, fp = match_device(image_ids, BB, table, thresholds)
+        return [_curve(tp[i], fp[i], npos, use_07_metric) for i in range(len(tp))]
     ovmax, jmax = best_overlaps(image_ids, BB, table)
     return [_curve(*mark_detections(image_ids, ovmax, jmax, table, t), npos, use_07_metric) for t in thresholds]
 
@@ -159,10 +203,12 @@ def voc_paths(root, year, image_set):
     return found
 
 
-def do_python_eval(data_loader, year, path, root='/tmp', classes=None, quiet=False):
+def do_python_eval(data_loader, year, path, root='/tmp', classes=None, quiet=False, matching="host"):
     """detection/voc_eval.py:225-266 ``_do_python_eval``: mAP@[.5:.95], AP50, AP75, mean recall@.5 and per-class AP50 of the
     results files under ``{root}/{path}``; prints the reference's table line and returns the numbers.
-    ``data_loader.dataset`` provides ``root``, ``image_set`` and the class list (``_transforms.transforms[0].CLASSES``)."""
+    ``data_loader.dataset`` provides ``root``, ``image_set`` and the class list (``_transforms.transforms[0].CLASSES``).
+    ``matching="device"`` matches on the GPU (voc_eval_thresholds); same numbers, same line."""
+    check_matching(matching)
     ds = data_loader.dataset
     imagesetfile, annopath = voc_paths(ds.root, year, ds.image_set)
     if classes is None:
@@ -173,7 +219,7 @@ def do_python_eval(data_loader, year, path, root='/tmp', classes=None, quiet=Fal
         if cls == '__background__':
             continue
         filename = os.path.join(root, path, 'det_test_{:s}.txt'.format(cls))
-        for iou, (rec, prec, ap) in zip(IOU_THRESHOLDS, voc_eval_thresholds(cls, filename, ann)):
+        for iou, (rec, prec, ap) in zip(IOU_THRESHOLDS, voc_eval_thresholds(cls, filename, ann, matching=matching)):
             if len(rec) == 0:
                 rec = 0.
             ap_iou.append(ap)

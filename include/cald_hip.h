@@ -319,6 +319,30 @@ int cald_op_consistency(cald_ctx* ctx, int N, const float* aug_box, const float*
                         float* consistency_out);
 /* cald_train.py:114-117 */
 int cald_op_cls_corr(cald_ctx* ctx, int n, const float* scores, const int64_t* labels, int C, float* out);
+/* ---- detection-to-ground-truth matching of the AP evaluators (eval.hip).  Host arrays in, host arrays out; IEEE double in the host
+ * code's operation order, so every output equals what the Python statement gives.  A segment is one unit of the greedy matching; its
+ * detections / ground truths are rows dt_off[s] .. dt_off[s + 1] - 1 / gt_off[s] .. gt_off[s + 1] - 1 of the flat arrays (offsets
+ * [n_seg + 1], from 0).  A segment with more than CALD_EVAL_MAX_DT detections or CALD_EVAL_MAX_GT ground truths, or more than 64
+ * variants (T * A, or T), returns CALD_ERR_UNSUPPORTED before anything is uploaded or written. */
+#define CALD_EVAL_MAX_DT 128
+#define CALD_EVAL_MAX_GT 256
+/* cald_amd/coco_eval.py COCOeval.evaluate_img for every segment = (image, category), every area range and every IoU threshold at once.
+ * dt_box [D][4] xywh in score order (stable, descending, already cut at maxDets), dt_area [D]; gt_box [G][4] xywh in annotation order,
+ * gt_area [G] the annotation's area, gt_iscrowd / gt_ignore_in [G]; iou_thrs [T]; area_rng [A][2].  Out: dt_match [A][T][D] = position
+ * of the matched ground truth inside its segment (annotation order) or -1; dt_ignore [A][T][D] = the matched ground truth's ignore flag,
+ * or for an unmatched detection "dt_area outside the range"; gt_ignore [A][G] = gt_ignore_in or the annotation area outside the range. */
+int cald_op_coco_match(cald_ctx* ctx, int n_seg, const int64_t* dt_off, const int64_t* gt_off,
+                       const double* dt_box, const double* dt_area,
+                       const double* gt_box, const double* gt_area, const uint8_t* gt_iscrowd, const uint8_t* gt_ignore_in,
+                       int T, const double* iou_thrs, int A, const double* area_rng,
+                       int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore);
+/* cald_amd/voc_eval.py best_overlaps + mark_detections of one class at T thresholds; a segment = one image.  gt_box [G][4] x1 y1 x2 y2
+ * and gt_difficult [G] per image; dt_box [nd][4] grouped by segment, inside a segment in the class's confidence order; dt_index [nd] =
+ * each detection's place in that order (a permutation of 0 .. nd - 1).  Out, at the place dt_index names: ovmax [nd] (-inf without a
+ * box of the class), jmax [nd] (the first maximum; 0 without a box), tp / fp [T][nd] (strict ovmax > thrs[t]). */
+int cald_op_voc_match(cald_ctx* ctx, int n_seg, const int64_t* dt_off, const int64_t* gt_off,
+                      const double* gt_box, const uint8_t* gt_difficult, const double* dt_box, const int64_t* dt_index,
+                      int T, const double* thrs, int64_t nd, double* ovmax, int64_t* jmax, uint8_t* tp, uint8_t* fp);
 /* cald_helper.resize: PIL.Image.resize((ow, oh), BILINEAR) on uint8 RGB */
 int cald_op_pil_resize(cald_ctx* ctx, const uint8_t* src_dev, int H, int W, uint8_t* dst_dev, int oh, int ow);
 /* cald_helper.cutout rectangle selection (host side RNG = Python random seeded per image) */
