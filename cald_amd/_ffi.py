@@ -117,6 +117,15 @@ class RpnPruneProbe(C.Structure):
                 ("check", C.c_float * 2), ("stat", C.c_uint64 * 4)]
 
 
+class ScoreProbe(C.Structure):
+    """cald_score_probe (include/cald_hip.h): one sweep batch for cald_op_score_batch."""
+    _fields_ = [("V", C.c_int), ("cap", C.c_int), ("C", C.c_int), ("n_img", C.c_int), ("P", C.c_int), ("bp", C.c_float),
+                ("boxes", c_f), ("props", c_f), ("scores", c_f), ("labels", c_i64), ("scores_cls", c_f), ("prob_max", c_f), ("count", c_i),
+                ("view_img", c_i), ("view_isref", c_i), ("ref_sel", c_i), ("ref_n", c_i),
+                ("ref_view", c_i), ("aug_view", c_i), ("pair_img", c_i), ("aug_kind", c_i), ("aug_param", c_f),
+                ("cons", c_f), ("cls_corr", c_f), ("pair_audit", c_f), ("max_iou", c_f), ("lt", c_f)]
+
+
 class WgradPlan(C.Structure):
     """cald_wgrad_plan (include/cald_hip.h): what cald_train_wgrad_plan answers."""
     _fields_ = [("variant", C.c_int), ("reduce", C.c_int), ("MT", C.c_int), ("JT", C.c_int), ("S", C.c_longlong), ("chunk", C.c_longlong),
@@ -178,6 +187,9 @@ SIGNATURES = {
     "cald_op_lossnet": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f]),
     "cald_op_consistency": (C.c_int, [C.c_void_p, C.c_int, c_f, c_f, c_f, C.c_int, c_f, c_f, c_f, C.c_int, C.c_float, c_f]),
     "cald_op_cls_corr": (C.c_int, [C.c_void_p, C.c_int, c_f, c_i64, C.c_int, c_f]),
+    "cald_op_score_batch": (C.c_int, [C.c_void_p, C.POINTER(ScoreProbe)]),
+    "cald_op_pair_params": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, c_f]),
+    "cald_op_ls_tail": (C.c_int, [C.c_int, c_f, C.c_int, c_f, c_i, c_i, c_d]),
     "cald_op_coco_match": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_d, c_d, c_d, c_d, c_u8, c_u8, C.c_int, c_d, C.c_int, c_d,
                                      C.POINTER(C.c_int32), c_u8, c_u8]),
     "cald_op_voc_match": (C.c_int, [C.c_void_p, C.c_int, c_i64, c_i64, c_d, c_u8, c_d, c_i64, C.c_int, c_d, C.c_int64, c_d, c_i64, c_u8, c_u8]),

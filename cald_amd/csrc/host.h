@@ -294,4 +294,26 @@ void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);
 // detection buffers that live for one API call
 struct ScopedDet { DetBuffers d{}; ~ScopedDet() { free_det(d); } int alloc(int V, int cap, int C) { return alloc_det(d, V, cap, C); } };
+// ---- the scoring stage's tables, shared by the sweeps (sweep.hip) and the hook cald_op_score_batch (ops.hip) ----
+// The `ints` block of a scoring stage, the same words on the host and on the device: per pair ref_view | aug_view | aug_kind | pair_img
+// (P_MAX each), ref_sel [B][50], ref_n [B], then per view view_img | view_isref (VT each; VT = 0: no per-view tail -- ls_c has no cls_corr).
+struct PairLayout {
+    int P_MAX, B, VT;
+    struct Ptrs { int *ref_view, *aug_view, *aug_kind, *pair_img, *ref_sel, *ref_n, *view_img, *view_isref; };
+    size_t n_ints() const { return (size_t)P_MAX * 4 + (size_t)B * 51 + (size_t)VT * 2; }
+    Ptrs at(int* base) const {
+        Ptrs p;
+        p.ref_view = base; p.aug_view = p.ref_view + P_MAX; p.aug_kind = p.aug_view + P_MAX; p.pair_img = p.aug_kind + P_MAX;
+        p.ref_sel = p.pair_img + P_MAX; p.ref_n = p.ref_sel + (size_t)B * 50; p.view_img = p.ref_n + B; p.view_isref = p.view_img + VT;
+        return p;
+    }
+    // the scoring kernels' arguments over the device copy of the block
+    ScoreArgs score_args(int* d_base, const DetBuffers& D, const float* d_par, int P, float bp, float* cons) const {
+        const Ptrs p = at(d_base);
+        ScoreArgs sa; sa.det = D;
+        sa.ref_view = p.ref_view; sa.aug_view = p.aug_view; sa.aug_kind = p.aug_kind; sa.pair_img = p.pair_img;
+        sa.ref_sel = p.ref_sel; sa.ref_n = p.ref_n; sa.aug_param = d_par; sa.P = P; sa.bp = bp; sa.cons = cons;
+        return sa;
+    }
+};
 }  // namespace cald_host

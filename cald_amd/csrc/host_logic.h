@@ -7,6 +7,7 @@
 //   * Pillow's Image.rotate(expand=True) matrix + 16.16 fixed-point coefficients, and cald_helper.rotate's box constants
 // Product code; the oracle holds its own independent restatement of each of these.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -258,6 +259,44 @@ static inline float np_sum_f32(const float* a, int n) {
     }
     int n2 = n / 2; n2 -= n2 % 8;
     return np_sum_f32(a, n2) + np_sum_f32(a + n2, n - n2);
+}
+
+
+// What a pair's aug_param holds for the augmentations that move boxes (score.hip aug_box; kind as ScoreArgs::aug_kind): 1 flip {W},
+// 2 resize {ratio} -- boxes * ratio is a float32 tensor times the scalar --, 3 rotate {the constants of rotate_box_params over Pillow's
+// expanded canvas}; anything else: zeros.
+static inline void pair_params(int kind, int H, int W, double param, float* par /*12*/) {
+    for (int q = 0; q < 12; q++) par[q] = 0.0f;
+    if (kind == 1) par[0] = (float)W;
+    else if (kind == 2) par[0] = (float)param;
+    else if (kind == 3) { int fx[6], nh, nw; pil_rotate_setup(H, W, param, fx, &nh, &nw); rotate_box_params(H, W, param, nw, nh, par); }
+}
+
+// ---- host tail of the ls_c sweep (ls_c_train.py:118-153) ----
+// the reference boxes that are scored: all n while n <= 30, otherwise the top 30 by prob_max (value descending, index ascending).
+// sel [30]; returns how many
+static inline int ls_select(int n, const float* pm, int* sel) {
+    std::vector<int> idx(n); for (int k = 0; k < n; k++) idx[k] = k;
+    if (n > 30) {
+        std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return pm[x] > pm[y]; });
+        idx.resize(30);
+    }
+    for (size_t k = 0; k < idx.size(); k++) sel[k] = idx[k];
+    return (int)idx.size();
+}
+// the float64 / float32 numpy arithmetic of ls_c_train.py:151-153: pm [N] the selected boxes' prob_max, rows[r][k] the maximum IoU of
+// selected box k in noisy view r (n_rows views; the mean is over six whatever n_rows is).  No box: 0.0
+static inline double ls_tail(int N, const float* pm, int n_rows, const float* const* rows) {
+    if (N <= 0) return 0.0;
+    std::vector<double> st(N, 0.0), prod(N);
+    float U = 0.0f;
+    for (int k = 0; k < N; k++) {
+        const float u = 1.0f - pm[k];
+        if (k == 0 || u > U) U = u;
+    }
+    for (int r = 0; r < n_rows; r++) for (int k = 0; k < N; k++) st[k] += (double)rows[r][k];
+    for (int k = 0; k < N; k++) { st[k] = st[k] / 6.0; prod[k] = (double)pm[k] * st[k]; }
+    return np_sum(prod.data(), N) / (double)np_sum_f32(pm, N) - (double)U;
 }
 
 

@@ -818,3 +818,84 @@ extern "C" int cald_op_cls_corr(cald_ctx* c, int n, const float* scores, const i
     HIPCHK(hipMemcpy(out, dout, (size_t)(C - 1) * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// The scoring stage of one sweep batch: the tables through PairLayout as the sweeps fill them, then score.hip's five launches.
+extern "C" int cald_op_score_batch(cald_ctx* c, cald_score_probe* q) {
+    if (!c || !q) return fail(CALD_ERR_INVALID, "null argument");
+    const int V = q->V, cap = q->cap, C = q->C, B = q->n_img, P = q->P;
+    if (!q->boxes || !q->props || !q->scores || !q->labels || !q->scores_cls || !q->prob_max || !q->count || !q->view_img || !q->view_isref ||
+        !q->ref_sel || !q->ref_n || !q->ref_view || !q->aug_view || !q->pair_img || !q->aug_kind || !q->aug_param ||
+        !q->cons || !q->cls_corr || !q->pair_audit || !q->max_iou || !q->lt) return fail(CALD_ERR_INVALID, "null argument");
+    if (C < 2 || C > 256) return fail(CALD_ERR_INVALID, "C %d outside 2..256", C);
+    if (V < 1 || V > CALD_MAX_VIEWS || cap < 1 || B < 1 || P < 0) return fail(CALD_ERR_INVALID, "bad geometry (1 <= V <= %d, cap >= 1, n_img >= 1, P >= 0)", CALD_MAX_VIEWS);
+    for (int v = 0; v < V; v++) {
+        if (q->count[v] < 0 || q->count[v] > cap) return fail(CALD_ERR_INVALID, "view %d: count %d outside 0..%d", v, q->count[v], cap);
+        if (q->view_img[v] < 0 || q->view_img[v] >= B) return fail(CALD_ERR_INVALID, "view %d: image %d out of range", v, q->view_img[v]);
+    }
+    for (int i = 0; i < B; i++) {
+        if (q->ref_n[i] < 0 || q->ref_n[i] > 50) return fail(CALD_ERR_INVALID, "image %d: ref_n %d outside 0..50 (cald_train.py:110-113)", i, q->ref_n[i]);
+        for (int k = 0; k < q->ref_n[i]; k++)
+            if (q->ref_sel[i * 50 + k] < 0 || q->ref_sel[i * 50 + k] >= cap) return fail(CALD_ERR_INVALID, "image %d: ref_sel[%d] = %d outside 0..%d", i, k, q->ref_sel[i * 50 + k], cap - 1);
+    }
+    for (int p = 0; p < P; p++) {
+        if (q->ref_view[p] < 0 || q->ref_view[p] >= V || q->aug_view[p] < 0 || q->aug_view[p] >= V) return fail(CALD_ERR_INVALID, "pair %d: view out of range", p);
+        if (q->pair_img[p] < 0 || q->pair_img[p] >= B) return fail(CALD_ERR_INVALID, "pair %d: image %d out of range", p, q->pair_img[p]);
+        if (q->aug_kind[p] < 0 || q->aug_kind[p] > 3) return fail(CALD_ERR_INVALID, "pair %d: unknown aug_kind %d", p, q->aug_kind[p]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream); ScopedDet sdet;
+    int rc = sdet.alloc(V, cap, C); if (rc) return rc;
+    const DetBuffers& D = sdet.d;
+    const size_t rows = (size_t)V * cap;
+    HIPCHK(hipMemcpy(D.boxes, q->boxes, rows * 16, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(D.props, q->props, rows * 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D.scores, q->scores, rows * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(D.labels, q->labels, rows * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D.scores_cls, q->scores_cls, rows * C * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(D.prob_max, q->prob_max, rows * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D.count, q->count, (size_t)V * 4, hipMemcpyHostToDevice));
+    const PairLayout lay{P > 0 ? P : 1, B, V};
+    std::vector<int> ints(lay.n_ints(), 0);
+    const PairLayout::Ptrs hp = lay.at(ints.data());
+    for (int p = 0; p < P; p++) { hp.ref_view[p] = q->ref_view[p]; hp.aug_view[p] = q->aug_view[p]; hp.aug_kind[p] = q->aug_kind[p]; hp.pair_img[p] = q->pair_img[p]; }
+    memcpy(hp.ref_sel, q->ref_sel, (size_t)B * 50 * 4); memcpy(hp.ref_n, q->ref_n, (size_t)B * 4);
+    memcpy(hp.view_img, q->view_img, (size_t)V * 4); memcpy(hp.view_isref, q->view_isref, (size_t)V * 4);
+    int* d_ints; float *d_par, *d_cons, *d_clsc, *d_pm, *d_rows, *d_lt;
+    if ((rc = sd.upload(&d_ints, ints.data(), ints.size() * 4)) || (rc = sd.alloc(&d_par, (size_t)P * 12 * 4)) || (rc = sd.alloc(&d_cons, (size_t)P * 4)) ||
+        (rc = sd.alloc(&d_clsc, (size_t)V * (C - 1) * 4)) || (rc = sd.alloc(&d_pm, (size_t)P * 2 * 4)) || (rc = sd.alloc(&d_rows, (size_t)P * 50 * 4)) ||
+        (rc = sd.alloc(&d_lt, (size_t)V * 4))) return rc;
+    if (P) HIPCHK(hipMemcpy(d_par, q->aug_param, (size_t)P * 12 * 4, hipMemcpyHostToDevice));
+    const PairLayout::Ptrs dp = lay.at(d_ints);
+    const ScoreArgs sa = lay.score_args(d_ints, D, d_par, P, q->bp, d_cons);
+    launch_consistency(sa, c->stream);
+    launch_cls_corr(D, dp.ref_sel, dp.ref_n, dp.view_img, dp.view_isref, V, d_clsc, c->stream);
+    launch_pair_audit(sa, d_pm, c->stream);
+    launch_max_iou(sa, d_rows, c->stream);
+    launch_lt_uncertainty(D, V, d_lt, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<float> h_rows((size_t)P * 50);
+    if (P) {
+        HIPCHK(hipMemcpy(q->cons, d_cons, (size_t)P * 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(q->pair_audit, d_pm, (size_t)P * 2 * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_rows.data(), d_rows, (size_t)P * 50 * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(q->cls_corr, d_clsc, (size_t)V * (C - 1) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(q->lt, d_lt, (size_t)V * 4, hipMemcpyDeviceToHost));
+    for (int p = 0; p < P; p++) memcpy(q->max_iou + (size_t)p * 50, &h_rows[(size_t)p * 50], (size_t)q->ref_n[q->pair_img[p]] * 4);      // the kernel writes the live slots only
+    return 0;
+}
+
+extern "C" int cald_op_pair_params(int kind, int H, int W, double param, float* par12_out) {
+    if (!par12_out || kind < 0 || kind > 3 || H < 1 || W < 1) return fail(CALD_ERR_INVALID, "bad argument (kind 0..3, H, W >= 1)");
+    pair_params(kind, H, W, param, par12_out);
+    return 0;
+}
+
+extern "C" int cald_op_ls_tail(int n, const float* prob_max, int n_rows, const float* max_iou, int* sel_out, int* n_sel_out, double* score_out) {
+    if (n < 0 || n_rows < 0 || (n && !prob_max) || !sel_out || !n_sel_out || (score_out && n && n_rows && !max_iou)) return fail(CALD_ERR_INVALID, "bad argument");
+    const int N = ls_select(n, prob_max, sel_out);
+    *n_sel_out = N;
+    if (!score_out) return 0;
+    std::vector<float> pm(N); std::vector<const float*> rows(n_rows);
+    for (int k = 0; k < N; k++) pm[k] = prob_max[sel_out[k]];
+    for (int r = 0; r < n_rows; r++) rows[r] = max_iou + (size_t)r * N;
+    *score_out = ls_tail(N, pm.data(), n_rows, rows.data());
+    return 0;
+}

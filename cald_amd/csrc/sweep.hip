@@ -86,28 +86,6 @@ static bool cut_reuse_env() {
 #define CUT_FPN_MAX_COST CUT_GATHER_MAX_COST
 
 namespace {
-// The `ints` block of a scoring stage, the same words on the host and on the device: per pair ref_view | aug_view | aug_kind | pair_img
-// (P_MAX each), ref_sel [B][50], ref_n [B], then per view view_img | view_isref (VT each; VT = 0: no per-view tail -- ls_c has no cls_corr).
-struct PairLayout {
-    int P_MAX, B, VT;
-    struct Ptrs { int *ref_view, *aug_view, *aug_kind, *pair_img, *ref_sel, *ref_n, *view_img, *view_isref; };
-    size_t n_ints() const { return (size_t)P_MAX * 4 + (size_t)B * 51 + (size_t)VT * 2; }
-    Ptrs at(int* base) const {
-        Ptrs p;
-        p.ref_view = base; p.aug_view = p.ref_view + P_MAX; p.aug_kind = p.aug_view + P_MAX; p.pair_img = p.aug_kind + P_MAX;
-        p.ref_sel = p.pair_img + P_MAX; p.ref_n = p.ref_sel + (size_t)B * 50; p.view_img = p.ref_n + B; p.view_isref = p.view_img + VT;
-        return p;
-    }
-    // the scoring kernels' arguments over the device copy of the block
-    ScoreArgs score_args(int* d_base, const DetBuffers& D, const float* d_par, int P, float bp, float* cons) const {
-        const Ptrs p = at(d_base);
-        ScoreArgs sa; sa.det = D;
-        sa.ref_view = p.ref_view; sa.aug_view = p.aug_view; sa.aug_kind = p.aug_kind; sa.pair_img = p.pair_img;
-        sa.ref_sel = p.ref_sel; sa.ref_n = p.ref_n; sa.aug_param = d_par; sa.P = P; sa.bp = bp; sa.cons = cons;
-        return sa;
-    }
-};
-
 // =============================================================================================
 // the sweep (get_uncertainty, cald_train.py:91-231)
 // =============================================================================================
@@ -390,7 +368,7 @@ struct SweepRun {
                 const int kd = cfg->augs[a].kind; const double prm = cfg->augs[a].param;
                 float par[12] = {0};
                 cur_a = a;
-                if (kd == CALD_AUG_FLIP) { ViewDesc v = base; v.flip = 1; par[0] = (float)Wi; add_view(v, 1, par); }
+                if (kd == CALD_AUG_FLIP) { ViewDesc v = base; v.flip = 1; pair_params(1, Hi, Wi, prm, par); add_view(v, 1, par); }
                 else if (kd == CALD_AUG_GAUSS) {            // image + torch.randn(size) * std / 255.0
                     NoiseSeg& sg = nj.seg[nj.nseg++]; sg.kind = 0; sg.p0 = (float)prm; sg.p1 = 0.0f;
                     sg.dst = take((size_t)Hi * Wi * 3 * sizeof(float));
@@ -415,14 +393,14 @@ struct SweepRun {
                     const int ow = (int)((double)Wi * prm), oh = (int)((double)Hi * prm);
                     uint8_t* dst = take((size_t)oh * ow * 3); uint8_t* tmp = take((size_t)Hi * ow * 3);
                     if ((r = pil_resize(c, images_dev[i0 + i], Hi, Wi, dst, oh, ow, tmp, 0))) break;
-                    par[0] = (float)prm; add_view(plain_view(dst, oh, ow), 2, par);          // boxes * ratio: float32 tensor times the scalar
+                    pair_params(2, Hi, Wi, prm, par); add_view(plain_view(dst, oh, ow), 2, par);
                 } else if (kd == CALD_AUG_ROTATE) {
                     int fx[6], nh, nw; pil_rotate_setup(Hi, Wi, prm, fx, &nh, &nw);
                     uint8_t* rot = take((size_t)nh * nw * 3); uint8_t* tmp = take((size_t)nh * Wi * 3); uint8_t* dst = take((size_t)Hi * Wi * 3);
                     launch_affine_nearest(images_dev[i0 + i], Hi, Wi, rot, nh, nw, fx, c->stream);
                     if ((r = pil_resize(c, rot, nh, nw, dst, Hi, Wi, tmp, 1))) break;      // new_image.resize((w, h)): BICUBIC default
                     ViewDesc v = base; v.src = dst;
-                    rotate_box_params(Hi, Wi, prm, nw, nh, par);
+                    pair_params(3, Hi, Wi, prm, par);
                     add_view(v, 3, par);
                 }
             }
@@ -915,7 +893,7 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
         if (hipMemcpyAsync(h_count.data(), D.count, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(h_pm.data(), D.prob_max, (size_t)nb * cap * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "D2H of reference detections failed"); break; }
-        // host: top-30 by prob_max (value desc, index asc), noise jobs, views
+        // host: the scored reference boxes (host_logic.h ls_select), noise jobs, views
         std::vector<int> ref_sel((size_t)B * 50, 0), ref_n(B, 0), pair_aug, pair_img;
         std::vector<ViewDesc> aviews; std::vector<NoiseJob> gjobs;
         size_t need = 0;
@@ -926,14 +904,7 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
         for (int i = 0; i < nb; i++) {
             const int n = h_count[i];
             if (n == 0) continue;
-            const float* pm = &h_pm[(size_t)i * cap];
-            std::vector<int> idx(n); for (int k = 0; k < n; k++) idx[k] = k;
-            if (n > 30) {
-                std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return pm[x] > pm[y]; });
-                idx.resize(30);
-            }
-            ref_n[i] = (int)idx.size();
-            for (size_t k = 0; k < idx.size(); k++) ref_sel[(size_t)i * 50 + k] = idx[k];
+            ref_n[i] = ls_select(n, &h_pm[(size_t)i * cap], &ref_sel[(size_t)i * 50]);
             const int Hi = H[i0 + i], Wi = W[i0 + i], ne = Hi * Wi * 3;
             float* nbase = reinterpret_cast<float*>(reinterpret_cast<char*>(d_noise) + noff); noff += ((size_t)ne * A * 4 + 255) & ~(size_t)255;
             NoiseJob gj; memset(&gj, 0, sizeof(gj));
@@ -967,22 +938,16 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
         launch_max_iou(L.score_args(d_ints, D, d_par, P, 0.f, nullptr), d_rows, c->stream);
         if ((P && hipMemcpyAsync(h_rows.data(), d_rows, (size_t)P * 50 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
             hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "ls_c scoring failed: %s", hipGetErrorString(hipGetLastError())); break; }
-        // host: float64 / float32 numpy arithmetic of ls_c_train.py:151-153
+        // host: float64 / float32 numpy arithmetic of ls_c_train.py:151-153 (host_logic.h ls_tail)
         std::vector<std::vector<int>> img_pairs(nb);
         for (int p = 0; p < P; p++) img_pairs[pair_img[p]].push_back(p);
         for (int i = 0; i < nb; i++) {
             if (h_count[i] == 0) { stability_out[i0 + i] = 0.0; continue; }
             const int N = ref_n[i];
-            std::vector<float> pm(N); std::vector<double> st(N, 0.0), prod(N);
-            float U = 0.0f;
-            for (int k = 0; k < N; k++) {
-                pm[k] = h_pm[(size_t)i * cap + ref_sel[(size_t)i * 50 + k]];
-                const float u = 1.0f - pm[k];
-                if (k == 0 || u > U) U = u;
-            }
-            for (int p : img_pairs[i]) for (int k = 0; k < N; k++) st[k] += (double)h_rows[(size_t)p * 50 + k];
-            for (int k = 0; k < N; k++) { st[k] = st[k] / 6.0; prod[k] = (double)pm[k] * st[k]; }
-            stability_out[i0 + i] = np_sum(prod.data(), N) / (double)np_sum_f32(pm.data(), N) - (double)U;
+            std::vector<float> pm(N); std::vector<const float*> rows;
+            for (int k = 0; k < N; k++) pm[k] = h_pm[(size_t)i * cap + ref_sel[(size_t)i * 50 + k]];
+            for (int p : img_pairs[i]) rows.push_back(&h_rows[(size_t)p * 50]);
+            stability_out[i0 + i] = ls_tail(N, pm.data(), (int)rows.size(), rows.data());
         }
     }
     hipStreamSynchronize(c->stream);

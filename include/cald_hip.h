@@ -319,6 +319,48 @@ int cald_op_consistency(cald_ctx* ctx, int N, const float* aug_box, const float*
                         float* consistency_out);
 /* cald_train.py:114-117 */
 int cald_op_cls_corr(cald_ctx* ctx, int n, const float* scores, const int64_t* labels, int C, float* out);
+/* The scoring stage of ONE sweep batch in the sweeps' own layout, on the sweeps' own table filling and launches (score.hip's five
+ * kernels in one call); host arrays in, host arrays out.  V views of `cap` detection slots each (count[v] <= cap of them live), n_img
+ * images, P (reference view, augmented view) pairs.  Rejected with CALD_ERR_INVALID, nothing written: a null pointer, C outside 2..256,
+ * cap < 1, a count outside 0..cap, ref_n outside 0..50, a live ref_sel slot outside 0..cap - 1, a view or image index out of range, an
+ * aug_kind outside 0..3. */
+typedef struct cald_score_probe {
+    int V, cap, C, n_img, P;
+    float bp;
+    /* in, per view */
+    const float* boxes;        /* [V][cap][4] */
+    const float* props;        /* [V][cap][4] the proposal each detection stems from */
+    const float* scores;       /* [V][cap] */
+    const int64_t* labels;     /* [V][cap] */
+    const float* scores_cls;   /* [V][cap][C] */
+    const float* prob_max;     /* [V][cap] */
+    const int* count;          /* [V] */
+    const int* view_img;       /* [V] image of the view */
+    const int* view_isref;     /* [V] != 0: a reference view (cls_corr reads its sub-sampled detections only) */
+    /* in, per image */
+    const int* ref_sel;        /* [n_img][50] the scored detections of the image's reference view */
+    const int* ref_n;          /* [n_img] how many of the 50 slots are live */
+    /* in, per pair */
+    const int* ref_view;       /* [P] */
+    const int* aug_view;       /* [P] */
+    const int* pair_img;       /* [P] */
+    const int* aug_kind;       /* [P] 0 boxes unchanged, 1 flip, 2 resize, 3 rotate */
+    const float* aug_param;    /* [P][12] cald_op_pair_params */
+    /* out */
+    float* cons;               /* [P] consistency_kernel */
+    float* cls_corr;           /* [V][C - 1] cls_corr_kernel */
+    float* pair_audit;         /* [P][2] pair_audit_kernel: {argmax gap, zero-row flag} */
+    float* max_iou;            /* [P][50] max_iou_kernel (boxes NOT transformed, as in ls_c); slots from ref_n on are left as they are */
+    float* lt;                 /* [V] lt_uncertainty_kernel */
+} cald_score_probe;
+int cald_op_score_batch(cald_ctx* ctx, cald_score_probe* p);
+/* host only: the aug_param row the sweep gives the scoring kernels for a pair of an H x W image; kind as aug_kind above (1: param unused,
+ * 2: the ratio, 3: the angle in degrees; 0: zeros).  par12_out [12] */
+int cald_op_pair_params(int kind, int H, int W, double param, float* par12_out);
+/* host only: the host tail of cald_sweep_lsc.  prob_max [n] of the reference view's detections -> sel_out [30] / *n_sel_out, the scored
+ * boxes (all while n <= 30, else the top 30: value descending, index ascending).  score_out (NULL: selection only): the image's float64
+ * score from max_iou [n_rows][*n_sel_out], row r = the maximum IoUs of the selected boxes in noisy view r; n == 0 gives 0.0 */
+int cald_op_ls_tail(int n, const float* prob_max, int n_rows, const float* max_iou, int* sel_out, int* n_sel_out, double* score_out);
 /* ---- detection-to-ground-truth matching of the AP evaluators (eval.hip).  Host arrays in, host arrays out; IEEE double in the host
  * code's operation order, so every output equals what the Python statement gives.  A segment is one unit of the greedy matching; its
  * detections / ground truths are rows dt_off[s] .. dt_off[s + 1] - 1 / gt_off[s] .. gt_off[s + 1] - 1 of the flat arrays (offsets
