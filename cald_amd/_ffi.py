@@ -211,6 +211,8 @@ SIGNATURES = {
                                        + [C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_f, c_f, c_i8]),
     "cald_op_rpn_prune": (C.c_int, [C.c_void_p, C.POINTER(RpnPruneProbe)]),
     "cald_op_roi_align": (C.c_int, [C.c_void_p, C.POINTER(c_f), c_i, C.c_int, C.c_int, c_f, c_f]),
+    "cald_op_roi_align_views": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(c_f), c_i, c_i, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_uint32), c_i]),
     "cald_op_conv2d": (C.c_int, [C.c_void_p, c_f, C.c_int, C.c_int, C.c_int, c_f, C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_int, c_f, c_f, c_f, c_f, C.c_int, c_f]),
     "cald_op_conv_probe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(ConvProbe), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),

@@ -81,7 +81,7 @@ struct RoiArgs {
     int* order;              // [V][1024] scratch: the view's RoIs sorted by (pyramid level, row band, column) -- processing order only
     int out16;               // CALD_PRECISION_F16X3: store the split form conv_h3.hip consumes (one word per element) instead of fp32
 };
-void launch_roi_align(const RoiArgs& a, hipStream_t st);
+void launch_roi_align(const RoiArgs& a, hipStream_t st, int kernel = 0);     // kernel 1: the gather kernel at C == 256 too (cald_op_roi_align_views)
 
 // MultiScaleRoIAlign pieces shared by the inference kernel (roi.hip) and the training kernels (train_roi.hip)
 __device__ inline int roi_level(const float4 b) {

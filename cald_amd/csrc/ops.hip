@@ -801,6 +801,54 @@ extern "C" int cald_op_roi_align(cald_ctx* c, const float* const* feats, const i
     HIPCHK(hipMemcpy(out, S.roi, (size_t)R * 49 * C * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+// The same stage on V views at once, in the forward's own layout: the views' maps of a level share one buffer (BatchPlan::seg carries each
+// view's size and pixel offset), proposals and output rows have CALD_ROI_CAP slots a view.  feats[4 v + l] = host [H][W][C] of view v's
+// level l, level_hw [V][4][2], rois = the views' RoIs one after the other (counts[v] rows each).  out [V][rows_back][49][C] 32-bit words
+// goes up into the first rows_back rows of each view's slot before the launch and comes back after it, so rows from counts[v] on show
+// whether anything wrote them.  kernel 0: what the forward runs, 1: the gather kernel at any C.  order_out (optional) [V][1024].
+extern "C" int cald_op_roi_align_views(cald_ctx* c, int V, const float* const* feats, const int* level_hw, const int* counts, const float* rois,
+                                       int C, int out16, int kernel, int rows_back, uint32_t* out, int* order_out) {
+    if (!c || !feats || !level_hw || !counts || !rois || !out) return fail(CALD_ERR_INVALID, "null argument");
+    if (V < 1 || V > CALD_MAX_VIEWS || C < 4 || C > 1024 || C % 4 || (out16 && C % 16) || (out16 != 0 && out16 != 1) || (kernel != 0 && kernel != 1) ||
+        rows_back < 1 || rows_back > CALD_ROI_CAP)
+        return fail(CALD_ERR_INVALID, "bad geometry (1 <= V <= %d, C a multiple of 4 (16 in split form) up to 1024, out16 and kernel 0 or 1, 1 <= rows_back <= %d)",
+                    CALD_MAX_VIEWS, CALD_ROI_CAP);
+    BatchPlan P; memset(&P, 0, sizeof(P));
+    size_t total = 0;
+    for (int v = 0; v < V; v++) {
+        if (counts[v] < 0 || counts[v] > CALD_ROI_CAP) return fail(CALD_ERR_INVALID, "view %d: count %d outside 0..%d", v, counts[v], CALD_ROI_CAP);
+        total += (size_t)counts[v];
+        for (int l = 0; l < 4; l++) {
+            const int H = level_hw[(v * 4 + l) * 2], W = level_hw[(v * 4 + l) * 2 + 1];
+            if (H < 1 || W < 1 || (long long)H * W > (1 << 22) || !feats[v * 4 + l]) return fail(CALD_ERR_INVALID, "view %d: level %d is malformed", v, l);
+            P.seg[2 + l][v].H = H; P.seg[2 + l][v].W = W; P.seg[2 + l][v + 1].pix_off = P.seg[2 + l][v].pix_off + (long long)H * W;
+        }
+    }
+    for (size_t i = 0; i < total * 4; i++) if (!std::isfinite(rois[i])) return fail(CALD_ERR_INVALID, "RoI %zu has a non-finite coordinate", i / 4);
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream);
+    ProposalBufs pb; RoiBufs S; float* d_f[4]; BatchPlan* d_p; int rc;
+    if ((rc = carve(sd, [&](Bump& B) { for (int l = 0; l < 4; l++) d_f[l] = B.get<float>((size_t)level_pix(P, 2 + l, V) * C); d_p = B.get<BatchPlan>(1);
+                                       pb.layout(B, V); S.layout(B, V, C); }))) return rc;
+    HIPCHK(hipMemset(pb.proposals, 0, (size_t)V * CALD_ROI_CAP * 16));
+    const size_t row = (size_t)49 * C;
+    for (size_t v = 0, at = 0; v < (size_t)V; at += (size_t)counts[v], v++) {
+        if (counts[v]) HIPCHK(hipMemcpy(pb.proposals + v * CALD_ROI_CAP * 4, rois + at * 4, (size_t)counts[v] * 16, hipMemcpyHostToDevice));
+        for (int l = 0; l < 4; l++) {
+            const LevelSeg& sg = P.seg[2 + l][v];
+            HIPCHK(hipMemcpy(d_f[l] + (size_t)sg.pix_off * C, feats[v * 4 + l], (size_t)sg.H * sg.W * C * 4, hipMemcpyHostToDevice));
+        }
+        HIPCHK(hipMemcpy(S.roi + v * CALD_ROI_CAP * row, out + v * rows_back * row, (size_t)rows_back * row * 4, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(pb.prop_count, counts, (size_t)V * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_p, &P, sizeof(P), hipMemcpyHostToDevice));
+    launch_roi_align(roi_args(S, d_f, d_p, C, V, pb, out16 != 0), c->stream, kernel);
+    HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t v = 0; v < (size_t)V; v++)
+        HIPCHK(hipMemcpy(out + v * rows_back * row, S.roi + v * CALD_ROI_CAP * row, (size_t)rows_back * row * 4, hipMemcpyDeviceToHost));
+    if (order_out) HIPCHK(hipMemcpy(order_out, S.order, (size_t)V * 1024 * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 extern "C" int cald_op_cls_corr(cald_ctx* c, int n, const float* scores, const int64_t* labels, int C, float* out) {
     if (!c || !out || n < 0 || C < 2 || C > 256) return fail(CALD_ERR_INVALID, "bad arguments");

@@ -222,10 +222,10 @@ __global__ __launch_bounds__(448, 4) void roi_align_rows_kernel(RoiArgs a) {
     else if (r2 == r1) roi_rows_walk<1>(f, Wf, sx, s_wt, Y0, Y1, ph, q, out, a.out16 != 0);
     else roi_rows_walk<0>(f, Wf, sx, s_wt, Y0, Y1, ph, q, out, a.out16 != 0);
 }
-void launch_roi_align(const RoiArgs& a, hipStream_t st) {
+void launch_roi_align(const RoiArgs& a, hipStream_t st, int kernel) {
     static const bool rows = !(getenv("CALD_ROI_ROWS") && atoi(getenv("CALD_ROI_ROWS")) == 0);
     hipLaunchKernelGGL(roi_order_kernel, dim3(a.V), dim3(1024), 0, st, a);
-    if (rows && a.C == 256) hipLaunchKernelGGL(roi_align_rows_kernel, dim3(8 * ((a.V + 7) / 8) * CALD_ROI_CAP), dim3(448), 0, st, a);
+    if (rows && kernel == 0 && a.C == 256) hipLaunchKernelGGL(roi_align_rows_kernel, dim3(8 * ((a.V + 7) / 8) * CALD_ROI_CAP), dim3(448), 0, st, a);
     else hipLaunchKernelGGL(roi_align_kernel, dim3(8 * ((a.V + 7) / 8) * CALD_ROI_CAP), dim3(256), 0, st, a);
 }
 

@@ -491,6 +491,17 @@ int cald_op_rpn_prune(cald_ctx* ctx, cald_rpn_prune_probe* p);
 /* MultiScaleRoIAlign(output 7, sampling_ratio 2, aligned=False; detection/frcnn_la.py:205-209) of one view on the forward's own
  * kernels: feats[l] = [H_l][W_l][C] (host) for P2..P5, level_hw = {H0, W0, ..., H3, W3}, rois [R][4]; out [R][49][C] (host) */
 int cald_op_roi_align(cald_ctx* ctx, const float* const* feats, const int* level_hw, int C, int R, const float* rois, float* out);
+/* The same stage on V views (1..CALD_MAX_VIEWS = 128) in the forward's own layout: one buffer a level with the views' maps one after the
+ * other, 1000 proposal slots and 1000 output rows a view.  feats[4 v + l] = [H][W][C] (host) of view v's level l, level_hw [V][4][2]
+ * (views may differ), counts [V] in 0..1000, rois = the views' RoIs one after the other ([sum counts][4], finite).  C a multiple of 4
+ * up to 1024 (of 16 when out16).  out16 1: the rows in split form (one 32-bit word an element: per 16 channels 16 fp16 hi, then 16 fp16
+ * lo of 16 x).  kernel 0: what the forward runs (the row walk at C == 256 unless CALD_ROI_ROWS=0), 1: the gather kernel.  out
+ * [V][rows_back][49][C] words (1 <= rows_back <= 1000), in AND out: uploaded into the first rows_back rows of each view's slot before
+ * the launch, downloaded after it -- rows from counts[v] on come back as they went.  order_out (NULL or [V][1024]): the processing
+ * order of each view, its first counts[v] entries a permutation of the view's RoIs.  Rejected with CALD_ERR_INVALID, nothing written:
+ * a null pointer, a size, count or flag out of range, a non-finite RoI. */
+int cald_op_roi_align_views(cald_ctx* ctx, int V, const float* const* feats, const int* level_hw, const int* counts, const float* rois,
+                            int C, int out16, int kernel, int rows_back, uint32_t* out, int* order_out);
 /* NHWC convolution on the MFMA kernel; weights in torch layout [Cout][Cin][KH][KW] (host) */
 int cald_op_conv2d(cald_ctx* ctx, const float* in, int H, int W, int Cin, const float* weight, int Cout, int KH, int KW,
                    int stride, int pad, const float* bias, const float* bn_scale, const float* bn_shift,
