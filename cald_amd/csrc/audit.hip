@@ -1,4 +1,5 @@
-// audit.hip -- decision margins of one Faster R-CNN forward (cald_sweep_audit; the cascade of DESIGN.md section 6b).
+// audit.hip -- decision margins of one forward (cald_sweep_audit; the cascade of DESIGN.md section 6b): Faster R-CNN first, RetinaNet's
+// tail (its own set of decisions) at the end of the file.
 //
 // The sweep's result is a continuous function of the GEMM outputs EXCEPT at its discrete decisions: the per-level top-k cut and the
 // NMS of the RPN (detection/frcnn_ll.py:284-321), the post-NMS top-n, the RoI level mapper and RoIAlign's border rule
@@ -135,7 +136,6 @@ __global__ __launch_bounds__(256) void audit_roi_kernel(AuditArgs a) {
 // ---------------------------------------------------------------------------------------------
 // postprocess_detections: grid V, block 256.
 // ---------------------------------------------------------------------------------------------
-#define AUDIT_MAX_DET 512
 __device__ __forceinline__ float4 audit_cand_box(const AuditArgs& a, int v, int r, int c, float Wr, float Hr, float maxc) {
     const float4 p = reinterpret_cast<const float4*>(a.proposals)[(long long)v * CALD_ROI_CAP + r];
     const float pb[4] = {p.x, p.y, p.z, p.w};
@@ -218,7 +218,163 @@ __global__ __launch_bounds__(256) void audit_post_kernel(AuditArgs a) {
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// RetinaNet.postprocess_detections (retina.hip; detection/retinanet_cal.py:402-490): grid (K classes, V), block 256, like the tail's NMS
+// kernel.  The decisions are per class: `>` at the score threshold over all anchors, remove_small_boxes(1e-2), one NMS, the first
+// per_class survivors; the output list is the classes' lists one after the other.  The workgroup holds its class's kept detections
+// (<= per_class <= AUDIT_MAX_DET, in the tail's order) in LDS and walks ALL anchors of the view: only an anchor above the threshold or
+// within 1e-3 of it is decoded, and compared by a whole wavefront.  "i precedes j" is the tail's sort order -- key orderable(score) << 32 | ~anchor, descending:
+// the higher score, on equal scores the lower anchor index -- so nothing here depends on where the tail sorted.
+//   VM_POST_THR    |s - thr| < 1e-3, unless the class is full (a score at the threshold ranks last and is cut), the box is small, or another
+//                  kept detection of the class covers the box with IoU > nms_thr + 0.01 (it is suppressed on either side of the threshold)
+//   VM_POST_SMALL  min(|w - min_box|, |h - min_box|) over every anchor above the threshold
+//   VM_POST_CAP    class full: last kept score - score, over the candidates (above the threshold, not small) behind the last kept one
+//   VM_POST_IOU    every other candidate: |mx - nms_thr|, mx its largest IoU with the kept boxes that precede it (0 if none does)
+//   VM_POST_ORDER  ... and for each of those with IoU > nms_thr: its score - the candidate's (had the candidate ranked first, it would suppress)
+//   VM_POST_TOP2   scores[0] - scores[1] of the view's list when both rows are of one class: this workgroup's, if no lower class kept a box
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float retina_score(const RetinaArgs& a, int v, int i, int k) {
+    int li;
+    const int l = retina_level_of(a, v, i, &li);
+    const LevelSeg sg = a.seg[l][v];
+    const int pix = li / a.A, an = li - pix * a.A;
+    return det_sigmoidf(a.cls[l][(sg.pix_off + pix) * (long long)a.cls_ld + an * a.K + k]);
+}
+__device__ __forceinline__ int retina_kept(const RetinaArgs& a, long long slot) {
+    int nk = a.kept_count[slot];
+    if (nk > a.per_class) nk = a.per_class;
+    return nk > AUDIT_MAX_DET ? AUDIT_MAX_DET : (nk < 0 ? 0 : nk);
+}
+__global__ __launch_bounds__(256) void audit_retina_kernel(RetinaArgs a, float* vm) {
+    __shared__ float4 kb[AUDIT_MAX_DET];
+    __shared__ float ks[AUDIT_MAX_DET];
+    __shared__ int ka[AUDIT_MAX_DET];
+    const int k = blockIdx.x, v = blockIdx.y, tid = threadIdx.x, per = a.per_class;
+    const long long slot = (long long)v * a.K + k;
+    float* out = vm + (long long)v * CALD_VM;
+    const int nk = retina_kept(a, slot);
+    const bool full = nk >= per;
+    int total = 0;
+#pragma unroll
+    for (int t = 0; t < 5; t++) total += a.seg[t][v].H * a.seg[t][v].W * a.A;
+    for (int i = tid; i < nk; i += 256) {
+        const int ai = a.kept_anchor[slot * per + i];
+        ka[i] = ai; kb[i] = reinterpret_cast<const float4*>(a.kept_box)[slot * per + i];
+        ks[i] = (ai >= 0 && ai < total) ? retina_score(a, v, ai, k) : NAN;
+    }
+    __syncthreads();
+    const ViewDesc vd = a.views[v];
+    const float Wr = (float)vd.Wr, Hr = (float)vd.Hr;
+    const float s_last = nk > 0 ? ks[nk - 1] : 0.0f;
+    const int a_last = nk > 0 ? ka[nk - 1] : 0;
+    float m_thr = INFINITY, m_small = INFINITY, m_iou = INFINITY, m_ord = INFINITY, m_cap = INFINITY;
+    // A wavefront scans 64 anchors, one per lane; the few that have something to compare (above the threshold or inside its window, not
+    // small) are then taken one at a time by the WHOLE wavefront, 64 kept boxes per step -- a lane walking its own anchor's kept list
+    // would leave the other 63 idle.  Everything below is a min or a max: the order the lanes contribute in does not show.
+    const int lane = tid & 63;
+    const float cover = a.nms_thr + 0.01f;
+    for (int i0 = (tid >> 6) * 64; i0 < total; i0 += 256) {
+        const int i = i0 + lane;
+        float s = 0.0f, d = 0.0f; float4 b = make_float4(0.0f, 0.0f, 0.0f, 0.0f); int what = 0;      // 1: above the threshold, 2: in the window
+        if (i < total) {
+            s = retina_score(a, v, i, k);
+            d = fabsf(s - a.score_thr);
+            what = (s > a.score_thr ? 1 : 0) | (d < 1e-3f ? 2 : 0);
+            if (what) {
+                b = retina_decode(a, v, i, Wr, Hr);
+                const float w = b.z - b.x, h = b.w - b.y;
+                if (what & 1) m_small = fminf(m_small, fminf(fabsf(w - a.min_box), fabsf(h - a.min_box)));
+                if (!(w >= a.min_box && h >= a.min_box)) what = 0;                                  // a small box takes no part in anything else
+            }
+        }
+        unsigned long long todo = __ballot(what != 0);
+        while (todo) {
+            const int src = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const int hi = i0 + src, hw = __shfl(what, src, 64);
+            const float hs = __shfl(s, src, 64), hd = __shfl(d, src, 64);
+            const float4 hb = make_float4(__shfl(b.x, src, 64), __shfl(b.y, src, 64), __shfl(b.z, src, 64), __shfl(b.w, src, 64));
+            const bool behind = (hw & 1) && full && (s_last > hs || (s_last == hs && a_last < hi));     // behind the class's cut
+            const bool thr = (hw & 2) && !full, nms = (hw & 1) && !behind;
+            if (behind) m_cap = fminf(m_cap, s_last - hs);
+            if (!thr && !nms) continue;
+            bool covered = false; float mx = 0.0f;
+            for (int j = lane; j < nk; j += 64) {
+                const float iou = nms_iou(kb[j], hb);
+                if (thr && ka[j] != hi && iou > cover) covered = true;
+                if (nms && (ks[j] > hs || (ks[j] == hs && ka[j] < hi))) {                              // kept entry j precedes the candidate
+                    if (iou > mx) mx = iou;
+                    if (iou > a.nms_thr) m_ord = fminf(m_ord, ks[j] - hs);
+                }
+            }
+            if (thr && __ballot(covered) == 0ull) m_thr = fminf(m_thr, hd);
+            if (nms) {
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+                m_iou = fminf(m_iou, fabsf(mx - a.nms_thr));
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        m_thr = fminf(m_thr, __shfl_xor(m_thr, o, 64)); m_small = fminf(m_small, __shfl_xor(m_small, o, 64)); m_iou = fminf(m_iou, __shfl_xor(m_iou, o, 64));
+        m_ord = fminf(m_ord, __shfl_xor(m_ord, o, 64)); m_cap = fminf(m_cap, __shfl_xor(m_cap, o, 64));
+    }
+    if (lane == 0) {
+        if (m_thr < INFINITY) upd(out + VM_POST_THR, m_thr);
+        if (m_small < INFINITY) upd(out + VM_POST_SMALL, m_small);
+        if (m_iou < INFINITY) upd(out + VM_POST_IOU, m_iou);
+        if (m_ord < INFINITY) upd(out + VM_POST_ORDER, m_ord);
+        if (m_cap < INFINITY) upd(out + VM_POST_CAP, m_cap);
+    }
+    if (tid == 0 && nk >= 2) {
+        bool first = true;
+        for (int q = 0; q < k && first; q++) first = retina_kept(a, (long long)v * a.K + q) == 0;
+        if (first) upd(out + VM_POST_TOP2, ks[0] - ks[1]);
+    }
+}
+// VM_POST_SUBORDER of a RetinaNet view: grid V, one wavefront.  Were this a reference view with more than 40 detections,
+// np.round(np.linspace(0, n - 1, 50)) picks 50 rows of its list; inside a class the rows are in score order, so a neighbour pair of one class
+// of which exactly one is picked swaps at a score tie.  Across a class boundary the order is fixed by the class index: no record.
+__global__ __launch_bounds__(64) void audit_retina_suborder_kernel(RetinaArgs a, float* vm) {
+    __shared__ int pk[50];
+    const int v = blockIdx.x, t = threadIdx.x, K = a.K;
+    int n = 0;
+    for (int q = 0; q < K; q++) n += retina_kept(a, (long long)v * K + q);
+    if (n <= 40) return;
+    const double step = (double)(n - 1) / 49.0;
+    if (t < 50) pk[t] = t == 49 ? n - 1 : (int)nearbyint((double)t * step);
+    __syncthreads();
+    float m = INFINITY;
+    if (t < 50) {
+        const int r = pk[t];
+        for (int d = -1; d <= 1; d += 2) {
+            const int nb = r + d;
+            if (nb < 0 || nb >= n) continue;
+            bool picked = false;
+            for (int u = 0; u < 50; u++) picked |= pk[u] == nb;
+            if (picked) continue;
+            const int lo = d < 0 ? nb : r;                      // rows lo, lo + 1
+            int q = 0, off = 0, cnt = retina_kept(a, (long long)v * K);
+            while (lo >= off + cnt && q + 1 < K) { off += cnt; q++; cnt = retina_kept(a, (long long)v * K + q); }
+            if (lo + 1 >= off + cnt) continue;                  // the pair straddles a class boundary
+            const int* an = a.kept_anchor + ((long long)v * K + q) * a.per_class + (lo - off);
+            m = fminf(m, retina_score(a, v, an[0], q) - retina_score(a, v, an[1], q));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fminf(m, __shfl_xor(m, o, 64));
+    if (t == 0 && m < INFINITY) upd(vm + (long long)v * CALD_VM + VM_POST_SUBORDER, m);
+}
 }   // namespace
+
+void launch_audit_retina(const RetinaArgs& a, float* out, hipStream_t st) {      // callers guarantee per_class <= AUDIT_MAX_DET; after launch_retina_postprocess
+    const int n = a.V * CALD_VM;
+    hipLaunchKernelGGL(audit_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, st, out, n);
+    hipLaunchKernelGGL(audit_retina_kernel, dim3(a.K, a.V), dim3(256), 0, st, a, out);
+    hipLaunchKernelGGL(audit_retina_suborder_kernel, dim3(a.V), dim3(64), 0, st, a, out);
+}
 
 void launch_audit(const AuditArgs& a, hipStream_t st) {      // callers guarantee pre_n <= 1024 and det cap <= AUDIT_MAX_DET
     const int n = a.V * CALD_VM;

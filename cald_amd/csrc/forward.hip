@@ -450,8 +450,10 @@ struct ForwardRun {
         retina = m->cfg.arch == CALD_ARCH_RETINANET;
         prune = m->prune && prune_ok;
         if (audit_out && m->box_min_size > 0.0f) return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit does not cover small-box removal (box_min_size > 0)");
-        if (audit_out && (retina || m->cfg.rpn_pre_nms_top_n > 1024 || m->det_cap() > 512))
-            return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit covers Faster R-CNN with rpn_pre_nms_top_n <= 1024 and <= 512 detections per image");
+        if (audit_out && retina && m->cfg.detections_per_img > AUDIT_MAX_DET)
+            return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit holds a class's detections in LDS: RetinaNet with detections_per_img <= %d (AUDIT_MAX_DET)", AUDIT_MAX_DET);
+        if (audit_out && !retina && (m->cfg.rpn_pre_nms_top_n > 1024 || m->det_cap() > AUDIT_MAX_DET))
+            return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit covers Faster R-CNN with rpn_pre_nms_top_n <= 1024 and <= %d detections per image", AUDIT_MAX_DET);
         build_plan(m->plan, V, views, hp, retina);
         m->last_V = V; m->last_views.assign(views, views + V);
         for (int v = 0; v < V; v++) {
@@ -564,8 +566,10 @@ struct ForwardRun {
             m->dbg["reg" + std::to_string(i)] = {Fr.reg_h[i], 3 + i, 36, 0};
         }
         if (rssm) return retina_ssm_tail();
-        launch_retina_postprocess(retina_args(Fr.tail, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
-                                              m->cfg.box_nms_thresh, m->cfg.detections_per_img, det), Fr.tail.max_anchors, st);
+        const RetinaArgs ra = retina_args(Fr.tail, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
+                                          m->cfg.box_nms_thresh, m->cfg.detections_per_img, det);
+        launch_retina_postprocess(ra, Fr.tail.max_anchors, st);
+        if (audit_out) launch_audit_retina(ra, audit_out, st);
         return 0;
     }
     // the SSM tail (retina_ssm.hip) on the same head tensors: phase A, the host stop for the picks, phase B

@@ -198,12 +198,14 @@ struct RpnPruneArgs {
 void launch_rpn_prune_select(const RpnPruneArgs& a, int max_pix, int stage, hipStream_t st);   // stage 0, then -- after stage 0's exact rows exist -- stage 1
 void launch_rpn_prune_scatter(const RpnPruneArgs& a, int max_pix, hipStream_t st);
 
-// audit.hip -- decision margins of one Faster R-CNN forward (cascade mode: which images may differ from the exact mode by more than
+// audit.hip -- decision margins of one forward (cascade mode: which images may differ from the exact mode by more than
 // continuous rounding).  Every discrete decision of the forward (top-k cut, NMS IoU test, score threshold, RoI level, sort
-// order where the order matters) leaves its distance to the flip point; a view's record keeps the minimum per kind.
+// order where the order matters) leaves its distance to the flip point; a view's record keeps the minimum per kind.  A RetinaNet view
+// fills the VM_POST_* slots only (launch_audit_retina, declared after RetinaArgs); VM_POST_SMALL is its remove_small_boxes.
 #define CALD_VM 16
+#define AUDIT_MAX_DET 512      // kept detections an audit workgroup holds in LDS: per view (Faster R-CNN), per class and view (RetinaNet)
 enum { VM_RPN_TOPK = 0, VM_RPN_IOU, VM_RPN_ORDER, VM_RPN_TRUNC, VM_RPN_SMALL, VM_ROI_LEVEL, VM_ROI_EDGE, VM_POST_THR, VM_POST_IOU,
-       VM_POST_ORDER, VM_POST_CAP, VM_POST_SUBORDER, VM_POST_TOP2 };
+       VM_POST_ORDER, VM_POST_CAP, VM_POST_SUBORDER, VM_POST_TOP2, VM_POST_SMALL };
 struct AuditArgs {
     // RPN stage (buffers of launch_rpn)
     const unsigned long long* cand_key; const float* cand_box; const float* sorted_box; const unsigned char* flags;
@@ -247,6 +249,8 @@ struct RetinaArgs {
     DetBuffers det;               // cap >= K * per_class
 };
 void launch_retina_postprocess(const RetinaArgs& a, int max_anchors, hipStream_t st);
+// audit.hip: the decision margins of the tail just run on `a` (it only reads), out [V][CALD_VM]; needs per_class <= AUDIT_MAX_DET
+void launch_audit_retina(const RetinaArgs& a, float* out, hipStream_t st);
 // anchor index -> pyramid level and the index inside it; the decoded, clipped box of an anchor (weights 1, 1, 1, 1): shared by the stock
 // tail (retina.hip) and the SSM tail (retina_ssm.hip)
 __device__ inline int retina_level_of(const RetinaArgs& a, int v, int i, int* local) {

@@ -657,6 +657,35 @@ extern "C" int cald_op_retina_postprocess(cald_ctx* c, const float* const* cls, 
     return download_dets(c, det.d, "retina", boxes_out, scores_out, labels_out, nullptr, prob_max_out, scores_cls_out, n_out);
 }
 
+// The stock tail of ONE view as above, then the view's decision margins (audit.hip launch_audit_retina) in the public CALD_MARGIN_* numbering.
+extern "C" int cald_op_retina_audit(cald_ctx* c, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                                    const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                                    float score_thr, float nms_thr, int per_class, int* n_out, float* margins_out) {
+    if (!c || !cls || !reg || !level_hw || !base_anchors || !n_out || !margins_out) return fail(CALD_ERR_INVALID, "null argument");
+    RetinaHookIn in; int rc;
+    if ((rc = in.check(cls, reg, level_hw, A, K, Hp, Wp, Hr, Wr, Ho, Wo, per_class))) return rc;
+    if (per_class > AUDIT_MAX_DET) return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit holds a class's detections in LDS: per_class <= %d (AUDIT_MAX_DET)", AUDIT_MAX_DET);
+    HIPCHK(hipSetDevice(c->device));
+    ScopedDev sd(c->stream); ScopedDet det;
+    RetinaTailBufs S; float* d_vm = nullptr;
+    if ((rc = carve(sd, [&](Bump& B) { in.layout(B, A, K); S.layout(B, 1, K, per_class, (int)in.anchors); d_vm = B.get<float>(CALD_VM); })) ||
+        (rc = det.alloc(1, K * per_class, K)) || (rc = in.upload(cls, reg, base_anchors, A, K))) return rc;
+    const RetinaArgs ra = retina_args(S, in.d_cls, in.d_reg, in.d_p, in.d_vd, in.d_base, A, K, 1, score_thr, nms_thr, per_class, det.d);
+    launch_retina_postprocess(ra, S.max_anchors, c->stream);
+    launch_audit_retina(ra, d_vm, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    float vm[CALD_VM];
+    HIPCHK(hipMemcpy(vm, d_vm, sizeof(vm), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_out, det.d.count, sizeof(int), hipMemcpyDeviceToHost));
+    for (int q = 0; q < CALD_N_MARGINS; q++) margins_out[q] = INFINITY;
+    for (int q = VM_POST_THR; q <= VM_POST_CAP; q++) margins_out[q] = vm[q];
+    margins_out[CALD_MARGIN_POST_SMALL] = vm[VM_POST_SMALL];
+    margins_out[CALD_MARGIN_REF_SUBSAMPLE] = vm[VM_POST_SUBORDER];
+    margins_out[CALD_MARGIN_ZERO_ROW] = vm[VM_POST_TOP2];
+    return 0;
+}
+
 // RetinaNet.ssm_postprocess_detections + the stock transform.postprocess of ONE view on the kernels of the SSM forward (retina_ssm.hip), through
 // the forward's own RetinaSsmBufs::layout, retina_ssm_args and host stop.  Parity hook for detection/retina_ssm.py:487-584.
 extern "C" int cald_op_retina_ssm_postprocess(cald_ctx* c, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,

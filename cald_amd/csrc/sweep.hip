@@ -586,7 +586,11 @@ struct SweepRun {
         launch_consistency(sa, c->stream);
         launch_cls_corr(D, dp.ref_sel, dp.ref_n, dp.view_img, dp.view_isref, VV, d_clsc, c->stream);
         if (audit) {
-            launch_pair_audit(sa, d_pm, c->stream);
+            // RetinaNet rows carry no proposal: "another proposal" reads "another box" -- the detections of one anchor (one per class above
+            // the threshold) share box, scores_cls and prob_max, as those of one proposal do
+            ScoreArgs pa = sa;
+            if (retina) pa.det.props = pa.det.boxes;
+            launch_pair_audit(pa, d_pm, c->stream);
             if (hipMemcpyAsync(b.h_vm, d_vm[k & 1], (size_t)VV * CALD_VM * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                 (P && hipMemcpyAsync(b.h_pm, d_pm, (size_t)P * 2 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return fail(CALD_ERR_HIP, "D2H of the audit records failed");
         }
@@ -626,7 +630,11 @@ struct SweepRun {
             for (int i = 0; i < nb; i++) {
                 float* mg = margins_out + (size_t)(b.i0 + i) * CALD_N_MARGINS;
                 for (int q = 0; q < CALD_N_MARGINS; q++) mg[q] = INFINITY;
-                auto take_view = [&](int v) { for (int q = 0; q <= VM_POST_CAP; q++) { const float t = b.h_vm[(size_t)v * CALD_VM + q]; if (t < mg[q]) mg[q] = t; } };
+                auto take_view = [&](int v) {
+                    for (int q = 0; q <= VM_POST_CAP; q++) { const float t = b.h_vm[(size_t)v * CALD_VM + q]; if (t < mg[q]) mg[q] = t; }
+                    const float t = b.h_vm[(size_t)v * CALD_VM + VM_POST_SMALL];        // RetinaNet's remove_small_boxes; +inf on a Faster R-CNN view
+                    if (t < mg[CALD_MARGIN_POST_SMALL]) mg[CALD_MARGIN_POST_SMALL] = t;
+                };
                 take_view(i);
                 for (int v : img_views[i]) take_view(v);
                 mg[CALD_MARGIN_REF_SUBSAMPLE] = b.h_vm[(size_t)i * CALD_VM + VM_POST_SUBORDER];

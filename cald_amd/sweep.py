@@ -80,7 +80,8 @@ def _to_u8_cuda(image, device):
 
 def sweep_device_images(task_model, images, positions, augs, bp=1.3, base_seed=0, batch_images=64, margins=False):
     """Scores uint8 HWC CUDA tensors already resident in HBM.  Returns (consistency [n] f64, cls_corr [n][C-1] f64); with
-    margins=True also the decision-margin records [n][N_MARGINS] float32 of cald_sweep_audit (include/cald_hip.h)."""
+    margins=True also the decision-margin records [n][N_MARGINS] float32 of cald_sweep_audit (include/cald_hip.h), for a Faster R-CNN
+    and for a RetinaNet; _ffi.MARGIN_NOISE_F16X3 / MARGIN_NOISE_F16X3_RETINA give the f16x3 rounding noise on each margin's scale."""
     for aug in augs:
         if aug not in KNOWN_AUGS:
             print('{} is not in the pre-set augmentations!'.format(aug))   # cald_train.py:92-95

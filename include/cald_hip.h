@@ -162,7 +162,10 @@ int cald_sweep(cald_model* m, int n_images, const uint8_t* const* images_dev, co
  * [n_images][CALD_N_MARGINS] receives, per image and per kind of decision, the smallest distance of any decision THAT CAN REACH THE
  * OUTPUT to its flip point, over all views of the image (+inf where the kind did not occur).  An image whose margins all exceed the
  * rounding noise of a faster precision took the same decisions there as in CALD_PRECISION_FP32, and its scores differ by rounding
- * only; the others are re-scored exactly (cald_amd/sweep.py get_uncertainty_cascade, cald_cascade_plan).  Faster R-CNN only. */
+ * only; the others are re-scored exactly (cald_amd/sweep.py get_uncertainty_cascade, cald_cascade_plan).  Both detectors: a RetinaNet
+ * (detection/retinanet_cal.py:402-490: per-class threshold, remove_small_boxes, per-class NMS and cap, output in class order) leaves the RPN
+ * and RoI kinds at +inf, a Faster R-CNN leaves POST_SMALL there.  CALD_ERR_UNSUPPORTED: Faster R-CNN with rpn_pre_nms_top_n > 1024, more
+ * than 512 detections per image or box_min_size > 0; RetinaNet with detections_per_img (per class) > 512. */
 #define CALD_N_MARGINS 16
 #define CALD_MARGIN_RPN_TOPK 0       /* logit: k-th vs (k+1)-th objectness of a level's top-k cut */
 #define CALD_MARGIN_RPN_IOU 1        /* IoU:   |max IoU with the kept boxes before it - rpn_nms_thresh| */
@@ -179,6 +182,7 @@ int cald_sweep(cald_model* m, int n_images, const uint8_t* const* images_dev, co
 #define CALD_MARGIN_ARGMAX 12        /* IoU:   best vs best-of-another-proposal in a reference box's IoU row */
 #define CALD_MARGIN_ZERO_ROW 13      /* prob:  score gap of an augmented view's first two detections when a row is all zero */
 #define CALD_MARGIN_CUTOUT 14        /* ratio: |largest overlap ratio - 0.4 or 0.1| of a cutout trial */
+#define CALD_MARGIN_POST_SMALL 15    /* pixel: |w or h - 1e-2| of a decoded, clipped RetinaNet candidate (remove_small_boxes) */
 int cald_sweep_audit(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                      const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out,
                      float* margins_out);
@@ -453,6 +457,13 @@ int cald_op_retina_postprocess(cald_ctx* ctx, const float* const* cls, const flo
                                float score_thr, float nms_thr, int per_class,
                                float* boxes_out, float* scores_out, int64_t* labels_out, float* prob_max_out,
                                float* scores_cls_out, int* n_out);
+/* The stock RetinaNet tail of one view as in cald_op_retina_postprocess (same inputs), then the decision-margin audit of that view
+ * (audit.hip audit_retina_kernel): *n_out = the number of detections, margins_out [CALD_N_MARGINS] = the view's records in the public
+ * numbering -- POST_THR / POST_IOU / POST_ORDER / POST_CAP (7-10) and POST_SMALL (15); REF_SUBSAMPLE (11) as if the view were a reference
+ * view; ZERO_ROW (13) = the gap of the list's first two rows when they are of one class; +inf everywhere else.  per_class <= 512. */
+int cald_op_retina_audit(cald_ctx* ctx, const float* const* cls, const float* const* reg, const int* level_hw, int A, int K,
+                         const float* base_anchors, int Hp, int Wp, int Hr, int Wr, int Ho, int Wo,
+                         float score_thr, float nms_thr, int per_class, int* n_out, float* margins_out);
 /* RetinaNet.ssm_postprocess_detections + the stock transform.postprocess of one view (detection/retina_ssm.py:487-584) on the SSM forward's
  * own kernels (retina_ssm.hip); inputs as for cald_op_retina_postprocess, K >= 2.  *al_out = 1 when the largest score over all K classes
  * is < 0.5: no rows, counts_out zero, `pick` not called.  Else counts_out[k] = anchors with score[k] > score_thr, `pick` is called once
