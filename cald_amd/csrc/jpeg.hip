@@ -5,6 +5,9 @@
 // The decoder follows libjpeg(-turbo)'s defaults, which is what Pillow runs: ITU T.81 Huffman decoding,
 // the 13-bit fixed-point LL&M inverse DCT (JDCT_ISLOW), triangle-filter ("fancy") chroma upsampling and the
 // 16-bit fixed-point YCbCr->RGB conversion.  All integer arithmetic: results are bit-identical to Pillow's.
+// One exception, outside the promise: a file whose dequantised values (coefficient x quantiser) do not fit int16.
+// libjpeg-turbo's SIMD inverse DCT saturates its 16-bit intermediates there; this decoder computes in 32 bits.  No
+// encoder produces such a file from 8-bit samples.  IDCT outputs that leave the sample range saturate, as turbo's do.
 //
 // Mapping onto the GPU
 //   host     : marker parsing only (a few hundred bytes per file); the entropy-coded bytes are copied verbatim
@@ -656,12 +659,11 @@ JHD void idct8(const int in[8], int out[8], int shift) {
     out[2] = jdescale(t12 + t1, shift); out[5] = jdescale(t12 - t1, shift);
     out[3] = jdescale(t13 + t0, shift); out[4] = jdescale(t13 - t0, shift);
 }
-JHD unsigned range_limit_idct(int x) {   // sample_range_limit + CENTERJSAMPLE, index masked to 10 bits
-    x &= 1023;
-    if (x < 128) return (unsigned)(x + 128);
-    if (x < 512) return 255u;
-    if (x < 896) return 0u;
-    return (unsigned)(x - 896);
+// Level shift + clamp.  libjpeg's C code indexes a range-limit table with x & 1023, which wraps once x + 128 leaves
+// [-384, 639]; libjpeg-turbo's SIMD inverse DCT, which is what Pillow runs, saturates instead, and so does this.
+JHD unsigned range_limit_idct(int x) {
+    x += 128;
+    return (unsigned)(x < 0 ? 0 : (x > 255 ? 255 : x));
 }
 __global__ __launch_bounds__(256) void jpeg_idct_kernel(const JImg* imgs, const short* coef, unsigned char* planes) {
     __shared__ int ws[32][8][9];

@@ -5,7 +5,8 @@ The reference re-reads and re-decodes every pool image on the CPU in every activ
 cald_train.py:434; ``Image.open(path).convert('RGB')`` in torchvision's VOCDetection.__getitem__ reached from
 detection/voc_utils.py:47-58; ``ToTensor`` in detection/train.py:54-59).  A MI355X has 288 GB of HBM: all of
 VOC07+12 trainval as uint8 RGB is 9 GB, COCO train2017 about 90 GB.  ``DevicePool`` therefore decodes each JPEG
-ONCE, on the GPU (``cald_jpeg_decode_batch_any``: bit-identical to Pillow), keeps the uint8 HWC images in one HBM arena,
+ONCE, on the GPU (``cald_jpeg_decode_batch_any``: bit-identical to Pillow, except for files whose dequantised
+coefficients do not fit int16, which no encoder makes from 8-bit samples), keeps the uint8 HWC images in one HBM arena,
 and hands the sweep device pointers; later cycles only change the subset of positions.
 
 Which file goes where (``jpeg_probe``): baseline and progressive 8-bit Huffman JPEGs (gray, YCbCr or RGB-coded; 4:4:4,

@@ -135,7 +135,8 @@ class VOCDetection(object):
 
     def device_pool(self, indices=None):
         """The image files of `indices` (default: all) decoded once into an HBM-resident pool (bit-identical to
-        Image.open(path).convert('RGB')); ``pool.loader()`` is what get_uncertainty takes.  Baseline and progressive
+        Image.open(path).convert('RGB'), except for files whose dequantised coefficients do not fit int16, which no encoder
+        makes from 8-bit samples); ``pool.loader()`` is what get_uncertainty takes.  Baseline and progressive
         JPEGs are decoded on the GPU; any other file (CMYK, arithmetic-coded, not a JPEG, ...) is decoded by Pillow on
         the host, file by file -- see ``DevicePool.from_files``; ``pool.decode_counts`` tells the routes taken."""
         from .pool import DevicePool

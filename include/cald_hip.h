@@ -596,7 +596,9 @@ int cald_debug_tensor(cald_model* m, const char* name, int view, float* host_out
 
 /* ---- input side: PIL.Image.open(path).convert('RGB') of torchvision's VOCDetection /
  * CocoDetection __getitem__ (detection/voc_utils.py:47-58, detection/coco_utils.py; DataLoader at cald_train.py:434).
- * Bit-identical to Pillow / libjpeg-turbo defaults (ISLOW IDCT, fancy upsampling).  Three kinds of file:
+ * Bit-identical to Pillow / libjpeg-turbo defaults (ISLOW IDCT, fancy upsampling; IDCT outputs beyond the sample range
+ * saturate as turbo's SIMD code does).  Outside the promise: files whose dequantised values (coefficient x quantiser)
+ * do not fit int16, where turbo saturates 16-bit intermediates; no encoder makes one from 8-bit samples.  Three kinds of file:
  *   BASELINE      8-bit sequential Huffman (SOF0 / SOF1), grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan,
  *                 restart intervals allowed.  This is the strict set of cald_jpeg_info / cald_jpeg_decode_batch: they
  *                 return CALD_ERR_UNSUPPORTED for anything else and decode nothing on the CPU.

@@ -237,12 +237,10 @@ static int extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 :
 #define F_3_072711026 25172
 static int32_t descale(int32_t x, int n) { return (x + (1 << (n - 1))) >> n; }
 static uint8_t range_limit_idct(int32_t x) {
-    /* sample_range_limit + CENTERJSAMPLE indexed with (x & 1023) */
-    x &= 1023;
-    if (x < 128) return (uint8_t)(x + 128);
-    if (x < 512) return 255;
-    if (x < 896) return 0;
-    return (uint8_t)(x - 896);
+    /* level shift + saturation, as libjpeg-turbo's SIMD inverse DCT (what Pillow runs) does it; libjpeg's C code
+     * indexes sample_range_limit with (x & 1023) instead, which wraps once x + 128 leaves [-384, 639] */
+    x += 128;
+    return (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x));
 }
 static void idct_1d(const int32_t in[8], int32_t out[8], int shift, int pass1) {
     int32_t z1, z2, z3, z4, z5, tmp0, tmp1, tmp2, tmp3, tmp10, tmp11, tmp12, tmp13;
