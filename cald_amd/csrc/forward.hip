@@ -1,5 +1,5 @@
 // forward.hip -- one forward of the detector over a ragged batch of views: the level plan, each stage's arena layout, the conv launches of every layer
-// (single, fused pair, group, gathered rows of the cut_out reuse), forward_model as a run of named stages (ForwardRun), cald_forward, cald_debug_tensor.
+// (single, fused pair, group, gathered rows of the cut_out reuse), forward_model as a run of named stages (ForwardRun) up to the tail its FwdRequest names, cald_forward, cald_debug_tensor.
 #include "host.h"
 
 // =============================================================================================
@@ -390,13 +390,15 @@ __global__ void accumulate_rows_kernel(const int* __restrict__ counts, int V, un
 
 static const float RPN_MIN_SIZE = 1e-3f;
 // One forward as a run of named stages (run() chains them).  views: host descriptors with src/H/W/flip/rects filled; Hr/Wr/Ho/Wo are filled
-// by prepare().  feat (host.h FwdFeatures): the forward stops after the FPN and hands out the pyramid; `det` is then not used, and pruning,
-// cut_out reuse and the audit do not apply.
+// by prepare().  rq (host.h FwdRequest) names the tail: STOCK ends in the detections; FEATURES stops after the FPN and hands out the pyramid;
+// SSM / RETINA_SSM run that tail in place of the stock one.  Pruning, cut_out reuse and the audit belong to the stock tail alone.
 struct ForwardRun {
-    cald_model* m; int V; ViewDesc* views; const DetBuffers& det; float* audit_out; bool prune_ok; const FwdReuse* ru; FwdFeatures* feat; FwdSsm* ssm; FwdRetinaSsm* rssm;
+    cald_model* m; int V; ViewDesc* views; const FwdRequest& rq;
     // ---- filled by prepare() ----
     cald_ctx* c = nullptr; hipStream_t st = nullptr; const BatchPlan* dp = nullptr;
+    const FwdReuse* ru = nullptr; float* audit_out = nullptr;      // the stock tail's (null for every other)
     bool retina = false, prune = false;
+    bool is(FwdRequest::Tail t) const { return rq.tail == t; }
     int hp[CALD_MAX_VIEWS][2], max_pix0 = 0, max_pix2 = 0, max_pix6 = 0;
     BodyBufs Fb; PyramidBufs Fp; RetinaBufs Fr; RpnBufs Fn; PruneBufs Fq; BoxBufs Fx; AuditBufs Fa;
     // the scratch of the stages this forward will run, in their order
@@ -408,29 +410,37 @@ struct ForwardRun {
         SplitReg S{m, B, m->cfg.precision == CALD_PRECISION_F16X3 && split_on};
         Fb.layout(B, S, px);
         Fp.layout(B, S, px, retina);
-        if (feat) return;
+        if (is(FwdRequest::FEATURES)) return;
         if (retina) {
             int maxa = 0;
             for (int v = 0; v < V; v++) { int t = 0; for (int l = 3; l < 8; l++) t += P.seg[l][v].H * P.seg[l][v].W * 9; if (t > maxa) maxa = t; }
-            Fr.layout(B, S, px, V, m->cls_out.Cout, m->cfg.num_classes, m->cfg.detections_per_img, maxa, rssm ? &rssm->out : nullptr);
+            Fr.layout(B, S, px, V, m->cls_out.Cout, m->cfg.num_classes, m->cfg.detections_per_img, maxa, is(FwdRequest::RETINA_SSM) ? &rq.rssm->out : nullptr);
             return;
         }
         Fn.layout(B, px, V, m->cfg.rpn_pre_nms_top_n);
         if (m->prune) Fq.layout(B, px, V, m->prune_capture);
         Fx.layout(B, S, V, m->pred.Cout, m->cfg.num_classes, m->key_cap);
         Fa.layout(B, V, m->det_cap());
-        if (ssm) ssm->out.layout(B, V, m->cfg.num_classes, m->cfg.detections_per_img);
+        if (is(FwdRequest::SSM)) rq.ssm->out.layout(B, V, m->cfg.num_classes, m->cfg.detections_per_img);
     }
     // argument checks, the level plan, the arena, the staging-ring copy of plan and views
     int prepare() {
         c = m->ctx;
         if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized (call cald_model_finalize)");
         if (V < 1 || V > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "n_views must be 1..%d", CALD_MAX_VIEWS);
-        if (feat && (audit_out || prune_ok || ru)) return fail(CALD_ERR_INVALID, "a features-only forward takes no audit, pruning or cut_out reuse");
-        if (ssm && (feat || audit_out || ru || m->cfg.arch != CALD_ARCH_FRCNN)) return fail(CALD_ERR_INVALID, "the SSM forward is a plain Faster R-CNN forward");
-        if (rssm && (feat || audit_out || ru || ssm || !rssm->pick || m->cfg.arch != CALD_ARCH_RETINANET || m->cfg.num_classes < 2))
-            return fail(CALD_ERR_INVALID, "the RetinaNet SSM forward is a plain RetinaNet forward with a pick callback and at least two classes");
-        if (!feat && !ssm && !rssm && det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", det.cap, m->det_cap());
+        switch (rq.tail) {      // what the tail needs of the model and of its own arguments
+        case FwdRequest::STOCK:
+            if (rq.stock.det.cap < m->det_cap()) return fail(CALD_ERR_INVALID, "detection capacity %d < required %d", rq.stock.det.cap, m->det_cap());
+            ru = rq.stock.ru; audit_out = rq.stock.audit_out; prune = m->prune && rq.stock.prune_ok;
+            break;
+        case FwdRequest::FEATURES: break;
+        case FwdRequest::SSM:
+            if (m->cfg.arch != CALD_ARCH_FRCNN) return fail(CALD_ERR_INVALID, "the SSM forward is a plain Faster R-CNN forward");
+            break;
+        case FwdRequest::RETINA_SSM:
+            if (!rq.rssm->pick || m->cfg.arch != CALD_ARCH_RETINANET || m->cfg.num_classes < 2)
+                return fail(CALD_ERR_INVALID, "the RetinaNet SSM forward is a plain RetinaNet forward with a pick callback and at least two classes");
+        }
         HIPCHK(hipSetDevice(c->device));
         for (int v = 0; v < V; v++) {
             ViewDesc& d = views[v];
@@ -438,8 +448,8 @@ struct ForwardRun {
             int Hp, Wp;
             transform_size(d.H, d.W, m->cfg.min_size, m->cfg.max_size, &d.Hr, &d.Wr, &Hp, &Wp);
             d.Ho = d.H; d.Wo = d.W;
-            if (feat && feat->pad_to) {      // the loader batch's common size (torchvision's ImageList): Hr / Wr stay the view's own, the rest is zero
-                const int Hq = feat->pad_to[v][0], Wq = feat->pad_to[v][1];
+            if (is(FwdRequest::FEATURES) && rq.feat->pad_to) {      // the loader batch's common size (torchvision's ImageList): Hr / Wr stay the view's own, the rest is zero
+                const int Hq = rq.feat->pad_to[v][0], Wq = rq.feat->pad_to[v][1];
                 if (Hq % 32 || Wq % 32 || Hq < Hp || Wq < Wp)
                     return fail(CALD_ERR_INVALID, "view %d: pad_to %d x %d must be a multiple of 32 and at least the view's own %d x %d", v, Hq, Wq, Hp, Wp);
                 Hp = Hq; Wp = Wq;
@@ -448,7 +458,6 @@ struct ForwardRun {
             if (Hp * Wp > max_pix0) max_pix0 = Hp * Wp;
         }
         retina = m->cfg.arch == CALD_ARCH_RETINANET;
-        prune = m->prune && prune_ok;
         if (audit_out && m->box_min_size > 0.0f) return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit does not cover small-box removal (box_min_size > 0)");
         if (audit_out && retina && m->cfg.detections_per_img > AUDIT_MAX_DET)
             return fail(CALD_ERR_UNSUPPORTED, "the decision-margin audit holds a class's detections in LDS: RetinaNet with detections_per_img <= %d (AUDIT_MAX_DET)", AUDIT_MAX_DET);
@@ -533,7 +542,7 @@ struct ForwardRun {
         if ((rc = kept && ru->mode == 2 && ru->gather_fpn ? gconv_group_on(m, sp, nl, V, *ru) : conv_group_on(m, sp, nl, V))) return rc;
         if (!retina) return 0;
         if ((rc = conv_on(m, m->p6, Fp.Pf[2], Fp.Pf[3], 5, 6, V, false))) return rc;
-        if (feat && !feat->p7) return 0;
+        if (is(FwdRequest::FEATURES) && !rq.feat->p7) return 0;
         return conv_on(m, m->p7, Fp.Pf[3], Fp.Pf[4], 6, 7, V, false, nullptr, nullptr, 0, nullptr, true);
     }
     // the features-only forward's result: `n` pyramid tensors from plan level `first` (neither LastLevelMaxPool nor a head runs)
@@ -541,7 +550,7 @@ struct ForwardRun {
         name_pyramid(first, n);
         for (int i = 0; i < n; i++) {
             auto sp = m->split.find(Fp.Pf[i]);
-            feat->P[i] = Fp.Pf[i]; feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; feat->plan_level[i] = first + i;
+            rq.feat->P[i] = Fp.Pf[i]; rq.feat->split_only[i] = sp != m->split.end() && sp->second.fp32_dead; rq.feat->plan_level[i] = first + i;
         }
     }
     // heads (retinanet_cal.py:36-241): 4 x (3x3 conv + ReLU) + 3x3 output conv, per level; then the tail
@@ -565,20 +574,20 @@ struct ForwardRun {
             m->dbg["cls" + std::to_string(i)] = {Fr.cls_h[i], 3 + i, m->cls_out.Cout, 0};
             m->dbg["reg" + std::to_string(i)] = {Fr.reg_h[i], 3 + i, 36, 0};
         }
-        if (rssm) return retina_ssm_tail();
+        if (is(FwdRequest::RETINA_SSM)) return retina_ssm_tail();
         const RetinaArgs ra = retina_args(Fr.tail, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
-                                          m->cfg.box_nms_thresh, m->cfg.detections_per_img, det);
+                                          m->cfg.box_nms_thresh, m->cfg.detections_per_img, rq.stock.det);
         launch_retina_postprocess(ra, Fr.tail.max_anchors, st);
         if (audit_out) launch_audit_retina(ra, audit_out, st);
         return 0;
     }
     // the SSM tail (retina_ssm.hip) on the same head tensors: phase A, the host stop for the picks, phase B
     int retina_ssm_tail() {
-        const RetinaSsmArgs sa = retina_ssm_args(rssm->out, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
+        const RetinaSsmArgs sa = retina_ssm_args(rq.rssm->out, Fr.cls_h, Fr.reg_h, dp, c->d_views, m->d_anchors, 9, m->cfg.num_classes, V, m->cfg.box_score_thresh,
                                                  m->cfg.box_nms_thresh, m->cfg.detections_per_img);
         launch_retina_ssm_phase_a(sa, st);
         HIPCHK(hipGetLastError());
-        if (int rc = retina_ssm_pick_stop(c, rssm->out, V, m->cfg.num_classes, rssm->pick, rssm->user, rssm->image0, nullptr)) return rc;
+        if (int rc = retina_ssm_pick_stop(c, rq.rssm->out, V, m->cfg.num_classes, rq.rssm->pick, rq.rssm->user, rq.rssm->image0, nullptr)) return rc;
         launch_retina_ssm_phase_b(sa, st);
         return 0;
     }
@@ -718,14 +727,14 @@ struct ForwardRun {
         return 0;
     }
     void postprocess() {
-        PostArgs pa = post_args(Fx.post, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh, m->cfg.box_nms_thresh, det);
+        PostArgs pa = post_args(Fx.post, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh, m->cfg.box_nms_thresh, rq.stock.det);
         pa.kept_key = audit_out ? Fa.kept_key : nullptr; pa.post_maxc = audit_out ? Fa.post_maxc : nullptr;
         pa.min_box = m->box_min_size;
         launch_frcnn_postprocess(pa, st);
     }
     // the SSM tail (ssm.hip) on the same predictor rows and proposals
     void ssm_postprocess() {
-        launch_ssm_postprocess(ssm_args(ssm->out, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh,
+        launch_ssm_postprocess(ssm_args(rq.ssm->out, Fx.pr, m->pred.Cout, m->cfg.num_classes, V, Fn.prop, c->d_views, m->cfg.box_score_thresh,
                                         m->cfg.detections_per_img), st);
     }
     void audit() {
@@ -737,21 +746,21 @@ struct ForwardRun {
         for (int i = 0; i < 4; i++) au.seg[i] = dp->seg[2 + i];
         au.prob = Fx.post.prob; au.pred = Fx.pr; au.pred_ld = m->pred.Cout; au.C = m->cfg.num_classes; au.views = c->d_views;
         au.keys = Fx.post.keys; au.key_count = Fx.post.key_count; au.key_cap = m->key_cap; au.kept_key = Fa.kept_key; au.post_maxc = Fa.post_maxc;
-        au.det_count = det.count; au.cap = det.cap; au.score_thr = m->cfg.box_score_thresh; au.post_nms_thr = m->cfg.box_nms_thresh;
+        au.det_count = rq.stock.det.count; au.cap = rq.stock.det.cap; au.score_thr = m->cfg.box_score_thresh; au.post_nms_thr = m->cfg.box_nms_thresh;
         au.V = V; au.delta = 1e-2f; au.out = audit_out;
         launch_audit(au, st);
     }
     int run() {
         int rc;
         if ((rc = prepare()) || (rc = body()) || (rc = fpn())) return rc;
-        if (feat) hand_out(retina ? 3 : 2, retina && feat->p7 ? 5 : 4);
+        if (is(FwdRequest::FEATURES)) hand_out(retina ? 3 : 2, retina && rq.feat->p7 ? 5 : 4);
         else if (retina) { name_pyramid(3, 5); if ((rc = retina_head_and_tail())) return rc; }
         else {
             p6_subsample();
             if ((rc = prune ? rpn_pruned() : rpn_dense())) return rc;
             proposals();
             if ((rc = box_head())) return rc;
-            if (ssm) ssm_postprocess(); else postprocess();
+            if (is(FwdRequest::SSM)) ssm_postprocess(); else postprocess();
             if (audit_out) audit();
         }
         HIPCHK(hipGetLastError());
@@ -759,10 +768,7 @@ struct ForwardRun {
     }
 };
 
-int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out, bool prune_ok, const FwdReuse* ru,
-                             FwdFeatures* feat, FwdSsm* ssm, FwdRetinaSsm* rssm) {
-    return ForwardRun{m, V, views, det, audit_out, prune_ok, ru, feat, ssm, rssm}.run();
-}
+int cald_host::forward_model(cald_model* m, int V, ViewDesc* views, const FwdRequest& rq) { return ForwardRun{m, V, views, rq}.run(); }
 
 static int fill_view(ViewDesc& d, const cald_view& v) {
     memset(&d, 0, sizeof(d));
@@ -778,12 +784,8 @@ extern "C" int cald_forward(cald_model* m, int n_views, const cald_view* views, 
     std::vector<ViewDesc> vd(n_views);
     for (int i = 0; i < n_views; i++) { int rc = fill_view(vd[i], views[i]); if (rc) return rc; }
     DetBuffers det;
-    det.boxes = out->boxes_dev; det.scores = out->scores_dev; det.labels = (long long*)out->labels_dev; det.props = out->props_dev;
-    det.prob_max = out->prob_max_dev; det.scores_cls = out->scores_cls_dev; det.count = out->count_dev;
-    det.cap = out->cap; det.C = m->cfg.num_classes;
-    if (!det.boxes || !det.scores || !det.labels || !det.props || !det.prob_max || !det.scores_cls || !det.count)
-        return fail(CALD_ERR_INVALID, "output buffers must all be provided");
-    return forward_model(m, n_views, vd.data(), det, nullptr, m->prune_capture);
+    if (int rc = dets_from_abi(out, m->cfg.num_classes, &det)) return rc;
+    return forward_model(m, n_views, vd.data(), FwdRequest::detect(det, m->prune_capture));
 }
 
 extern "C" int cald_debug_tensor(cald_model* m, const char* name, int view, float* host_out, int64_t capacity, int64_t* shape3) {

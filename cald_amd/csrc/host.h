@@ -1,6 +1,6 @@
-// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, eval.hip, model.hip, forward.hip, sweep.hip, lossnet.hip) share: the context and the model
-// behind the opaque handles of include/cald_hip.h, and the host functions that cross a file boundary.  Host-only, and included by those seven
-// files alone: the train_*.hip files (train_host.h), jpeg.hip and comm.hip reach the context through the cald_internal_* accessors of ctx.hip.
+// host.h -- what the host files of the C ABI (ctx.hip, ops.hip, eval.hip, model.hip, forward.hip, cutout_reuse.hip, sweep.hip, lossnet.hip, vaal.hip) share: the
+// context and the model behind the opaque handles of include/cald_hip.h, a forward's request (FwdRequest), the cut_out reuse planner (CutPlanner), and the host
+// functions that cross a file boundary.  Host-only, and included by those nine alone: the train_*.hip files (train_host.h), jpeg.hip and comm.hip reach the context through ctx.hip's cald_internal_* accessors.
 #pragma once
 #include "../../include/cald_hip.h"
 #include "common.h"
@@ -161,7 +161,7 @@ struct cald_model {
     } ss;
     float box_min_size = 0.0f;   // cald_model_set_box_min_size: stock remove_small_boxes in the ordinary tail (0 = off, frcnn_la.py)
     int key_cap = 32768;   // FRCNN candidate (proposal, class) list capacity per view, sized from box_score_thresh at create
-    // cut_out reuse (sweep.hip SweepRun): the reference forward's block outputs of the first three stages, one slot per batch parity (batch k + 1's
+    // cut_out reuse (cutout_reuse.hip CutPlanner): the reference forward's block outputs of the first three stages, one slot per batch parity (batch k + 1's
     // reference forward runs before batch k's cut_out forward), and the gather plans of the cut_out forwards (pinned by parity + device)
     struct CutReuse {
         int mode = -1;              // cald_model_set_cutout_reuse: -1 the process default (CALD_CUTOUT_REUSE), 0 off, 1 on, 2 on with every stage dense
@@ -230,14 +230,17 @@ struct PostBufs {
     unsigned char* skip = nullptr;      // remove_small_boxes marks (PostArgs::skip)
     void layout(Bump& B, int V, int C, int key_cap);
 };
+// what either SSM tail leaves on the device for the host to collect (ssm_collect_rows): per view al and count, the batch's total, its rows
+struct SsmRows { const int *al, *count, *total; const float *boxes, *scores; const signed char* labels; };
 // the SSM tail (ssm.hip): scratch and results of V views; the results hold (C - 1) * cap rows a view, the most a view can give
 struct SsmBufs {
     float *prob = nullptr, *kept_box = nullptr, *boxes = nullptr, *scores = nullptr; unsigned* vmax = nullptr; signed char* labels = nullptr;
     int *kept_prop = nullptr, *cls_count = nullptr, *row_off = nullptr, *al = nullptr, *count = nullptr, *total = nullptr;
     void layout(Bump& B, int V, int C, int cap);
+    SsmRows rows() const { return {al, count, total, boxes, scores, labels}; }
 };
-// ---- the SSM forward (cald_sweep_ssm): Faster R-CNN up to the box predictor, then ssm_postprocess() in place of postprocess().  `det` is
-// not used.  Filled by forward_model: the tail's buffers in the arena (valid until the context's next forward) ----
+// ---- the SSM forward (cald_sweep_ssm): Faster R-CNN up to the box predictor, then ssm_postprocess() in place of postprocess().  Filled by
+// forward_model: the tail's buffers in the arena (valid until the context's next forward) ----
 struct FwdSsm { SsmBufs out; };
 #define SSM_NMS_THR 0.3f     // frcnn_ssm.py:88
 #define SSM_CONF_THR 0.5f    // frcnn_ssm.py:60 CONF_THRESH
@@ -252,11 +255,49 @@ struct RetinaSsmBufs {
         *row_off = nullptr, *count = nullptr, *total = nullptr, cand_cap = 0, nblk = 0;
     unsigned* vmax = nullptr; float *kept_box = nullptr, *boxes = nullptr, *scores = nullptr; signed char* labels = nullptr;
     void layout(Bump& B, int V, int K, int per_class, int max_anchors);      // max_anchors: the largest anchor count of a view
+    SsmRows rows() const { return {al, count, total, boxes, scores, labels}; }
 };
 // ---- the SSM forward of RetinaNet (cald_sweep_ssm_retina): the heads, then phase A, the host stop (`pick` once per image with al == 0;
-// image = image0 + view) and phase B in place of the stock tail.  `det` is not used.  Filled by forward_model: the tail's buffers in the
-// arena (valid until the context's next forward) ----
+// image = image0 + view) and phase B in place of the stock tail.  Filled by forward_model: the tail's buffers in the arena (valid until the
+// context's next forward) ----
 struct FwdRetinaSsm { cald_ssm_pick_fn pick = nullptr; void* user = nullptr; int image0 = 0; RetinaSsmBufs out; };
+// ---- what one forward is run for: ONE tail, and only what that tail reads.  STOCK: the detections into stock.det (+ the decision-margin
+// records of audit_out, the certified pruning where the model has it and prune_ok allows it, the cut_out reuse of `ru`); FEATURES / SSM /
+// RETINA_SSM: the struct above of that name, which forward_model fills.  What a maker's argument points to outlives the call. ----
+struct FwdRequest {
+    enum Tail { STOCK, FEATURES, SSM, RETINA_SSM } tail;
+    struct Stock { DetBuffers det; float* audit_out; bool prune_ok; const FwdReuse* ru; };
+    union { Stock stock; FwdFeatures* feat; FwdSsm* ssm; FwdRetinaSsm* rssm; };
+    static FwdRequest detect(const DetBuffers& det, bool prune_ok = false, const FwdReuse* ru = nullptr) { FwdRequest r; r.tail = STOCK; r.stock = Stock{det, nullptr, prune_ok, ru}; return r; }
+    FwdRequest audited(float* out) const { FwdRequest r = *this; r.stock.audit_out = out; return r; }      // a stock request with the audit's records (null: none)
+    static FwdRequest features(FwdFeatures* f) { FwdRequest r; r.tail = FEATURES; r.feat = f; return r; }
+    static FwdRequest ssm_tail(FwdSsm* s) { FwdRequest r; r.tail = SSM; r.ssm = s; return r; }
+    static FwdRequest retina_ssm_tail(FwdRetinaSsm* s) { FwdRequest r; r.tail = RETINA_SSM; r.rssm = s; return r; }
+};
+// ---- the cut_out reuse planner (cutout_reuse.hip) of one run over model m: which blocks are retained and gathered, the retention slot of a
+// reference forward (one per batch parity, grown on demand) and the gather plan of the cut_out forward over it.  Books the context's cut_*
+// counters (cald_profile_cutout / _stages). ----
+struct CutPlanner {
+    CutPlanner() {}                                     // off, until a run builds its own
+    CutPlanner(cald_model* m, bool prune_ok);           // the block tables of m
+    void enable(bool has_cutout, bool audit);           // is the reuse on for this model?  The caller's own terms: the run has a cut_out augmentation, and it is no audit
+    // the retention slot `parity` for a reference forward of nb views, and `ru` over it: returns what the forward retains (CUT_KEPT_*), or an error
+    int retain(int parity, int nb, const ViewDesc* views, FwdReuse& ru);
+    // gather plan of the cut_out forward (V views in the reference forward's order) over slot `parity` into the pinned set `parity`, one H2D, and `ru`
+    int cut_plan(int parity, bool kept_fpn, int V, const ViewDesc* views, FwdReuse& ru);
+private:
+    cald_model* m = nullptr; bool prune_ok = false, retina = false;
+    bool on = false;        // enable()'s verdict: off, every retain() keeps nothing and books nothing
+    // blocks of the first three stages (retained and gathered)
+    int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
+    // the whole backbone for the geometry (ngeo >= nblk blocks, geo_stride = conv2's strides; the first nblk are blk_stride) and the blocks
+    // whose outputs are C2..C5; fpn_ok: Faster R-CNN with four stages -- the FPN output convs can be retained and patched
+    int ngeo = 0, geo_stride[CUT_MAX_BLOCKS], c_blk[4] = {0, 0, 0, 0};
+    bool fpn_ok = false;
+    BatchPlan rplan;        // the plan of the views at hand (plan_of)
+    void plan_of(int nv, const ViewDesc* vs);
+    size_t retain_layout(int nv, bool fpn, char* base, FwdReuse* ru) const;
+};
 RetinaSsmArgs retina_ssm_args(const RetinaSsmBufs& S, const float* const* cls, const float* const* reg, const BatchPlan* plan, const ViewDesc* views,
                               const float* base_anchors, int A, int K, int V, float score_thr, float nms_thr, int per_class);
 // the host stop between the two phases: waits for phase A, reads al and the counts, asks `pick` for every view with al == 0 (in view order),
@@ -287,13 +328,34 @@ void pack_conv(const std::vector<const float*>& ts, const std::vector<int>& cout
 void build_plan(BatchPlan& P, int V, const ViewDesc* views, const int (*hp)[2], bool retina);
 bool stem_grid_exact(const LevelSeg* seg, int V);
 bool conv_pack_default();       // packed row tiles (ConvArgs::packed_rows) in the dense conv_p4 launches: on unless CALD_CONV_PACK=0
-int forward_model(cald_model* m, int V, ViewDesc* views, const DetBuffers& det, float* audit_out = nullptr, bool prune_ok = false,
-                  const FwdReuse* ru = nullptr, FwdFeatures* feat = nullptr, FwdSsm* ssm = nullptr, FwdRetinaSsm* rssm = nullptr);
+int forward_model(cald_model* m, int V, ViewDesc* views, const FwdRequest& rq);
+// the caller's output buffers as DetBuffers of C classes; every one must be there
+inline int dets_from_abi(const cald_dets* abi, int C, DetBuffers* det) {
+    if (!abi || !abi->boxes_dev || !abi->scores_dev || !abi->labels_dev || !abi->props_dev || !abi->prob_max_dev || !abi->scores_cls_dev || !abi->count_dev)
+        return fail(CALD_ERR_INVALID, "output buffers must all be provided");
+    *det = DetBuffers{abi->boxes_dev, abi->scores_dev, (long long*)abi->labels_dev, abi->props_dev, abi->prob_max_dev, abi->scores_cls_dev, abi->count_dev, abi->cap, C};
+    return 0;
+}
 // sweep.hip
 void free_det(DetBuffers& d);
 int alloc_det(DetBuffers& d, int V, int cap, int C);
 // detection buffers that live for one API call
 struct ScopedDet { DetBuffers d{}; ~ScopedDet() { free_det(d); } int alloc(int V, int cap, int C) { return alloc_det(d, V, cap, C); } };
+// the untouched view of one image, and the reference views of images [i0, i0 + nb)
+inline ViewDesc plain_view(const uint8_t* src, int H, int W) { ViewDesc d; memset(&d, 0, sizeof(d)); d.src = src; d.H = H; d.W = W; return d; }
+inline std::vector<ViewDesc> ref_views(const uint8_t* const* images_dev, const int* H, const int* W, int i0, int nb) {
+    std::vector<ViewDesc> views(nb);
+    for (int i = 0; i < nb; i++) views[i] = plain_view(images_dev[i0 + i], H[i0 + i], W[i0 + i]);
+    return views;
+}
+// images per batch of a sweep: the caller's request, `dflt` where it gives none, CALD_MAX_VIEWS at the most
+inline int sweep_batch(int requested, int dflt) { const int B = requested > 0 ? requested : dflt; return B > CALD_MAX_VIEWS ? CALD_MAX_VIEWS : B; }
+// The rows of one batch of an SSM tail (V views): drains the stream, reads al and count of every view into al_out / count_out [V] and the
+// batch's total into *total_out, checks them (a view has 0..view_rows rows, none with al set; the counts add up to the total), and copies the
+// rows to row `row0` of boxes_out / scores_out [score_cols] / labels_out [label_cols] where row0 + total <= rows_cap.  hook: the one-view
+// hooks of ops.hip word the refusal in their own way (null: the sweeps' words, naming image image0 + view)
+int ssm_collect_rows(hipStream_t st, const char* hook, int image0, const SsmRows& R, int V, size_t score_cols, size_t label_cols, int64_t view_rows,
+                     int64_t row0, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out, int8_t* labels_out, int* total_out);
 // ---- the scoring stage's tables, shared by the sweeps (sweep.hip) and the hook cald_op_score_batch (ops.hip) ----
 // The `ints` block of a scoring stage, the same words on the host and on the device: per pair ref_view | aug_view | aug_kind | pair_img
 // (P_MAX each), ref_sel [B][50], ref_n [B], then per view view_img | view_isref (VT each; VT = 0: no per-view tail -- ls_c has no cls_corr).

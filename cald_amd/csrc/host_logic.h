@@ -300,7 +300,7 @@ static inline double ls_tail(int N, const float* pm, int n_rows, const float* co
 }
 
 
-// ---- cut_out view reuse (sweep.hip SweepRun::cut_plan): the pixels of each backbone tensor that can differ from the reference view's ----
+// ---- cut_out view reuse (cutout_reuse.hip CutPlanner::cut_plan): the pixels of each backbone tensor that can differ from the reference view's ----
 // The cut_out view is the reference view with up to CALD_MAX_CUT rectangles filled, same size, same transform.  Every conv output is one
 // fixed k-ordered fma chain over its window, so an output whose window misses every filled input pixel has the reference's bits.  A set
 // is a union of rectangles (inclusive bounds), one per cutout rectangle, each carried through the layers on its own; supersets are safe

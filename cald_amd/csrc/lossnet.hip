@@ -300,7 +300,7 @@ extern "C" int cald_sweep_ll(cald_model* m, cald_lossnet* ln, int n_images, cons
         if (levels[j] < 0 || levels[j] >= n_pyr) return fail(CALD_ERR_INVALID, "level %d of branch %d is outside the pyramid (0..%d)", levels[j], j, n_pyr - 1);
         p7 |= retina && levels[j] == 4;
     }
-    int B = cfg && cfg->batch_views > 0 ? cfg->batch_views : 32; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    const int B = sweep_batch(cfg ? cfg->batch_views : 0, 32);
     // an image is padded to its loader batch's common size: the per-dimension maximum of the members' own padded sizes (a maximum of multiples
     // of 32 is one) -- computed here from the whole group, so a group may straddle launch batches
     std::vector<int> pad((size_t)2 * (n_images ? n_images : 1));
@@ -331,11 +331,9 @@ extern "C" int cald_sweep_ll(cald_model* m, cald_lossnet* ln, int n_images, cons
     int rc = 0;
     for (int i0 = 0; i0 < n_images && !rc; i0 += B) {
         const int nb = (n_images - i0 < B) ? n_images - i0 : B;
-        std::vector<ViewDesc> views(nb);
-        for (int i = 0; i < nb; i++) { memset(&views[i], 0, sizeof(ViewDesc)); views[i].src = images_dev[i0 + i]; views[i].H = H[i0 + i]; views[i].W = W[i0 + i]; }
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
         FwdFeatures ft; ft.pad_to = reinterpret_cast<const int (*)[2]>(pad.data() + 2 * (size_t)i0); ft.p7 = p7;
-        DetBuffers none; memset(&none, 0, sizeof(none));
-        if ((rc = forward_model(m, nb, views.data(), none, nullptr, false, nullptr, &ft))) break;
+        if ((rc = forward_model(m, nb, views.data(), FwdRequest::features(&ft)))) break;
         GapArgs a; memset(&a, 0, sizeof(a));
         int max_chunks = 1; long long bytes = 0;
         for (int s = 0; s < nslot; s++) {

@@ -587,15 +587,8 @@ extern "C" int cald_op_ssm_postprocess(cald_ctx* c, int R, int C, const float* l
     HIPCHK(hipMemcpy(d_pred, pred.data(), pred.size() * 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_vd, &vd, sizeof(vd), hipMemcpyHostToDevice));
     launch_ssm_postprocess(ssm_args(S, d_pred, 5 * C, C, 1, pb, d_vd, score_thr, det_max), c->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int al = 0, n = 0, total = 0;
-    HIPCHK(hipMemcpy(&al, S.al, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&n, S.count, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&total, S.total, 4, hipMemcpyDeviceToHost));
-    if (n < 0 || n > (C - 1) * det_max || total != n || (al && n)) return fail(CALD_ERR_HIP, "ssm postprocess returned %d rows (al %d, total %d, cap %d)", n, al, total, (C - 1) * det_max);
-    if (n) {
-        HIPCHK(hipMemcpy(boxes_out, S.boxes, (size_t)n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(scores_out, S.scores, (size_t)n * (C - 1) * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(labels_out, S.labels, (size_t)n * (C - 1), hipMemcpyDeviceToHost));
-    }
+    int al = 0, n = 0, total = 0, cap = (C - 1) * det_max;
+    if ((rc = ssm_collect_rows(c->stream, "ssm", 0, S.rows(), 1, (size_t)C - 1, (size_t)C - 1, cap, 0, cap, &al, &n, boxes_out, scores_out, labels_out, &total))) return rc;
     *al_out = al; *n_out = n;
     return 0;
 }
@@ -707,15 +700,8 @@ extern "C" int cald_op_retina_ssm_postprocess(cald_ctx* c, const float* const* c
     if ((rc = retina_ssm_pick_stop(c, S, 1, K, pick, user, 0, counts_out))) return rc;
     launch_retina_ssm_phase_b(sa, c->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int al = 0, n = 0, total = 0;
-    HIPCHK(hipMemcpy(&al, S.al, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&n, S.count, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(&total, S.total, 4, hipMemcpyDeviceToHost));
-    if (n < 0 || n > K * per_class || total != n || (al && n)) return fail(CALD_ERR_HIP, "retina ssm postprocess returned %d rows (al %d, total %d, cap %d)", n, al, total, K * per_class);
-    if (n) {
-        HIPCHK(hipMemcpy(boxes_out, S.boxes, (size_t)n * 16, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(scores_out, S.scores, (size_t)n * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(labels_out, S.labels, (size_t)n * (K - 1), hipMemcpyDeviceToHost));
-    }
+    int al = 0, n = 0, total = 0, cap = K * per_class;
+    if ((rc = ssm_collect_rows(c->stream, "retina ssm", 0, S.rows(), 1, 1, (size_t)K - 1, cap, 0, cap, &al, &n, boxes_out, scores_out, labels_out, &total))) return rc;
     if (al) memset(counts_out, 0, (size_t)K * 4);
     *al_out = al; *n_out = n;
     return 0;

@@ -1,6 +1,7 @@
-// sweep.hip -- the sweeps of the C ABI on the detector forward: cald_sweep / cald_sweep_audit as a pipeline of named stages (SweepRun), and
-// the baselines cald_sweep_ltc / cald_sweep_lsc.  Host-side restatements used here (host_logic.h): Python `random` (MT19937) + cutout
-// rectangle selection (cald/cald_helper.py:88-132), np.linspace sub-sampling (cald_train.py:110-113), the float64 means of cald_train.py:225-228.
+// sweep.hip -- the sweeps of the C ABI on the detector forward: cald_sweep / cald_sweep_audit as a pipeline of named stages (SweepRun; what its
+// forwards retain and gather is cutout_reuse.hip's), the baselines cald_sweep_ltc / _lsc, the SSM sweeps cald_sweep_ssm / _ssm_retina.  Host-side
+// restatements used here (host_logic.h): Python `random` (MT19937) + cutout rectangle selection (cald/cald_helper.py:88-132), np.linspace
+// sub-sampling (cald_train.py:110-113), the float64 means of cald_train.py:225-228.
 #include "host.h"
 
 // helper: device detection buffers
@@ -47,18 +48,6 @@ static DetBuffers det_at(const DetBuffers& D, size_t o) {
     d2.prob_max += o * cap; d2.scores_cls += o * cap * C; d2.count += o;
     return d2;
 }
-// the untouched view of one image, and the reference views of images [i0, i0 + nb)
-static ViewDesc plain_view(const uint8_t* src, int H, int W) {
-    ViewDesc d; memset(&d, 0, sizeof(d));
-    d.src = src; d.H = H; d.W = W;
-    return d;
-}
-static std::vector<ViewDesc> ref_views(const uint8_t* const* images_dev, const int* H, const int* W, int i0, int nb) {
-    std::vector<ViewDesc> views(nb);
-    for (int i = 0; i < nb; i++) views[i] = plain_view(images_dev[i0 + i], H[i0 + i], W[i0 + i]);
-    return views;
-}
-
 // views per augmented forward: 96 fills whole rounds of the 768 workgroup slots in the mid-size layers and fc6 (CALD_FWD_VIEWS overrides)
 static int sweep_fwd_views() {
     static const int env = getenv("CALD_FWD_VIEWS") ? atoi(getenv("CALD_FWD_VIEWS")) : 96;
@@ -72,18 +61,6 @@ static void fwd_span(int n, int f, int* a0, int* nv) {
     const int n_fw = fwd_count(n);
     *a0 = (int)(((long long)n * f) / n_fw); *nv = (int)(((long long)n * (f + 1)) / n_fw) - *a0;
 }
-// cut_out reuse on by default in the exact sweeps; CALD_CUTOUT_REUSE=0 turns it off for the process (A/B, escape hatch)
-static bool cut_reuse_env() {
-    static const bool on = !(getenv("CALD_CUTOUT_REUSE") && atoi(getenv("CALD_CUTOUT_REUSE")) == 0);
-    return on;
-}
-#define CUT_GATHER_MAX_COST 0.7    // a stage runs gathered while its tiles cost at most this fraction of the dense stage
-// The FPN output convs are one more gated stage under the same rule.  A value of its own is not needed: on the bench pool the grouped
-// gathered launch runs at 141.5 TF/s on the rows it computes against the dense group's 144.9 (profiles/cutout_fpn_launches_new.csv), 0.98 of
-// it, so it pays up to about 0.97 of the dense tiles, and every cut_out forward of that pool is far below either value (tile fraction
-// 0.64).  (The parent's table could not price it: its gathered 3 x 3 256 -> 256 launches, layer3's, are 280 - 540 tiles, under one round of
-// the 768 workgroup slots, so their TF/s shows the round's quantisation and not the gathered rows' cost.)
-#define CUT_FPN_MAX_COST CUT_GATHER_MAX_COST
 
 namespace {
 // =============================================================================================
@@ -98,8 +75,7 @@ struct SweepBatch {
     std::vector<int> ref_n, pair_img, view_img, pair_aug, view_aug;   // pair_img: the pair's image slot = the view index of its reference view
     std::vector<char> view_inert;     // cut_out reuse: a stand-in view of an image without detections (its results are not used)
     std::vector<float> cut_margin;
-    bool kept = false;                // the reference forward retained its first three stages (retention slot k & 1)
-    bool kept_fpn = false;            // ... and the FPN output convs' results (the extended slot)
+    int kept = CUT_KEPT_NONE;         // what the reference forward retained in slot k & 1 (CutPlanner::retain)
     // what build_aug_views hands to enqueue_aug_forwards and enqueue_scoring
     std::vector<int> ref_sel, pair_kind, view_isref;
     std::vector<float> pair_par;
@@ -113,20 +89,14 @@ struct SweepRun {
     const cald_sweep_cfg* cfg; double* consistency_out; double* cls_corr_out; float* margins_out; bool force_dense;
     // ---- filled by setup() ----
     cald_ctx* c = nullptr;
-    bool audit = false, prune_ok = false, retina = false, reuse = false;
+    bool audit = false, prune_ok = false;
     int C = 0, cap = 0, A = 0, B = 0, VT = 0, NB = 0, P_MAX = 0, cut_a = -1;
     PairLayout lay{0, 0, 0}; size_t n_ints = 0;
     DetBuffers* DS[2] = {nullptr, nullptr};
     int* d_ints = nullptr; float *d_par = nullptr, *d_cons = nullptr, *d_clsc = nullptr; NoiseJob* d_jobs = nullptr; unsigned long long* d_lsum = nullptr;
     float *d_vm[2] = {nullptr, nullptr}, *d_pm = nullptr;     // decision-margin audit: per-view records of the two detection-buffer sets, per-pair records
     SweepBatch bt[2];
-    // blocks of the first three stages (cut_out reuse), and the plan scratch of the reuse
-    int nblk = 0, blk_lin[CUT_MAX_BLOCKS], blk_lout[CUT_MAX_BLOCKS], blk_stage[CUT_MAX_BLOCKS], blk_stride[CUT_MAX_BLOCKS];
-    // the whole backbone for the geometry (ngeo >= nblk blocks, geo_stride = conv2's strides; the first nblk are blk_stride) and the blocks
-    // whose outputs are C2..C5; fpn_ok: Faster R-CNN with four stages -- the FPN output convs can be retained and patched
-    int ngeo = 0, geo_stride[CUT_MAX_BLOCKS], c_blk[4] = {0, 0, 0, 0};
-    bool fpn_ok = false;
-    std::vector<BatchPlan> rplan;
+    CutPlanner planner;      // cut_out reuse
 
     static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -156,8 +126,7 @@ struct SweepRun {
             for (int i = 0; i < n_images; i++)
                 if (randn_unsupported(H[i], W[i]))
                     return fail(CALD_ERR_UNSUPPORTED, "GaussianNoise on image %d (%dx%d): torch.randn of fewer than 16 elements takes torch's scalar path, which is not implemented", i, H[i], W[i]);
-        B = cfg->batch_images > 0 ? cfg->batch_images : 64;
-        if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+        B = sweep_batch(cfg->batch_images, 64);
         VT = B * (1 + A);
         NB = (n_images + B - 1) / B;
         // the second set of detection buffers exists only when two batches are really in flight (a one-batch shard would pay VT x cap x C
@@ -199,62 +168,10 @@ struct SweepRun {
         // ---- cut_out reuse (exact fp32, conv_p4.hip's gathered rows): the reference forward keeps the block outputs of the first three stages,
         // and the batch's first cut_out augmentation recomputes only its dirty pixels over them ----
         for (int a = 0; a < A && cut_a < 0; a++) if (cfg->augs[a].kind == CALD_AUG_CUTOUT) cut_a = a;
-        init_blocks();
-        reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && cut_a >= 0 && !audit && m->cfg.precision == CALD_PRECISION_FP32 && nblk < CUT_MAX_BLOCKS;
-        rplan.resize(reuse ? 1 : 0);
+        planner = CutPlanner(m, prune_ok);
+        planner.enable(cut_a >= 0, audit);
         return 0;
     }
-    // the blocks the cut_out reuse retains and gathers (the first three stages), and the whole backbone for its geometry
-    void init_blocks() {
-        retina = m->cfg.arch == CALD_ARCH_RETINANET;
-        for (int b = 0, layer = 0, l = 2; b < (int)m->blocks.size() && layer < 3 && nblk < CUT_MAX_BLOCKS; b++) {
-            const Bottleneck& Bk = m->blocks[b];
-            blk_stride[nblk] = Bk.c2.stride; blk_lin[nblk] = l; l += Bk.c2.stride == 2 ? 1 : 0; blk_lout[nblk] = l; blk_stage[nblk] = layer;
-            nblk++;
-            if (Bk.layer_end) layer++;
-        }
-        {
-            int layer = 0; bool fits = true;
-            for (size_t b = 0; b < m->blocks.size(); b++) {
-                if (ngeo == CUT_MAX_BLOCKS || layer > 3) { fits = false; break; }
-                geo_stride[ngeo] = m->blocks[b].c2.stride;
-                if (m->blocks[b].layer_end) c_blk[layer++] = ngeo;
-                ngeo++;
-            }
-            fpn_ok = fits && layer == 4 && !retina && ngeo >= nblk;
-            if (!fpn_ok) { ngeo = nblk; for (int b = 0; b < nblk; b++) geo_stride[b] = blk_stride[b]; }
-        }
-    }
-
-    void plan_of(int nv, const ViewDesc* vs, BatchPlan& P) const {
-        int hp[CALD_MAX_VIEWS][2];
-        for (int v = 0; v < nv; v++) { int Hr, Wr; transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &hp[v][0], &hp[v][1]); }
-        build_plan(P, nv, vs, hp, retina);
-    }
-    // retained block outputs of a plan, back to back in one slot
-    size_t retain_layout(const BatchPlan& P, int nv, char* base, float** out) const {
-        size_t off = 0;
-        for (int b = 0; b < nblk; b++) {
-            if (out) out[b] = reinterpret_cast<float*>(base + off);
-            off += al((size_t)level_pix(P, blk_lout[b], nv) * (size_t)m->blocks[b].c3.Cout * 4);
-        }
-        return off;
-    }
-    // the extended slot: the same, then P2..P5 of the FPN output convs and, where this run prunes, the split copy and the energy of P2 / P3
-    // (forward.hip PruneBufs) -- a slot laid out this way serves the three-stage retention unchanged
-    size_t retain_layout_fpn(const BatchPlan& P, int nv, char* base, FwdReuse* ru) const {
-        size_t off = retain_layout(P, nv, base, ru ? ru->out : nullptr);
-        auto take = [&](size_t bytes) { char* p = base + off; off += al(bytes); return p; };
-        for (int i = 0; i < 4; i++) { char* p = take((size_t)level_pix(P, 2 + i, nv) * 256 * 4); if (ru) ru->pf[i] = reinterpret_cast<float*>(p); }
-        if (m->prune && prune_ok)
-            for (int i = 0; i < 2; i++) {
-                char* p = take((size_t)level_pix(P, 2 + i, nv) * 256 * 4); char* e = take((size_t)level_pix(P, 2 + i, nv) * 4 * 4);
-                if (ru) { ru->p16[i] = reinterpret_cast<unsigned*>(p); ru->energy[i] = reinterpret_cast<float*>(e); }
-            }
-        if (ru) ru->fpn = true;
-        return off;
-    }
-
     // reference views of batch k -> detections into set k & 1, counts + boxes to the pinned host set, event
     int enqueue_ref(int k) {
         SweepBatch& b = bt[k & 1];
@@ -262,47 +179,16 @@ struct SweepRun {
         std::vector<ViewDesc> views = ref_views(images_dev, H, W, b.i0, b.nb);
         const DetBuffers& D = *DS[k & 1];
         FwdReuse ru;
-        if (int r = retain(k, views.data(), ru)) return r;
-        int r = forward_model(m, b.nb, views.data(), D, audit ? d_vm[k & 1] : nullptr, prune_ok, b.kept ? &ru : nullptr);
-        if (r) return r;
+        const int kept = planner.retain(k & 1, b.nb, views.data(), ru);
+        if (kept < 0) return kept;
+        b.kept = kept;
+        const FwdRequest rq = FwdRequest::detect(D, prune_ok, kept != CUT_KEPT_NONE ? &ru : nullptr).audited(audit ? d_vm[k & 1] : nullptr);
+        if (int r = forward_model(m, b.nb, views.data(), rq)) return r;
         if (hipMemcpyAsync(b.h_count, D.count, (size_t)b.nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(b.h_boxes, D.boxes, (size_t)b.nb * cap * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipEventRecord(m->ss.ev_ref[k & 1], c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "D2H of reference detections failed");
         return 0;
     }
-    // the retention slot of batch k's reference forward (bt[k & 1].nb views), grown on demand, and `ru` over it; sets the batch's kept / kept_fpn
-    int retain(int k, const ViewDesc* views, FwdReuse& ru) {
-        SweepBatch& b = bt[k & 1];
-        b.kept = b.kept_fpn = false;
-        if (reuse) {
-            plan_of(b.nb, views, rplan[0]);
-            cald_model::CutReuse& R = m->cr;
-            const int q = k & 1;
-            // graded: the extended slot (+ the FPN outputs); where that is refused -- by the allocator, once and for the model's life, or by the
-            // test hook's cap -- the three stages only; where that fails too, nothing (the batch's cut_out views run dense)
-            const size_t need3 = retain_layout(rplan[0], b.nb, nullptr, nullptr), needx = fpn_ok ? retain_layout_fpn(rplan[0], b.nb, nullptr, nullptr) : 0;
-            bool ext = fpn_ok && !R.ext_refused && !(R.ext_cap && needx > R.ext_cap);
-            for (int attempt = 0; attempt < 2; attempt++) {
-                const size_t need = ext ? needx : need3;
-                if (need <= R.cap[q]) break;
-                // grown on demand; the slot's last reader (batch k - 2's cut_out forward) is in the stream ahead
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (R.slot[q]) hipFree(R.slot[q]);
-                R.slot[q] = nullptr; R.cap[q] = 0;
-                if (hipMalloc((void**)&R.slot[q], need + (need >> 3)) == hipSuccess) { R.cap[q] = need + (need >> 3); break; }
-                (void)hipGetLastError(); R.slot[q] = nullptr;
-                if (!ext) break;
-                ext = false; R.ext_refused = true;
-            }
-            if (R.slot[q]) {
-                ru.mode = 1; ru.nblk = nblk; b.kept = true; b.kept_fpn = ext;
-                if (ext) retain_layout_fpn(rplan[0], b.nb, R.slot[q], &ru); else retain_layout(rplan[0], b.nb, R.slot[q], ru.out);
-            } else c->cut_fallbacks++;       // no room on a shared GPU: this batch's cut_out views run dense
-            c->cut_kept[!b.kept ? CUT_KEPT_NONE : b.kept_fpn ? CUT_KEPT_FPN : CUT_KEPT_STAGES]++;
-        }
-        return 0;
-    }
-
     // augmented views of batch k, built on the host in the reference's order (cald_train.py:124-183; needs the batch's reference detections
     // on the host), with the augmentation launches they need
     int build_aug_views(int k) {
@@ -414,112 +300,6 @@ struct SweepRun {
         return 0;
     }
 
-    // gather plan of batch k's cut_out forward (V views in the reference forward's order) into the pinned set k & 1, one H2D, and `ru`
-    int cut_plan(int k, int V, const ViewDesc* vs, FwdReuse& ru) {
-        cald_model::CutReuse& R = m->cr;
-        const bool fpn = bt[k & 1].kept_fpn;
-        const size_t per = cut_plan_set_bytes(V), total = per * (2 * (size_t)nblk + (fpn ? 4 : 0));
-        if (!R.d_gp) {
-            const size_t cap = cut_plan_set_bytes(CALD_MAX_VIEWS) * (2 * CUT_MAX_BLOCKS + 4);
-            HIPCHK(hipMalloc((void**)&R.d_gp, cap));
-            HIPCHK(hipHostMalloc((void**)&R.h_gp[0], cap)); HIPCHK(hipHostMalloc((void**)&R.h_gp[1], cap));
-        }
-        plan_of(V, vs, rplan[0]);
-        const BatchPlan& P = rplan[0];
-        char* const h = R.h_gp[k & 1];
-        std::vector<CutSet> g_out((size_t)V * ngeo), g_t1((size_t)V * ngeo), g_fpn((size_t)V * 4);
-        for (int v = 0; v < V; v++) {
-            int Hr, Wr, Hp, Wp; CutSet pool1;
-            transform_size(vs[v].H, vs[v].W, m->cfg.min_size, m->cfg.max_size, &Hr, &Wr, &Hp, &Wp);
-            cut_geometry(vs[v].H, vs[v].W, Hr, Wr, Hp, Wp, vs[v].nrect, vs[v].rects, ngeo, geo_stride, &pool1, &g_out[(size_t)v * ngeo], &g_t1[(size_t)v * ngeo]);
-            if (fpn) {
-                CutSet cs[4], inner[4];
-                for (int i = 0; i < 4; i++) cs[i] = g_out[(size_t)v * ngeo + c_blk[i]];
-                cut_fpn_geometry(Hp, Wp, cs, inner, &g_fpn[(size_t)v * 4]);
-            }
-        }
-        // one gather set of the plan: per view the level's geometry with tile_start counting the set's tiles, then the set as disjoint rectangles
-        auto put_set = [&](size_t index, int lvl, const CutSet* sets, size_t stride_v, int* tiles_out, double* rows_out) {
-            LevelSeg* sg = reinterpret_cast<LevelSeg*>(h + index * per);
-            GatherSet* gs = reinterpret_cast<GatherSet*>(reinterpret_cast<char*>(sg) + (size_t)(V + 1) * sizeof(LevelSeg));
-            int tiles = 0; double rows = 0.0;
-            for (int v = 0; v < V; v++) {
-                LevelSeg L = P.seg[lvl][v]; L.tile_start = tiles; sg[v] = L;
-                CutRect rr[CALD_GATHER_RECTS];
-                int n = cut_disjoint(sets[(size_t)v * stride_v], rr, CALD_GATHER_RECTS);
-                if (n < 0) { n = 1; rr[0] = {0, 0, L.W - 1, L.H - 1}; }       // too fragmented: the whole view
-                GatherSet& G = gs[v]; memset(&G, 0, sizeof(G));
-                G.nr = n;
-                for (int q = 0; q < n; q++) {
-                    G.x0[q] = rr[q].x0; G.y0[q] = rr[q].y0; G.w[q] = rr[q].x1 - rr[q].x0 + 1;
-                    G.cum[q + 1] = G.cum[q] + G.w[q] * (rr[q].y1 - rr[q].y0 + 1);
-                }
-                tiles += (G.cum[n] + 127) / 128; rows += (double)G.cum[n];
-            }
-            sg[V] = P.seg[lvl][V]; sg[V].tile_start = tiles;
-            *tiles_out = tiles; *rows_out = rows;
-        };
-        auto kf = [](const ConvLayer& L) { return (double)L.Cout * (double)(L.KH * L.KW * L.CinTrue); };
-        double cost_g[3] = {0, 0, 0}, cost_d[3] = {0, 0, 0}, rows_g[3] = {0, 0, 0}, rows_d[3] = {0, 0, 0}, tiles_g[3] = {0, 0, 0}, tiles_d[3] = {0, 0, 0};
-        for (int b = 0; b < nblk; b++)
-            for (int kind = 0; kind < 2; kind++) {
-                const int lvl = kind ? blk_lin[b] : blk_lout[b];
-                int tiles; double rows;
-                put_set((size_t)(2 * b + kind), lvl, (kind ? g_t1.data() : g_out.data()) + b, (size_t)ngeo, &tiles, &rows);
-                ru.tiles[b][kind] = tiles; ru.rows[b][kind] = rows;
-                const Bottleneck& Bk = m->blocks[b];
-                const double w = kind ? kf(Bk.c1) : kf(Bk.c2) + kf(Bk.c3) + (Bk.has_down ? kf(Bk.down) : 0.0);
-                const double nconv = kind ? 1.0 : (Bk.has_down ? 3.0 : 2.0), dense = (double)level_pix(P, lvl, V);
-                const int st = blk_stage[b];
-                cost_g[st] += 128.0 * tiles * w; cost_d[st] += dense * w;
-                rows_g[st] += rows * nconv; rows_d[st] += dense * nconv;
-                tiles_g[st] += tiles * nconv; tiles_d[st] += (double)P.seg[lvl][V].tile_start * nconv;
-            }
-        // a stage runs gathered while its tiles cost at most CUT_GATHER_MAX_COST of the dense stage (the rest pays the halo, the per-view
-        // tile tails and the unfused layer-1 pair); otherwise dense, over the retained tensors all the same
-        for (int st = 0; st < 3; st++) {
-            ru.gather[st] = m->cr.mode != 2 && cost_g[st] <= CUT_GATHER_MAX_COST * cost_d[st];
-            c->cut_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_dense[st] += rows_d[st];
-            c->cut_st_rows[st] += ru.gather[st] ? rows_g[st] : rows_d[st]; c->cut_st_dense[st] += rows_d[st];
-            c->cut_st_tiles[st] += ru.gather[st] ? tiles_g[st] : tiles_d[st]; c->cut_st_dense_tiles[st] += tiles_d[st];
-        }
-        // layer4 and the laterals run dense (their rows are booked as such); the FPN output convs are one more gated stage, all four levels
-        // in one grouped gathered launch -- every level has the same weight per row, so its cost is its tiles
-        {
-            double r4 = 0.0, t4 = 0.0, rl = 0.0, tl = 0.0;
-            int lvl = 2;
-            for (size_t b = 0; b < m->blocks.size(); b++) {
-                const Bottleneck& Bk = m->blocks[b];
-                const int lo = lvl + (Bk.c2.stride == 2 ? 1 : 0);
-                if ((int)b >= nblk) {
-                    const double n_in = 1.0, n_out = Bk.has_down ? 3.0 : 2.0;
-                    r4 += n_in * (double)level_pix(P, lvl, V) + n_out * (double)level_pix(P, lo, V);
-                    t4 += n_in * (double)P.seg[lvl][V].tile_start + n_out * (double)P.seg[lo][V].tile_start;
-                }
-                lvl = lo;
-            }
-            if (!retina) for (int i = 0; i < 4; i++) { rl += (double)level_pix(P, 2 + i, V); tl += (double)P.seg[2 + i][V].tile_start; }
-            c->cut_st_rows[3] += r4; c->cut_st_dense[3] += r4; c->cut_st_tiles[3] += t4; c->cut_st_dense_tiles[3] += t4;
-            c->cut_st_rows[CUT_STAGE_LATERAL] += rl; c->cut_st_dense[CUT_STAGE_LATERAL] += rl;
-            c->cut_st_tiles[CUT_STAGE_LATERAL] += tl; c->cut_st_dense_tiles[CUT_STAGE_LATERAL] += tl;
-            double fg = 0.0, fd = 0.0, frg = 0.0, frd = 0.0;
-            if (fpn)
-                for (int i = 0; i < 4; i++) {
-                    put_set(2 * (size_t)nblk + i, 2 + i, g_fpn.data() + i, 4, &ru.fpn_tiles[i], &ru.fpn_rows[i]);
-                    fg += ru.fpn_tiles[i]; frg += ru.fpn_rows[i];
-                }
-            if (!retina) for (int i = 0; i < 4; i++) { fd += (double)P.seg[2 + i][V].tile_start; frd += (double)level_pix(P, 2 + i, V); }
-            ru.gather_fpn = fpn && m->cr.mode != 2 && 128.0 * fg <= CUT_FPN_MAX_COST * frd;
-            c->cut_st_rows[CUT_STAGE_OUTPUT] += ru.gather_fpn ? frg : frd; c->cut_st_dense[CUT_STAGE_OUTPUT] += frd;
-            c->cut_st_tiles[CUT_STAGE_OUTPUT] += ru.gather_fpn ? fg : fd; c->cut_st_dense_tiles[CUT_STAGE_OUTPUT] += fd;
-        }
-        if (hipMemcpyAsync(R.d_gp, h, total, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(CALD_ERR_HIP, "H2D of the cut_out gather plan failed");
-        ru.mode = 2; ru.nblk = nblk; ru.d_gp = R.d_gp;
-        if (fpn) retain_layout_fpn(P, V, m->cr.slot[k & 1], &ru); else retain_layout(P, V, m->cr.slot[k & 1], ru.out);
-        c->cut_batches++;
-        return 0;
-    }
-
     // forwards of batch k's augmented views: with the cut_out reuse its cut_out views first, as one forward in the reference forward's
     // image order; the others in evenly sized forwards (fwd_span)
     int enqueue_aug_forwards(int k) {
@@ -532,7 +312,7 @@ struct SweepRun {
         int n_cut = 0;
         for (int j = 0; j < na; j++) n_cut += b.view_aug[nb + j] == cut_a;
         b.VV = nb + na;
-        if (b.kept && n_cut > 0 && 2 * nb + (na - n_cut) <= VT) {
+        if (b.kept != CUT_KEPT_NONE && n_cut > 0 && 2 * nb + (na - n_cut) <= VT) {
             // cut_out reuse: image i's cut_out view takes slot nb + i (a stand-in copy of the reference view, no rectangle, for an image
             // without detections: same plan as the reference forward), the other augmented views slots 2 nb + ... in their order
             std::vector<ViewDesc> cutv(nb);
@@ -554,16 +334,17 @@ struct SweepRun {
             for (size_t p = 0; p < b.pair_aug.size(); p++) b.pair_aug[p] = slot[b.pair_aug[p] - nb];
             b.view_img = nimg; b.view_aug = naug; b.view_inert = ninert;
             FwdReuse ru;
-            if ((r = cut_plan(k, nb, cutv.data(), ru))) return r;
-            if ((r = forward_model(m, nb, cutv.data(), det_at(D, (size_t)nb), nullptr, prune_ok, &ru))) return r;
+            if ((r = planner.cut_plan(k & 1, b.kept == CUT_KEPT_FPN, nb, cutv.data(), ru))) return r;
+            if ((r = forward_model(m, nb, cutv.data(), FwdRequest::detect(det_at(D, (size_t)nb), prune_ok, &ru)))) return r;
             b.VV = 2 * nb + nr2; n_rest = nr2; rest_slot = 2 * nb; rest_views = rest.data();
-        } else if (b.kept) {
+        } else if (b.kept != CUT_KEPT_NONE) {
             c->cut_fallbacks++;
         }
         for (int f = 0; f < fwd_count(n_rest); f++) {
             int a0, nv; fwd_span(n_rest, f, &a0, &nv);
             const size_t o = (size_t)(rest_slot + a0);
-            if ((r = forward_model(m, nv, rest_views + a0, det_at(D, o), audit ? d_vm[k & 1] + o * CALD_VM : nullptr, prune_ok))) return r;
+            const FwdRequest rq = FwdRequest::detect(det_at(D, o), prune_ok).audited(audit ? d_vm[k & 1] + o * CALD_VM : nullptr);
+            if ((r = forward_model(m, nv, rest_views + a0, rq))) return r;
         }
         return 0;
     }
@@ -589,7 +370,7 @@ struct SweepRun {
             // RetinaNet rows carry no proposal: "another proposal" reads "another box" -- the detections of one anchor (one per class above
             // the threshold) share box, scores_cls and prob_max, as those of one proposal do
             ScoreArgs pa = sa;
-            if (retina) pa.det.props = pa.det.boxes;
+            if (m->cfg.arch == CALD_ARCH_RETINANET) pa.det.props = pa.det.boxes;
             launch_pair_audit(pa, d_pm, c->stream);
             if (hipMemcpyAsync(b.h_vm, d_vm[k & 1], (size_t)VV * CALD_VM * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
                 (P && hipMemcpyAsync(b.h_pm, d_pm, (size_t)P * 2 * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess)) return fail(CALD_ERR_HIP, "D2H of the audit records failed");
@@ -672,44 +453,6 @@ struct SweepRun {
 };
 }  // namespace
 
-// Test hook: the cut_out forward of a sweep batch on its own.  The views without their rectangles run as the reference forward (retaining
-// what the model's reuse mode retains), then the views as given run as the cut_out forward over it -- mode 0: a plain dense forward -- and
-// leave their detections in `out` and their tensors to cald_debug_tensor.  prune != 0: both forwards take the certified pruning's path.
-extern "C" int cald_debug_cutout_forward(cald_model* m, int n_views, const cald_view* views, const cald_dets* out, int prune) {
-    if (!m || !views || !out || n_views < 1 || n_views > CALD_MAX_VIEWS) return fail(CALD_ERR_INVALID, "bad argument");
-    if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
-    std::vector<ViewDesc> cut(n_views), ref(n_views);
-    for (int i = 0; i < n_views; i++) {
-        const cald_view& v = views[i];
-        if (v.nrect < 0 || v.nrect > CALD_MAX_CUT || v.flip || v.noise_dev) return fail(CALD_ERR_INVALID, "view %d is no cut_out view", i);
-        cut[i] = plain_view(v.image_dev, v.H, v.W); ref[i] = cut[i];
-        cut[i].nrect = v.nrect;
-        for (int q = 0; q < 4 * v.nrect; q++) cut[i].rects[q] = v.rects[q];
-    }
-    DetBuffers det;
-    det.boxes = out->boxes_dev; det.scores = out->scores_dev; det.labels = (long long*)out->labels_dev; det.props = out->props_dev;
-    det.prob_max = out->prob_max_dev; det.scores_cls = out->scores_cls_dev; det.count = out->count_dev;
-    det.cap = out->cap; det.C = m->cfg.num_classes;
-    if (!det.boxes || !det.scores || !det.labels || !det.props || !det.prob_max || !det.scores_cls || !det.count)
-        return fail(CALD_ERR_INVALID, "output buffers must all be provided");
-    SweepRun R{m, n_views, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false};
-    R.c = m->ctx;
-    HIPCHK(hipSetDevice(R.c->device));
-    R.prune_ok = prune != 0;
-    R.init_blocks();
-    R.reuse = (m->cr.mode < 0 ? cut_reuse_env() : m->cr.mode != 0) && m->cfg.precision == CALD_PRECISION_FP32 && R.nblk < CUT_MAX_BLOCKS;
-    R.rplan.resize(1);
-    R.bt[0].nb = n_views;
-    if (m->prune && R.prune_ok) HIPCHK(hipMemsetAsync(R.c->d_prune_check, 0, 8, R.c->stream));
-    FwdReuse ru, ru2;
-    int rc = R.retain(0, ref.data(), ru);
-    if (!rc) rc = forward_model(m, n_views, ref.data(), det, nullptr, R.prune_ok, R.bt[0].kept ? &ru : nullptr);
-    if (!rc && R.bt[0].kept) rc = R.cut_plan(0, n_views, cut.data(), ru2);
-    if (!rc) rc = forward_model(m, n_views, cut.data(), det, nullptr, R.prune_ok, R.bt[0].kept ? &ru2 : nullptr);
-    if (!rc) HIPCHK(hipStreamSynchronize(R.c->stream));
-    return rc;
-}
-
 static int sweep_checked(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W,
                          const int64_t* pool_pos, const cald_sweep_cfg* cfg, double* consistency_out, double* cls_corr_out, float* margins_out) {
     SweepRun first{m, n_images, images_dev, H, W, pool_pos, cfg, consistency_out, cls_corr_out, margins_out, false};
@@ -753,26 +496,79 @@ extern "C" int cald_sweep_ltc(cald_model* m, int n_images, const uint8_t* const*
     if (m->cfg.arch != CALD_ARCH_FRCNN) return fail(CALD_ERR_INVALID, "lt_c needs the Faster R-CNN outputs (props)");
     cald_ctx* c = m->ctx;
     HIPCHK(hipSetDevice(c->device));
-    int B = batch_images > 0 ? batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    const int B = sweep_batch(batch_images, 64);
     { int rc0 = ensure_det(m, m->sweep_det, m->sweep_det_views, B); if (rc0) return rc0; }
-    float* d_out = nullptr; HIPCHK(hipMalloc((void**)&d_out, (size_t)B * 4));
+    ScopedDev scratch(c->stream); float* d_out = nullptr;
+    if (int rc0 = scratch.alloc(&d_out, (size_t)B * 4)) return rc0;
     std::vector<float> h(B);
     int rc = 0;
     for (int i0 = 0; i0 < n_images && !rc; i0 += B) {
         const int nb = (n_images - i0 < B) ? n_images - i0 : B;
         std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
-        if ((rc = forward_model(m, nb, views.data(), m->sweep_det))) break;
+        if ((rc = forward_model(m, nb, views.data(), FwdRequest::detect(m->sweep_det)))) break;
         launch_lt_uncertainty(m->sweep_det, nb, d_out, c->stream);
         if (hipMemcpyAsync(h.data(), d_out, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "lt_c scoring failed: %s", hipGetErrorString(hipGetLastError())); break; }
         for (int i = 0; i < nb; i++) uncertainty_out[i0 + i] = (double)h[i];
     }
-    hipStreamSynchronize(c->stream); hipFree(d_out);
     return rc;
 }
 
-// ssm/ssm_helper.py:9-33 get_uncertainty: one forward per image, the SSM tail (ssm.hip) in place of the ordinary one.  Per batch the
-// flags and counts come back first, then exactly the batch's rows, appended to the caller's arrays.
+int cald_host::ssm_collect_rows(hipStream_t st, const char* hook, int image0, const SsmRows& R, int V, size_t score_cols, size_t label_cols, int64_t view_rows,
+                                int64_t row0, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out, int8_t* labels_out, int* total_out) {
+    int total = 0;
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(al_out, R.al, (size_t)V * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(count_out, R.count, (size_t)V * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&total, R.total, 4, hipMemcpyDeviceToHost));
+    int64_t sum = 0;
+    for (int i = 0; i < V; i++) {
+        const int n = count_out[i];
+        if (n < 0 || n > view_rows || (al_out[i] && n) || (hook && n != total))
+            return hook ? fail(CALD_ERR_HIP, "%s postprocess returned %d rows (al %d, total %d, cap %d)", hook, n, al_out[i], total, (int)view_rows)
+                        : fail(CALD_ERR_HIP, "ssm postprocess returned %d rows for image %d (cap %lld)", n, image0 + i, (long long)view_rows);
+        sum += n;
+    }
+    if (sum != total) return fail(CALD_ERR_HIP, "ssm postprocess: the batch's rows (%d) are not the sum of its images' (%lld)", total, (long long)sum);
+    if (total && row0 + total <= rows_cap) {
+        HIPCHK(hipMemcpy(boxes_out + row0 * 4, R.boxes, (size_t)total * 16, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(scores_out + row0 * score_cols, R.scores, (size_t)total * score_cols * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(labels_out + row0 * label_cols, R.labels, (size_t)total * label_cols, hipMemcpyDeviceToHost));
+    }
+    *total_out = total;
+    return 0;
+}
+
+// ssm/ssm_helper.py:9-33 get_uncertainty, the body of both SSM sweeps: one forward per image with the tail `tail` names in place of the
+// ordinary one -- Faster R-CNN's (ssm.hip), or RetinaNet's (retina_ssm.hip), whose host stop (the picks of the batch's images, in order) sits
+// inside forward_model, between the tail's two phases.  Per batch the flags and counts come back first, then exactly the batch's rows,
+// appended to the caller's arrays.  The entry points have checked the arguments and the architecture.
+static int ssm_sweep(cald_model* m, FwdRequest::Tail tail, cald_ssm_pick_fn pick, void* user, const char* name, int n_images, const uint8_t* const* images_dev,
+                     const int* H, const int* W, int batch_images, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out,
+                     int8_t* labels_out, int64_t* rows_needed_out) {
+    if (n_images < 0 || rows_cap < 0) return fail(CALD_ERR_INVALID, "n_images and rows_cap must be >= 0");
+    cald_ctx* c = m->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    const int B = sweep_batch(batch_images, 64);
+    const bool retina = tail == FwdRequest::RETINA_SSM;
+    // Faster R-CNN: C - 1 foreground classes, a score and a label per class and row; RetinaNet: C classes, one score and C - 1 labels per row
+    const size_t C = (size_t)m->cfg.num_classes, score_cols = retina ? 1 : C - 1, label_cols = C - 1;
+    const int64_t view_rows = (int64_t)(retina ? C : C - 1) * m->cfg.detections_per_img;
+    int64_t rows = 0;
+    for (int i0 = 0; i0 < n_images; i0 += B) {
+        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
+        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
+        FwdSsm fs; FwdRetinaSsm fr; fr.pick = pick; fr.user = user; fr.image0 = i0;
+        int rc, total = 0;
+        if ((rc = forward_model(m, nb, views.data(), retina ? FwdRequest::retina_ssm_tail(&fr) : FwdRequest::ssm_tail(&fs)))) return rc;
+        if ((rc = ssm_collect_rows(c->stream, nullptr, i0, retina ? fr.out.rows() : fs.out.rows(), nb, score_cols, label_cols, view_rows, rows, rows_cap,
+                                   al_out + i0, count_out + i0, boxes_out, scores_out, labels_out, &total))) return rc;
+        rows += total;
+    }
+    *rows_needed_out = rows;
+    if (rows > rows_cap) return fail(CALD_ERR_INVALID, "%s: rows_cap %lld is too small, the sweep needs %lld rows", name, (long long)rows_cap, (long long)rows);
+    return 0;
+}
 extern "C" int cald_sweep_ssm(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
                               int64_t rows_cap, int* al_out, int* count_out, float* boxes_out, float* scores_out, int8_t* labels_out,
                               int64_t* rows_needed_out) {
@@ -780,45 +576,9 @@ extern "C" int cald_sweep_ssm(cald_model* m, int n_images, const uint8_t* const*
         return fail(CALD_ERR_INVALID, "null argument");
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
     if (m->cfg.arch != CALD_ARCH_FRCNN) return fail(CALD_ERR_INVALID, "the SSM sweep covers Faster R-CNN only");
-    if (n_images < 0 || rows_cap < 0) return fail(CALD_ERR_INVALID, "n_images and rows_cap must be >= 0");
-    cald_ctx* c = m->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    int B = batch_images > 0 ? batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
-    const size_t K = (size_t)m->cfg.num_classes - 1;
-    const int64_t view_rows = (int64_t)K * m->cfg.detections_per_img;
-    const DetBuffers none{};
-    int64_t rows = 0;
-    for (int i0 = 0; i0 < n_images; i0 += B) {
-        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
-        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
-        FwdSsm fs; int rc;
-        if ((rc = forward_model(m, nb, views.data(), none, nullptr, false, nullptr, nullptr, &fs))) return rc;
-        int total = 0;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(al_out + i0, fs.out.al, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(count_out + i0, fs.out.count, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&total, fs.out.total, 4, hipMemcpyDeviceToHost));
-        int64_t sum = 0;
-        for (int i = 0; i < nb; i++) {
-            const int n = count_out[i0 + i];
-            if (n < 0 || n > view_rows || (al_out[i0 + i] && n)) return fail(CALD_ERR_HIP, "ssm postprocess returned %d rows for image %d (cap %lld)", n, i0 + i, (long long)view_rows);
-            sum += n;
-        }
-        if (sum != total) return fail(CALD_ERR_HIP, "ssm postprocess: the batch's rows (%d) are not the sum of its images' (%lld)", total, (long long)sum);
-        if (total && rows + total <= rows_cap) {
-            HIPCHK(hipMemcpy(boxes_out + rows * 4, fs.out.boxes, (size_t)total * 16, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(scores_out + rows * K, fs.out.scores, (size_t)total * K * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(labels_out + rows * K, fs.out.labels, (size_t)total * K, hipMemcpyDeviceToHost));
-        }
-        rows += total;
-    }
-    *rows_needed_out = rows;
-    if (rows > rows_cap) return fail(CALD_ERR_INVALID, "cald_sweep_ssm: rows_cap %lld is too small, the sweep needs %lld rows", (long long)rows_cap, (long long)rows);
-    return 0;
+    return ssm_sweep(m, FwdRequest::SSM, nullptr, nullptr, "cald_sweep_ssm", n_images, images_dev, H, W, batch_images, rows_cap, al_out, count_out, boxes_out,
+                     scores_out, labels_out, rows_needed_out);
 }
-
-// ssm/ssm_helper.py:9-33 get_uncertainty on RetinaNet: cald_sweep_ssm's loop with the tail of retina_ssm.hip, whose host stop (the picks of
-// the batch's images, in order) sits inside forward_model, between the tail's two phases
 extern "C" int cald_sweep_ssm_retina(cald_model* m, int n_images, const uint8_t* const* images_dev, const int* H, const int* W, int batch_images,
                                      cald_ssm_pick_fn pick, void* user, int64_t rows_cap, int* al_out, int* count_out, float* boxes_out,
                                      float* scores_out, int8_t* labels_out, int64_t* rows_needed_out) {
@@ -827,42 +587,8 @@ extern "C" int cald_sweep_ssm_retina(cald_model* m, int n_images, const uint8_t*
     if (!m->finalized) return fail(CALD_ERR_STATE, "model not finalized");
     if (m->cfg.arch != CALD_ARCH_RETINANET) return fail(CALD_ERR_INVALID, "cald_sweep_ssm_retina covers RetinaNet only (Faster R-CNN: cald_sweep_ssm)");
     if (m->cfg.num_classes < 2) return fail(CALD_ERR_INVALID, "the RetinaNet SSM tail needs at least two classes (labels have K - 1 columns)");
-    if (n_images < 0 || rows_cap < 0) return fail(CALD_ERR_INVALID, "n_images and rows_cap must be >= 0");
-    cald_ctx* c = m->ctx;
-    HIPCHK(hipSetDevice(c->device));
-    int B = batch_images > 0 ? batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
-    const size_t K = (size_t)m->cfg.num_classes;
-    const int64_t view_rows = (int64_t)K * m->cfg.detections_per_img;
-    const DetBuffers none{};
-    int64_t rows = 0;
-    for (int i0 = 0; i0 < n_images; i0 += B) {
-        const int nb = (n_images - i0 < B) ? n_images - i0 : B;
-        std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
-        FwdRetinaSsm fs; fs.pick = pick; fs.user = user; fs.image0 = i0;
-        int rc;
-        if ((rc = forward_model(m, nb, views.data(), none, nullptr, false, nullptr, nullptr, nullptr, &fs))) return rc;
-        int total = 0;
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(al_out + i0, fs.out.al, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(count_out + i0, fs.out.count, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(&total, fs.out.total, 4, hipMemcpyDeviceToHost));
-        int64_t sum = 0;
-        for (int i = 0; i < nb; i++) {
-            const int n = count_out[i0 + i];
-            if (n < 0 || n > view_rows || (al_out[i0 + i] && n)) return fail(CALD_ERR_HIP, "ssm postprocess returned %d rows for image %d (cap %lld)", n, i0 + i, (long long)view_rows);
-            sum += n;
-        }
-        if (sum != total) return fail(CALD_ERR_HIP, "ssm postprocess: the batch's rows (%d) are not the sum of its images' (%lld)", total, (long long)sum);
-        if (total && rows + total <= rows_cap) {
-            HIPCHK(hipMemcpy(boxes_out + rows * 4, fs.out.boxes, (size_t)total * 16, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(scores_out + rows, fs.out.scores, (size_t)total * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(labels_out + rows * (K - 1), fs.out.labels, (size_t)total * (K - 1), hipMemcpyDeviceToHost));
-        }
-        rows += total;
-    }
-    *rows_needed_out = rows;
-    if (rows > rows_cap) return fail(CALD_ERR_INVALID, "cald_sweep_ssm_retina: rows_cap %lld is too small, the sweep needs %lld rows", (long long)rows_cap, (long long)rows);
-    return 0;
+    return ssm_sweep(m, FwdRequest::RETINA_SSM, pick, user, "cald_sweep_ssm_retina", n_images, images_dev, H, W, batch_images, rows_cap, al_out, count_out,
+                     boxes_out, scores_out, labels_out, rows_needed_out);
 }
 
 // ls_c_train.py:108-155 get_uncertainty: reference view + GaussianNoise(image, 8 i), i = 1..6 (six consecutive torch.randn
@@ -878,7 +604,7 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
     cald_ctx* c = m->ctx;
     HIPCHK(hipSetDevice(c->device));
     const int A = 6;
-    int B = batch_images > 0 ? batch_images : 32; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    const int B = sweep_batch(batch_images, 32);
     const int cap = m->det_cap(), VT = B * (1 + A), P_MAX = B * A;
     { int rc0 = ensure_det(m, m->sweep_det, m->sweep_det_views, VT); if (rc0) return rc0; }
     DetBuffers& D = m->sweep_det;
@@ -897,7 +623,7 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
     for (int i0 = 0; i0 < n_images && !rc; i0 += B) {
         const int nb = (n_images - i0 < B) ? n_images - i0 : B;
         std::vector<ViewDesc> views = ref_views(images_dev, H, W, i0, nb);
-        if ((rc = forward_model(m, nb, views.data(), D))) break;
+        if ((rc = forward_model(m, nb, views.data(), FwdRequest::detect(D)))) break;
         if (hipMemcpyAsync(h_count.data(), D.count, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipMemcpyAsync(h_pm.data(), D.prob_max, (size_t)nb * cap * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
             hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(CALD_ERR_HIP, "D2H of reference detections failed"); break; }
@@ -934,7 +660,7 @@ extern "C" int cald_sweep_lsc(cald_model* m, int n_images, const uint8_t* const*
         // evenly sized forwards, as cald_sweep issues them (192 views run 96 + 96, not 128 + 64; CALD_MAX_VIEWS is the hard cap)
         for (int f = 0; f < fwd_count(na) && !rc; f++) {
             int a0, nv; fwd_span(na, f, &a0, &nv);
-            rc = forward_model(m, nv, aviews.data() + a0, det_at(D, (size_t)(nb + a0)));
+            rc = forward_model(m, nv, aviews.data() + a0, FwdRequest::detect(det_at(D, (size_t)(nb + a0))));
         }
         if (rc) break;
         const int P = (int)pair_img.size();

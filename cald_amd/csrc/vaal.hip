@@ -346,7 +346,7 @@ extern "C" int cald_sweep_vaal(cald_ctx* c, cald_vaal* v, int n_images, const ui
     if (v->ctx != c) return fail(CALD_ERR_INVALID, "the VAAL model belongs to another context");
     const int mode = cfg ? cfg->bn_mode : CALD_VAAL_BN_BATCH;
     if (mode != CALD_VAAL_BN_BATCH && mode != CALD_VAAL_BN_RUNNING) return fail(CALD_ERR_INVALID, "bn_mode %d is not a CALD_VAAL_BN_* value", mode);
-    int B = cfg && cfg->batch_images > 0 ? cfg->batch_images : 64; if (B > CALD_MAX_VIEWS) B = CALD_MAX_VIEWS;
+    int B = sweep_batch(cfg ? cfg->batch_images : 0, 64);
     if (B > n_images) B = n_images;
     for (int i = 0; i < n_images; i++)
         if (!images_dev[i] || H[i] < 1 || W[i] < 1 || (long long)H[i] * W[i] > (1ll << 28)) return fail(CALD_ERR_INVALID, "image %d is malformed", i);

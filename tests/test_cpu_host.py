@@ -990,3 +990,16 @@ def test_roi_sample_host_labels_balanced_sampling_and_index_lists():
         assert pidx.tolist() == [r * pred_ld + ncls + 4 * int(lab[r]) for r in range(R) if lab[r] > 0]
     with pytest.raises(RuntimeError):
         train_ops.roi_sample_host([10], [1], [11], np.zeros(12, np.int32), np.ones(1, np.int64), np.zeros(11), 8, 0.25, 108, 21)
+
+
+def test_sweep_host_folds_run_clean_as_a_sanitized_program(tmp_path):
+    """The pure-host pieces the sweeps share (host.h sweep_batch: the default for a request <= 0, CALD_MAX_VIEWS above it, the request
+    otherwise; dets_from_abi: every missing buffer refused with the entry points' text, nothing written) in tests/host_fold_check.hip, a
+    program of its own built with the address and undefined-behaviour sanitizers on its host code."""
+    import subprocess
+    exe = str(tmp_path / "host_fold_check")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-Wno-unused-value", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-Xarch_host", "-fno-sanitize-recover=undefined", "-o", exe, os.path.join(ROOT, "tests", "host_fold_check.hip")])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout

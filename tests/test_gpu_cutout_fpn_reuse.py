@@ -1,4 +1,4 @@
-"""cut_out reuse through the FPN output convs (sweep.hip retain / cut_plan, forward.hip fpn, conv_p4.hip's grouped gathered launch with the
+"""cut_out reuse through the FPN output convs (cutout_reuse.hip retain / cut_plan, forward.hip fpn, conv_p4.hip's grouped gathered launch with the
 pruning's extras): the cut_out forward patches the reference forward's retained P2..P5 -- and, under the certified pruning, P2 / P3's split
 copy and energy -- on the output dirty sets.  Nothing may change by a bit: sweeps with the reuse off, on, and on with every stage dense;
 single cut_out forwards tensor by tensor; pruning on and off; the extended retention slot refused."""

@@ -1,4 +1,4 @@
-"""cut_out reuse (sweep.hip SweepRun + conv_p4.hip's gathered rows): the batch's cut_out views recompute only the pixels of their first
+"""cut_out reuse (cutout_reuse.hip CutPlanner + conv_p4.hip's gathered rows): the batch's cut_out views recompute only the pixels of their first
 three stages that the filled rectangles reach, over the reference forward's retained block outputs.  The results must not change by a
 bit: reuse on, off, and on with every stage forced dense give identical consistency and cls_corr."""
 import ctypes as C
