@@ -65,7 +65,7 @@ class PackJob(C.Structure):
     """cald_pack_job of include/cald_hip.h: the arguments of one cald_train_pack_conv call (device pointers)."""
     _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p),
                 ("Cout", C.c_int), ("Cin", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("CinK", C.c_int), ("mode", C.c_int),
-                ("packed", C.c_void_p)]
+                ("packed", C.c_void_p), ("w16", C.c_void_p), ("w16_S", C.c_int)]
 
 
 class LLCfg(C.Structure):
@@ -251,6 +251,9 @@ SIGNATURES = {
     # training step (device pointers as c_void_p)
     "cald_train_packed_floats": (C.c_int, [C.c_int] * 6 + [c_i64]),
     "cald_train_pack_conv": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p]),
+    "cald_train_packed16_bytes": (C.c_int, [C.c_int] * 6 + [c_i64]),
+    "cald_train_f16x3_scale": (C.c_int, [C.c_float, c_i, c_f]),
+    "cald_train_pack_conv16": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int]),
     "cald_train_pack_plan_scratch_floats": (C.c_int, [C.c_int, C.POINTER(PackJob), c_i64]),
     "cald_train_pack_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(PackJob), C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
     "cald_train_pack_plan_run": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -259,6 +262,12 @@ SIGNATURES = {
                         + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "cald_train_conv_group": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)] + [C.c_int] * 8
                               + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]),
+    "cald_train_conv_f16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 8
+                              + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+                              + [C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_char_p)]),
+    "cald_train_conv_group_f16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)] + [C.c_int] * 8
+                                    + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]
+                                    + [C.POINTER(C.c_void_p), c_f, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]),
     "cald_train_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cald_train_linear_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,

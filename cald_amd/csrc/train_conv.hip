@@ -1,5 +1,5 @@
 // train_conv.hip -- the inference kernels on a dense batch (task_model(images, targets) in train mode, cald_train.py:40-74): forward conv /
-// linear layers and their data gradients (conv_p4.hip / conv_mfma.hip on the packs of train_pack.hip; a stride-2 layer's dY is first
+// linear layers (on conv_h3.hip / conv_h4.hip where the caller hands in the pack's split twin) and their data gradients (conv_p4.hip / conv_mfma.hip on the packs of train_pack.hip; a stride-2 layer's dY is first
 // scattered onto the stride-1 grid, train_elementwise.hip), and the input side of the training forward: GeneralizedRCNNTransform
 // (normalize, bilinear resize, zero-pad to the batch size), the stem's max-pool and LastLevelMaxPool on the kernels of elementwise.hip.
 // Activations are dense NHWC batches [N][H][W][C].
@@ -25,9 +25,13 @@ static int conv_args(cald_ctx* c, ConvArgs& a, const PackGeom& g, const float* p
 // in  [N][H][W][CinK];  out [N][Ho][Wo][out_ld] (channels >= Cout of a row are not written);  residual: same geometry as out
 // with row stride Cout... (out_ld == Cout required when residual / up is given);  up: [N][Hup][Wup][Cout] nearest-upsampled and added.
 // flags: bit 0 bias, bit 1 scale/shift (FrozenBatchNorm), bit 2 ReLU.  mode as in cald_train_pack_conv (the packed buffer's).
-extern "C" int cald_train_conv(cald_ctx* c, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
-                               int KH, int KW, int stride, int pad, int mode, int flags, const float* residual, const float* up,
-                               int Hup, int Wup, const float* mask, float* out, int out_ld) {
+// The split twin of the pack (w16, or null) and of activations, checked against the shapes conv_h3.hip takes: a launch with w16 on another
+// shape runs the exact kernels (the dispatcher's fall-through), which know no split activations.
+struct Split16 { const void* w16; float unscale; const void* in16; int ex16; void* out16; };
+static int train_conv(cald_ctx* c, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
+                      int KH, int KW, int stride, int pad, int mode, int flags, const float* residual, const float* up,
+                      int Hup, int Wup, const float* mask, float* out, int out_ld, const Split16& s16, const char** kernel) {
+    if (kernel) *kernel = nullptr;
     if (!c || !in || !packed || !out) TFAIL(CALD_ERR_INVALID, "null argument");
     if (N < 1 || H < 1 || W < 1 || stride < 1) TFAIL(CALD_ERR_INVALID, "bad geometry");
     THIP(hipSetDevice(cald_internal_device(c)));
@@ -46,18 +50,50 @@ extern "C" int cald_train_conv(cald_ctx* c, int N, int H, int W, const float* in
     const bool fused = mask && p4_takes(g, kh * kw);
     if (mask && !fused && (out_ld != g.n_true || out_ld % 4)) TFAIL(CALD_ERR_INVALID, "mask on this shape needs a dense output with C %% 4 == 0");
     a.mask = fused ? mask : nullptr;
-    if (!launch_conv(a, cald_internal_stream(c))) TFAIL(CALD_ERR_UNSUPPORTED, "no conv kernel implements this layer's features");
+    if (s16.w16) {
+        if ((mode != 0 && mode != 2) || mask) TFAIL(CALD_ERR_INVALID, "w16 belongs to a forward pack and takes no mask");
+        if (h3_takes(g, KH * KW, mode)) { a.w16 = s16.w16; a.w16_unscale = s16.unscale; }
+    }
+    // Split activations exist for conv_h3 / conv_h4 alone: refuse every launch with them that those would not take (the exact kernels it
+    // would fall through to read a twin as fp32) -- no w16 on a taking shape, the 4-channel stem, residual AND up, channels not in 16s
+    const bool split_act = s16.in16 || s16.ex16 || s16.out16;
+    if (split_act) {
+        if (!a.w16 || g.cin_conv == 4 || (residual && up) || g.n_true % 16 || (s16.in16 && g.cin_conv % 16) ||
+            ((s16.ex16 || s16.out16) && out_ld != g.n_true) || (s16.ex16 && !residual && !up))
+            TFAIL(CALD_ERR_INVALID, "split activations need w16 on a shape conv_h3 takes, not residual and up together, channels %% 16 == 0 and out_ld == Cout");
+        a.in16 = (const unsigned*)s16.in16; a.ex16 = s16.ex16 ? 1 : 0; a.out16 = (unsigned*)s16.out16;
+    }
+    const char* name = launch_conv(a, cald_internal_stream(c));
+    if (!name) TFAIL(CALD_ERR_UNSUPPORTED, "no conv kernel implements this layer's features");
+    if (split_act && strncmp(name, "conv_h", 6) != 0 && strncmp(name, "none", 4) != 0)      // (cannot happen while h3_takes mirrors conv_h3.hip)
+        TFAIL(CALD_ERR_STATE, "a launch with split activations ran on %s, which reads them as fp32", name);
+    if (kernel) *kernel = name;
     if (mask && !fused) launch_relu_bwd(out, mask, nullptr, (long long)N * Ho * Wo * out_ld / 4, out_ld / 4, cald_internal_stream(c));
     THIP(hipGetLastError());
     return 0;
+}
+extern "C" int cald_train_conv(cald_ctx* c, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
+                               int KH, int KW, int stride, int pad, int mode, int flags, const float* residual, const float* up,
+                               int Hup, int Wup, const float* mask, float* out, int out_ld) {
+    return train_conv(c, N, H, W, in, CinK, packed, Cout, Cin, KH, KW, stride, pad, mode, flags, residual, up, Hup, Wup, mask, out, out_ld,
+                      Split16{nullptr, 1.0f, nullptr, 0, nullptr}, nullptr);
+}
+extern "C" int cald_train_conv_f16x3(cald_ctx* c, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
+                                     int KH, int KW, int stride, int pad, int mode, int flags, const float* residual, const float* up,
+                                     int Hup, int Wup, const float* mask, float* out, int out_ld, const void* w16, float w16_unscale,
+                                     const void* in16, int ex16, void* out16, const char** kernel) {
+    return train_conv(c, N, H, W, in, CinK, packed, Cout, Cin, KH, KW, stride, pad, mode, flags, residual, up, Hup, Wup, mask, out, out_ld,
+                      Split16{w16, w16_unscale, in16, ex16, out16}, kernel);
 }
 
 // The same layer shape applied to several tensors in ONE launch (the pyramid levels under shared-weight heads; problems may carry
 // different weights of equal shape, e.g. RetinaNet's two towers): workgroups of the small levels fill the tail of the large ones.
 // Falls back to one launch per problem when the shape does not qualify for the grouped kernel (conv_p4.hip launch_conv_p4_group).
-extern "C" int cald_train_conv_group(cald_ctx* c, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
-                                     int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
-                                     float* const* outs, int out_ld) {
+static int train_conv_group(cald_ctx* c, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
+                            int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
+                            float* const* outs, int out_ld, const void* const* w16, const float* w16_unscale, const void* const* in16,
+                            const char** kernels) {
+    if (kernels) for (int i = 0; i < n && i < CALD_MAX_GROUP; i++) kernels[i] = nullptr;
     if (!c || !hw || !ins || !packed || !outs) TFAIL(CALD_ERR_INVALID, "null argument");
     if (n < 1 || n > CALD_MAX_GROUP) TFAIL(CALD_ERR_INVALID, "1..%d problems per group", CALD_MAX_GROUP);
     THIP(hipSetDevice(cald_internal_device(c)));
@@ -66,6 +102,9 @@ extern "C" int cald_train_conv_group(cald_ctx* c, int n, int N, const int* hw, c
     const int kh = mode >= 2 ? 1 : KH, kw = mode >= 2 ? 1 : KW;
     if (out_ld < g.n_true) TFAIL(CALD_ERR_INVALID, "out_ld < Cout");
     if (masks && !p4_takes(g, kh * kw)) TFAIL(CALD_ERR_INVALID, "masks need a shape the tiled kernel covers");
+    if (w16 && (!w16_unscale || (mode != 0 && mode != 2) || masks)) TFAIL(CALD_ERR_INVALID, "w16 belongs to forward packs, comes with its unscale and takes no masks");
+    const bool split = w16 && h3_takes(g, KH * KW, mode);
+    if (in16 && (!split || g.cin_conv % 16)) TFAIL(CALD_ERR_INVALID, "split inputs need w16 on a shape conv_h3 takes and channels %% 16 == 0");
     ConvArgs probs[CALD_MAX_GROUP];
     for (int i = 0; i < n; i++) {
         const int H = hw[2 * i], W = hw[2 * i + 1];
@@ -73,12 +112,31 @@ extern "C" int cald_train_conv_group(cald_ctx* c, int n, int N, const int* hw, c
         if (H < 1 || W < 1 || Ho < 1 || Wo < 1 || !ins[i] || !outs[i] || !packed[i]) TFAIL(CALD_ERR_INVALID, "bad problem %d", i);
         if (int rc = conv_args(c, probs[i], g, packed[i], flags, N, H, W, Ho, Wo, kh, kw, stride, pad, ins[i], outs[i], out_ld)) return rc;
         probs[i].mask = masks ? masks[i] : nullptr;
+        if (split) {
+            if (!w16[i]) TFAIL(CALD_ERR_INVALID, "problem %d has no w16", i);
+            probs[i].w16 = w16[i]; probs[i].w16_unscale = w16_unscale[i];
+            if (in16) probs[i].in16 = (const unsigned*)in16[i];
+        }
     }
     const char* names[CALD_MAX_GROUP];
     launch_conv_group(probs, n, cald_internal_stream(c), names);
     for (int i = 0; i < n; i++) if (!names[i]) TFAIL(CALD_ERR_UNSUPPORTED, "no conv kernel implements problem %d's features", i);
+    if (in16) for (int i = 0; i < n; i++) if (in16[i] && strncmp(names[i], "conv_h", 6) != 0 && strncmp(names[i], "none", 4) != 0)
+        TFAIL(CALD_ERR_STATE, "problem %d with a split input ran on %s, which reads it as fp32", i, names[i]);
+    if (kernels) for (int i = 0; i < n; i++) kernels[i] = names[i];
     THIP(hipGetLastError());
     return 0;
+}
+extern "C" int cald_train_conv_group(cald_ctx* c, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
+                                     int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
+                                     float* const* outs, int out_ld) {
+    return train_conv_group(c, n, N, hw, ins, CinK, packed, Cout, Cin, KH, KW, stride, pad, mode, flags, masks, outs, out_ld, nullptr, nullptr, nullptr, nullptr);
+}
+extern "C" int cald_train_conv_group_f16x3(cald_ctx* c, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
+                                           int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
+                                           float* const* outs, int out_ld, const void* const* w16, const float* w16_unscale,
+                                           const void* const* in16, const char** kernels) {
+    return train_conv_group(c, n, N, hw, ins, CinK, packed, Cout, Cin, KH, KW, stride, pad, mode, flags, masks, outs, out_ld, w16, w16_unscale, in16, kernels);
 }
 
 // images[i]: device uint8 [H_i][W_i][3]; hw = host {H_0, W_0, Hr_0, Wr_0, ...} (source size, resized size); remainders[i]: optional

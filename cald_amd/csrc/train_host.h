@@ -58,6 +58,13 @@ inline PackGeom pack_geom(int Cout, int Cin, int KH, int KW, int CinK, int mode)
     g.floats = 2ll * g.Kpad * g.NPad + 3ll * g.NPad;
     return g;
 }
+// Whether conv_h3.hip / conv_h4.hip take a FORWARD launch on this pack (the geometric part of conv_h3.hip's h3_refuses, model.hip pack_conv's
+// `tiled`): only such a pack has a split twin (train_pack.hip), and only such a launch may carry split activations (train_conv.hip).
+// taps: KH * KW of the pack's torch weight; a mode-2 pack is applied as a 1 x 1 conv over taps * Cin channels.
+inline bool h3_takes(const PackGeom& g, int taps, int mode) {
+    if (mode != 0 && mode != 2) return false;
+    return g.NPad % 64 == 0 && ((g.cin_conv % 16 == 0 && (mode == 2 ? 1 : taps) <= 32) || g.cin_conv == 4);
+}
 inline bool p4_takes(const PackGeom& g, int taps) { return g.NPad % 64 == 0 && g.cin_conv % 16 == 0 && taps <= 32; }   // the tiled kernel (conv_p4.hip) covers the shape
 
 // train_targets.hip: the AnchorGenerator base anchors of the five levels, base[5][A][4]; returns A (kind 0: Faster R-CNN, 3; kind 1: RetinaNet, 9)

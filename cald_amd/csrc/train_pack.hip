@@ -1,6 +1,7 @@
 // train_pack.hip -- weight packing ON THE DEVICE, every step, from the torch-layout parameter tensors into what the inference conv kernels
 // (conv_p4.hip / conv_mfma.hip) read: forward packs, and the spatially flipped, channel-transposed filter on which the same kernels compute
-// the data gradient.  cald_train_packed_floats, cald_train_pack_conv, and the cald_train_pack_plan_* family (every layer's packs in two launches).
+// the data gradient, and -- for a forward_precision "f16x3" trainer -- the split-fp16 twin of a forward pack that conv_h3.hip / conv_h4.hip read.
+// cald_train_packed_floats, cald_train_pack_conv(16), and the cald_train_pack_plan_* family (every layer's packs in two launches).
 #include "train_host.h"
 
 // mode 0: forward      K rows = (tap, ci) of a Cin_k-channel input (Cin_k >= Cin, the input buffer's channel stride), N = Cout
@@ -8,7 +9,8 @@
 // mode 2: forward of a linear layer whose torch weight is [Cout][Cin][taps] (fc6: [1024][256][7*7]) applied to rows laid out
 //         [tap][Cin] (the RoIAlign output [R][49][256]): K rows = tap * Cin + ci
 // mode 3: data gradient of a mode-2 layer: K rows = co of a CinK-channel dY, N = tap * Cin + ci
-struct PackArgs { const float* w; float* wk; float* w4; int Cout, Cin, taps, CinK, Kpad, NPad, mode; const float* rowscale; };
+// w16 (forward packs only, or null): the split-fp16 twin conv_h3.hip / conv_h4.hip read, [Kpad/16][2 (hi, lo)][NPad][16] of w * 2^S
+struct PackArgs { const float* w; float* wk; float* w4; int Cout, Cin, taps, CinK, Kpad, NPad, mode; const float* rowscale; unsigned short* w16; int S; };
 __device__ __forceinline__ void pack_weight_body(const PackArgs& a, long long blk) {
     const long long i = blk * 256 + threadIdx.x;
     if (i >= (long long)a.Kpad * a.NPad) return;
@@ -66,6 +68,20 @@ __device__ __forceinline__ void pack_transpose_body(const PackArgs& a, const flo
         const int kt = k >> 4, kk = k & 15, kq = kk >> 3, j = (kk & 7) >> 1, h = kk & 1;
         a.w4[(((long long)(kt * 2 + kq) * a.NPad + n) * 2 + h) * 4 + j] = v;
     }
+    if (!a.w16) return;
+    // the split twin of the same 32 x 32 tile (model.hip pack_w16, byte for byte): hi = fp16(w * 2^S), lo = fp16(w * 2^S - hi).  16 lanes
+    // write the 16 k of one (k-tile, n) -- 32 contiguous bytes -- and the 32 n of the tile follow each other: 1 KB runs per plane
+    for (int it = 0; it < 4; it++) {
+        const int idx = threadIdx.x + 256 * it, kk = idx & 15, nl = (idx >> 4) & 31, ktl = idx >> 9;
+        const int k = k0 + ktl * 16 + kk, n = n0 + nl;
+        if (k >= a.Kpad || n >= a.NPad) continue;
+        const float x = ldexpf(tile[nl][ktl * 16 + kk], a.S);
+        const _Float16 hi = (_Float16)x;
+        const _Float16 lo = (_Float16)(x - (float)hi);
+        const long long o = ((long long)(k >> 4) * 2 * a.NPad + n) * 16 + kk;
+        a.w16[o] = __builtin_bit_cast(unsigned short, hi);
+        a.w16[o + (long long)a.NPad * 16] = __builtin_bit_cast(unsigned short, lo);
+    }
 }
 __global__ __launch_bounds__(256) void pack_transpose_kernel(PackArgs a, const float* T) { pack_transpose_body(a, T, blockIdx.x, blockIdx.y); }
 __device__ __forceinline__ void pack_vec_body(const float* bias, const float* scale, const float* shift, int n, float* dst, int npad, int blk) {
@@ -103,14 +119,36 @@ extern "C" int cald_train_packed_floats(int Cout, int Cin, int KH, int KW, int C
     *floats_out = pack_geom(Cout, Cin, KH, KW, CinK, mode).floats;
     return 0;
 }
-extern "C" int cald_train_pack_conv(cald_ctx* c, const float* w, const float* bias, const float* scale, const float* shift,
-                                    int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed) {
+// The split twin exists for forward packs of the shapes conv_h3.hip takes (model.hip pack_conv's `tiled`): 0 bytes otherwise.
+static long long w16_bytes(const PackGeom& g, int taps, int mode) {
+    return h3_takes(g, taps, mode) ? 4ll * g.Kpad * g.NPad : 0;
+}
+#define W16_RULE "a split twin needs a forward pack of a shape conv_h3 takes (cald_train_packed16_bytes > 0) and |S| <= 40"
+extern "C" int cald_train_packed16_bytes(int Cout, int Cin, int KH, int KW, int CinK, int mode, int64_t* bytes_out) {
+    if (!bytes_out || Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || mode < 0 || mode > 3) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    *bytes_out = w16_bytes(pack_geom(Cout, Cin, KH, KW, CinK, mode), KH * KW, mode);
+    return 0;
+}
+// model.hip pack_w16's scale: max |w| = f * 2^e, f in [0.5, 1) -> S = 14 - e, clamped to +-40; 0 for an all-zero or non-finite tensor
+extern "C" int cald_train_f16x3_scale(float max_abs, int* S_out, float* unscale_out) {
+    if (!S_out || !unscale_out) TFAIL(CALD_ERR_INVALID, "null argument");
+    int S = 0;
+    if (max_abs > 0.0f && std::isfinite(max_abs)) { int e; std::frexp(max_abs, &e); S = 14 - e; }
+    if (S > 40) S = 40;
+    if (S < -40) S = -40;
+    *S_out = S; *unscale_out = std::ldexp(1.0f, -(S + 4));
+    return 0;
+}
+static int pack_conv(cald_ctx* c, const float* w, const float* bias, const float* scale, const float* shift,
+                     int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed, void* w16, int S) {
     if (!c || !w || !packed) TFAIL(CALD_ERR_INVALID, "null argument");
     if (mode < 0 || mode > 3) TFAIL(CALD_ERR_INVALID, "mode must be 0 (forward), 1 (data gradient), 2 (tap-major linear) or 3 (its data gradient)");
     if (!cink_ok(Cout, Cin, CinK, mode)) TFAIL(CALD_ERR_INVALID, CINK_RULE);
     THIP(hipSetDevice(cald_internal_device(c)));
     const PackGeom g = pack_geom(Cout, Cin, KH, KW, CinK, mode);
-    PackArgs a{w, packed, packed + (long long)g.Kpad * g.NPad, Cout, Cin, KH * KW, CinK, g.Kpad, g.NPad, mode, (mode == 1 || mode == 3) ? scale : nullptr};
+    if (w16 && (!w16_bytes(g, KH * KW, mode) || S < -40 || S > 40)) TFAIL(CALD_ERR_INVALID, W16_RULE);
+    PackArgs a{w, packed, packed + (long long)g.Kpad * g.NPad, Cout, Cin, KH * KW, CinK, g.Kpad, g.NPad, mode, (mode == 1 || mode == 3) ? scale : nullptr,
+               (unsigned short*)w16, S};
     hipStream_t st = cald_internal_stream(c);
     const long long n = (long long)g.Kpad * g.NPad;
     if (mode == 0 || mode == 2) {
@@ -133,6 +171,15 @@ extern "C" int cald_train_pack_conv(cald_ctx* c, const float* w, const float* bi
     THIP(hipGetLastError());
     return 0;
 }
+extern "C" int cald_train_pack_conv(cald_ctx* c, const float* w, const float* bias, const float* scale, const float* shift,
+                                    int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed) {
+    return pack_conv(c, w, bias, scale, shift, Cout, Cin, KH, KW, CinK, mode, packed, nullptr, 0);
+}
+extern "C" int cald_train_pack_conv16(cald_ctx* c, const float* w, const float* bias, const float* scale, const float* shift,
+                                      int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed, void* w16, int S) {
+    if (!w16) TFAIL(CALD_ERR_INVALID, "null argument");
+    return pack_conv(c, w, bias, scale, shift, Cout, Cin, KH, KW, CinK, mode, packed, w16, S);
+}
 
 struct cald_pack_plan {
     int device; PackSeg *seg1, *seg2; PackJobDev* jobs; int nseg1, nseg2; unsigned blocks1, blocks2;
@@ -145,6 +192,8 @@ static int pack_plan_check(int n, const cald_pack_job* jobs) {
         if (!q.weight || !q.packed) TFAIL(CALD_ERR_INVALID, "job %d: null weight / packed", i);
         if (q.Cout < 1 || q.Cin < 1 || q.KH < 1 || q.KW < 1 || q.mode < 0 || q.mode > 3) TFAIL(CALD_ERR_INVALID, "job %d: bad shape / mode", i);
         if (!cink_ok(q.Cout, q.Cin, q.CinK, q.mode)) TFAIL(CALD_ERR_INVALID, "job %d: " CINK_RULE, i);
+        if (q.w16 && (!w16_bytes(pack_geom(q.Cout, q.Cin, q.KH, q.KW, q.CinK, q.mode), q.KH * q.KW, q.mode) || q.w16_S < -40 || q.w16_S > 40))
+            TFAIL(CALD_ERR_INVALID, "job %d: " W16_RULE, i);
     }
     return 0;
 }
@@ -175,7 +224,8 @@ extern "C" int cald_train_pack_plan_create(cald_ctx* c, int n, const cald_pack_j
         const long long nn = (long long)g.Kpad * g.NPad;
         const bool fwd = q.mode == 0 || q.mode == 2;
         PackJobDev& d = dj[i];
-        d.a = PackArgs{q.weight, q.packed, q.packed + nn, q.Cout, q.Cin, q.KH * q.KW, q.CinK, g.Kpad, g.NPad, q.mode, fwd ? nullptr : q.bn_scale};
+        d.a = PackArgs{q.weight, q.packed, q.packed + nn, q.Cout, q.Cin, q.KH * q.KW, q.CinK, g.Kpad, g.NPad, q.mode, fwd ? nullptr : q.bn_scale,
+                       (unsigned short*)q.w16, q.w16_S};
         d.T = nullptr; d.bias = q.bias; d.scale = q.bn_scale; d.shift = q.bn_shift; d.vec = q.packed + 2 * nn; d.n_true = g.n_true;
         d.gx = (g.Kpad + 31) / 32;
         if (fwd) {

@@ -151,7 +151,11 @@ class TrainableDetector(object):
         return dict(zip(self.net.LOSS_NAMES, out))
 
     def train(self, mode=True):
+        """As nn.Module.train().  Over a forward_precision "f16x3" trainer a switch to train mode also re-derives the layers' weight
+        scales (refresh_f16x3_scales): the reference's loops switch once per epoch, where the host has synchronised anyway."""
         self.training = bool(mode)
+        if self.training:
+            self.net.refresh_f16x3_scales()
         return self
 
 

@@ -19,6 +19,14 @@ def _bn_fold(sd, prefix, eps=1e-5):
     return scale.float(), (b - rm * scale).float()
 
 
+def _bn_fold_f32(sd, prefix, eps=1e-5):
+    """The same fold in float32, operation by operation what an inference model's finalize computes (scale = w * (1 / sqrt(var + eps)),
+    shift = b - mean * scale): a forward_precision "f16x3" trainer reproduces HipDetector(precision="f16x3") bit for bit."""
+    w, b, rm, rv = [sd[prefix + s].float().numpy() for s in (".weight", ".bias", ".running_mean", ".running_var")]
+    scale = w * (np.float32(1.0) / np.sqrt(rv + np.float32(eps)))
+    return torch.from_numpy(scale), torch.from_numpy(b - rm * scale)
+
+
 def choose_k(n, k, generator=None):
     """k distinct indices of range(n), every k-subset equally likely -- what ``torch.randperm(n)[:k]`` of torchvision's
     BalancedPositiveNegativeSampler selects, without permuting all n candidates (n is ~10^5 RPN negatives per image):
@@ -125,13 +133,16 @@ class _Conv(object):
         self.out_ld = out_ld if out_ld is not None else self.Cout
         self._pk = self._pkd = None
         self._pk_version = self._pkd_version = -1
+        self.w16_S = None               # forward_precision "f16x3": the weight scale of the forward pack's split twin (refresh_f16x3_scales)
         self.x = None
+        self.out16 = None               # the split twin of the last forward's output, where fwd(split_out=True) wrote one
         net.convs.append(self)
 
     def _packed(self):
         if self._pk is None or (self.trainable and self._pk_version != self.net.version):
-            buf = self._pk.buf if self._pk is not None else None
-            self._pk = ops.PackedConv(self.w, self.b, self.scale, self.shift, CinK=self.cin_k, mode=self.mode, taps=self.taps, out=buf)
+            buf, buf16 = (self._pk.buf, self._pk.w16) if self._pk is not None else (None, None)
+            self._pk = ops.PackedConv(self.w, self.b, self.scale, self.shift, CinK=self.cin_k, mode=self.mode, taps=self.taps, out=buf,
+                                      w16_S=self.w16_S, w16_out=buf16)
             self._pk_version = self.net.version
             self._pkd_version = -1
         return self._pk
@@ -139,7 +150,8 @@ class _Conv(object):
     def _plan_packs(self):
         """The forward and data-gradient PackedConv of a trainable layer for a PackPlan (allocated, not packed, on first use)."""
         if self._pk is None:
-            self._pk = ops.PackedConv(self.w, self.b, self.scale, self.shift, CinK=self.cin_k, mode=self.mode, taps=self.taps, pack=False)
+            self._pk = ops.PackedConv(self.w, self.b, self.scale, self.shift, CinK=self.cin_k, mode=self.mode, taps=self.taps, pack=False,
+                                      w16_S=self.w16_S)
         if self._pkd is None:
             self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, pack=False)
         return [self._pk, self._pkd]
@@ -163,11 +175,21 @@ class _Conv(object):
                 rows, k = x.shape[0] * ho * wo, (3 if self.Cin == 4 else self.Cin) * self.K * self.K
             net.flops += 2.0 * rows * self.Cout * k * passes
 
-    def fwd(self, x, relu=False, residual=None, up=None, out=None):
+    def fwd(self, x, relu=False, residual=None, up=None, out=None, x16=None, ex16=None, split_out=False):
+        """forward_precision "f16x3" only (ignored otherwise): x16 / ex16 = the split twins of x and of residual / up (train_ops.conv);
+        split_out: the output is later ADDED in another layer's epilogue (a residual, the FPN's top-down term), where the inference mode
+        adds its split form -- the twin is written beside the fp32 tensor and kept in self.out16."""
         if self.trainable:
             self.x = x
         self._count(x, 1)
-        return ops.conv(x, self._packed(), stride=self.stride, pad=self.pad, relu=relu, residual=residual, up=up, out=out, out_ld=self.out_ld)
+        pk = self._packed()
+        if pk.w16 is None:
+            self.out16 = None
+            return ops.conv(x, pk, stride=self.stride, pad=self.pad, relu=relu, residual=residual, up=up, out=out, out_ld=self.out_ld)
+        res = ops.conv(x, pk, stride=self.stride, pad=self.pad, relu=relu, residual=residual, up=up, out=out, out_ld=self.out_ld,
+                       x16=x16, ex16=ex16, split_out=split_out)
+        res, self.out16 = res if split_out else (res, None)
+        return res
 
     def bwd(self, g, need_dx=True, residual=None, accumulate=False, x=None, mask=None):
         """g: gradient wrt this layer's output AFTER its FrozenBatchNorm (if any) and after the ReLU mask, row stride out_ld: the BN
@@ -202,11 +224,13 @@ class _Bottleneck(object):
         self.down = _Conv(net, [prefix + ".downsample.0.weight"], bn=prefix + ".downsample.1", stride=stride) if has_down else None
         self.trainable, self.need_dx = self.c1.trainable, need_dx
 
-    def fwd(self, x):
-        self.a1 = self.c1.fwd(x, relu=True)
+    def fwd(self, x, x16=None):
+        """x16: the split twin of x (forward_precision "f16x3": the previous block's out16), or None.  Sets self.out16 likewise."""
+        self.a1 = self.c1.fwd(x, relu=True, x16=x16)
         self.a2 = self.c2.fwd(self.a1, relu=True)
-        idt = self.down.fwd(x) if self.down is not None else x
-        self.out = self.c3.fwd(self.a2, relu=True, residual=idt)
+        idt, idt16 = (self.down.fwd(x, x16=x16, split_out=True), self.down.out16) if self.down is not None else (x, x16)
+        self.out = self.c3.fwd(self.a2, relu=True, residual=idt, ex16=idt16, split_out=True)
+        self.out16 = self.c3.out16
         return self.out
 
     def bwd(self, g, mask_input):
@@ -233,9 +257,16 @@ class _TrainerBase(object):
     LAT_BODY = ()               # LAT_BODY[i]: the body layer (index into self.layers / feats) that feeds FPN lateral i
     _PACK_PLAN = os.environ.get("CALD_TRAIN_PACK_PLAN", "1") != "0"      # all trainable layers re-packed in two launches per step
 
-    def _init_common(self, state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler="choose_k"):
+    def _init_common(self, state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler="choose_k",
+                     forward_precision="fp32"):
         if sampler not in ("choose_k", "randperm"):
             raise ValueError("sampler must be 'choose_k' or 'randperm', got %r" % (sampler,))
+        if forward_precision not in ("fp32", "f16x3"):
+            raise ValueError("forward_precision must be 'fp32' or 'f16x3', got %r" % (forward_precision,))
+        # "f16x3": every forward conv / linear layer of a shape the split-fp16 kernels take (conv_h3 / conv_h4: three fp16 MFMAs per
+        # product, fp32-grade results) runs there, bit for bit what a HipDetector(precision="f16x3") computes; the backward, the weight
+        # gradients and SGD stay the exact fp32 ones, on the activations that forward saved.  "fp32" launches exactly what it always did.
+        self.forward_precision = forward_precision
         self.sampler = sampler
         self.dev = torch.device(device)
         self.C, self.min_size, self.max_size = num_classes, int(min_size), int(max_size)
@@ -283,7 +314,7 @@ class _TrainerBase(object):
         for k in sd:
             if k.endswith(".running_var"):
                 p = k[:-len(".running_var")]
-                sc, sh = _bn_fold(sd, p)
+                sc, sh = (_bn_fold_f32 if forward_precision == "f16x3" else _bn_fold)(sd, p)
                 self.bn[p] = (sc.to(self.dev), sh.to(self.dev))
         # ---- graph ----
         w1 = self.frozen["backbone.body.conv1.weight"]
@@ -317,6 +348,26 @@ class _TrainerBase(object):
             # then waits for the match kernels, not for the previous step's backward still queued on the main stream
             st2 = torch.cuda.Stream(device=self.dev)
             self.aux = (st2, get_side_ctx(di, st2))
+
+    def refresh_f16x3_scales(self):
+        """forward_precision "f16x3": derives every layer's weight scale 2^S from its CURRENT weights (S = 14 - exponent of max |w|, the
+        inference mode's policy) -- at construction, at every TrainableDetector.train() switch, and whenever the caller asks.  One host
+        synchronisation; between refreshes S is fixed, so a step neither stops the host nor depends on anything but its inputs.  A weight
+        that outgrows fp16's range under a stale S (x 4 from the last refresh at the least) packs as inf and the step's losses turn
+        non-finite; one that shrinks keeps fewer bits in its lo half.  Returns the number of layers whose S changed."""
+        if self.forward_precision != "f16x3":
+            return 0
+        convs = [cv for cv in self.convs if cv.mode in (0, 2)]
+        mx = torch.stack([cv.w.abs().max() for cv in convs]).cpu().tolist()
+        changed = 0
+        for cv, m in zip(convs, mx):
+            S = ops.f16x3_scale(m)[0]
+            if S != cv.w16_S:
+                cv.w16_S, cv._pk, cv._pk_version = S, None, -1     # a new pack; a frozen layer's is made on its next use
+                changed += 1
+        if changed:
+            self._pack_plan = None
+        return changed
 
     def _join_side(self):
         if self.side is not None:
@@ -403,9 +454,11 @@ class _TrainerBase(object):
         """The FPN's lateral 1x1 convs from the top level down, each adding the upsampled level above it in its epilogue."""
         top = len(self.lat) - 1
         inner = [None] * (top + 1)
-        inner[top] = self.lat[top].fwd(feats[self.LAT_BODY[top]])
+        f16 = self.split_twins["feats"]
+        inner[top] = self.lat[top].fwd(feats[self.LAT_BODY[top]], x16=f16[self.LAT_BODY[top]], split_out=True)
         for i in range(top - 1, -1, -1):
-            inner[i] = self.lat[i].fwd(feats[self.LAT_BODY[i]], up=inner[i + 1])
+            inner[i] = self.lat[i].fwd(feats[self.LAT_BODY[i]], up=inner[i + 1], x16=f16[self.LAT_BODY[i]], ex16=self.lat[i + 1].out16, split_out=True)
+        self.split_twins["inner"] = [cv.out16 for cv in self.lat]
         return inner
 
     def _fpn_top_down_bwd(self, ginner):
@@ -422,7 +475,8 @@ class _TrainerBase(object):
         """The FPN output 3x3 convs (one weight per level) of all levels in one grouped launch."""
         for cv, x in zip(self.fout, inner):
             cv.x = x; cv._count(x, 1)
-        return ops.conv_group(inner, [cv._packed() for cv in self.fout], pad=1)
+        i16 = self.split_twins["inner"]
+        return ops.conv_group(inner, [cv._packed() for cv in self.fout], pad=1, xs16=i16 if all(t is not None for t in i16) else None)
 
     def _fpn_out_bwd(self, gP):
         """Weight gradients per level (side stream), data gradients of all levels in one grouped launch."""
@@ -490,15 +544,17 @@ class _TrainerBase(object):
         x = ops.preprocess(u8, img_sizes, Hp, Wp, rem)
         x = ops.maxpool(self.stem.fwd(x, relu=True))
         self._mark("stem")
-        feats = []
+        feats, x16 = [], None
+        self.split_twins = {"feats": [], "inner": []}       # forward_precision "f16x3": the split twins of feats / the laterals (None entries in "fp32")
         waited = self.side is None
         for li, (trainable, blocks) in enumerate(self.layers):
             if trainable and not waited:                    # first layer that reads a freshly packed weight
                 self._main.wait_event(self._packs_ready)
                 waited = True
             for blk in blocks:
-                x = blk.fwd(x)
-            feats.append(x)
+                x = blk.fwd(x, x16)
+                x16 = blk.out16
+            feats.append(x); self.split_twins["feats"].append(x16)
             if li < 3:
                 self._mark("layer%d" % (li + 1))
         if not waited:

@@ -38,13 +38,14 @@ class FasterRCNNTrainer(_TrainerBase):
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
                  rpn_pre_nms_top_n=2000, rpn_post_nms_top_n=2000, rpn_nms_thresh=0.7, rpn_fg_iou=0.7, rpn_bg_iou=0.3,
                  rpn_batch=256, rpn_pos_fraction=0.5, box_fg_iou=0.5, box_bg_iou=0.5, box_batch=512, box_pos_fraction=0.25,
-                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k", loss_mode=None):
+                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k", loss_mode=None, forward_precision="fp32"):
         if loss_mode not in (None, "ll"):
             raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
         # "ll": the learning-loss baseline's task model (detection/frcnn_ll.py): one loss per IMAGE (frcnn_ll.py:29-64, :243-276) and the
         # four pooled pyramid vectors LossNet reads (ll_train.py:77); None launches exactly what it always launched
         self.loss_mode = loss_mode
-        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler)
+        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler,
+                          forward_precision=forward_precision)
         self.cfg = dict(pre_n=rpn_pre_nms_top_n, post_n=rpn_post_nms_top_n, nms=rpn_nms_thresh, rpn_fg=rpn_fg_iou, rpn_bg=rpn_bg_iou,
                         rpn_batch=rpn_batch, rpn_pos=rpn_pos_fraction, box_fg=box_fg_iou, box_bg=box_bg_iou, box_batch=box_batch,
                         box_pos=box_pos_fraction, w=tuple(bbox_reg_weights))
@@ -57,6 +58,7 @@ class FasterRCNNTrainer(_TrainerBase):
         self.pred_ld = ops.round_up(5 * num_classes, 4)
         self.pred = _Conv(self, self._merge_groups[2], self._merge_groups[3], out_ld=self.pred_ld)
         assert self.pred.Cout == 5 * num_classes, "box predictor does not match num_classes"
+        self.refresh_f16x3_scales()
 
     def forward(self, images, targets):
         """Training forward.  Returns the four losses as 1-element device tensors (no autograd) and keeps what backward needs.

@@ -3,6 +3,7 @@
 torch supplies device memory and the stream only; every arithmetic step is a libcaldhip kernel.  Activations are NHWC
 float32 [N, H, W, C].  No fallback: without the library or an MI355X every call raises.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -38,10 +39,39 @@ def packed_floats(Cout, Cin, KH, KW, CinK, mode):
     return int(n.value)
 
 
-class PackedConv(object):
-    """A torch-layout weight [Cout, Cin, KH, KW] (+ bias / frozen-BN scale, shift) in the layout the MFMA kernels read."""
+def f16x3_scale(max_abs):
+    """(S, unscale) of a layer whose largest |weight| is max_abs: the scale policy of an inference model's finalize (cald_train_f16x3_scale)."""
+    S, u = C.c_int(), C.c_float()
+    _ffi.check(_ffi.lib().cald_train_f16x3_scale(float(max_abs), C.byref(S), C.byref(u)))
+    return int(S.value), float(u.value)
 
-    def __init__(self, weight, bias=None, scale=None, shift=None, CinK=None, mode=0, taps=None, out=None, pack=True):
+
+def packed16_bytes(Cout, Cin, KH, KW, CinK, mode):
+    """Bytes of a forward pack's split twin; 0 for a shape the split-fp16 kernels do not take."""
+    n = C.c_int64()
+    _ffi.check(_ffi.lib().cald_train_packed16_bytes(Cout, Cin, KH, KW, CinK, mode, C.byref(n)))
+    return int(n.value)
+
+
+_KERNEL_LOG = [None]    # a list while record_kernels() is open: (layer, kernel) of every forward conv / linear launch
+
+
+@contextlib.contextmanager
+def record_kernels():
+    """Collects (layer shape, kernel that took the launch) of every forward conv / linear issued inside the block."""
+    prev, log = _KERNEL_LOG[0], []
+    _KERNEL_LOG[0] = log
+    try:
+        yield log
+    finally:
+        _KERNEL_LOG[0] = prev
+
+
+class PackedConv(object):
+    """A torch-layout weight [Cout, Cin, KH, KW] (+ bias / frozen-BN scale, shift) in the layout the MFMA kernels read.  w16_S (forward
+    packs): also its split-fp16 twin at weight scale 2^w16_S for conv_h3 / conv_h4 -- self.w16 stays None where those take no such shape."""
+
+    def __init__(self, weight, bias=None, scale=None, shift=None, CinK=None, mode=0, taps=None, out=None, pack=True, w16_S=None, w16_out=None):
         _chk(weight, "weight")
         if mode in (2, 3):                               # linear on [tap][Cin] rows, torch weight [Cout, Cin * taps] (3: its data gradient)
             self.Cout, self.Cin, self.KH, self.KW = weight.shape[0], weight.shape[1] // taps, taps, 1
@@ -59,7 +89,17 @@ class PackedConv(object):
         self.flags = ((FLAG_BIAS if bias is not None else 0) | (FLAG_BN if scale is not None else 0)) if mode in (0, 2) else 0
         # what a PackPlan needs to repeat this pack (the tensors are kept alive: the plan holds their device pointers)
         self.src = (weight, bias, scale, shift)
-        if pack:
+        self.w16, self.w16_S, self.w16_unscale = None, 0, 1.0
+        if w16_S is not None and mode in (0, 2):
+            nb = packed16_bytes(self.Cout, self.Cin, self.KH, self.KW, self.CinK, mode)
+            if nb:
+                self.w16 = w16_out if w16_out is not None else torch.empty(nb // 2, dtype=torch.int16, device=weight.device)
+                assert self.w16.numel() * 2 >= nb
+                self.w16_S, self.w16_unscale = int(w16_S), 2.0 ** -(int(w16_S) + 4)
+        if pack and self.w16 is not None:
+            _ffi.check(_ffi.lib().cald_train_pack_conv16(_wctx(weight), _p(weight), _p(bias), _p(scale), _p(shift), self.Cout, self.Cin, self.KH,
+                                                         self.KW, self.CinK, mode, _p(self.buf), _p(self.w16), self.w16_S))
+        elif pack:
             _ffi.check(_ffi.lib().cald_train_pack_conv(_wctx(weight), _p(weight), _p(bias), _p(scale), _p(shift), self.Cout,
                                                        self.Cin, self.KH, self.KW, self.CinK, mode, _p(self.buf)))
 
@@ -68,6 +108,8 @@ class PackedConv(object):
         q = _ffi.PackJob()
         q.weight, q.bias, q.bn_scale, q.bn_shift = [t.data_ptr() if t is not None else None for t in (w, b, sc, sh)]
         q.Cout, q.Cin, q.KH, q.KW, q.CinK, q.mode, q.packed = self.Cout, self.Cin, self.KH, self.KW, self.CinK, self.mode, self.buf.data_ptr()
+        if self.w16 is not None:
+            q.w16, q.w16_S = self.w16.data_ptr(), self.w16_S
         return q
 
 
@@ -99,8 +141,16 @@ class PackPlan(object):
                 pass
 
 
-def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, out_ld=None, mask=None):
-    """Forward conv / linear (pk.mode 0 or 2) or stride-1 data gradient (pk.mode 1) of a dense NHWC batch."""
+def _layer_label(pk, x, stride):
+    kind = "linear" if pk.mode == 2 or (pk.KH == 1 and x.shape[0] == 1 and x.shape[1] == 1) else "conv"
+    return "%s %dx%d/%d %d->%d on %dx%dx%d" % (kind, pk.KH, pk.KW, stride, pk.Cin, pk.Cout, x.shape[0], x.shape[1], x.shape[2])
+
+
+def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, out_ld=None, mask=None, x16=None, ex16=None, split_out=False):
+    """Forward conv / linear (pk.mode 0 or 2) or stride-1 data gradient (pk.mode 1) of a dense NHWC batch.  A pack with a split twin
+    (pk.w16) runs on the split-fp16 kernels where they take the launch.  Such a launch may use split twins of activations (int32 tensors of
+    the fp32 tensor's shape, the layout of an inference model of precision "f16x3"): x16 = the twin of x, ex16 = the twin of residual / up
+    -- the sum then takes the 22-bit value that model adds -- and split_out=True makes it write its output's twin: it returns (out, twin)."""
     _chk(x, "x")
     N, H, W, Cx = x.shape
     n_out = pk.Cin if pk.mode == 1 else (pk.Cin * pk.KH if pk.mode == 3 else pk.Cout)
@@ -119,13 +169,33 @@ def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, o
         out = (torch.zeros if ld != n_out else torch.empty)((N, Ho, Wo, ld), dtype=torch.float32, device=x.device)
     Hup, Wup = (up.shape[1], up.shape[2]) if up is not None else (0, 0)
     flags = pk.flags | (FLAG_RELU if relu else 0)
-    _ffi.check(_ffi.lib().cald_train_conv(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout,
-                                          pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags, _p(residual), _p(up), Hup, Wup, _p(mask), _p(out), ld))
-    return out
+    if (x16 is not None or ex16 is not None or split_out) and pk.w16 is None:
+        raise ValueError("split activations need a pack with a split twin")
+    log = _KERNEL_LOG[0] if pk.mode in (0, 2) else None
+    if pk.w16 is None and log is None:
+        _ffi.check(_ffi.lib().cald_train_conv(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout,
+                                              pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags, _p(residual), _p(up), Hup, Wup, _p(mask), _p(out), ld))
+        return out
+    ex = residual if residual is not None else up
+    if ex16 is not None and (ex is None or (residual is not None and up is not None) or ex16.shape != ex.shape):
+        raise ValueError("ex16 is the twin of ONE addend, residual or up, of that addend's shape")
+    if x16 is not None and x16.shape != x.shape:
+        raise ValueError("x16 must have the shape of x")
+    out16 = torch.empty(out.shape, dtype=torch.int32, device=out.device) if split_out else None
+    # (the epilogue reads ONE tensor: with ex16 the residual / up pointer is the twin's)
+    res_p, up_p = (_p(ex16) if residual is not None else None, _p(ex16) if up is not None else None) if ex16 is not None else (_p(residual), _p(up))
+    name = C.c_char_p()
+    _ffi.check(_ffi.lib().cald_train_conv_f16x3(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode,
+                                                flags, res_p, up_p, Hup, Wup, _p(mask), _p(out), ld, _p(pk.w16), pk.w16_unscale, _p(x16),
+                                                int(ex16 is not None), _p(out16), C.byref(name)))
+    if log is not None:
+        log.append((_layer_label(pk, x, stride), name.value.decode()))
+    return (out, out16) if split_out else out
 
 
-def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, masks=None):
-    """The same layer shape on several NHWC tensors in one launch; pks: one PackedConv per tensor (all of one shape) or a single one."""
+def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, masks=None, xs16=None):
+    """The same layer shape on several NHWC tensors in one launch; pks: one PackedConv per tensor (all of one shape) or a single one.
+    xs16 (packs with split twins only): the split twins of xs, one per tensor (see conv)."""
     if not isinstance(pks, (list, tuple)):
         pks = [pks] * len(xs)
     pk = pks[0]
@@ -140,9 +210,25 @@ def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, mas
         res.append(o)
     hw = [v for x in xs for v in (x.shape[1], x.shape[2])]
     flags = pk.flags | (FLAG_RELU if relu else 0)
-    _ffi.check(_ffi.lib().cald_train_conv_group(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
-                                                _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
-                                                _ptr_array(masks) if masks is not None else None, _ptr_array(res), ld))
+    log = _KERNEL_LOG[0] if pk.mode in (0, 2) else None
+    split = all(p.w16 is not None for p in pks)
+    if not split and log is None:
+        _ffi.check(_ffi.lib().cald_train_conv_group(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
+                                                    _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
+                                                    _ptr_array(masks) if masks is not None else None, _ptr_array(res), ld))
+        return res
+    if xs16 is not None and (not split or len(xs16) != len(xs) or any(t.shape != x.shape for t, x in zip(xs16, xs))):
+        raise ValueError("xs16: one twin of its tensor's shape per tensor, and packs with split twins")
+    w16 = uns = in16 = None
+    if split:
+        w16, uns = _ptr_array([p.w16 for p in pks]), (C.c_float * len(pks))(*[p.w16_unscale for p in pks])
+        in16 = _ptr_array(xs16) if xs16 is not None else None
+    names = (C.c_char_p * len(xs))()
+    _ffi.check(_ffi.lib().cald_train_conv_group_f16x3(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
+                                                      _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
+                                                      _ptr_array(masks) if masks is not None else None, _ptr_array(res), ld, w16, uns, in16, names))
+    if log is not None:
+        log.extend((_layer_label(p, x, stride), nm.decode()) for p, x, nm in zip(pks, xs, names))
     return res
 
 

@@ -27,14 +27,14 @@ class RetinaNetTrainer(_TrainerBase):
     LAT_BODY = (1, 2, 3)        # returned_layers = [2, 3, 4]
 
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
-                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None):
+                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None, forward_precision="fp32"):
         if loss_mode not in (None, "ll"):
             raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
         if loss_mode is not None:
             raise NotImplementedError("loss_mode=%r: the RetinaNet that trains LossNet beside it (ll_train.py:97-120, retina_ll.py's per-image "
                                       "losses) is a model of its own, as in the reference: build a RetinaNetLLTrainer" % (loss_mode,))
         self.loss_mode = None
-        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator)
+        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, forward_precision=forward_precision)
         self.cfg = dict(fg=fg_iou_thresh, bg=bg_iou_thresh)
         self.lat = [_Conv(self, ["backbone.fpn.inner_blocks.%d.weight" % i], ["backbone.fpn.inner_blocks.%d.bias" % i]) for i in range(3)]
         self.fout = [_Conv(self, ["backbone.fpn.layer_blocks.%d.weight" % i], ["backbone.fpn.layer_blocks.%d.bias" % i], pad=1) for i in range(3)]
@@ -47,6 +47,7 @@ class RetinaNetTrainer(_TrainerBase):
         self.cls_out = _Conv(self, ["head.classification_head.cls_logits.weight"], ["head.classification_head.cls_logits.bias"], pad=1, out_ld=self.cls_ld)
         self.reg_out = _Conv(self, ["head.regression_head.bbox_reg.weight"], ["head.regression_head.bbox_reg.bias"], pad=1)
         assert self.cls_out.Cout == 9 * num_classes and self.reg_out.Cout == 36, "RetinaNet heads must have 9 * num_classes / 36 outputs"
+        self.refresh_f16x3_scales()
 
     def forward(self, images, targets):
         """Training forward.  Returns the two losses as 1-element device tensors (no autograd) and keeps what backward needs."""

@@ -697,6 +697,18 @@ int cald_train_packed_floats(int Cout, int Cin, int KH, int KW, int CinK, int mo
  *   mode 3  data gradient of a mode-2 layer (dY rows with channel stride CinK >= Cout -> rows laid out [tap][Cin]) */
 int cald_train_pack_conv(cald_ctx* ctx, const float* weight, const float* bias, const float* bn_scale, const float* bn_shift,
                          int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed);
+/* The forward of a forward_precision "f16x3" trainer runs on the split-fp16 kernels of CALD_PRECISION_F16X3 (conv_h3 / conv_h4); the
+ * backward stays the exact fp32 one.  A forward pack (mode 0 or 2) then has a split twin w16, [Kpad/16][2 (hi, lo)][CoutPad][16] fp16 with
+ * hi = fp16(w * 2^S), lo = fp16(w * 2^S - hi): byte for byte what cald_model_finalize packs for an inference model at the same S.
+ *   cald_train_packed16_bytes  size of the twin; 0 for a shape those kernels do not take (such a layer runs the exact kernels)
+ *   cald_train_f16x3_scale     finalize's scale policy from max |w|: S = 14 - exponent, clamped to +-40, 0 for an all-zero or
+ *                              non-finite tensor; unscale = 2^-(S + 4), what cald_train_conv_f16x3 takes
+ *   cald_train_pack_conv16     cald_train_pack_conv that also writes the twin, in the same launches
+ * S is the caller's: the kernels take the unscale by value, so a step cannot derive it from the device without stopping the host. */
+int cald_train_packed16_bytes(int Cout, int Cin, int KH, int KW, int CinK, int mode, int64_t* bytes_out);
+int cald_train_f16x3_scale(float max_abs, int* S_out, float* unscale_out);
+int cald_train_pack_conv16(cald_ctx* ctx, const float* weight, const float* bias, const float* bn_scale, const float* bn_shift,
+                           int Cout, int Cin, int KH, int KW, int CinK, int mode, float* packed, void* w16, int S);
 /* Every trainable layer's packs in two launches: the optimizer step changes all weights at once (cald_train.py:62-64), and one
  * cald_train_pack_conv per layer and form is ~220 launch-bound launches at the start of every step.  A plan records the jobs (the
  * arguments of cald_train_pack_conv, device pointers that stay valid for the plan's lifetime); cald_train_pack_plan_run packs them
@@ -707,6 +719,8 @@ typedef struct cald_pack_job {
     const float *weight, *bias, *bn_scale, *bn_shift;
     int Cout, Cin, KH, KW, CinK, mode;
     float* packed;
+    void* w16;      /* optional split-fp16 twin of a forward pack (cald_train_pack_conv16), or null */
+    int w16_S;      /* its weight scale 2^S */
 } cald_pack_job;
 typedef struct cald_pack_plan cald_pack_plan;
 int cald_train_pack_plan_scratch_floats(int n, const cald_pack_job* jobs, int64_t* floats_out);
@@ -725,6 +739,20 @@ int cald_train_conv(cald_ctx* ctx, int N, int H, int W, const float* in, int Cin
 int cald_train_conv_group(cald_ctx* ctx, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
                           int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
                           float* const* outs, int out_ld);
+/* The two calls above with the split twin of a forward pack: w16 / w16_unscale (or null: the exact kernels, as above) send the launch to
+ * conv_h3 / conv_h4 where they take it and to the exact kernels where they refuse.  Activations may carry split twins (h16.h's layout, 4
+ * bytes per element like the fp32 tensor; they need w16, Cout % 16 == 0 and out_ld == Cout): in16 = the input's, out16 = one the launch
+ * writes beside out, ex16 != 0 = residual / up POINT AT the split twin of that tensor -- the epilogue then adds the 22-bit value an
+ * inference model of CALD_PRECISION_F16X3 adds.  Data-gradient packs and mask take no w16.  kernel / kernels (or null) receive the name
+ * of the kernel that took the launch / each problem (static strings). */
+int cald_train_conv_f16x3(cald_ctx* ctx, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
+                          int KH, int KW, int stride, int pad, int mode, int flags, const float* residual, const float* up,
+                          int Hup, int Wup, const float* mask, float* out, int out_ld, const void* w16, float w16_unscale,
+                          const void* in16, int ex16, void* out16, const char** kernel);
+int cald_train_conv_group_f16x3(cald_ctx* ctx, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
+                                int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
+                                float* const* outs, int out_ld, const void* const* w16, const float* w16_unscale,
+                                const void* const* in16, const char** kernels);
 /* dw[Cout][Cin][KH][KW] (=, or += when accumulate) sum over output pixels of g[q][co] * x[q @ tap][ci]; db[Cout] likewise (or
  * null).  x [N][H][W][ldx], g [N][Ho][Wo][ldg]; Cin, ldx, ldg multiples of 4.  Deterministic (fixed-order split reduction).
  * row_scale (or null): dw[co] is multiplied by row_scale[co] -- g is then the gradient wrt the FrozenBatchNorm OUTPUT of the layer. */
