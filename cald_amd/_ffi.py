@@ -268,6 +268,12 @@ SIGNATURES = {
     "cald_train_conv_group_f16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)] + [C.c_int] * 8
                                     + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]
                                     + [C.POINTER(C.c_void_p), c_f, C.POINTER(C.c_void_p), C.POINTER(C.c_char_p)]),
+    "cald_train_packed_grad16_bytes": (C.c_int, [C.c_int] * 6 + [c_i64]),
+    "cald_train_f16x3_grad_scale": (C.c_int, [C.c_float, c_i, c_f]),
+    "cald_train_conv_dgrad_f16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 6
+                                    + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_char_p)]),
+    "cald_train_conv_dgrad_group_f16x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_i, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)] + [C.c_int] * 6
+                                          + [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), c_f, c_f, C.POINTER(C.c_char_p)]),
     "cald_train_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "cald_train_linear_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,

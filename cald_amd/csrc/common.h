@@ -94,7 +94,7 @@ struct ConvArgs {
     const float* w;        // [Kpad][CoutPad], rows in chain order (model.hip pack_conv, conv_k_index: (16-channel chunk, kh, kw, channel) or (kh, kw, cin))
     const float* w4;       // same weights packed [Kpad/16][2][CoutPad][2][4] for conv_p4.hip (k = 16 kt + 8 kq + 2 j + h), or null
     const void* w16;       // fp16 hi/lo split of the same weights * 2^S, [Kpad/16][2 (hi, lo)][CoutPad][16] (conv_h3.hip), or null
-    float w16_unscale;     // 2^-(S + 4): undoes the weight scale 2^S and conv_h3's activation scale 2^4 (exact powers of two)
+    float w16_unscale;     // 2^-(S + 4): undoes the weight scale 2^S and conv_h3's activation scale 2^4 (exact powers of two; in_scale below)
     const float* bias;     // [CoutPad] or null
     const float* scale;    // FrozenBN scale/shift or null
     const float* shift;
@@ -114,7 +114,7 @@ struct ConvArgs {
     int out_ld;            // output row stride in floats (== Cout normally)
     const float* zeros;    // >= 16 bytes of zeros, 16-byte aligned (source of out-of-image taps)
     int in_relu;           // apply ReLU to the input while gathering (LastLevelP6P7: p7(relu(p6)))
-    // training backward only (train_conv.hip; honoured by conv_p4.hip): after everything else, out = mask > 0 ? out : 0 -- the ReLU backward
+    // training backward only (train_conv.hip; honoured by conv_p4.hip and conv_h3.hip): after everything else, out = mask > 0 ? out : 0 -- the ReLU backward
     // of the layer whose saved post-ReLU output `mask` (same geometry and row stride as out) this data gradient flows into; else null
     const float* mask;
     // conv_stem.hip: the 7 x 7 / 2 stem's weights packed [20 quads of k-pairs][2 h][64 n][4] over the 154-slot chain (7 filter rows x
@@ -131,6 +131,10 @@ struct ConvArgs {
     // through out16, the split-fp16 copy its look-ahead conv reads.
     float* energy4;
     int ex16;              // `residual` / `up` point at a split-form tensor (same element count) instead of an fp32 one
+    // conv_h3.hip, fp32 input only: the exact power of two an input element is multiplied by before its hi / lo split; 0 = 16.0f, the
+    // activation scale every forward launch uses.  A data-gradient launch of a backward_precision "f16x3" trainer passes 2^(4 + G) (G per
+    // gradient tensor, cald_train_f16x3_grad_scale) with w16_unscale = 2^-(S + 4 + G): the output is the unscaled fp32 gradient
+    float in_scale;
     // tuning only (cald_op_conv_bench under CALD_CONV_TRACE; null in the product path): per workgroup eight 64-bit words -- s_memtime at
     // entry, after the prologue's first barrier, after the k-loop, after the epilogue's last store was issued, after the stores drained;
     // HW_ID; XCC_ID; blockIdx -- the timeline of a launch on the chip (tools/conv_trace.py)
@@ -343,6 +347,10 @@ const char* launch_conv_generic(const ConvArgs& a, hipStream_t stream);         
 const char* launch_conv_stem(const ConvArgs& a, hipStream_t stream);                                 // conv_stem.hip
 const char* launch_conv_h3(const ConvArgs& a, hipStream_t stream);                                   // conv_h3.hip
 const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream);
+// the data-gradient launches of a backward_precision "f16x3" trainer (train_conv.hip alone calls them; the dispatcher never does, so a
+// masked launch stays refused everywhere else): fp32 input staged at ConvArgs::in_scale, plain or + residual, then the ReLU-backward mask
+const char* launch_conv_h3_dgrad(const ConvArgs& a, hipStream_t stream);
+const char* launch_conv_h3_dgrad_group(const ConvArgs* p, int n, hipStream_t stream);
 const char* launch_conv_h4(const ConvArgs& a, hipStream_t stream, bool forced = false);              // conv_h4.hip
 const char* launch_conv_h4_group(const ConvArgs* p, int n, hipStream_t stream, bool forced = false);
 bool conv_h4_group_takes(const ConvArgs* p, int n, bool forced = false);                                  // would launch_conv_h4_group take it?

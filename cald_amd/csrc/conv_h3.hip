@@ -72,6 +72,9 @@ __device__ __forceinline__ void conv_h3_body(const ConvArgs& a, const int blk) {
     const float* __restrict__ in_v = (in16 ? reinterpret_cast<const float*>(a.in16) : a.in) + si.pix_off * (long long)a.Cin;
     const int Cin = a.Cin, KW = a.KW, KH = a.KH, CoutPad = a.CoutPad;
     const bool in_relu = a.in_relu != 0;
+    // fp32 input: the power of two applied before the split -- 2^4 for activations (|x| < 4094), 2^(4 + G) for a gradient tensor, whose
+    // entries of 1e-3 .. 1e-8 would otherwise leave their lo halves in fp16's subnormals (ConvArgs::in_scale)
+    const float in_scale = a.in_scale != 0.0f ? a.in_scale : 16.0f;
 
     // ---- A gather: rows arow, arow + 64; k group g = 4 consecutive k ----
     const int g = tid & 3, arow = tid >> 2;
@@ -157,7 +160,7 @@ __device__ __forceinline__ void conv_h3_body(const ConvArgs& a, const int blk) {
             *reinterpret_cast<f32x4*>(tb + aw16_off[0]) = ra0;                                             \
             *reinterpret_cast<f32x4*>(tb + aw16_off[1]) = ra1;                                             \
         } else {                                                                                           \
-        ra0 = ra0 * 16.0f; ra1 = ra1 * 16.0f;                                                              \
+        ra0 = ra0 * in_scale; ra1 = ra1 * in_scale;                                                        \
         const h4 hi0 = __builtin_convertvector(ra0, h4), hi1 = __builtin_convertvector(ra1, h4);           \
         const h4 lo0 = __builtin_convertvector(ra0 - __builtin_convertvector(hi0, f32x4), h4);             \
         const h4 lo1 = __builtin_convertvector(ra1 - __builtin_convertvector(hi1, f32x4), h4);             \
@@ -251,10 +254,11 @@ __global__ __launch_bounds__(256, 3) void conv_h3_group_kernel(const ConvGroup g
     conv_h3_body<EPI, TN, C4>(g.p[i], (int)blockIdx.x - g.blk0[i]);
 }
 
-// features no conv_h3 kernel implements: the training mask, gathered rows (row_map / gather), the pruning's energy, residual AND top-down
-static inline bool h3_refuses(const ConvArgs& a) {
-    return !a.w16 || a.CoutPad % 64 != 0 || (a.in16 && a.in_relu) || a.mask || a.gather || a.row_map || a.energy4 || (a.residual && a.up) ||
-           (!a.out && !a.out16);
+// features no conv_h3 kernel implements: the training mask (outside the data-gradient launchers below), gathered rows (row_map / gather),
+// the pruning's energy, residual AND top-down
+static inline bool h3_refuses(const ConvArgs& a, const bool mask_ok = false) {
+    return !a.w16 || a.CoutPad % 64 != 0 || (a.in16 && a.in_relu) || (a.mask && !mask_ok) || a.gather || a.row_map || a.energy4 ||
+           (a.residual && a.up) || (!a.out && !a.out16);
 }
 template <int EPI, int TN, bool C4>
 static const char* h3_go(const dim3 grid, hipStream_t stream, const ConvArgs& a, const char* name) {
@@ -263,16 +267,24 @@ static const char* h3_go(const dim3 grid, hipStream_t stream, const ConvArgs& a,
 }
 #define H3_GO(EPI, TN, C4) h3_go<EPI, TN, C4>(grid, stream, a, "conv_h3_kernel<" #EPI "," #TN "," #C4 ">")
 
-const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream) {
-    if (n < 1 || n > CALD_MAX_GROUP) return nullptr;
-    const bool wide = p[0].CoutPad % 128 == 0;
-    ConvGroup g; g.n = n; int blk = 0;
+// the problems of a grouped launch in one ConvGroup, or false unless every problem qualifies for the same tile (dgrad: the data-gradient
+// launch, where all problems carry a mask or none does)
+static bool h3_group(const ConvArgs* p, int n, const bool dgrad, ConvGroup& g, bool& wide, int& blk) {
+    if (n < 1 || n > CALD_MAX_GROUP) return false;
+    wide = p[0].CoutPad % 128 == 0;
+    g.n = n; blk = 0;
     for (int i = 0; i < n; i++) {
         const ConvArgs& a = p[i];
-        if (h3_refuses(a) || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return nullptr;
+        if (h3_refuses(a, dgrad) || (a.CoutPad % 128 == 0) != wide || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.residual || a.up) return false;
+        if (dgrad && ((a.mask != nullptr) != (p[0].mask != nullptr) || a.in16 || a.out16 || !a.in)) return false;
         g.blk0[i] = blk; blk += a.total_mtiles * (a.CoutPad / (wide ? 128 : 64)); g.p[i] = a;
     }
     g.blk0[n] = blk;
+    return true;
+}
+const char* launch_conv_h3_group(const ConvArgs* p, int n, hipStream_t stream) {
+    ConvGroup g; bool wide; int blk;
+    if (!h3_group(p, n, false, g, wide, blk)) return nullptr;
     if (wide) { hipLaunchKernelGGL((conv_h3_group_kernel<0, 2, false>), dim3((unsigned)blk), dim3(256), 0, stream, g); return "conv_h3_group_kernel<0,2,false>"; }
     hipLaunchKernelGGL((conv_h3_group_kernel<0, 1, false>), dim3((unsigned)blk), dim3(256), 0, stream, g);
     return "conv_h3_group_kernel<0,1,false>";
@@ -294,6 +306,26 @@ const char* launch_conv_h3(const ConvArgs& a, hipStream_t stream) {
     }
     const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64)));
     return a.residual ? H3_GO(1, 1, false) : a.up ? H3_GO(2, 1, false) : H3_GO(0, 1, false);
+}
+// Data gradients (common.h): a stride-1 conv of the fp32 gradient on the transposed, flipped pack's twin -- the forward kernels, the input
+// staged at a.in_scale, the mask step compiled into EPI 4 / 5.  Unmasked launches are the forward instantiations.
+const char* launch_conv_h3_dgrad(const ConvArgs& a, hipStream_t stream) {
+    if (h3_refuses(a, true) || a.Cin % 16 != 0 || a.KH * a.KW > 32 || a.up || !a.in || a.in16 || a.out16 || a.ex16 || a.in_relu) return nullptr;
+    if (!a.mask) return launch_conv_h3(a, stream);
+    if (a.CoutPad % 128 == 0) {
+        const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 128)));
+        return a.residual ? H3_GO(5, 2, false) : H3_GO(4, 2, false);
+    }
+    const dim3 grid((unsigned)(a.total_mtiles * (a.CoutPad / 64)));
+    return a.residual ? H3_GO(5, 1, false) : H3_GO(4, 1, false);
+}
+const char* launch_conv_h3_dgrad_group(const ConvArgs* p, int n, hipStream_t stream) {
+    ConvGroup g; bool wide; int blk;
+    if (!h3_group(p, n, true, g, wide, blk)) return nullptr;
+    if (!p[0].mask) return launch_conv_h3_group(p, n, stream);
+    if (wide) { hipLaunchKernelGGL((conv_h3_group_kernel<4, 2, false>), dim3((unsigned)blk), dim3(256), 0, stream, g); return "conv_h3_group_kernel<4,2,false>"; }
+    hipLaunchKernelGGL((conv_h3_group_kernel<4, 1, false>), dim3((unsigned)blk), dim3(256), 0, stream, g);
+    return "conv_h3_group_kernel<4,1,false>";
 }
 #undef H3_GO
 

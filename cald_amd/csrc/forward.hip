@@ -252,7 +252,7 @@ static double fill_conv_args(cald_model* m, ConvArgs& a, const ConvLayer& L, con
             return (double)fail(CALD_ERR_UNSUPPORTED, "a view's activation tensor exceeds 2 GB (level %d -> %d, %lld x %d / %lld x %d elements)", lin, lout, pin, L.Cin, pout, L.Cout);
         }
     }
-    a.in16 = nullptr; a.out16 = nullptr; a.ex16 = 0; a.energy4 = nullptr; a.trace = nullptr;
+    a.in16 = nullptr; a.out16 = nullptr; a.ex16 = 0; a.in_scale = 0.0f; a.energy4 = nullptr; a.trace = nullptr;
     a.head_w = nullptr; a.head_out = nullptr; a.head_ld = 0; a.head_b[0] = a.head_b[1] = a.head_b[2] = 0.0f;
     if (!m->split.empty()) {
         const float* ex = residual ? residual : up;

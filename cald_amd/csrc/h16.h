@@ -64,12 +64,16 @@ __device__ __forceinline__ void h16_store4(unsigned char* row, const int c, cons
 // ReLU -- the exact mode's operation order -- then fp32 and / or split-form stores.  The wave owns TM x TN accumulator tiles of
 // 32 x 32 whose first row / column are m_w0 (inside the view) / n_w0; lane l holds column l & 31, rows 4 (l >> 5) + (r & 3) + 8 (r >> 2).
 //   EPI 0: nothing extra; 1: residual (same geometry as out); 2: FPN top-down (nearest up-sampling of the coarser level).
+//   EPI 4 / 5 (conv_h3.hip's data-gradient launches only): 0 / 1, then the training mask after everything else -- out = mask > 0 ? val : 0,
+//   the ReLU backward of the layer whose saved activation a.mask is (conv_p4.hip's MASK step); it loads the way the residual loads.
 // residual / up are fp32 tensors, or split-form ones when a.ex16 is set (then a.residual / a.up point at the split tensor).
 // ---------------------------------------------------------------------------------------------------------------------------
 typedef float h16_f32x16 __attribute__((ext_vector_type(16)));
 template <int EPI, int TM, int TN>
 __device__ __forceinline__ void h16_epilogue(const ConvArgs& a, const h16_f32x16 (&acc)[TM][TN], const LevelSeg so, const int v,
                                              const int m_w0, const int n_w0, const int Mv, const int lane) {
+    constexpr bool MASK = (EPI & 4) != 0;
+    constexpr int EX = EPI & 3;                     // the addend part of EPI
     // Addresses stay off the VALU (conv_p4.hip's scheme): one byte offset per lane and accumulator tile, the 16 rows of a tile through
     // the SCALAR offset of the buffer instruction; the descriptors end at the view's last valid row, so rows past it (and the lanes of
     // padded output channels, whose offset is out of range) load zeros and store nothing -- no per-element tests or branches.  All 16
@@ -86,15 +90,17 @@ __device__ __forceinline__ void h16_epilogue(const ConvArgs& a, const h16_f32x16
     int upH = 1, upW = 1;
     float uph_s = 0.f, upw_s = 0.f;
     unsigned ex_b = valid_b;
-    if (EPI == 1) ex_v = a.residual + so.pix_off * (long long)out_ld;
-    if (EPI == 2) {
+    if (EX == 1) ex_v = a.residual + so.pix_off * (long long)out_ld;
+    if (EX == 2) {
         const LevelSeg su = a.seg_up[v];
         ex_v = a.up + su.pix_off * (long long)out_ld;
         upH = su.H; upW = su.W;
         uph_s = (float)upH / (float)Ho; upw_s = (float)upW / (float)Wo;
         ex_b = (unsigned)(upH * upW) * (unsigned)row_b;
     }
-    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI != 0 ? (void*)ex_v : (void*)out_v), 0, ex_b, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)(EX != 0 ? (void*)ex_v : (void*)out_v), 0, ex_b, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsM = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(MASK ? (void*)(a.mask + so.pix_off * (long long)out_ld) : (void*)out_v), 0, valid_b, 0x00020000);
     const bool relu = a.relu != 0, has_bias = a.bias != nullptr, has_bn = a.scale != nullptr;
     const int Mlast = Mv - 1;
     const float unscale = a.w16_unscale;
@@ -114,7 +120,7 @@ __device__ __forceinline__ void h16_epilogue(const ConvArgs& a, const h16_f32x16
             const int vrow = 4 * kh_lane * row_b;
             const int vo32 = nok ? vrow + n * 4 : 0x7FFF0000, vo16 = nok ? vrow + poff : 0x7FFF0000;
             float extra[16];
-            if (EPI == 1) {
+            if (EX == 1) {
                 // (issuing tile t + 1's loads before tile t is processed was measured: no gain on the HBM-bound expand layers, round 4)
                 unsigned raw[16];
 #pragma unroll
@@ -123,7 +129,7 @@ __device__ __forceinline__ void h16_epilogue(const ConvArgs& a, const h16_f32x16
 #pragma unroll
                 for (int r = 0; r < 16; r++)
                     extra[r] = ex16 ? h16_join(h16_unpair_word(raw[r], h16_partner(raw[r]), odd)) : __builtin_bit_cast(float, raw[r]);
-            } else if (EPI == 2) {
+            } else if (EX == 2) {
                 unsigned raw[16];
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
@@ -149,13 +155,21 @@ __device__ __forceinline__ void h16_epilogue(const ConvArgs& a, const h16_f32x16
 #pragma unroll
                 for (int r = 0; r < 16; r++) { val[r] = val[r] * sc; val[r] = val[r] + sh; }
             }
-            if (EPI != 0) {
+            if (EX != 0) {
 #pragma unroll
                 for (int r = 0; r < 16; r++) val[r] = val[r] + extra[r];
             }
             if (relu) {
 #pragma unroll
                 for (int r = 0; r < 16; r++) val[r] = val[r] > 0.0f ? val[r] : 0.0f;
+            }
+            if (MASK) {      // rows past the view's end load 0 and store nothing, like the residual's
+                float mk[16];
+#pragma unroll
+                for (int r = 0; r < 16; r++)
+                    mk[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsM, vo32, (mrow + (r & 3) + 8 * (r >> 2)) * row_b, 0));
+#pragma unroll
+                for (int r = 0; r < 16; r++) val[r] = mk[r] > 0.0f ? val[r] : 0.0f;
             }
             if (out_v) {
 #pragma unroll

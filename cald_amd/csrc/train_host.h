@@ -65,6 +65,12 @@ inline bool h3_takes(const PackGeom& g, int taps, int mode) {
     if (mode != 0 && mode != 2) return false;
     return g.NPad % 64 == 0 && ((g.cin_conv % 16 == 0 && (mode == 2 ? 1 : taps) <= 32) || g.cin_conv == 4);
 }
+// Whether conv_h3.hip takes the DATA GRADIENT on this pack (modes 1 / 3: a stride-1 conv / 1 x 1 conv over cin_conv = CinK channels of dY
+// with n_true = Cin (x taps) outputs): only such a pack has a split twin, only such a launch reads it (conv_h3.hip launch_conv_h3_dgrad).
+inline bool h3_takes_grad(const PackGeom& g, int taps, int mode) {
+    if (mode != 1 && mode != 3) return false;
+    return g.NPad % 64 == 0 && g.cin_conv % 16 == 0 && (mode == 3 ? 1 : taps) <= 32;
+}
 inline bool p4_takes(const PackGeom& g, int taps) { return g.NPad % 64 == 0 && g.cin_conv % 16 == 0 && taps <= 32; }   // the tiled kernel (conv_p4.hip) covers the shape
 
 // train_targets.hip: the AnchorGenerator base anchors of the five levels, base[5][A][4]; returns A (kind 0: Faster R-CNN, 3; kind 1: RetinaNet, 9)

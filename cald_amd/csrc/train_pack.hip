@@ -1,6 +1,7 @@
 // train_pack.hip -- weight packing ON THE DEVICE, every step, from the torch-layout parameter tensors into what the inference conv kernels
 // (conv_p4.hip / conv_mfma.hip) read: forward packs, and the spatially flipped, channel-transposed filter on which the same kernels compute
-// the data gradient, and -- for a forward_precision "f16x3" trainer -- the split-fp16 twin of a forward pack that conv_h3.hip / conv_h4.hip read.
+// the data gradient, and -- for a forward_precision / backward_precision "f16x3" trainer -- the split-fp16 twin of a forward / data-gradient
+// pack that conv_h3.hip / conv_h4.hip read.
 // cald_train_packed_floats, cald_train_pack_conv(16), and the cald_train_pack_plan_* family (every layer's packs in two launches).
 #include "train_host.h"
 
@@ -9,7 +10,8 @@
 // mode 2: forward of a linear layer whose torch weight is [Cout][Cin][taps] (fc6: [1024][256][7*7]) applied to rows laid out
 //         [tap][Cin] (the RoIAlign output [R][49][256]): K rows = tap * Cin + ci
 // mode 3: data gradient of a mode-2 layer: K rows = co of a CinK-channel dY, N = tap * Cin + ci
-// w16 (forward packs only, or null): the split-fp16 twin conv_h3.hip / conv_h4.hip read, [Kpad/16][2 (hi, lo)][NPad][16] of w * 2^S
+// w16 (or null): the split-fp16 twin conv_h3.hip / conv_h4.hip read, [Kpad/16][2 (hi, lo)][NPad][16] of w * 2^S -- of a data-gradient pack:
+// of the values the fp32 pack holds (transposed, flipped, rowscale folded in)
 struct PackArgs { const float* w; float* wk; float* w4; int Cout, Cin, taps, CinK, Kpad, NPad, mode; const float* rowscale; unsigned short* w16; int S; };
 __device__ __forceinline__ void pack_weight_body(const PackArgs& a, long long blk) {
     const long long i = blk * 256 + threadIdx.x;
@@ -34,6 +36,14 @@ __device__ __forceinline__ void pack_weight_body(const PackArgs& a, long long bl
     a.wk[i] = v;
     const int kt = k >> 4, kk = k & 15, kq = kk >> 3, j = (kk & 7) >> 1, h = kk & 1;
     a.w4[(((long long)(kt * 2 + kq) * a.NPad + n) * 2 + h) * 4 + j] = v;
+    if (!a.w16) return;
+    // the split twin of a data-gradient pack, the arithmetic of pack_transpose_body's: hi = fp16(v * 2^S), lo = fp16(v * 2^S - hi)
+    const float x = ldexpf(v, a.S);
+    const _Float16 hi = (_Float16)x;
+    const _Float16 lo = (_Float16)(x - (float)hi);
+    const long long o = ((long long)kt * 2 * a.NPad + n) * 16 + kk;
+    a.w16[o] = __builtin_bit_cast(unsigned short, hi);
+    a.w16[o + (long long)a.NPad * 16] = __builtin_bit_cast(unsigned short, lo);
 }
 __global__ __launch_bounds__(256) void pack_weight_kernel(PackArgs a) { pack_weight_body(a, blockIdx.x); }
 // Forward packs (modes 0, 2) in two coalesced passes: (1) every torch row n (Cin * taps contiguous floats) is read in order and
@@ -119,14 +129,22 @@ extern "C" int cald_train_packed_floats(int Cout, int Cin, int KH, int KW, int C
     *floats_out = pack_geom(Cout, Cin, KH, KW, CinK, mode).floats;
     return 0;
 }
-// The split twin exists for forward packs of the shapes conv_h3.hip takes (model.hip pack_conv's `tiled`): 0 bytes otherwise.
+// The split twin exists for forward packs of the shapes conv_h3.hip takes (model.hip pack_conv's `tiled`), and for data-gradient packs
+// whose data gradient -- a stride-1 conv over CinK channels of dY -- conv_h3.hip takes: 0 bytes otherwise.
 static long long w16_bytes(const PackGeom& g, int taps, int mode) {
-    return h3_takes(g, taps, mode) ? 4ll * g.Kpad * g.NPad : 0;
+    return (h3_takes(g, taps, mode) || h3_takes_grad(g, taps, mode)) ? 4ll * g.Kpad * g.NPad : 0;
 }
-#define W16_RULE "a split twin needs a forward pack of a shape conv_h3 takes (cald_train_packed16_bytes > 0) and |S| <= 40"
+#define W16_RULE "a split twin needs a pack of a shape conv_h3 takes (cald_train_packed16_bytes / cald_train_packed_grad16_bytes > 0) and |S| <= 40"
 extern "C" int cald_train_packed16_bytes(int Cout, int Cin, int KH, int KW, int CinK, int mode, int64_t* bytes_out) {
     if (!bytes_out || Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || mode < 0 || mode > 3) TFAIL(CALD_ERR_INVALID, "bad arguments");
-    *bytes_out = w16_bytes(pack_geom(Cout, Cin, KH, KW, CinK, mode), KH * KW, mode);
+    const PackGeom g = pack_geom(Cout, Cin, KH, KW, CinK, mode);
+    *bytes_out = h3_takes(g, KH * KW, mode) ? w16_bytes(g, KH * KW, mode) : 0;
+    return 0;
+}
+extern "C" int cald_train_packed_grad16_bytes(int Cout, int Cin, int KH, int KW, int CinK, int mode, int64_t* bytes_out) {
+    if (!bytes_out || Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || mode < 0 || mode > 3) TFAIL(CALD_ERR_INVALID, "bad arguments");
+    const PackGeom g = pack_geom(Cout, Cin, KH, KW, CinK, mode);
+    *bytes_out = h3_takes_grad(g, KH * KW, mode) ? w16_bytes(g, KH * KW, mode) : 0;
     return 0;
 }
 // model.hip pack_w16's scale: max |w| = f * 2^e, f in [0.5, 1) -> S = 14 - e, clamped to +-40; 0 for an all-zero or non-finite tensor
@@ -137,6 +155,19 @@ extern "C" int cald_train_f16x3_scale(float max_abs, int* S_out, float* unscale_
     if (S > 40) S = 40;
     if (S < -40) S = -40;
     *S_out = S; *unscale_out = std::ldexp(1.0f, -(S + 4));
+    return 0;
+}
+// The input scale of a data-gradient launch on conv_h3.hip from the largest |g| of the gradient tensor it reads (a backward_precision
+// "f16x3" trainer reads it on its calibration step): max |g| = f * 2^e, f in [0.5, 1) -> G = 7 - e, so that max |g| * 2^(4 + G) lies in
+// [2^10, 2^11) -- x 32 of growth before fp16 overflows at 65 504, x 2^13 of shrink before the tensor's largest entry loses a bit of its lo
+// half.  Clamped to +-60; 0 for an all-zero or non-finite tensor.  in_scale = 2^(4 + G).
+extern "C" int cald_train_f16x3_grad_scale(float max_abs, int* G_out, float* in_scale_out) {
+    if (!G_out || !in_scale_out) TFAIL(CALD_ERR_INVALID, "null argument");
+    int G = 0;
+    if (max_abs > 0.0f && std::isfinite(max_abs)) { int e; std::frexp(max_abs, &e); G = 7 - e; }
+    if (G > 60) G = 60;
+    if (G < -60) G = -60;
+    *G_out = G; *in_scale_out = std::ldexp(1.0f, 4 + G);
     return 0;
 }
 static int pack_conv(cald_ctx* c, const float* w, const float* bias, const float* scale, const float* shift,

@@ -152,7 +152,8 @@ class TrainableDetector(object):
 
     def train(self, mode=True):
         """As nn.Module.train().  Over a forward_precision "f16x3" trainer a switch to train mode also re-derives the layers' weight
-        scales (refresh_f16x3_scales): the reference's loops switch once per epoch, where the host has synchronised anyway."""
+        scales (refresh_f16x3_scales): the reference's loops switch once per epoch, where the host has synchronised anyway.  Over a
+        backward_precision "f16x3" trainer it makes the next backward a calibration step (exact data gradients, new gradient exponents)."""
         self.training = bool(mode)
         if self.training:
             self.net.refresh_f16x3_scales()

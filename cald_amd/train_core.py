@@ -134,6 +134,9 @@ class _Conv(object):
         self._pk = self._pkd = None
         self._pk_version = self._pkd_version = -1
         self.w16_S = None               # forward_precision "f16x3": the weight scale of the forward pack's split twin (refresh_f16x3_scales)
+        self.grad16_S = None            # backward_precision "f16x3": the weight scale S_d of the data-gradient pack's split twin (likewise)
+        self.name = wnames[0]
+        self.idx = len(net.convs)       # names this layer's data-gradient launches in the trainer's table of gradient exponents
         self.x = None
         self.out16 = None               # the split twin of the last forward's output, where fwd(split_out=True) wrote one
         net.convs.append(self)
@@ -153,14 +156,16 @@ class _Conv(object):
             self._pk = ops.PackedConv(self.w, self.b, self.scale, self.shift, CinK=self.cin_k, mode=self.mode, taps=self.taps, pack=False,
                                       w16_S=self.w16_S)
         if self._pkd is None:
-            self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, pack=False)
+            self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, pack=False,
+                                       grad16_S=self.grad16_S)
         return [self._pk, self._pkd]
 
     def _packed_grad(self):
         if self._pkd is None or self._pkd_version != self.net.version:
-            buf = self._pkd.buf if self._pkd is not None else None
+            buf, buf16 = (self._pkd.buf, self._pkd.w16) if self._pkd is not None else (None, None)
             # FrozenBatchNorm layers: the scale rides in the packed filter, so the incoming gradient is the one wrt the BN output
-            self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, out=buf)
+            self._pkd = ops.PackedConv(self.w, scale=self.scale, CinK=self.out_ld, mode=3 if self.mode == 2 else 1, taps=self.taps, out=buf,
+                                       grad16_S=self.grad16_S, w16_out=buf16)
             self._pkd_version = self.net.version
         return self._pkd
 
@@ -211,9 +216,10 @@ class _Conv(object):
         if not need_dx:
             return None
         pkd = self._packed_grad()
+        G = self.net._dgrad_G((self.idx, 0), g)
         if self.mode == 2 or self.w.dim() == 2:
-            return ops.conv(g, pkd, residual=residual, mask=mask)
-        return ops.conv_dgrad(g, pkd, x.shape[1], x.shape[2], self.stride, self.pad, residual=residual, mask=mask)
+            return ops.conv(g, pkd, residual=residual, mask=mask, G=G)
+        return ops.conv_dgrad(g, pkd, x.shape[1], x.shape[2], self.stride, self.pad, residual=residual, mask=mask, G=G)
 
 
 class _Bottleneck(object):
@@ -258,7 +264,7 @@ class _TrainerBase(object):
     _PACK_PLAN = os.environ.get("CALD_TRAIN_PACK_PLAN", "1") != "0"      # all trainable layers re-packed in two launches per step
 
     def _init_common(self, state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler="choose_k",
-                     forward_precision="fp32"):
+                     forward_precision="fp32", backward_precision="fp32"):
         if sampler not in ("choose_k", "randperm"):
             raise ValueError("sampler must be 'choose_k' or 'randperm', got %r" % (sampler,))
         if forward_precision not in ("fp32", "f16x3"):
@@ -267,6 +273,15 @@ class _TrainerBase(object):
         # product, fp32-grade results) runs there, bit for bit what a HipDetector(precision="f16x3") computes; the backward, the weight
         # gradients and SGD stay the exact fp32 ones, on the activations that forward saved.  "fp32" launches exactly what it always did.
         self.forward_precision = forward_precision
+        if backward_precision not in ("fp32", "f16x3"):
+            raise ValueError("backward_precision must be 'fp32' or 'f16x3', got %r" % (backward_precision,))
+        # "f16x3": every data gradient of a shape conv_h3 takes runs there, on the split twin of the data-gradient pack, the gradient staged
+        # at its own power of two 2^(4 + G) (per layer and pyramid level; _dgrad_G); the weight gradients, the RoIAlign backward, the losses
+        # and SGD stay exact fp32.  Independent of forward_precision; "fp32" launches exactly what it always did.
+        self.backward_precision = backward_precision
+        self._grad_G = {}               # (layer, level) -> gradient exponent G, fixed between refreshes
+        self._grad_max = {}             # (layer, level) -> the max |g| the last calibration step saw
+        self._calib = None              # a list while the next / current backward is a calibration step: ((layer, level), max |g| on the device)
         self.sampler = sampler
         self.dev = torch.device(device)
         self.C, self.min_size, self.max_size = num_classes, int(min_size), int(max_size)
@@ -355,19 +370,60 @@ class _TrainerBase(object):
         synchronisation; between refreshes S is fixed, so a step neither stops the host nor depends on anything but its inputs.  A weight
         that outgrows fp16's range under a stale S (x 4 from the last refresh at the least) packs as inf and the step's losses turn
         non-finite; one that shrinks keeps fewer bits in its lo half.  Returns the number of layers whose S changed."""
-        if self.forward_precision != "f16x3":
-            return 0
-        convs = [cv for cv in self.convs if cv.mode in (0, 2)]
-        mx = torch.stack([cv.w.abs().max() for cv in convs]).cpu().tolist()
         changed = 0
-        for cv, m in zip(convs, mx):
-            S = ops.f16x3_scale(m)[0]
-            if S != cv.w16_S:
-                cv.w16_S, cv._pk, cv._pk_version = S, None, -1     # a new pack; a frozen layer's is made on its next use
-                changed += 1
+        convs = [cv for cv in self.convs if cv.mode in (0, 2)]
+        if self.forward_precision == "f16x3":
+            mx = torch.stack([cv.w.abs().max() for cv in convs]).cpu().tolist()
+            for cv, m in zip(convs, mx):
+                S = ops.f16x3_scale(m)[0]
+                if S != cv.w16_S:
+                    cv.w16_S, cv._pk, cv._pk_version = S, None, -1     # a new pack; a frozen layer's is made on its next use
+                    changed += 1
+        if self.backward_precision == "f16x3":
+            # S_d of the data-gradient packs: the same policy on max |w * bn_scale|, what those packs hold.  The gradient exponents are
+            # re-derived too: the next backward is a calibration step -- its data gradients run on the exact kernels while the largest
+            # |g| of every data gradient's input is collected on the device, read once at its end (_end_backward)
+            rows = lambda cv: cv.w if cv.scale is None else cv.w * cv.scale.view((-1,) + (1,) * (cv.w.dim() - 1))
+            mx = torch.stack([rows(cv).abs().max() for cv in convs]).cpu().tolist()
+            for cv, m in zip(convs, mx):
+                S = ops.f16x3_scale(m)[0]
+                if S != cv.grad16_S:
+                    cv.grad16_S, cv._pkd, cv._pkd_version = S, None, -1
+                    changed += 1
+            self._grad_G, self._calib = {}, []
         if changed:
             self._pack_plan = None
         return changed
+
+    def _dgrad_G(self, key, g):
+        """The gradient exponent of the data-gradient launch `key` = (layer, level) reading g; None = the exact kernels: in the default
+        mode, on a calibration step (which records max |g|) and for a launch no calibration step has seen."""
+        if self.backward_precision != "f16x3":
+            return None
+        if self._calib is not None:
+            self._calib.append((key, g.abs().max()))
+            return None
+        return self._grad_G.get(key)
+
+    def _dgrad_Gs(self, keys, gs):
+        """_dgrad_G of every problem of a grouped launch; None (the exact kernels) unless every problem has one."""
+        Gs = [self._dgrad_G(k, g) for k, g in zip(keys, gs)]
+        return None if any(G is None for G in Gs) else Gs
+
+    def _end_backward(self):
+        """Closes a calibration step: one read of the collected maxima (the refresh's one synchronisation), G per launch by the policy of
+        cald_train_f16x3_grad_scale; a launch that ran several times in the step takes the largest."""
+        if self._calib is not None and not self._calib:
+            self._calib = None                              # (a backward without a data gradient)
+        if self._calib:
+            torch.cuda.synchronize(self.dev)                # the maxima were collected on all three streams
+            mx = torch.stack([m for _, m in self._calib]).cpu().tolist()
+            top = {}
+            for (key, _), m in zip(self._calib, mx):
+                top[key] = m if key not in top or not (m <= top[key]) else top[key]
+            self._grad_G = {k: ops.f16x3_grad_scale(m)[0] for k, m in top.items()}
+            self._grad_max = top                            # what the calibration step saw (tools/train_grad_ranges.py)
+            self._calib = None
 
     def _join_side(self):
         if self.side is not None:
@@ -482,7 +538,7 @@ class _TrainerBase(object):
         """Weight gradients per level (side stream), data gradients of all levels in one grouped launch."""
         for cv, g in zip(self.fout, gP):
             cv.bwd(g, need_dx=False); cv._count(cv.x, 1)
-        return ops.conv_group(gP, [cv._packed_grad() for cv in self.fout], pad=1)
+        return ops.conv_group(gP, [cv._packed_grad() for cv in self.fout], pad=1, Gs=self._dgrad_Gs([(cv.idx, 0) for cv in self.fout], gP))
 
     def _mark(self, name):
         if self.timing is not None:

@@ -38,14 +38,15 @@ class FasterRCNNTrainer(_TrainerBase):
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
                  rpn_pre_nms_top_n=2000, rpn_post_nms_top_n=2000, rpn_nms_thresh=0.7, rpn_fg_iou=0.7, rpn_bg_iou=0.3,
                  rpn_batch=256, rpn_pos_fraction=0.5, box_fg_iou=0.5, box_bg_iou=0.5, box_batch=512, box_pos_fraction=0.25,
-                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k", loss_mode=None, forward_precision="fp32"):
+                 bbox_reg_weights=(10.0, 10.0, 5.0, 5.0), generator=None, sampler="choose_k", loss_mode=None, forward_precision="fp32",
+                 backward_precision="fp32"):
         if loss_mode not in (None, "ll"):
             raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
         # "ll": the learning-loss baseline's task model (detection/frcnn_ll.py): one loss per IMAGE (frcnn_ll.py:29-64, :243-276) and the
         # four pooled pyramid vectors LossNet reads (ll_train.py:77); None launches exactly what it always launched
         self.loss_mode = loss_mode
         self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, sampler,
-                          forward_precision=forward_precision)
+                          forward_precision=forward_precision, backward_precision=backward_precision)
         self.cfg = dict(pre_n=rpn_pre_nms_top_n, post_n=rpn_post_nms_top_n, nms=rpn_nms_thresh, rpn_fg=rpn_fg_iou, rpn_bg=rpn_bg_iou,
                         rpn_batch=rpn_batch, rpn_pos=rpn_pos_fraction, box_fg=box_fg_iou, box_bg=box_bg_iou, box_batch=box_batch,
                         box_pos=box_pos_fraction, w=tuple(bbox_reg_weights))
@@ -313,7 +314,8 @@ class FasterRCNNTrainer(_TrainerBase):
         for i in range(5):
             self.rpn_head.bwd(ghs[i], need_dx=False, accumulate=i > 0, x=L["tl"][i])
             self.rpn_head._count(L["tl"][i], 1)
-        gts_ = ops.conv_group(ghs, self.rpn_head._packed_grad(), masks=L["tl"])       # 1x1 head: data gradient of the five levels + ReLU backward, one launch
+        gts_ = ops.conv_group(ghs, self.rpn_head._packed_grad(), masks=L["tl"],       # 1x1 head: data gradient of the five levels + ReLU backward, one launch
+                              Gs=self._dgrad_Gs([(self.rpn_head.idx, i) for i in range(5)], ghs))
         for i in range(5):
             self.rpn_conv.bwd(gts_[i], need_dx=False, accumulate=i > 0, x=P[i])
         return gts_
@@ -323,7 +325,8 @@ class FasterRCNNTrainer(_TrainerBase):
         P = L["P"]
         for i in range(5):
             self.rpn_conv._count(P[i], 1)
-        g = ops.conv_group(gts_, self.rpn_conv._packed_grad(), pad=1)       # the five levels in one launch, like the forward
+        g = ops.conv_group(gts_, self.rpn_conv._packed_grad(), pad=1,       # the five levels in one launch, like the forward
+                           Gs=self._dgrad_Gs([(self.rpn_conv.idx, i) for i in range(5)], gts_))
         return g[:4], g[4]
 
     # ---- backward ----
@@ -382,5 +385,6 @@ class FasterRCNNTrainer(_TrainerBase):
         self._mark("bwd fpn")
         self._body_backward(gC)
         self._mark("bwd body dgrad")
+        self._end_backward()
         self._join_side()
         return self.grads

@@ -53,6 +53,21 @@ def packed16_bytes(Cout, Cin, KH, KW, CinK, mode):
     return int(n.value)
 
 
+def packed_grad16_bytes(Cout, Cin, KH, KW, CinK, mode):
+    """Bytes of a data-gradient pack's split twin; 0 where conv_h3 does not take the data gradient's shape."""
+    n = C.c_int64()
+    _ffi.check(_ffi.lib().cald_train_packed_grad16_bytes(Cout, Cin, KH, KW, CinK, mode, C.byref(n)))
+    return int(n.value)
+
+
+def f16x3_grad_scale(max_abs):
+    """(G, in_scale) of a gradient tensor whose largest |entry| is max_abs (cald_train_f16x3_grad_scale): in_scale = 2^(4 + G) places that
+    maximum in [2^10, 2^11) before conv_h3 splits it; G is clamped to +-60 and 0 for an all-zero or non-finite tensor."""
+    G, s = C.c_int(), C.c_float()
+    _ffi.check(_ffi.lib().cald_train_f16x3_grad_scale(float(max_abs), C.byref(G), C.byref(s)))
+    return int(G.value), float(s.value)
+
+
 _KERNEL_LOG = [None]    # a list while record_kernels() is open: (layer, kernel) of every forward conv / linear launch
 
 
@@ -67,11 +82,29 @@ def record_kernels():
         _KERNEL_LOG[0] = prev
 
 
+_DGRAD_LOG = [None]     # a list while record_dgrad_kernels() is open: (layer, kernel) of every data-gradient launch
+
+
+@contextlib.contextmanager
+def record_dgrad_kernels():
+    """Collects (layer shape, kernel that took the launch) of every data gradient issued through conv / conv_dgrad / conv_group inside the
+    block (record_kernels() logs forward launches only)."""
+    prev, log = _DGRAD_LOG[0], []
+    _DGRAD_LOG[0] = log
+    try:
+        yield log
+    finally:
+        _DGRAD_LOG[0] = prev
+
+
 class PackedConv(object):
     """A torch-layout weight [Cout, Cin, KH, KW] (+ bias / frozen-BN scale, shift) in the layout the MFMA kernels read.  w16_S (forward
-    packs): also its split-fp16 twin at weight scale 2^w16_S for conv_h3 / conv_h4 -- self.w16 stays None where those take no such shape."""
+    packs): also its split-fp16 twin at weight scale 2^w16_S for conv_h3 / conv_h4 -- self.w16 stays None where those take no such shape.
+    grad16_S (data-gradient packs, modes 1 / 3): the twin of the fp32 pack's values (transposed, flipped, `scale` folded in) at weight scale
+    2^grad16_S, which conv(..., G=) / conv_dgrad / conv_group read -- None where conv_h3 does not take the data gradient's shape."""
 
-    def __init__(self, weight, bias=None, scale=None, shift=None, CinK=None, mode=0, taps=None, out=None, pack=True, w16_S=None, w16_out=None):
+    def __init__(self, weight, bias=None, scale=None, shift=None, CinK=None, mode=0, taps=None, out=None, pack=True, w16_S=None, w16_out=None,
+                 grad16_S=None):
         _chk(weight, "weight")
         if mode in (2, 3):                               # linear on [tap][Cin] rows, torch weight [Cout, Cin * taps] (3: its data gradient)
             self.Cout, self.Cin, self.KH, self.KW = weight.shape[0], weight.shape[1] // taps, taps, 1
@@ -96,6 +129,12 @@ class PackedConv(object):
                 self.w16 = w16_out if w16_out is not None else torch.empty(nb // 2, dtype=torch.int16, device=weight.device)
                 assert self.w16.numel() * 2 >= nb
                 self.w16_S, self.w16_unscale = int(w16_S), 2.0 ** -(int(w16_S) + 4)
+        if grad16_S is not None and mode in (1, 3):
+            nb = packed_grad16_bytes(self.Cout, self.Cin, self.KH, self.KW, self.CinK, mode)
+            if nb:
+                self.w16 = w16_out if w16_out is not None else torch.empty(nb // 2, dtype=torch.int16, device=weight.device)
+                assert self.w16.numel() * 2 >= nb
+                self.w16_S = int(grad16_S)          # (the launch's unscale also undoes the gradient's scale: 2^-(S + 4 + G), per launch)
         if pack and self.w16 is not None:
             _ffi.check(_ffi.lib().cald_train_pack_conv16(_wctx(weight), _p(weight), _p(bias), _p(scale), _p(shift), self.Cout, self.Cin, self.KH,
                                                          self.KW, self.CinK, mode, _p(self.buf), _p(self.w16), self.w16_S))
@@ -146,11 +185,18 @@ def _layer_label(pk, x, stride):
     return "%s %dx%d/%d %d->%d on %dx%dx%d" % (kind, pk.KH, pk.KW, stride, pk.Cin, pk.Cout, x.shape[0], x.shape[1], x.shape[2])
 
 
-def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, out_ld=None, mask=None, x16=None, ex16=None, split_out=False):
+def _dgrad_label(pk, x):
+    return "dgrad %dx%d %d<-%d on %dx%dx%d" % (pk.KH if pk.mode == 1 else 1, pk.KW if pk.mode == 1 else 1, pk.Cin * (pk.KH if pk.mode == 3 else 1),
+                                                pk.Cout, x.shape[0], x.shape[1], x.shape[2])
+
+
+def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, out_ld=None, mask=None, x16=None, ex16=None, split_out=False, G=None):
     """Forward conv / linear (pk.mode 0 or 2) or stride-1 data gradient (pk.mode 1) of a dense NHWC batch.  A pack with a split twin
     (pk.w16) runs on the split-fp16 kernels where they take the launch.  Such a launch may use split twins of activations (int32 tensors of
     the fp32 tensor's shape, the layout of an inference model of precision "f16x3"): x16 = the twin of x, ex16 = the twin of residual / up
-    -- the sum then takes the 22-bit value that model adds -- and split_out=True makes it write its output's twin: it returns (out, twin)."""
+    -- the sum then takes the 22-bit value that model adds -- and split_out=True makes it write its output's twin: it returns (out, twin).
+    G (data-gradient packs with a twin, PackedConv(grad16_S=)): the gradient exponent of x (f16x3_grad_scale) -- the launch runs on conv_h3
+    with x staged at 2^(4 + G); None: the exact kernels."""
     _chk(x, "x")
     N, H, W, Cx = x.shape
     n_out = pk.Cin if pk.mode == 1 else (pk.Cin * pk.KH if pk.mode == 3 else pk.Cout)
@@ -172,6 +218,23 @@ def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, o
     if (x16 is not None or ex16 is not None or split_out) and pk.w16 is None:
         raise ValueError("split activations need a pack with a split twin")
     log = _KERNEL_LOG[0] if pk.mode in (0, 2) else None
+    if pk.mode in (1, 3):
+        dlog = _DGRAD_LOG[0]
+        name = C.c_char_p()
+        if pk.w16 is not None and G is not None:
+            assert stride == 1 and up is None
+            _ffi.check(_ffi.lib().cald_train_conv_dgrad_f16x3(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout, pk.Cin, pk.KH, pk.KW, pad, pk.mode,
+                                                              _p(residual), _p(mask), _p(out), ld, _p(pk.w16), 2.0 ** -(pk.w16_S + 4 + int(G)),
+                                                              2.0 ** (4 + int(G)), C.byref(name)))
+        elif dlog is not None:                           # the exact kernels, with the name of the one that took the launch
+            _ffi.check(_ffi.lib().cald_train_conv_f16x3(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode,
+                                                        flags, _p(residual), _p(up), Hup, Wup, _p(mask), _p(out), ld, None, 1.0, None, 0, None, C.byref(name)))
+        else:
+            _ffi.check(_ffi.lib().cald_train_conv(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout,
+                                                  pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags, _p(residual), _p(up), Hup, Wup, _p(mask), _p(out), ld))
+        if dlog is not None:
+            dlog.append((_dgrad_label(pk, x), name.value.decode()))
+        return out
     if pk.w16 is None and log is None:
         _ffi.check(_ffi.lib().cald_train_conv(_wctx(x), N, H, W, _p(x), pk.CinK, _p(pk.buf), pk.Cout,
                                               pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags, _p(residual), _p(up), Hup, Wup, _p(mask), _p(out), ld))
@@ -193,9 +256,10 @@ def conv(x, pk, stride=1, pad=0, relu=False, residual=None, up=None, out=None, o
     return (out, out16) if split_out else out
 
 
-def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, masks=None, xs16=None):
+def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, masks=None, xs16=None, Gs=None):
     """The same layer shape on several NHWC tensors in one launch; pks: one PackedConv per tensor (all of one shape) or a single one.
-    xs16 (packs with split twins only): the split twins of xs, one per tensor (see conv)."""
+    xs16 (packs with split twins only): the split twins of xs, one per tensor (see conv).  Gs (data-gradient packs with twins): one gradient
+    exponent per tensor (see conv); None: the exact kernels."""
     if not isinstance(pks, (list, tuple)):
         pks = [pks] * len(xs)
     pk = pks[0]
@@ -212,6 +276,28 @@ def conv_group(xs, pks, stride=1, pad=0, relu=False, outs=None, out_ld=None, mas
     flags = pk.flags | (FLAG_RELU if relu else 0)
     log = _KERNEL_LOG[0] if pk.mode in (0, 2) else None
     split = all(p.w16 is not None for p in pks)
+    if pk.mode in (1, 3):
+        dlog = _DGRAD_LOG[0]
+        names = (C.c_char_p * len(xs))()
+        mk = _ptr_array(masks) if masks is not None else None
+        if split and Gs is not None:
+            assert stride == 1 and len(Gs) == len(xs)
+            uns = (C.c_float * len(xs))(*[2.0 ** -(p.w16_S + 4 + int(G)) for p, G in zip(pks, Gs)])
+            ins = (C.c_float * len(xs))(*[2.0 ** (4 + int(G)) for G in Gs])
+            _ffi.check(_ffi.lib().cald_train_conv_dgrad_group_f16x3(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
+                                                                    _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, pad, pk.mode, mk,
+                                                                    _ptr_array(res), ld, _ptr_array([p.w16 for p in pks]), uns, ins, names))
+        elif dlog is not None:
+            _ffi.check(_ffi.lib().cald_train_conv_group_f16x3(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
+                                                              _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
+                                                              mk, _ptr_array(res), ld, None, None, None, names))
+        else:
+            _ffi.check(_ffi.lib().cald_train_conv_group(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
+                                                        _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
+                                                        mk, _ptr_array(res), ld))
+        if dlog is not None:
+            dlog.extend((_dgrad_label(p, x), nm.decode()) for p, x, nm in zip(pks, xs, names))
+        return res
     if not split and log is None:
         _ffi.check(_ffi.lib().cald_train_conv_group(_wctx(xs[0]), len(xs), xs[0].shape[0], _int_array(hw), _ptr_array(xs), pk.CinK,
                                                     _ptr_array([p.buf for p in pks]), pk.Cout, pk.Cin, pk.KH, pk.KW, stride, pad, pk.mode, flags,
@@ -239,16 +325,16 @@ def dilate(g, s, Hd, Wd):
     return out
 
 
-def conv_dgrad(g, pk_d, H, W, stride, pad, residual=None, mask=None):
-    """dX [N, H, W, Cin] of a conv whose forward had (stride, pad); g [N, Ho, Wo, CinK(pk_d)], pk_d packed with mode 1."""
+def conv_dgrad(g, pk_d, H, W, stride, pad, residual=None, mask=None, G=None):
+    """dX [N, H, W, Cin] of a conv whose forward had (stride, pad); g [N, Ho, Wo, CinK(pk_d)], pk_d packed with mode 1.  G: see conv."""
     K = pk_d.KH
     if stride > 1 and K == 1 and pk_d.KW == 1 and pad == 0 and residual is None and mask is None:
         # strided 1x1 (the bottleneck's downsample path): only every stride-th input pixel receives a gradient -- multiply on the
         # coarse grid and scatter the result, instead of scattering dY first and multiplying 3/4 zeros
-        return dilate(conv(g, pk_d), stride, H, W)
+        return dilate(conv(g, pk_d, G=G), stride, H, W)
     if stride > 1:
         g = dilate(g, stride, H + 2 * pad - K + 1, W + 2 * pad - pk_d.KW + 1)
-    out = conv(g, pk_d, stride=1, pad=K - 1 - pad, residual=residual, mask=mask)
+    out = conv(g, pk_d, stride=1, pad=K - 1 - pad, residual=residual, mask=mask, G=G)
     assert out.shape[1] == H and out.shape[2] == W, (out.shape, H, W)
     return out
 

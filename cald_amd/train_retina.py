@@ -27,14 +27,16 @@ class RetinaNetTrainer(_TrainerBase):
     LAT_BODY = (1, 2, 3)        # returned_layers = [2, 3, 4]
 
     def __init__(self, state_dict, num_classes, depth=50, min_size=600, max_size=1000, device="cuda", trainable_layers=3,
-                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None, forward_precision="fp32"):
+                 fg_iou_thresh=0.5, bg_iou_thresh=0.4, generator=None, loss_mode=None, forward_precision="fp32",
+                 backward_precision="fp32"):
         if loss_mode not in (None, "ll"):
             raise ValueError("loss_mode must be None or 'll', got %r" % (loss_mode,))
         if loss_mode is not None:
             raise NotImplementedError("loss_mode=%r: the RetinaNet that trains LossNet beside it (ll_train.py:97-120, retina_ll.py's per-image "
                                       "losses) is a model of its own, as in the reference: build a RetinaNetLLTrainer" % (loss_mode,))
         self.loss_mode = None
-        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, forward_precision=forward_precision)
+        self._init_common(state_dict, num_classes, depth, min_size, max_size, device, trainable_layers, generator, forward_precision=forward_precision,
+                          backward_precision=backward_precision)
         self.cfg = dict(fg=fg_iou_thresh, bg=bg_iou_thresh)
         self.lat = [_Conv(self, ["backbone.fpn.inner_blocks.%d.weight" % i], ["backbone.fpn.inner_blocks.%d.bias" % i]) for i in range(3)]
         self.fout = [_Conv(self, ["backbone.fpn.layer_blocks.%d.weight" % i], ["backbone.fpn.layer_blocks.%d.bias" % i], pad=1) for i in range(3)]
@@ -157,6 +159,7 @@ class RetinaNetTrainer(_TrainerBase):
     def backward(self, gscale=(1.0, 1.0)):
         """Gradients of gscale[0] * classification + gscale[1] * bbox_regression into the flat gradient buffer."""
         self._fpn_backward(self._heads_backward(gscale))
+        self._end_backward()
         self._join_side()
         return self.grads
 
@@ -180,7 +183,8 @@ class RetinaNetTrainer(_TrainerBase):
             self.reg_out.bwd(g_reg[l], need_dx=False, accumulate=l > 0, x=acts["reg"][l][4])
             self.cls_out._count(acts["cls"][l][4], 1); self.reg_out._count(acts["reg"][l][4], 1)
         # every ReLU backward of the towers rides in the epilogue of the data gradient that produces its input gradient
-        g_cls = ops.conv_group(g_cls, self.cls_out._packed_grad(), pad=1, masks=[acts["cls"][l][4] for l in range(5)])
+        g_cls = ops.conv_group(g_cls, self.cls_out._packed_grad(), pad=1, masks=[acts["cls"][l][4] for l in range(5)],
+                               Gs=self._dgrad_Gs([(self.cls_out.idx, l) for l in range(5)], g_cls))
         g_reg = ops.conv_group(g_reg, self.reg_out._packed_grad(), pad=1)              # 36 channels: not a tiled-kernel shape
         for l in range(5):
             ops.relu_bwd_(g_reg[l], acts["reg"][l][4])
@@ -190,7 +194,9 @@ class RetinaNetTrainer(_TrainerBase):
                 self.reg_tower[j].bwd(g_reg[l], need_dx=False, accumulate=l > 0, x=acts["reg"][l][j])
                 self.cls_tower[j]._count(acts["cls"][l][j], 1); self.reg_tower[j]._count(acts["reg"][l][j], 1)
             masks = ([acts["cls"][l][j] for l in range(5)] + [acts["reg"][l][j] for l in range(5)]) if j > 0 else None
-            gs = ops.conv_group(g_cls + g_reg, [self.cls_tower[j]._packed_grad()] * 5 + [self.reg_tower[j]._packed_grad()] * 5, pad=1, masks=masks)
+            keys = [(self.cls_tower[j].idx, l) for l in range(5)] + [(self.reg_tower[j].idx, l) for l in range(5)]
+            gs = ops.conv_group(g_cls + g_reg, [self.cls_tower[j]._packed_grad()] * 5 + [self.reg_tower[j]._packed_grad()] * 5, pad=1, masks=masks,
+                                Gs=self._dgrad_Gs(keys, g_cls + g_reg))
             g_cls, g_reg = gs[:5], gs[5:]
         if g_pooled is None:
             return [ops.add(g_cls[l], g_reg[l]) for l in range(5)]

@@ -55,5 +55,6 @@ class RetinaNetLLTrainer(RetinaNetTrainer):
             g_pooled = g_pooled.to(torch.float32).contiguous()
             assert tuple(g_pooled.shape) == tuple(L["pooled"].shape)
         self._fpn_backward(self._heads_backward(gscale, g_pooled))
+        self._end_backward()
         self._join_side()
         return self.grads

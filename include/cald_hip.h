@@ -719,7 +719,7 @@ typedef struct cald_pack_job {
     const float *weight, *bias, *bn_scale, *bn_shift;
     int Cout, Cin, KH, KW, CinK, mode;
     float* packed;
-    void* w16;      /* optional split-fp16 twin of a forward pack (cald_train_pack_conv16), or null */
+    void* w16;      /* optional split-fp16 twin of the pack (cald_train_pack_conv16; a data-gradient pack's: see cald_train_conv_dgrad_f16x3), or null */
     int w16_S;      /* its weight scale 2^S */
 } cald_pack_job;
 typedef struct cald_pack_plan cald_pack_plan;
@@ -753,6 +753,25 @@ int cald_train_conv_group_f16x3(cald_ctx* ctx, int n, int N, const int* hw, cons
                                 int Cout, int Cin, int KH, int KW, int stride, int pad, int mode, int flags, const float* const* masks,
                                 float* const* outs, int out_ld, const void* const* w16, const float* w16_unscale,
                                 const void* const* in16, const char** kernels);
+/* The data gradients of a backward_precision "f16x3" trainer on conv_h3: a data-gradient pack (mode 1 or 3) whose data gradient -- a
+ * stride-1 conv over CinK channels of dY -- is a shape conv_h3 takes has a split twin too (cald_train_packed_grad16_bytes > 0; written by
+ * cald_train_pack_conv16 / a plan job with w16 set, in the launch that writes the fp32 pack): the split of the values the fp32 pack holds
+ * (transposed, flipped, bn_scale folded in) times 2^S, S by cald_train_f16x3_scale from max |w * bn_scale|.  Gradient entries are 1e-3 ..
+ * 1e-8, so the kernel stages dY at in_scale = 2^(4 + G) instead of 2^4, G per gradient tensor:
+ *   cald_train_f16x3_grad_scale  the policy, host-only: max |g| = f * 2^e, f in [0.5, 1) -> G = 7 - e (max |g| * in_scale in [2^10, 2^11)),
+ *                                clamped to +-60, 0 for an all-zero or non-finite tensor; in_scale = 2^(4 + G)
+ * and the launch takes w16_unscale = 2^-(S + 4 + G): out is the true, unscaled fp32 gradient.  residual (or null) is added, then mask (or
+ * null) applied, in the kernel's epilogue.  pad is the data gradient's own (K - 1 - forward pad), the stride 1.  A shape conv_h3 does not
+ * take runs the exact kernels, which never read the twin.  A gradient that outgrew a stale G splits as (inf, -inf): non-finite outputs,
+ * no error.  kernel / kernels as above. */
+int cald_train_packed_grad16_bytes(int Cout, int Cin, int KH, int KW, int CinK, int mode, int64_t* bytes_out);
+int cald_train_f16x3_grad_scale(float max_abs, int* G_out, float* in_scale_out);
+int cald_train_conv_dgrad_f16x3(cald_ctx* ctx, int N, int H, int W, const float* in, int CinK, const float* packed, int Cout, int Cin,
+                                int KH, int KW, int pad, int mode, const float* residual, const float* mask, float* out, int out_ld,
+                                const void* w16, float w16_unscale, float in_scale, const char** kernel);
+int cald_train_conv_dgrad_group_f16x3(cald_ctx* ctx, int n, int N, const int* hw, const float* const* ins, int CinK, const float* const* packed,
+                                      int Cout, int Cin, int KH, int KW, int pad, int mode, const float* const* masks, float* const* outs,
+                                      int out_ld, const void* const* w16, const float* w16_unscale, const float* in_scale, const char** kernels);
 /* dw[Cout][Cin][KH][KW] (=, or += when accumulate) sum over output pixels of g[q][co] * x[q @ tap][ci]; db[Cout] likewise (or
  * null).  x [N][H][W][ldx], g [N][Ho][Wo][ldg]; Cin, ldx, ldg multiples of 4.  Deterministic (fixed-order split reduction).
  * row_scale (or null): dw[co] is multiplied by row_scale[co] -- g is then the gradient wrt the FrozenBatchNorm OUTPUT of the layer. */
